@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- tokens/sec through SAE encode + TopK + decode (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--tokens T] [--k 32] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--tokens T] [--k 32] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one pass of the hot path over one batch of T synthetic activations already resident in
@@ -17,7 +17,7 @@ truncation re-check; (b) per-shard top-C candidates by upper bound, one RCCL all
 token's owner against the replicated f32 W_enc (the HBM-bound re-score then runs once per token instead of
 once per token and rank), all-gather of the results.  The decode is token-sharded with an all-gather of the
 reconstruction.  Total work is fixed as G grows: "scaling": "strong", value = T * steps / max-over-ranks
-time; the first 256 tokens are compared with a single-GPU encode.  The reference's own
+time; the first 256 tokens are compared with a single-GPU encode.  With --full, the reference's own
 multi-GPU mode -- token-sharded replicas, no data-path collective (launch/cache/cache.py:66) -- is
 measured FIRST in the same run and reported under "replicas" (weak scaling); it is also the provisional
 headline, so a feature-sharded leg that raises, stalls (watchdog) or is not bit-identical on some node
@@ -26,15 +26,23 @@ still leaves a measured whole-job line ("headline" says which leg the line's val
 Optional real inputs (N = 1): --sae_path <dir with cfg.json + sae.safetensors> and/or
 --acts <file.safetensors holding one [T, d] tensor> replace the synthetic SAE / activations.
 
-Secondary records in the same line (N = 1, synthetic inputs; round-4 verdict items 1, 6): "k256" (the released checkpoint's k on
+A plain run (no --full) does only what the headline needs: set-up, W warm-up steps, K timed steps, the line.  Everything
+else is measured with --full only: the instrumented pass and what is computed from it (stage clocks, re-score statistics,
+"roofline"), the clock / power sampler, the CPU baseline, for N > 1 the replicas leg and each leg's side measurements, and
+for N = 1 the secondary records below.
+
+--dump-outputs DIR writes what the timed loop returned in its last step (output_sample) to DIR/<name>.npy: the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
+
+Secondary records in the same line (--full, N = 1, synthetic inputs; round-4 verdict items 1, 6): "k256" (the released checkpoint's k on
 the same batch), "zipf" (heavy-tailed feature usage: firing frequency proportional to 1 / rank, a handful of dense features),
 "exact_modes" (ms per step of the fused encode under msae_options::certified / ::exact on the bench batch) and "dither_off"
 (the round-to-nearest statistical mode of ABI 3 beside the dithered default the headline runs); round 6: "t2880" / "t65536" (one
 anyres image per call, eight bench batches per call), "sustained" (2000 steps: clock and power at equilibrium), and in
 "roofline" the STEP's own fraction of BASELINE.md section 3's max(...) ("step_frac").
 
-Timing protocol (round 6): the headline's K steps run on the UN-instrumented loop; the stage clocks / re-score statistics come
-from a pass of the same W + K steps with the HIP events on that runs first ("ms_per_step_instrumented"; "timing_order" says so in
+Timing protocol (round 6): the headline's K steps run on the UN-instrumented loop; with --full the stage clocks / re-score statistics
+come from a pass of the same W + K steps with the HIP events on that runs first ("ms_per_step_instrumented"; "timing_order" says so in
 the line; the events cost 0.02-0.03 ms per step).  The wall clock of a timed loop is read INSIDE the clock sampler's context: until
 round 6 the region enclosed the sampler's exit -- a join on a thread sitting in a sleep or an hwmon read, 0-4 ms per loop
 (profiles/r06_timing_harness.txt).
@@ -347,6 +355,26 @@ def zipf_bias(x, b_dec, N, k, dev):
     return out
 
 
+DUMP_BUDGET = 48 << 20      # bytes of the token sample --dump-outputs writes (well under its 64 MB cap)
+
+
+def output_sample(out, seed=0):
+    """--dump-outputs: what a caller of the timed path receives from one step -- top_acts [T, k], top_indices [T, k] and the
+    reconstruction sae_out [T, d] -- for a fixed, seeded sample of the step's T tokens (all of them when they fit DUMP_BUDGET),
+    as float32 / float64 host arrays; `token_rows` names the sampled tokens.  The per-token `status` is left out: it depends
+    on the dither seeds the library draws per call, the outputs do not."""
+    acts, idx, recon = out["top_acts"], out["top_indices"], out["sae_out"]
+    T = acts.shape[0]
+    assert idx.shape[0] == recon.shape[0] == T, (tuple(idx.shape), tuple(recon.shape), T)
+    n = min(T, DUMP_BUDGET // (4 * acts.shape[1] + 8 * idx.shape[1] + 4 * recon.shape[1] + 8))
+    rows = np.arange(T) if n == T else np.sort(np.random.default_rng(seed).choice(T, n, replace=False))
+    r = torch.from_numpy(rows).to(acts.device)
+    return {"token_rows": rows.astype(np.float64),
+            "top_acts": acts.index_select(0, r).float().cpu().numpy(),
+            "top_indices": idx.index_select(0, r).double().cpu().numpy(),
+            "sae_out": recon.index_select(0, r).float().cpu().numpy()}
+
+
 class HipRuntime:
     """Everything of the bench that touches a device or a collective backend.  tests/test_bench_dryrun.py substitutes a CPU /
     gloo runtime with injected kernels to run main()'s control flow without a GPU."""
@@ -446,7 +474,15 @@ def main(argv=None, rt=None):
     ap.add_argument("--sae_path", default=None, help="N = 1: checkpoint dir (cfg.json + sae.safetensors)")
     ap.add_argument("--acts", default=None, help="N = 1: safetensors file with one [T, d] activation tensor")
     ap.add_argument("--json-out", default=None, help="also write the JSON line to this file")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the instrumented pass (stage clocks, re-score "
+                         "statistics, roofline), clock / power sampling, the secondary records and the CPU baseline (N = 1), "
+                         "the replicas leg and each leg's side measurements (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step to DIR/<name>.npy (see output_sample)")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # stdout carries exactly ONE line, the JSON record: whatever a library prints there (RCCL's version banner at
     # communicator creation, for one) goes to stderr instead
@@ -511,6 +547,8 @@ def main(argv=None, rt=None):
 
     rows_buf = torch.zeros(max(T, 65536), dtype=torch.int32, device=dev)    # (the t65536 record's tokens fit as well)
     sampler_out = {}
+    last_plain_out = {}     # the outputs of the latest un-instrumented loop's last step: what --dump-outputs writes
+    dumped = None
 
     def timed(eng, xin, steps, warmup, profile, gather=True):
         xs = xin if isinstance(xin, list) else [xin]
@@ -526,7 +564,7 @@ def main(argv=None, rt=None):
         if ddp:
             dist.barrier()
         rt.sync()
-        sampler = rt.clock_sampler(dev)
+        sampler = rt.clock_sampler(dev) if args.full else contextlib.nullcontext()
         # (an un-instrumented loop carries neither the stage events nor the per-token statistics store)
         ctx_a, ctx_b = rt.contexts(prof, rows_buf) if profile else (contextlib.nullcontext(), contextlib.nullcontext())
         # The clock starts INSIDE the contexts and stops before they exit: the sampler's thread start and, above all, its join --
@@ -543,7 +581,8 @@ def main(argv=None, rt=None):
                 dist.barrier()
             el = time.perf_counter() - t0
         sampler_out.clear()
-        sampler_out.update(sampler.summary())
+        if args.full:
+            sampler_out.update(sampler.summary())
         stage, dec_ms = np.zeros((0, 6)), float("nan")
         if profile and prof is not None:
             stage = prof.read().astype(np.float64)
@@ -555,6 +594,8 @@ def main(argv=None, rt=None):
             tmax = torch.tensor([el], device=dev)
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             el = float(tmax.item())
+        if not profile:
+            last_plain_out["out"] = out
         return el, out, stage, dec_ms
 
     def timed_clean(eng, xin, steps, warmup, gather=True):
@@ -563,7 +604,11 @@ def main(argv=None, rt=None):
         then the un-instrumented one, whose time is the headline -- an instrument must not sit inside the number it decorates
         (the events cost 0.02-0.03 ms per step; the order of the passes does not matter: tools/pass_order.py,
         profiles/r06_timing_harness.txt).  Both passes' times are reported, and the order is named in the line ("timing_order").
+        Without --full only the un-instrumented pass runs (stage empty, elapsed_instrumented None) and `out` is its own.
         -> (elapsed, out, stage, dec_ms, elapsed_instrumented)"""
+        if not args.full:
+            el, out, stage, dec_ms = timed(eng, xin, steps, warmup, profile=False, gather=gather)
+            return el, out, stage, dec_ms, None
         el_i, out_i, stage, dec_ms = timed(eng, xin, steps, warmup, profile=True, gather=gather)
         el, out, _, _ = timed(eng, xin, steps, warmup, profile=False, gather=gather)
         return el, out_i, stage, dec_ms, el_i
@@ -711,16 +756,19 @@ def main(argv=None, rt=None):
     if not sharded:
         xs = more_batches(x, rank)
         elapsed, out, stage, dec_ms, el_inst = timed_clean(engine, xs, args.steps, args.warmup)
+        if args.dump_outputs:
+            dumped = output_sample(last_plain_out["out"])
         res.update(ms_per_step=elapsed / args.steps * 1e3, value=T * args.steps / elapsed,
-                   ms_per_step_instrumented=el_inst / args.steps * 1e3,
-                   timing_order="instrumented pass (W warm-up + K steps, stage events on) first, then the headline pass (W warm-up + K "
-                                "steps, no instrumentation)",
                    config={"workload": workload % ("T=%d" % T), "tokens_per_step": T, "k": k,
                            "parallelism": "single GPU", "distinct_batches": len(xs)})
+        if args.full:
+            res.update(ms_per_step_instrumented=el_inst / args.steps * 1e3,
+                       timing_order="instrumented pass (W warm-up + K steps, stage events on) first, then the headline pass (W "
+                                    "warm-up + K steps, no instrumentation)")
         if len(stage):
             roofline_fields(stage, dec_ms, out, N, T, with_traffic=True)
         # ---- secondary records (same batches; never the headline).  Each is guarded: a failure is recorded, not raised.
-        if not args.no_secondary and not (args.sae_path or args.acts) and world == 1:
+        if args.full and not args.no_secondary and not (args.sae_path or args.acts) and world == 1:
             sec_steps, sec_warm = max(3, min(args.steps, 10)), 2      # (each record: the instrumented pass, then the timed one -- as the headline)
 
             def record(name, fn):
@@ -815,7 +863,7 @@ def main(argv=None, rt=None):
         # scaling).  Every rank holds the WHOLE SAE and encodes its own batch; no data-path collective, so nothing in
         # it can wedge.  It is the PROVISIONAL headline: if a feature-sharded leg below raises or stalls on this node,
         # the printed line still carries a measured whole-job number and names the leg that failed.
-        if not args.no_replicas:
+        if args.full and not args.no_replicas:
             _, _, _, _, x_own = rt.make_inputs(dev, T, d, min(N, 8192), seed=1 + rank)        # this rank's own batches
             x_own = more_batches(x_own, 1 + rank)
             rep = rt.engine(W_full, b_full, W_dec, b_dec, k)
@@ -859,6 +907,8 @@ def main(argv=None, rt=None):
                                      {"candidates_per_shard": eng.n_cand})
             if ok and (best is None or el < best[0]):
                 best = (el, o, st, dm, eng, desc)
+                if args.dump_outputs and rank == 0:
+                    dumped = output_sample(last_plain_out["out"])
                 # the headline from here on (also what the watchdog prints if the next leg stalls)
                 res.update(value=T * args.steps / el, ms_per_step=el / args.steps * 1e3, scaling="strong",
                            headline="feature-sharded: " + name,
@@ -872,6 +922,8 @@ def main(argv=None, rt=None):
                     roofline_fields(st, dm, o, n_loc, -(-T // world), with_traffic=False)
             # beside the timed step, never inside it: the same leg with the reconstruction left token-sharded (what a
             # token-sharded consumer needs: no 16 KiB/token all-gather), and each collective of the step on its own
+            if not args.full:
+                continue
             try:
                 el_n, _, _, _ = timed(eng, xs, args.steps, min(args.warmup, 2), profile=False, gather=False)
                 shard_modes[name]["ms_per_step_no_recon_gather"] = el_n / args.steps * 1e3
@@ -887,8 +939,12 @@ def main(argv=None, rt=None):
                 m = shard_modes["per_shard_topk"]
                 res.update(value=T / (m["ms_per_step"] * 1e-3), ms_per_step=m["ms_per_step"], scaling="strong")
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not (args.sae_path or args.acts) and not rt.dry_run:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not (args.sae_path or args.acts) and not rt.dry_run:
         res["cpu_baseline"] = cpu_baseline(W_enc, b_enc, W_dec, b_dec, x, k, args.cpu_sample)
+    if dumped is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in dumped.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
     emit()
     if ddp:
         if watchdog is not None:

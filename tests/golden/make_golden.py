@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 HERE = Path(__file__).resolve().parent
-OUT = HERE                      # where the fixtures are written (--out: a scratch directory, tests/test_golden_recipe.py)
+OUT = HERE                      # where the fixtures are written (--out: a scratch directory)
 REPO = HERE.parent.parent
 REF = Path("/root/reference")
 sys.path.insert(0, str(REPO / "tests"))

@@ -46,7 +46,8 @@ def _run(tmp_path, world, argv, fault=None):
 
 
 def test_bench_world_8_control_flow_and_schema(tmp_path):
-    res = _run(tmp_path, 8, ["--gpus", "8", "--steps", "2", "--warmup", "1", "--tokens", "80", "--k", "8", "--batches", "2"])
+    res = _run(tmp_path, 8, ["--gpus", "8", "--steps", "2", "--warmup", "1", "--tokens", "80", "--k", "8", "--batches", "2",
+                             "--full"])
     assert "error" not in res, res.get("error")
     assert res["n_gpus"] == 8 and res["rccl_world"] == 8 and res["collective_backend"] == "gloo" and "dry_run" in res
     assert res["scaling"] == "strong" and res["headline"].startswith("feature-sharded: ")
@@ -70,6 +71,36 @@ def test_bench_world_4_one_token_fewer_than_ranks(tmp_path):
     res = _run(tmp_path, 4, ["--gpus", "4", "--steps", "1", "--warmup", "1", "--tokens", "3", "--k", "8", "--batches", "1"])
     assert "error" not in res, res.get("error")
     assert res["shard_modes"]["candidate_exchange"]["bit_identical_256"] is True
+    # a plain run (no --full): the two feature-sharded legs only, without the replicas leg or the side measurements
+    assert "replicas" not in res and "collective_ms" not in res["shard_modes"]["per_shard_topk"]
+
+
+def test_bench_plain_run_and_dumped_outputs_of_its_last_step(tmp_path):
+    """One rank, no --full: the line carries the headline alone, and --dump-outputs writes what the last of the --steps timed
+    steps returned.  With 2 steps over 2 batches that is the second batch, recomputed here with the oracle."""
+    import numpy as np
+
+    import synth
+    from oracle import oracle
+
+    dump = tmp_path / "dump"
+    res = _run(tmp_path, 1, ["--gpus", "1", "--steps", "2", "--warmup", "1", "--tokens", "40", "--k", "8", "--batches", "2",
+                             "--dump-outputs", str(dump)])
+    assert "error" not in res, res.get("error")
+    assert res["steps"] == 2 and res["ms_per_step"] > 0 and res["value"] > 0 and res["higher_is_better"] is True
+    for key in ("metric", "unit", "dtype"):
+        assert key in res
+    for key in ("roofline", "stage_ms", "ms_per_step_instrumented", "clock", "k256", "sustained", "zipf", "cpu_baseline"):
+        assert key not in res, key
+    got = {n: np.load(dump / f"{n}.npy") for n in ("token_rows", "top_acts", "top_indices", "sae_out")}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    W_enc, b_enc, W_dec, b_dec = synth.sae_weights(64, 1024, seed=31)          # shard_fakes.FakeRuntime.make_inputs
+    x = synth.activations(40, 64, seed=100 + 7919)                              # batch 1 (bench.main: more_batches)
+    v, i = oracle.encode_topk(x, W_enc, b_enc, b_dec, 8)
+    rows = got["token_rows"].astype(np.int64)
+    assert np.array_equal(rows, np.arange(40))
+    assert np.array_equal(got["top_indices"], i) and np.array_equal(got["top_acts"], v)
+    assert np.array_equal(got["sae_out"], oracle.decode(i, v, W_dec, b_dec))
 
 
 @pytest.mark.parametrize("fault", [{"raise_rank": 2, "watchdog_s": 60}, {"stall_rank": 3, "watchdog_s": 15}])

@@ -413,8 +413,7 @@ _ALIAS_ENV = dict(os.environ, PYTHONPATH=os.pathsep.join([str(REPO / "multimodal
 def test_reference_decode_test_runs_through_the_sae_alias(dev, tmp_path):
     """train/sae/tests/test_decode.py:3-20 -- the reference's ONLY test -- against the drop-in: its import line
     (`from sae.utils import eager_decode, triton_decode`), its inputs (batch 2, d_in 50, d_sae 100, k 10, W_dec passed as
-    `.mT`) and its assertion, in a fresh interpreter with the opt-in alias on the path.  Where the reference checkout exists
-    (the build container has no GPU, the GPU box no reference: normally neither) the file itself is run verbatim as well."""
+    `.mT`) and its assertion, in a fresh interpreter with the opt-in alias on the path."""
     code = ("import torch\n"
             "from sae.utils import eager_decode, triton_decode\n"
             "batch, d_in, d_sae, k = 2, 50, 100, 10\n"
@@ -429,11 +428,6 @@ def test_reference_decode_test_runs_through_the_sae_alias(dev, tmp_path):
             "print('ok')")
     r = subprocess.run([sys.executable, "-c", code], env=_ALIAS_ENV, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stderr[-2000:]
-    ref_test = Path("/root/reference/train/sae/tests/test_decode.py")
-    if ref_test.exists():
-        r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-p", "no:cacheprovider", str(ref_test)], env=_ALIAS_ENV,
-                           capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
 
 
 def test_sae_decode_goes_through_the_module_level_decoder_impl(dev):

@@ -746,7 +746,7 @@ def test_bench_under_torchrun_with_rccl_collectives(dev):
     env = dict(os.environ, MSAE_FORCE_COLLECTIVES="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(port), str(REPO / "bench.py"),
-           "--gpus", "1", "--steps", "2", "--warmup", "1", "--tokens", "1024", "--no-cpu-baseline"]
+           "--gpus", "1", "--steps", "2", "--warmup", "1", "--tokens", "1024", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]

@@ -17,11 +17,11 @@ fi
 echo "== smoke =="
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke exit $?" | tee -a $OUT/smoke.log; tail -2 $OUT/smoke.log
 echo "== bench =="
-timeout 600 python bench.py --steps 20 --warmup 5 > $OUT/${R}_bench.json 2> $OUT/bench.err; echo "bench exit $?"; cat $OUT/${R}_bench.json
-MSAE_COARSE=bf16 timeout 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-secondary > $OUT/${R}_bench_bf16.json 2>> $OUT/bench.err; echo "bench bf16 exit $?"
+timeout 600 python bench.py --full --steps 20 --warmup 5 > $OUT/${R}_bench.json 2> $OUT/bench.err; echo "bench exit $?"; cat $OUT/${R}_bench.json
+MSAE_COARSE=bf16 timeout 600 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-secondary > $OUT/${R}_bench_bf16.json 2>> $OUT/bench.err; echo "bench bf16 exit $?"
 echo "== rocprof kernel stats =="
 rm -rf $OUT/prof
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o $R -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-secondary > $OUT/${R}_bench_under_rocprof.json 2> $OUT/rocprof.err; echo "rocprof exit $?"
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o $R -- python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-secondary > $OUT/${R}_bench_under_rocprof.json 2> $OUT/rocprof.err; echo "rocprof exit $?"
 for f in $(find $OUT/prof -name "*kernel_stats*.csv" | head -1); do head -12 $f | cut -c1-160; done
 find $OUT/prof -name "*kernel_trace*" -size +2M -delete
 echo "== PMC passes =="

@@ -5,7 +5,7 @@
 cd "$(dirname "$0")/.."
 name=$1; lib=$2; steps=${3:-400}
 OUT=gpurun_out/power; mkdir -p $OUT
-( [ -n "$lib" ] && export MSAE_HIP_LIB=$lib; timeout 300 python bench.py --steps $steps --warmup 5 --no-cpu-baseline > $OUT/$name.json 2>$OUT/$name.err ) &
+( [ -n "$lib" ] && export MSAE_HIP_LIB=$lib; timeout 300 python bench.py --full --steps $steps --warmup 5 --no-cpu-baseline > $OUT/$name.json 2>$OUT/$name.err ) &
 BP=$!
 sleep 20   # import + input generation
 : > $OUT/$name.smi
