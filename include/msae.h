@@ -25,6 +25,7 @@
  *   msae_decode_bwd_acts_f32 TritonDecoder.backward (acts) sae/kernels.py:421-425,287-400
  *   msae_decode_bwd_wdec_f32 TritonDecoder.backward (W)    sae/kernels.py:417-419,10-175
  *   msae_sparsify_*          scatter_ + Cache.add/get_nonzeros  features/cache.py:214-217,42-92
+ *   msae_feature_stats_*     per-feature counts + top examples  features/loader.py:103-106, constructors.py:28-141
  *
  * Numerics contract: all dot products are ascending-k f32 fused
  * multiply-add chains (v_mfma_f32_32x32x2_f32 / v_fma_f32), bit-identical to oracle/sae_oracle.c.
@@ -352,6 +353,41 @@ int msae_sparsify_write(const float *vals, const int32_t *idx, int B, int S, int
                         const uint8_t *filter_bitmap, int N, int64_t row_base,
                         const int64_t *counts, int64_t *locations, float *activations,
                         void *stream);
+
+/* ---- per-feature statistics and top-example tables (opt-in part of the cache loop) ----------------
+ * What the reference's explain side re-derives per feature from the split files afterwards, kept for ALL N
+ * features as the batches stream by:
+ *   how often it fires   the loader's min_examples cut       sae_auto_interp/features/loader.py:103-106
+ *   its top examples     pool_max_activation_windows          features/constructors.py:28-85 (window mode)
+ *                        pool_max_activations_windows_image   features/constructors.py:88-141 (image mode)
+ * Input: one batch's top-k vals/idx[B*S][k] (any order inside a token; a token's indices distinct).  An entry is
+ * kept when |v| > thresh and 0 <= idx < N (msae_sparsify's rule; there is no filter bitmap: the statistics cover
+ * every feature, so filters can be chosen from them).  Per feature f, accumulated in place:
+ *   count[f]    u64  kept (token, f) records                                         exact
+ *   act_max[f]  f32  maximum kept value (initialise to -inf)                          exact
+ *   act_sum[f]  f64  sum of kept values, one f64 atomic per (segment, f)             order-dependent at rounding level
+ *   top_val[f][n_top] f32, top_id[f][n_top] i64: the n_top largest NONZERO pooled values of f seen so far, sorted by
+ *               value descending then id ascending (a total order: the table is the same however the rows are cut
+ *               into calls); free slots (0, -1) at the tail (initialise so).
+ * Pooling segments (a row never spans two calls, so each segment is complete in one call):
+ *   MSAE_POOL_IMAGE   one per row b: pooled = (f32 sum of the values at s < pool_len, ascending s) / pool_len
+ *                     (avg_pool1d over the first num_image_tokens positions); id = row_base + b.
+ *   MSAE_POOL_WINDOW  [w*W, (w+1)*W) of a row, W = window, w < S / W (positions >= (S / W) * W are not pooled, as
+ *                     unfold / max_pool1d drop them); pooled = max over the window's dense values, i.e. a window
+ *                     where f did not fire on every position also holds a 0; id = (row_base + b) * (S / W) + w.
+ * Envelope: B*S <= 65536, k <= 256, N <= 262144, n_top <= 256, pool_len <= 2880, window <= 4096 (else
+ * MSAE_EINVAL).  No host synchronisation, no allocation: the workspace is msae_feature_stats_ws_bytes(B*S, k, N).
+ * _merge: dst += src for two sets of statistics of the same N and n_top (ranks, modules): counts add, maxima max,
+ * sums add, tables merge in the same total order. */
+enum { MSAE_POOL_IMAGE = 0, MSAE_POOL_WINDOW = 1, MSAE_STATS_MAX_T = 65536 };
+size_t msae_feature_stats_ws_bytes(int T, int k, int N);
+int msae_feature_stats_update(const float *vals, const int32_t *idx, int B, int S, int k, float thresh, int N,
+                              int mode, int pool_len, int window, int64_t row_base, int n_top, uint64_t *count,
+                              float *act_max, double *act_sum, float *top_val, int64_t *top_id, void *ws,
+                              size_t ws_bytes, void *stream);
+int msae_feature_stats_merge(int N, int n_top, uint64_t *count, float *act_max, double *act_sum, float *top_val,
+                             int64_t *top_id, const uint64_t *src_count, const float *src_max,
+                             const double *src_sum, const float *src_val, const int64_t *src_id, void *stream);
 
 /* ---- merge of per-shard results (feature-sharded encode; no reference counterpart) ----
  * gathered: int32 [G][2][T][kl], the all-gather of each rank's packed block [2][T][kl]

@@ -1,0 +1,368 @@
+// feature_stats.hip -- per-feature statistics and top-example tables, updated from the cache loop's top-k.
+//
+// Answers, for every feature as the tokens stream by, the two questions the reference's explain side re-derives
+// from the COO split files afterwards: how often a feature fires (loader.py:103-106, min_examples) and which rows
+// / windows activate it most (features/constructors.py:28-85 pool_max_activation_windows, 88-141
+// pool_max_activations_windows_image -- there a dense [rows, seq] tensor per feature on the CPU).
+//
+// One update per batch of [B*S][k] top-k pairs:
+//   1. key build      every kept entry (|v| > thresh, sparsify's rule; no filter bitmap) becomes the key
+//                     (feature << tb | t) with its value; dropped entries get feature = N and sort last.
+//   2. radix sort     rocPRIM's device radix sort over the used key bits: entries grouped by feature, and inside a
+//                     feature in token order (t is unique per feature: a token's top-k indices are distinct).
+//   3. group pass     a GROUP is the run of one feature inside one pooling segment (window mode: [w*W, (w+1)*W) of
+//                     a row, the ragged tail its own group; image mode: the row).  The thread on a group's first
+//                     entry walks it in ascending position: count / max / f64 sum -> ONE atomic each per (group,
+//                     feature), not one per token (a feature that fires on every token costs B*S/W atomics, not
+//                     B*S); the pooled value of the segment -> cand[i] (0 = no candidate).
+//   4. table merge    one wave per feature with records in this batch: the candidates of its run are ranked
+//                     against its sorted top-n table (value descending, id ascending: a total order) and merged.
+//                     The table after a batch is the top-n of every candidate seen, whatever the cut into calls.
+// No host synchronisation, no allocation (workspace: msae_feature_stats_ws_bytes).
+#include <rocprim/device/device_radix_sort.hpp>
+
+#include "common.h"
+
+namespace {
+
+constexpr int FS_MAX_TOP = 256;
+
+struct FsGeom {      // where token t = b*S + s belongs
+  int S, mode, P, W, nw, tb;
+  long long row_base;
+};
+
+__device__ __forceinline__ int fs_group(const FsGeom &g, int s) { return g.mode == MSAE_POOL_WINDOW ? s / g.W : 0; }
+
+// the pooled candidate's id: image = global row, window = global row * (S / W) + w
+__device__ __forceinline__ long long fs_id(const FsGeom &g, int b, int grp) {
+  return g.mode == MSAE_POOL_WINDOW ? (g.row_base + b) * (long long)g.nw + grp : g.row_base + b;
+}
+
+// strict "a ranks before b": value descending, then id ascending
+__device__ __forceinline__ bool fs_before(float av, long long ai, float bv, long long bi) {
+  return av > bv || (av == bv && ai < bi);
+}
+
+__device__ __forceinline__ void atomic_max_f32(float *p, float v) {
+  if (v >= 0.f)
+    atomicMax((int *)p, __float_as_int(v));
+  else
+    atomicMin((unsigned *)p, __float_as_uint(v));
+}
+
+__global__ __launch_bounds__(256) void fs_keys_kernel(const float *__restrict__ vals, const int32_t *__restrict__ idx,
+                                                      long M, int k, float thresh, int N, int tb,
+                                                      unsigned long long *__restrict__ keys, float *__restrict__ kv) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= M) return;
+  const float v = vals[i];
+  const int f = idx[i];
+  const unsigned long long t = (unsigned long long)(i / k);
+  const bool keep = fabsf(v) > thresh && (unsigned)f < (unsigned)N;   // sparsify_count_kernel's rule, no bitmap
+  keys[i] = ((unsigned long long)(keep ? f : N) << tb) | t;
+  kv[i] = v;
+}
+
+// one thread per sorted entry: run boundaries of every feature, and the walk of every group from its first entry
+__global__ __launch_bounds__(256) void fs_group_kernel(const unsigned long long *__restrict__ keys,
+                                                       const float *__restrict__ kv, long M, int N, FsGeom g,
+                                                       int *__restrict__ run_start, int *__restrict__ run_end,
+                                                       float *__restrict__ cand, unsigned long long *__restrict__ count,
+                                                       float *__restrict__ act_max, double *__restrict__ act_sum) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= M) return;
+  const unsigned long long tmask = (1ull << g.tb) - 1ull;
+  const unsigned long long key = keys[i];
+  const int f = (int)(key >> g.tb);
+  if (f >= N) return;                               // dropped entries: sorted behind every kept one
+  const int t = (int)(key & tmask), b = t / g.S, s = t - b * g.S, grp = fs_group(g, s);
+  bool first = true;
+  if (i == 0 || (int)(keys[i - 1] >> g.tb) != f) {
+    run_start[f] = (int)i;
+  } else {
+    const int pt = (int)(keys[i - 1] & tmask), pb = pt / g.S;
+    first = !(pb == b && fs_group(g, pt - pb * g.S) == grp);
+  }
+  if (i == M - 1 || (int)(keys[i + 1] >> g.tb) != f) run_end[f] = (int)i + 1;
+  if (!first) {
+    cand[i] = 0.f;
+    return;
+  }
+  int cnt = 0, pooled_n = 0;
+  float mx = -INFINITY, pool = 0.f;               // window: max; image: f32 sum in ascending s
+  double sum = 0.0;
+  for (long j = i; j < M; ++j) {
+    const unsigned long long kj = keys[j];
+    if ((int)(kj >> g.tb) != f) break;
+    const int tj = (int)(kj & tmask), bj = tj / g.S, sj = tj - bj * g.S;
+    if (bj != b || fs_group(g, sj) != grp) break;
+    const float v = kv[j];
+    ++cnt;
+    mx = fmaxf(mx, v);
+    sum += (double)v;
+    if (g.mode == MSAE_POOL_WINDOW) {
+      pool = pooled_n ? fmaxf(pool, v) : v;
+      ++pooled_n;
+    } else if (sj < g.P) {
+      pool += v;
+      ++pooled_n;
+    }
+  }
+  atomicAdd(count + f, (unsigned long long)cnt);
+  atomic_max_f32(act_max + f, mx);
+  atomicAdd(act_sum + f, sum);
+  float c = 0.f;
+  if (g.mode == MSAE_POOL_WINDOW) {
+    // max_pool1d over the dense row: a window with a position this feature did not fire on also holds a 0
+    if (grp < g.nw) c = cnt < g.W ? fmaxf(pool, 0.f) : pool;
+  } else if (pooled_n) {
+    c = pool / (float)g.P;                          // avg_pool1d over the first P positions
+  }
+  cand[i] = (c == c) ? c : 0.f;                     // NaN never enters a table
+}
+
+// one single-wave workgroup per feature (grid-stride): rank this batch's candidates against the table, merge
+__global__ __launch_bounds__(64) void fs_merge_kernel(const unsigned long long *__restrict__ keys,
+                                                      const float *__restrict__ cand, int N, int n, FsGeom g,
+                                                      const int *__restrict__ run_start, const int *__restrict__ run_end,
+                                                      float *__restrict__ top_val, long long *__restrict__ top_id) {
+  __shared__ float av[2][FS_MAX_TOP];
+  __shared__ long long ai[2][FS_MAX_TOP];
+  __shared__ float cv[64];
+  __shared__ long long ci[64];
+  const int lane = threadIdx.x;
+  const unsigned long long tmask = (1ull << g.tb) - 1ull;
+  for (int f = blockIdx.x; f < N; f += gridDim.x) {
+    const int e = run_end[f];
+    if (e == 0) continue;                           // no record of f in this batch
+    const int s0 = run_start[f];
+    float *tv = top_val + (size_t)f * n;
+    long long *ti = top_id + (size_t)f * n;
+    int tn = 0;
+    for (int j = lane; j < n; j += 64) {
+      av[0][j] = tv[j];
+      ai[0][j] = ti[j];
+      tn += ti[j] >= 0;                             // valid entries sit at the front
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) tn += __shfl_xor(tn, off, 64);
+    int cur = 0;
+    bool changed = false;
+    __syncthreads();
+    for (int base = s0; base < e; base += 64) {
+      const int i = base + lane;
+      const float c = i < e ? cand[i] : 0.f;
+      const bool is_c = c != 0.f;
+      const unsigned long long mask = __ballot(is_c);
+      if (mask == 0ull) continue;
+      changed = true;
+      long long id = 0;
+      if (is_c) {
+        const int t = (int)(keys[i] & tmask), b = t / g.S;
+        id = fs_id(g, b, fs_group(g, t - b * g.S));
+      }
+      cv[lane] = c;
+      ci[lane] = id;
+      __syncthreads();
+      const float *A = av[cur];
+      const long long *AI = ai[cur];
+      float *Bv = av[cur ^ 1];
+      long long *Bi = ai[cur ^ 1];
+      if (is_c) {
+        int r = 0;                                  // candidates of this chunk ranked before this one
+        for (unsigned long long m = mask; m; m &= m - 1) {
+          const int o = __builtin_ctzll(m);
+          r += fs_before(cv[o], ci[o], c, id) || (cv[o] == c && ci[o] == id && o < lane);
+        }
+        int lo = 0, hi = tn;                        // table entries ranked before or equal: upper bound
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if (fs_before(c, id, A[mid], AI[mid])) hi = mid; else lo = mid + 1;
+        }
+        r += lo;
+        if (r < n) {
+          Bv[r] = c;
+          Bi[r] = id;
+        }
+      }
+      for (int j = lane; j < tn; j += 64) {
+        int r = j;
+        for (unsigned long long m = mask; m; m &= m - 1) {
+          const int o = __builtin_ctzll(m);
+          r += fs_before(cv[o], ci[o], A[j], AI[j]);
+        }
+        if (r < n) {
+          Bv[r] = A[j];
+          Bi[r] = AI[j];
+        }
+      }
+      tn = min(n, tn + __popcll(mask));
+      cur ^= 1;
+      __syncthreads();
+    }
+    if (changed) {
+      for (int j = lane; j < n; j += 64) {
+        tv[j] = j < tn ? av[cur][j] : 0.f;
+        ti[j] = j < tn ? ai[cur][j] : -1ll;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// dst += src, feature by feature: counts add, maxima max, sums add, tables merge in the same total order
+__global__ __launch_bounds__(64) void fs_merge_tables_kernel(
+    int N, int n, unsigned long long *__restrict__ count, float *__restrict__ act_max, double *__restrict__ act_sum,
+    float *__restrict__ top_val, long long *__restrict__ top_id, const unsigned long long *__restrict__ s_count,
+    const float *__restrict__ s_max, const double *__restrict__ s_sum, const float *__restrict__ s_val,
+    const long long *__restrict__ s_id) {
+  __shared__ float av[FS_MAX_TOP], bv[FS_MAX_TOP];
+  __shared__ long long ai[FS_MAX_TOP], bi[FS_MAX_TOP];
+  const int lane = threadIdx.x;
+  for (int f = blockIdx.x; f < N; f += gridDim.x) {
+    if (lane == 0) {
+      count[f] += s_count[f];
+      act_max[f] = fmaxf(act_max[f], s_max[f]);
+      act_sum[f] += s_sum[f];
+    }
+    float *tv = top_val + (size_t)f * n;
+    long long *ti = top_id + (size_t)f * n;
+    const float *sv = s_val + (size_t)f * n;
+    const long long *si = s_id + (size_t)f * n;
+    int na = 0, nb = 0;
+    for (int j = lane; j < n; j += 64) {
+      av[j] = tv[j];
+      ai[j] = ti[j];
+      bv[j] = sv[j];
+      bi[j] = si[j];
+      na += ai[j] >= 0;
+      nb += bi[j] >= 0;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      na += __shfl_xor(na, off, 64);
+      nb += __shfl_xor(nb, off, 64);
+    }
+    __syncthreads();
+    if (nb) {
+      for (int j = lane; j < na; j += 64) {         // dst entries: after the src entries strictly before them
+        int lo = 0, hi = nb;
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if (fs_before(bv[mid], bi[mid], av[j], ai[j])) lo = mid + 1; else hi = mid;
+        }
+        if (j + lo < n) {
+          tv[j + lo] = av[j];
+          ti[j + lo] = ai[j];
+        }
+      }
+      for (int j = lane; j < nb; j += 64) {         // src entries: after the dst entries before or equal
+        int lo = 0, hi = na;
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if (fs_before(bv[j], bi[j], av[mid], ai[mid])) hi = mid; else lo = mid + 1;
+        }
+        if (j + lo < n) {
+          tv[j + lo] = bv[j];
+          ti[j + lo] = bi[j];
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
+int bit_width(unsigned long long v) { return v ? 64 - __builtin_clzll(v) : 0; }
+
+struct FsLayout {
+  size_t keys0, keys1, vals0, vals1, starts, ends, sort, total;
+};
+
+size_t fs_sort_bound(long M) { return (size_t)M * 8 + (1u << 20); }
+
+FsLayout fs_layout(long M, int N) {
+  FsLayout L;
+  size_t o = 0;
+  auto take = [&](size_t b) { size_t r = o; o = msae_align_up(o + b, 256); return r; };
+  L.keys0 = take((size_t)M * 8);
+  L.keys1 = take((size_t)M * 8);
+  L.vals0 = take((size_t)M * 4);
+  L.vals1 = take((size_t)M * 4);
+  L.starts = take((size_t)N * 4);
+  L.ends = take((size_t)N * 4);
+  L.sort = take(fs_sort_bound(M));
+  L.total = o;
+  return L;
+}
+
+bool fs_args_ok(int T, int k, int N, int n_top, int mode, int pool_len, int window) {
+  if (T < 0 || T > MSAE_STATS_MAX_T || k <= 0 || k > 256 || N <= 0 || N > 262144) return false;
+  if (n_top <= 0 || n_top > FS_MAX_TOP) return false;
+  if (mode == MSAE_POOL_IMAGE) return pool_len > 0 && pool_len <= 2880;
+  if (mode == MSAE_POOL_WINDOW) return window > 0 && window <= 4096;
+  return false;
+}
+
+}  // namespace
+
+extern "C" size_t msae_feature_stats_ws_bytes(int T, int k, int N) {
+  if (T < 0 || k <= 0 || N <= 0) return 0;
+  return fs_layout((long)T * k, N).total;
+}
+
+extern "C" int msae_feature_stats_update(const float *vals, const int32_t *idx, int B, int S, int k, float thresh,
+                                         int N, int mode, int pool_len, int window, int64_t row_base, int n_top,
+                                         uint64_t *count, float *act_max, double *act_sum, float *top_val,
+                                         int64_t *top_id, void *ws, size_t ws_bytes, void *stream) {
+  if (B < 0 || S < 0 || (B > 0 && S > MSAE_STATS_MAX_T / B)) return MSAE_EINVAL;
+  const int T = B * S;
+  if (!fs_args_ok(T, k, N, n_top, mode, pool_len, window) || row_base < 0) return MSAE_EINVAL;
+  if (T == 0) return 0;
+  const long M = (long)T * k;
+  const FsLayout L = fs_layout(M, N);
+  if (!ws || ws_bytes < L.total) return MSAE_EWS;
+  hipStream_t st = (hipStream_t)stream;
+  char *w = (char *)ws;
+  unsigned long long *k0 = (unsigned long long *)(w + L.keys0), *k1 = (unsigned long long *)(w + L.keys1);
+  float *v0 = (float *)(w + L.vals0), *v1 = (float *)(w + L.vals1);
+  int *starts = (int *)(w + L.starts), *ends = (int *)(w + L.ends);
+  FsGeom g;
+  g.S = S;
+  g.mode = mode;
+  g.P = pool_len;
+  g.W = window;
+  g.nw = mode == MSAE_POOL_WINDOW ? S / window : 1;
+  g.tb = bit_width((unsigned long long)(T - 1));
+  g.row_base = row_base;
+  const unsigned blocks = (unsigned)((M + 255) / 256);
+  hipLaunchKernelGGL(fs_keys_kernel, dim3(blocks), dim3(256), 0, st, vals, idx, M, k, thresh, N, g.tb, k0, v0);
+  MSAE_HIP_TRY(hipMemsetAsync(ends, 0, (size_t)N * 4, st));
+  rocprim::double_buffer<unsigned long long> kb(k0, k1);
+  rocprim::double_buffer<float> vb(v0, v1);
+  const unsigned end_bit = (unsigned)(g.tb + bit_width((unsigned long long)N));
+  size_t sort_bytes = 0;
+  MSAE_HIP_TRY(rocprim::radix_sort_pairs(nullptr, sort_bytes, kb, vb, (size_t)M, 0u, end_bit, st));
+  if (sort_bytes > fs_sort_bound(M)) return MSAE_EWS;
+  MSAE_HIP_TRY(rocprim::radix_sort_pairs((void *)(w + L.sort), sort_bytes, kb, vb, (size_t)M, 0u, end_bit, st));
+  // the group pass writes the candidates over the sort's other value buffer (dead after the sort)
+  float *cand = vb.current() == v0 ? v1 : v0;
+  hipLaunchKernelGGL(fs_group_kernel, dim3(blocks), dim3(256), 0, st, kb.current(), vb.current(), M, N, g, starts,
+                     ends, cand, (unsigned long long *)count, act_max, act_sum);
+  const unsigned mblocks = (unsigned)(N < 8192 ? N : 8192);
+  hipLaunchKernelGGL(fs_merge_kernel, dim3(mblocks), dim3(64), 0, st, kb.current(), cand, N, n_top, g, starts, ends,
+                     top_val, (long long *)top_id);
+  return msae_launch_status();
+}
+
+extern "C" int msae_feature_stats_merge(int N, int n_top, uint64_t *count, float *act_max, double *act_sum,
+                                        float *top_val, int64_t *top_id, const uint64_t *src_count,
+                                        const float *src_max, const double *src_sum, const float *src_val,
+                                        const int64_t *src_id, void *stream) {
+  if (N <= 0 || N > 262144 || n_top <= 0 || n_top > FS_MAX_TOP) return MSAE_EINVAL;
+  const unsigned blocks = (unsigned)(N < 8192 ? N : 8192);
+  hipLaunchKernelGGL(fs_merge_tables_kernel, dim3(blocks), dim3(64), 0, (hipStream_t)stream, N, n_top,
+                     (unsigned long long *)count, act_max, act_sum, top_val, (long long *)top_id,
+                     (const unsigned long long *)src_count, src_max, src_sum, src_val, (const long long *)src_id);
+  return msae_launch_status();
+}

@@ -35,6 +35,12 @@ class CacheConfig:
     """Verbosity level"""
     filters_path: Optional[str] = None
     """The json file for filtering the features and sae should be in a json file"""
+    feature_stats: bool = False
+    """Also write per-feature statistics and top-example tables (feature_stats.safetensors per module)"""
+    stats_top: int = 64
+    """Top examples kept per feature in the statistics (55..256)"""
+    example_ctx_len: int = 64
+    """Window length of the text statistics' max-pooled examples"""
 
     def to_dict(self):
         return dataclasses.asdict(self)

@@ -7,6 +7,12 @@ save_splits / concate_safetensors` methods, and byte-compatible output files
     <save_dir>/<module>/Rank{r}_{start}_{end}.safetensors      per rank   (cache.py:282-309)
     <save_dir>/<module>/{start}_{end}.safetensors              after rank-0 concat (cache.py:249-280)
 
+and, when the cache is built with `stats=` (opt-in; no reference counterpart), per-feature statistics and top-example
+tables (msae/features/stats.py) next to them:
+
+    <save_dir>/<module>/Rank{r}_feature_stats.safetensors      per rank
+    <save_dir>/<module>/feature_stats.safetensors              the ranks merged in rank order by the concat
+
 with keys `locations [nnz,3] int64 = (row, pos, feature)` and `activations [nnz] f32`, which is what
 `features/loader.py:143-196` (FeatureDataset) reads.
 
@@ -33,6 +39,7 @@ from torch import Tensor
 
 from .. import ops
 from ..sae import Sae
+from .stats import FeatureStats
 
 
 def generate_split_indices(width: int, n_splits: int):
@@ -46,12 +53,16 @@ class Cache:
     """Accumulates COO feature records per hooked module (cache.py:23-92)."""
 
     def __init__(self, shard_size: int, filters: Optional[Dict[str, Tensor]] = None,
-                 batch_size: int = 64, spill_dir: Optional[str] = None, device_budget_bytes: int = 256 << 20):
+                 batch_size: int = 64, spill_dir: Optional[str] = None, device_budget_bytes: int = 256 << 20,
+                 stats: Optional[dict] = None):
         """`spill_dir`: stream every batch's records to disk instead of holding the whole run in host
         RAM (the reference keeps everything in Python lists until save_splits, cache.py:56-57);
         `save()` reads them back in batch order, so the final tensors are identical.
         `device_budget_bytes`: records of the fused path wait on the device (worst-case sized buffers, 7 MB
-        per 8192-token batch at k = 32) and cross to the host in one transfer once this much is pending."""
+        per 8192-token batch at k = 32) and cross to the host in one transfer once this much is pending.
+        `stats`: keyword arguments of `FeatureStats` (pool, n_top, pool_len, window, thresh) -- one `FeatureStats` per
+        module is then updated in `add_topk` on the compute stream, over every feature (the filter is not applied);
+        None (default): nothing of it runs."""
         self.feature_locations = defaultdict(list)
         self.feature_activations = defaultdict(list)
         self.spill_dir = spill_dir
@@ -66,6 +77,8 @@ class Cache:
         # groups of batches on their way to the host: (copy-done event, device buffers kept alive, pinned staging, layout)
         self._inflight = []
         self._copy_stream = None
+        self.stats = None if stats is None else dict(stats)
+        self.feature_stats: Dict[str, FeatureStats] = {}
 
     def _bitmap(self, module_path: str, num_latents: int, device) -> Optional[Tensor]:
         if self.filters is None:
@@ -82,6 +95,11 @@ class Cache:
                  module_path: str):
         """Fused equivalent of scatter_ + Cache.add (cache.py:214-217, 42-57) for `[B,S,k]` pairs."""
         row_base = batch_number * self.batch_size + self.shard_size  # cache.py:55
+        if self.stats is not None:
+            st = self.feature_stats.get(module_path)
+            if st is None:
+                st = self.feature_stats[module_path] = FeatureStats(num_latents, device=top_acts.device, **self.stats)
+            st.update(top_acts, top_indices, row_base)
         loc, act, nnz = ops.sparsify(top_acts, top_indices, num_latents, row_base=row_base, thresh=1e-5,
                                      filter_bitmap=self._bitmap(module_path, num_latents, top_acts.device), sync=False)
         # stays on the device, stream-ordered (the reference does a nonzero() + two .cpu() per batch inside the
@@ -193,7 +211,7 @@ class Cache:
 
 class FeatureCache:
     def __init__(self, model, tokenizer, submodule_dict: Dict[str, Sae], batch_size: int,
-                 shard_size: int, filters: Optional[Dict[str, Tensor]] = None):
+                 shard_size: int, filters: Optional[Dict[str, Tensor]] = None, stats: Optional[dict] = None):
         # LlavaNextForConditionalGeneration wraps the language model (cache.py:104-109)
         if hasattr(model, "language_model") and hasattr(model, "vision_tower"):
             self.llava_model, self.model = model, model.language_model
@@ -206,7 +224,7 @@ class FeatureCache:
         self.batch_size = batch_size
         first = next(iter(submodule_dict.values()))
         self.width = first.cfg.num_latents or first.d_in * first.cfg.expansion_factor
-        self.cache = Cache(shard_size, filters, batch_size=batch_size)
+        self.cache = Cache(shard_size, filters, batch_size=batch_size, stats=stats)
         if filters is not None:
             self.filter_submodules(filters)
 
@@ -284,6 +302,10 @@ class FeatureCache:
                 mask = (feats >= start) & (feats < hi)
                 save_file({"locations": loc[mask].contiguous(), "activations": act[mask].contiguous()},
                           f"{module_dir}/Rank{rank}_{start}_{end}.safetensors")
+        for module_path, st in self.cache.feature_stats.items():
+            module_dir = f"{save_dir}/{module_path}"
+            os.makedirs(module_dir, exist_ok=True)
+            st.save(f"{module_dir}/Rank{rank}_feature_stats.safetensors")
 
     def concate_safetensors(self, n_splits: int, save_dir):
         for module_path in self.cache.feature_locations.keys():
@@ -300,6 +322,26 @@ class FeatureCache:
                     os.remove(os.path.join(module_dir, fname))
                 save_file({"locations": torch.cat(locs, dim=0), "activations": torch.cat(acts, dim=0)},
                           f"{module_dir}/{start}_{end}.safetensors")
+        for module_path, st in self.cache.feature_stats.items():
+            merge_rank_stats(f"{save_dir}/{module_path}", st.device)
+
+
+def merge_rank_stats(module_dir: str, device) -> Optional[str]:
+    """Merge `Rank{r}_feature_stats.safetensors` of `module_dir` in rank order (on `device`, a HIP device) into
+    `feature_stats.safetensors` and remove the rank files.  Returns the written path (None: no rank file)."""
+    pat = re.compile(r"^Rank(\d+)_feature_stats\.safetensors$")
+    parts = sorted((int(m.group(1)), f) for f in os.listdir(module_dir) if (m := pat.match(f)))
+    if not parts:
+        return None
+    total = None
+    for _, fname in parts:
+        st = FeatureStats.load(os.path.join(module_dir, fname), device=device)
+        total = st if total is None else total.merge(st)
+    out = os.path.join(module_dir, "feature_stats.safetensors")
+    total.save(out)
+    for _, fname in parts:
+        os.remove(os.path.join(module_dir, fname))
+    return out
 
 
 class FeatureImageCache(FeatureCache):
@@ -307,8 +349,8 @@ class FeatureImageCache(FeatureCache):
     BOS position dropped before the SAE."""
 
     def __init__(self, model, tokenizer, submodule_dict, batch_size: int, shard_size: int,
-                 filters=None, processor=None):
-        super().__init__(model, tokenizer, submodule_dict, batch_size, shard_size, filters)
+                 filters=None, processor=None, stats: Optional[dict] = None):
+        super().__init__(model, tokenizer, submodule_dict, batch_size, shard_size, filters, stats=stats)
         if processor is None:  # resolved lazily, not at import time as cache.py:321 does
             from transformers import LlavaNextProcessor
 

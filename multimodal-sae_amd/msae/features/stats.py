@@ -1,0 +1,164 @@
+"""Per-feature statistics and top-example tables, built while the cache runs.
+
+The reference's explain side re-derives two facts per feature from the COO split files after the cache is written:
+how often the feature fires (the loader's `min_examples` cut, sae_auto_interp/features/loader.py:103-106) and which
+rows activate it most (features/constructors.py:28-85 for text windows, 88-141 for images) -- the latter through a
+dense `[rows, seq]` tensor per feature on the CPU, so only behind a small filter.  `FeatureStats` answers both for
+every feature from the top-k pairs the cache loop already holds on the device (msae_feature_stats_update,
+include/msae.h): count / max / sum of the kept records, and the `n_top` largest nonzero pooled values per feature
+with their ids.
+
+    pool="image"   one segment per row: mean of the first `pool_len` positions; id = global row
+    pool="window"  windows of `window` positions: max; id = global row * (S // window) + w
+
+The keep rule is the cache's (|v| > thresh, default 1e-5), without the cache's feature filter.
+"""
+from __future__ import annotations
+
+import json
+from typing import Optional, Tuple
+
+import torch
+from safetensors import safe_open
+from safetensors.torch import save_file
+from torch import Tensor
+
+from .. import _hip, ops
+
+POOL_MODES = {"image": 0, "window": 1}
+MIN_TOP, MAX_TOP = 55, 256      # 55 = the README's --max_examples 5 + the image constructor's 50 spare ids
+
+
+@torch.library.custom_op("msae::feature_stats_update", mutates_args=("count", "act_max", "act_sum", "top_val",
+                                                                      "top_id"))
+def feature_stats_update(top_acts: Tensor, top_indices: Tensor, row_base: int, thresh: float, mode: int,
+                         pool_len: int, window: int, count: Tensor, act_max: Tensor, act_sum: Tensor, top_val: Tensor,
+                         top_id: Tensor) -> None:
+    """One batch of `[B, S, k]` top-k pairs into the statistics (in place, stream-ordered, no host read)."""
+    dev = _hip.require_device(top_acts, top_indices, count, act_max, act_sum, top_val, top_id)
+    lib = _hip.load()
+    assert top_acts.dim() == 3 and top_acts.shape == top_indices.shape
+    B, S, k = top_acts.shape
+    N, n = top_val.shape
+    vals, idx = ops._f32c(top_acts), ops._idx32(top_indices)
+    with torch.cuda.device(dev):
+        ws = ops._workspace(dev, lib.msae_feature_stats_ws_bytes(B * S, k, N))
+        _hip.check(lib.msae_feature_stats_update(
+            _hip.ptr(vals), _hip.ptr(idx), B, S, k, thresh, N, mode, pool_len, window, row_base, n,
+            _hip.ptr(count), _hip.ptr(act_max), _hip.ptr(act_sum), _hip.ptr(top_val), _hip.ptr(top_id),
+            _hip.ptr(ws), ws.numel(), _hip.stream_of(vals)), "msae_feature_stats_update")
+
+
+@feature_stats_update.register_fake
+def _(top_acts, top_indices, row_base, thresh, mode, pool_len, window, count, act_max, act_sum, top_val, top_id):
+    return None
+
+
+class FeatureStats:
+    """Statistics of `num_latents` features: count (int64), act_max (f32), act_sum (f64), and the sorted top-n tables
+    top_val [N, n] (f32) / top_id [N, n] (int64; -1 = free slot).  The tables live on `device`; `update` and `merge`
+    need a HIP device, reading a loaded file does not."""
+
+    def __init__(self, num_latents: int, n_top: int = 64, pool: str = "image", pool_len: int = 576, window: int = 64,
+                 thresh: float = 1e-5, device=None):
+        if pool not in POOL_MODES:
+            raise ValueError(f"pool must be one of {sorted(POOL_MODES)}, got {pool!r}")
+        if not MIN_TOP <= n_top <= MAX_TOP:
+            raise ValueError(f"n_top must lie in [{MIN_TOP}, {MAX_TOP}], got {n_top}")
+        if not 0 < num_latents <= 262144:
+            raise ValueError(f"num_latents must lie in [1, 262144], got {num_latents}")
+        if pool == "image" and not 0 < pool_len <= 2880:
+            raise ValueError(f"pool_len must lie in [1, 2880], got {pool_len}")
+        if pool == "window" and not 0 < window <= 4096:
+            raise ValueError(f"window must lie in [1, 4096], got {window}")
+        self.num_latents, self.n_top, self.pool = num_latents, n_top, pool
+        self.pool_len, self.window, self.thresh = pool_len, window, float(thresh)
+        self.tokens_seen = 0
+        self.windows_per_row: Optional[int] = None      # S // window of the rows seen (window mode)
+        dev = torch.device("cpu") if device is None else torch.device(device)
+        N = num_latents
+        self.count = torch.zeros(N, dtype=torch.int64, device=dev)
+        self.act_max = torch.full((N,), float("-inf"), dtype=torch.float32, device=dev)
+        self.act_sum = torch.zeros(N, dtype=torch.float64, device=dev)
+        self.top_val = torch.zeros(N, n_top, dtype=torch.float32, device=dev)
+        self.top_id = torch.full((N, n_top), -1, dtype=torch.int64, device=dev)
+
+    @property
+    def device(self) -> torch.device:
+        return self.count.device
+
+    def _same_kind(self, other: "FeatureStats") -> None:
+        mine = (self.num_latents, self.n_top, self.pool, self.pool_len if self.pool == "image" else self.window,
+                self.thresh)
+        theirs = (other.num_latents, other.n_top, other.pool, other.pool_len if other.pool == "image" else other.window,
+                  other.thresh)
+        if mine != theirs:
+            raise ValueError(f"cannot merge feature statistics of different kinds: {mine} vs {theirs}")
+
+    def update(self, top_acts: Tensor, top_indices: Tensor, row_base: int) -> None:
+        """Add one batch of `[B, S, k]` top-k pairs whose rows are `row_base + b` (complete rows only)."""
+        B, S, _ = top_acts.shape
+        if self.pool == "window":
+            nw = S // self.window
+            if self.windows_per_row is not None and self.windows_per_row != nw:
+                raise ValueError(f"rows of {S} positions give {nw} windows, earlier rows gave {self.windows_per_row}")
+            self.windows_per_row = nw
+        torch.ops.msae.feature_stats_update(top_acts, top_indices, int(row_base), self.thresh, POOL_MODES[self.pool],
+                                            self.pool_len, self.window, self.count, self.act_max, self.act_sum,
+                                            self.top_val, self.top_id)
+        self.tokens_seen += B * S
+
+    def merge(self, other: "FeatureStats") -> "FeatureStats":
+        """self += other (another rank's or module part's statistics of the same kind), on self's device."""
+        self._same_kind(other)
+        if (self.windows_per_row is not None and other.windows_per_row is not None
+                and self.windows_per_row != other.windows_per_row):
+            raise ValueError("cannot merge window statistics of different row lengths")
+        dev = _hip.require_device(self.count)
+        o = [t.to(dev).contiguous() for t in (other.count, other.act_max, other.act_sum, other.top_val, other.top_id)]
+        with torch.cuda.device(dev):
+            _hip.check(_hip.load().msae_feature_stats_merge(
+                self.num_latents, self.n_top, _hip.ptr(self.count), _hip.ptr(self.act_max), _hip.ptr(self.act_sum),
+                _hip.ptr(self.top_val), _hip.ptr(self.top_id), *[_hip.ptr(t) for t in o],
+                _hip.stream_of(self.count)), "msae_feature_stats_merge")
+        self.tokens_seen += other.tokens_seen
+        if self.windows_per_row is None:
+            self.windows_per_row = other.windows_per_row
+        return self
+
+    def density(self) -> Tensor:
+        """Fraction of the tokens seen on which each feature fired (f64)."""
+        return self.count.double() / max(self.tokens_seen, 1)
+
+    def top_examples(self, feature: int) -> Tuple[Tensor, Tensor]:
+        """(ids int64, pooled values f32) of the feature's top examples, best first (host tensors)."""
+        ids, vals = self.top_id[feature].cpu(), self.top_val[feature].cpu()
+        keep = ids >= 0
+        return ids[keep], vals[keep]
+
+    def metadata(self) -> dict:
+        return {"format": "msae.feature_stats.v1", "pool": self.pool, "pool_len": str(self.pool_len),
+                "window": str(self.window), "n_top": str(self.n_top), "thresh": repr(self.thresh),
+                "num_latents": str(self.num_latents), "tokens_seen": str(self.tokens_seen),
+                "windows_per_row": json.dumps(self.windows_per_row)}
+
+    def save(self, path: str) -> None:
+        tensors = {"count": self.count, "act_max": self.act_max, "act_sum": self.act_sum, "top_val": self.top_val,
+                   "top_id": self.top_id}
+        save_file({k: v.detach().contiguous().cpu() for k, v in tensors.items()}, path, metadata=self.metadata())
+
+    @classmethod
+    def load(cls, path: str, device=None) -> "FeatureStats":
+        with safe_open(path, framework="pt") as fh:
+            meta = fh.metadata() or {}
+            if meta.get("format") != "msae.feature_stats.v1":
+                raise ValueError(f"{path}: not a feature statistics file")
+            tensors = {k: fh.get_tensor(k) for k in fh.keys()}
+        st = cls(int(meta["num_latents"]), n_top=int(meta["n_top"]), pool=meta["pool"],
+                 pool_len=int(meta["pool_len"]), window=int(meta["window"]), thresh=float(meta["thresh"]),
+                 device="cpu")
+        for k, v in tensors.items():
+            setattr(st, k, v if device is None else v.to(device))
+        st.tokens_seen = int(meta["tokens_seen"])
+        st.windows_per_row = json.loads(meta["windows_per_row"])
+        return st

@@ -101,8 +101,9 @@ def main(cfg: CacheConfig):
         dataset = dataset.shard(world, rank, contiguous=True)       # contiguous chunks (cache.py:66)
         shard_size = sum(shard_offsets(len(dataset), model.device)[:rank])   # all_gather_into_tensor (cache.py:67-75)
     saes = load_saes(cfg.sae_path, filters=filters, device=model.device)
+    stats = dict(pool="window", window=cfg.example_ctx_len, n_top=cfg.stats_top) if cfg.feature_stats else None
     cache = FeatureCache(model, tokenizer, saes, batch_size=cfg.batch_size, shard_size=shard_size,
-                         filters=filters)
+                         filters=filters, stats=stats)
     if ddp:
         dist.barrier()
     cache.run(cfg.ctx_len, dataset)

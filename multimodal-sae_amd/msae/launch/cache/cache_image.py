@@ -26,8 +26,11 @@ def main(cfg: CacheConfig):
         dataset = dataset.shard(world, rank, contiguous=True)
         shard_size = sum(shard_offsets(len(dataset), model.device)[:rank])
     saes = load_saes(cfg.sae_path, filters=filters, device=model.device)
+    stats = None
+    if cfg.feature_stats:   # the image constructor pools the processor's first num_image_tokens positions
+        stats = dict(pool="image", pool_len=getattr(processor, "num_image_tokens", None) or 576, n_top=cfg.stats_top)
     cache = FeatureImageCache(model, tokenizer, saes, batch_size=cfg.batch_size, shard_size=shard_size,
-                              processor=processor, filters=filters)
+                              processor=processor, filters=filters, stats=stats)
     if ddp:
         dist.barrier()
     cache.run(cfg.ctx_len, dataset)

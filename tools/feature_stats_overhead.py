@@ -1,0 +1,87 @@
+"""What the per-feature statistics (FeatureStats, msae_feature_stats_update) add to the cache loop at C2 width
+(d = 4096, N = 131072): Sae.encode (fused) + Cache.add_topk with stats off and on, same batches, per-batch median of
+CUDA-event timings, and the statistics update alone.  Feature usage is Zipf-biased: the encoder's bias favours a few
+features, so hot features fire on most tokens.  Shapes: T = 8192 at k = 32 and 256 (window mode, W = 64, rows of
+256 tokens), T = 2880 in image mode (one row of 2880 tokens, P = 576).  Writes profiles/feature_stats_overhead.txt."""
+import statistics
+import sys
+from pathlib import Path
+
+import torch
+
+REPO = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(REPO)); sys.path.insert(0, str(REPO / "multimodal-sae_amd"))
+import bench  # noqa: E402
+from msae import ops  # noqa: E402
+from msae.features.cache import Cache  # noqa: E402
+from msae.features.stats import FeatureStats  # noqa: E402
+
+dev = torch.device("cuda:0")
+d, N, REPS = 4096, 131072, 24
+
+
+def timed(fn):
+    ts = []
+    for _ in range(REPS):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(); fn(); b.record(); b.synchronize()
+        ts.append(a.elapsed_time(b))
+    return statistics.median(ts)
+
+
+def shape(T, k, rows, pool, W_enc, b_enc, b_dec, prep, x):
+    S = T // rows
+    stats = dict(pool="window", window=64) if pool == "window" else dict(pool="image", pool_len=576)
+    v, i, _ = ops.encode_topk(x, W_enc, b_enc, b_dec, prep, k)
+    v, i = v.view(rows, S, k), i.view(rows, S, k)
+    hot = torch.bincount(i.reshape(-1), minlength=N).max().item()
+    res = {}
+    for on in (False, True):
+        cache = Cache(0, None, batch_size=rows, stats=stats if on else None)
+        n = [0]
+
+        def step():
+            vv, ii, _ = ops.encode_topk(x, W_enc, b_enc, b_dec, prep, k)
+            cache.add_topk(vv.view(rows, S, k), ii.view(rows, S, k), N, n[0], "layers.24")
+            n[0] += 1
+        for _ in range(3):
+            step()
+        res[on] = timed(step)
+        cache.flush_pending()
+    st = FeatureStats(N, device=dev, **stats)
+    base = [0]
+
+    def upd():
+        st.update(v, i, base[0]); base[0] += rows
+    upd()
+    alone = timed(upd)
+    over = (res[True] - res[False]) / res[False] * 100
+    return (f"T={T:5d} k={k:3d} {pool:6s} rows={rows:3d}x{S:4d}  hottest feature on {hot / T:6.1%} of tokens | "
+            f"loop stats off {res[False]:.3f} ms  on {res[True]:.3f} ms  (+{over:.1f} %) | update alone {alone:.3f} ms"), over
+
+
+def main():
+    torch.manual_seed(0)
+    lines = [__doc__.strip(), ""]
+    worst = 0.0
+    for T, k, rows, pool in ((8192, 32, 32, "window"), (8192, 256, 32, "window"), (2880, 32, 1, "image")):
+        W_enc, b_enc, W_dec, b_dec, x = bench.make_inputs(dev, T, d, N)
+        with torch.no_grad():   # Zipf-biased usage: bias rank r gets +c / r^0.5 on top of the weights' own spread
+            ranks = torch.randperm(N, device=dev).float() + 1
+            b_enc.add_(b_enc.abs().mean() * 8 / ranks.sqrt())
+        prep = ops.prepare_encoder(W_enc)
+        line, over = shape(T, k, rows, pool, W_enc, b_enc, b_dec, prep, x)
+        print(line, flush=True)
+        lines.append(line)
+        if T == 8192 and k == 32:
+            worst = over
+        del W_enc, W_dec, prep
+        torch.cuda.empty_cache()
+    verdict = "within" if worst <= 5 else "ABOVE"
+    lines += ["", f"target: <= 5 % at T = 8192, k = 32 -> measured +{worst:.1f} %: {verdict} the target"]
+    out = REPO / "profiles" / "feature_stats_overhead.txt"
+    out.write_text("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
