@@ -389,6 +389,33 @@ int msae_feature_stats_merge(int N, int n_top, uint64_t *count, float *act_max, 
                              int64_t *top_id, const uint64_t *src_count, const float *src_max,
                              const double *src_sum, const float *src_val, const int64_t *src_id, void *stream);
 
+/* ---- probe: segment-pooled feature ranking and activation maps (Sae.probe) ---------------------------------------
+ * Replaces the dense probe of tools/probe_activations.py:109-126 (latents = pre_acts(h); latents.mean(0).topk(k);
+ * latents[:, :, idx]) without materialising the [T][N] latents.  x[T][d] (element type x_dtype) as msae_pre_acts_f32;
+ * seg: int32 [S][2] device array of token ranges [start, end) over the T rows.  Segments are trusted but never fault: each
+ * is clamped to [0, T), an empty (or inverted) one pools to 0.  Neither call reads anything back to the host, allocates,
+ * or needs scratch.
+ * Numerics contract (v[t][f] = relu((x[t] - b_dec) W_enc[f]^T + b_enc[f]) as msae_pre_acts_f32 computes it, bit for bit):
+ *   MSAE_REDUCE_MEAN  out[s][f] = (float)(S_f / n): S_f the f64 sum of (double)v[t][f] over the segment's tokens, added one
+ *                     by one in ascending t from +0.0; n the segment length as a double.  Independent of the chunk plan, the
+ *                     tile packing and the other segments: a segment gives the same bits alone or in any batch.
+ *   MSAE_REDUCE_MAX   out[s][f] = max_t v[t][f], exact; 0 for an all-zero column.
+ *   ranking           msae_topk_f32 on out[S][N] (canonical: value desc, index asc).
+ *   maps              maps[t][j] = v[t][idx[s][j]] bit for bit for t in segment s; 0 for a t outside every segment and for
+ *                     an idx outside [0, N).  (Overlapping segments: a token of two takes either one's map.)
+ * msae_pooled_acts_f32: out[S][N].  chunks (optional, int32 [C][2] device array: segment ranges [first, last) in ascending
+ *   order, each a run of ADJACENT segments -- no token between them -- and every segment in exactly one; msae/sae/probe.py
+ *   plans them) groups short segments so that one workgroup walks them as packed 128-token tiles; NULL = one chunk per
+ *   segment (what device-side segments use).  A segment no chunk names pools to 0.
+ *   Envelope: any d, N (N % 128 != 0 included), S <= 65535 * 65535; reduce MSAE_REDUCE_MEAN or MSAE_REDUCE_MAX.
+ * msae_probe_maps_f32: maps[T][k], idx int32 [S][k] (the ranking's indices).  Envelope: 1 <= k <= MSAE_PROBE_MAX_K. */
+enum { MSAE_REDUCE_MEAN = 0, MSAE_REDUCE_MAX = 1, MSAE_PROBE_MAX_K = 256 };
+int msae_pooled_acts_f32(const void *x, int x_dtype, const float *W_enc, const float *b_enc, const float *b_dec, int T,
+                         int d, int N, const int32_t *seg, int S, const int32_t *chunks, int C, int reduce, float *out,
+                         void *stream);
+int msae_probe_maps_f32(const void *x, int x_dtype, const float *W_enc, const float *b_enc, const float *b_dec, int T,
+                        int d, int N, const int32_t *seg, int S, const int32_t *idx, int k, float *maps, void *stream);
+
 /* ---- merge of per-shard results (feature-sharded encode; no reference counterpart) ----
  * gathered: int32 [G][2][T][kl], the all-gather of each rank's packed block [2][T][kl]
  * (plane 0 = f32 activation bits, plane 1 = GLOBAL feature index).  Writes the canonical top-k of

@@ -86,6 +86,10 @@ PROTOTYPES = {
                                           c_size_t, c_void_p]),
     "msae_feature_stats_merge": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "msae_pooled_acts_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int,
+                                     c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "msae_probe_maps_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int,
+                                    c_void_p, c_int, c_void_p, c_void_p]),
     "msae_merge_topk": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "msae_compact_flags": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "msae_merge_topk_masked": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -8,6 +8,8 @@ These are the operators the drop-in ``Sae`` module (msae/sae/sae.py) and the fea
     msae::encode_topk   Sae.encode, fused (+ hook edits)     sae/sae.py:183-185, steering.py:113-114
     msae::decode        decoder_impl / TritonDecoder.apply   sae/utils.py:107-129, kernels.py:403-429
     msae::sparsify      scatter_ + Cache.get_nonzeros/add    features/cache.py:214-217,42-92
+    msae::pooled_acts   pre_acts(h).mean(0) per segment      tools/probe_activations.py:109-126
+    msae::probe_maps    latents[:, :, idx]                   tools/probe_activations.py:126
 
 All ops run on the tensor's device on the current stream, never synchronise (``sparsify`` reads one
 int64 back, as ``torch.nonzero`` does), and raise on CPU tensors.
@@ -380,6 +382,62 @@ def _topk_backward(ctx, g_vals, _g_idx):
 
 
 topk.register_autograd(_topk_backward, setup_context=_topk_setup)
+
+
+# ------------------------------------------------------------------------------------------------
+@torch.library.custom_op("msae::pooled_acts", mutates_args=())
+def pooled_acts(x: Tensor, W_enc: Tensor, b_enc: Optional[Tensor], b_dec: Optional[Tensor], segments: Tensor,
+                chunks: Optional[Tensor], reduce: int) -> Tensor:
+    """Per segment s (int32 [S, 2] device rows [start, end) over x's [T, d] rows): the mean (reduce 0) or max (1) over its
+    tokens of relu((x - b_dec) @ W_enc.T + b_enc) -> [S, N] f32, without the dense [T, N] latents.  `chunks`: int32 [C, 2]
+    device segment ranges of msae.sae.probe.plan_chunks, or None (one per segment).  include/msae.h: numerics contract."""
+    dev = _hip.require_device(x, W_enc, b_enc, b_dec, segments, chunks)
+    lib = _hip.load()
+    xa, W, be, bd = _act(x), _f32c(W_enc), _f32c(b_enc), _f32c(b_dec)
+    N, d = W.shape
+    assert xa.dim() == 2 and xa.shape[1] == d, f"x must be [T, {d}], got {tuple(xa.shape)}"
+    seg = segments.contiguous()
+    ch = None if chunks is None else chunks.contiguous()
+    S = seg.shape[0]
+    out = torch.empty(S, N, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.msae_pooled_acts_f32(_hip.ptr(xa), _hip.DTYPE_CODE[xa.dtype], _hip.ptr(W), _hip.ptr(be), _hip.ptr(bd),
+                                            xa.shape[0], d, N, _hip.ptr(seg), S, _hip.ptr(ch),
+                                            0 if ch is None else ch.shape[0], reduce, _hip.ptr(out), _hip.stream_of(xa)),
+                   "msae_pooled_acts_f32")
+    return out
+
+
+@pooled_acts.register_fake
+def _(x, W_enc, b_enc, b_dec, segments, chunks, reduce):
+    return x.new_empty(segments.shape[0], W_enc.shape[0], dtype=torch.float32)
+
+
+@torch.library.custom_op("msae::probe_maps", mutates_args=())
+def probe_maps(x: Tensor, W_enc: Tensor, b_enc: Optional[Tensor], b_dec: Optional[Tensor], segments: Tensor,
+               indices: Tensor) -> Tensor:
+    """maps[t, j] = relu((x[t] - b_dec) @ W_enc[indices[s, j]] + b_enc[...]) for the tokens t of segment s, 0 elsewhere ->
+    [T, k] f32, bit-identical to pre_acts(x)[t, indices[s, j]]."""
+    dev = _hip.require_device(x, W_enc, b_enc, b_dec, segments, indices)
+    lib = _hip.load()
+    xa, W, be, bd = _act(x), _f32c(W_enc), _f32c(b_enc), _f32c(b_dec)
+    N, d = W.shape
+    assert xa.dim() == 2 and xa.shape[1] == d, f"x must be [T, {d}], got {tuple(xa.shape)}"
+    seg = segments.contiguous()
+    idx = indices.to(torch.int32).contiguous()
+    S, k = idx.shape
+    assert seg.shape[0] == S, f"{seg.shape[0]} segments but {S} rows of indices"
+    maps = torch.empty(xa.shape[0], k, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.msae_probe_maps_f32(_hip.ptr(xa), _hip.DTYPE_CODE[xa.dtype], _hip.ptr(W), _hip.ptr(be), _hip.ptr(bd),
+                                           xa.shape[0], d, N, _hip.ptr(seg), S, _hip.ptr(idx), k, _hip.ptr(maps),
+                                           _hip.stream_of(xa)), "msae_probe_maps_f32")
+    return maps
+
+
+@probe_maps.register_fake
+def _(x, W_enc, b_enc, b_dec, segments, indices):
+    return x.new_empty(x.shape[0], indices.shape[1], dtype=torch.float32)
 
 
 def set_coarse_mode(mode: str) -> None:

@@ -1,4 +1,5 @@
 from .config import SaeConfig, TrainConfig
+from .probe import ProbeOutput
 from .sae import EncoderOutput, ForwardOutput, Sae
 
-__all__ = ["Sae", "SaeConfig", "TrainConfig", "EncoderOutput", "ForwardOutput"]
+__all__ = ["Sae", "SaeConfig", "TrainConfig", "EncoderOutput", "ForwardOutput", "ProbeOutput"]

@@ -10,6 +10,8 @@ unchanged.  What differs is underneath:
 * `select_topk`   -> torch.ops.msae.topk       (canonical order: value desc, index asc)
 * `encode`        -> torch.ops.msae.encode_topk (fused: the dense [T, N] latents never reach HBM)
 * `decode`        -> torch.ops.msae.decode     (coalesced gather-matmul over W_dec rows, autograd)
+* `probe`         -> torch.ops.msae.pooled_acts + topk + probe_maps (tools/probe_activations.py:109-126 without the
+                     dense latents: new)
 
 SAE math is f32 whatever dtype the LLM hands over, as in the reference (sae.py:140,174).
 There is no CPU implementation: calling a compute method with CPU tensors raises.
@@ -27,8 +29,10 @@ import torch
 from torch import Tensor, nn
 
 from .. import ops
+from . import probe as _probe
 from . import utils as _seam
 from .config import SaeConfig
+from .probe import ProbeOutput
 
 
 class EncoderOutput(NamedTuple):
@@ -250,6 +254,59 @@ class Sae(nn.Module):
         if impl is _seam.hip_decode:
             return ops.decode(top_indices, top_acts.to(self.dtype), self.W_dec, self.b_dec)
         return impl(top_indices, top_acts.to(self.dtype), self.W_dec.mT) + self.b_dec
+
+    # ---- probe (tools/probe_activations.py:109-126) ----------------------------------------------------
+    def _probe_inputs(self, x: Tensor, segments, what: str):
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise RuntimeError(f"Sae.{what} is an inference path: call it under torch.no_grad() or on a detached input "
+                               "(differentiate pre_acts for gradients)")
+        kind, seg = _probe.parse_segments(segments, x.shape)
+        flat = x.reshape(-1, x.shape[-1])
+        dev = self.encoder.weight.device
+        if kind == "device":
+            return flat, seg, None
+        chunks = _probe.plan_chunks(seg, self.num_latents, self._cu_count(dev))
+        # one pinned buffer, copied without a host synchronisation: the segments, then the chunk plan
+        host = torch.tensor(seg + chunks, dtype=torch.int32)
+        both = host.pin_memory().to(dev, non_blocking=True) if dev.type == "cuda" else host
+        return flat, both[:len(seg)], both[len(seg):]
+
+    @staticmethod
+    def _cu_count(dev: torch.device) -> int:
+        return torch.cuda.get_device_properties(dev).multi_processor_count if dev.type == "cuda" else 256
+
+    def pooled_acts(self, x: Tensor, segments=None, reduce: str = "mean") -> Tensor:
+        """[S, N] f32: the mean (or max) of `pre_acts(x)` over the tokens of each segment, without the dense [T, N] latents.
+        x: [T, d] or [B, L, d] in f32 / bf16 / f16.  segments: None (one per row of a [B, L, d] input, one over everything
+        for [T, d]), a host sequence of (start, end) pairs over the flattened tokens (validated: sorted, disjoint,
+        non-empty, inside [0, T)), or an int32 [S, 2] CUDA tensor (used as is: no host read; clamped to [0, T), an empty
+        segment pools to 0).  Bits: include/msae.h, "probe" -- mean = (float)(ascending-token f64 sum / length)."""
+        if reduce not in _probe.REDUCE:
+            raise ValueError(f"reduce must be one of {sorted(_probe.REDUCE)}, got {reduce!r}")
+        flat, seg, chunks = self._probe_inputs(x, segments, "pooled_acts")
+        with torch.no_grad():
+            return ops.pooled_acts(flat, self.encoder.weight, self.encoder.bias, self.b_dec, seg, chunks,
+                                   _probe.REDUCE[reduce])
+
+    def probe(self, x: Tensor, k: int, segments=None, reduce: str = "mean", maps: bool = True) -> ProbeOutput:
+        """Which features each segment of `x` activates, and where (tools/probe_activations.py:109-126: pre_acts ->
+        mean over the tokens -> topk -> the chosen features' activations per token), in one pooled GEMM, a top-k of the
+        [S, N] pooled rows and a small recompute of the T x k map values.  Returns ProbeOutput(values [S, k] f32,
+        indices [S, k] int64, maps [T, k] f32 or None); `segments` / `reduce` as in `pooled_acts`.  k <= min(N, 16384);
+        with maps, k <= 256.  Every value equals what pre_acts -> mean / max -> topk -> gather computes (include/msae.h)."""
+        if not 0 < k <= min(self.num_latents, 16384):
+            raise ValueError(f"k must be in [1, {min(self.num_latents, 16384)}], got {k}")
+        if maps and k > _probe.MAX_MAPS_K:
+            raise ValueError(f"maps=True supports k <= {_probe.MAX_MAPS_K}, got {k}: probe with maps=False, or fewer features")
+        if reduce not in _probe.REDUCE:
+            raise ValueError(f"reduce must be one of {sorted(_probe.REDUCE)}, got {reduce!r}")
+        flat, seg, chunks = self._probe_inputs(x, segments, "probe")
+        with torch.no_grad():
+            pooled = ops.pooled_acts(flat, self.encoder.weight, self.encoder.bias, self.b_dec, seg, chunks,
+                                     _probe.REDUCE[reduce])
+            values, indices = ops.topk(pooled, k)
+            m = ops.probe_maps(flat, self.encoder.weight, self.encoder.bias, self.b_dec, seg, indices) if maps else None
+        return ProbeOutput(values, indices, m)
 
     def forward(self, x: Tensor, dead_mask: Union[Tensor, None] = None) -> ForwardOutput:
         """Training forward (sae.py:193-247): reconstruction, FVU, AuxK and Multi-TopK terms, fully
