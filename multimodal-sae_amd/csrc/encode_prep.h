@@ -517,8 +517,11 @@ __global__ __launch_bounds__(256) void quant_x_kernel(const void *__restrict__ x
         int iv;
         if constexpr (SD) {
           const int hx = sd_hx(tb[e]), gw = sd_g(sd_hw(tb[e]));
-          // (an outlier dim: what its tile's entry rint(A / m) leaves -- the same float expression as below, so both agree)
-          const float rem = outl ? (coarse_out ? 0.f : sv - (float)m * rintf(v[e] * inv_o)) : sv;
+          // (an outlier dim: what its tile's entry hi = rint(A / m) leaves -- hi is the same float expression as below, so both
+          // agree.  The remainder is formed with ONE rounding, v - m hi scale in a fused multiply-add (m hi is an exact integer
+          // below 2^15), then scaled: evaluated as sv - m hi it would carry the rounding of sv at |A| up to 127 m, ~1e-3 step)
+          const float hi = rintf(v[e] * inv_o);
+          const float rem = outl ? (coarse_out ? 0.f : __builtin_fmaf(-(float)m * hi, scale, v[e]) * inv) : sv;
           iv = (outl && coarse_out) ? 0 : (int)floorf(rem + sd_r(hx));
           iv = iv > 127 ? 127 : (iv < -127 ? -127 : iv);
           e1 += gw * iv;

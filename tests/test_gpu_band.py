@@ -22,6 +22,7 @@ import pytest
 import torch
 
 import hostile
+from candidate_ref import _emulate, _header, _records, _view
 
 pytestmark = pytest.mark.gpu
 
@@ -31,65 +32,6 @@ def dev():
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
     return torch.device("cuda:0")
-
-
-def _header(prepared: torch.Tensor) -> dict:
-    """csrc/encode_defs.h struct Prepared, as prepare_impl copies it to the head of the buffer."""
-    raw = prepared[:256].cpu().numpy().tobytes()
-    u32 = np.frombuffer(raw, dtype=np.uint32)
-    u64 = np.frombuffer(raw, dtype=np.uint64)
-    names = ["off_wb", "off_ws", "off_wstat", "off_wstat_s", "off_colbf", "off_colbf_s", "off_wq", "off_wqs", "off_wqp",
-             "off_wqsp", "off_wqf", "off_wqsf", "bytes"]
-    h = {"magic": int(u32[0]), "N": int(u32[1]), "d": int(u32[2]), "S": int(u32[3]), "valid": int(u32[30])}
-    for i, n in enumerate(names):
-        h[n] = int(u64[2 + i])
-    h["dseed"], h["off_ds"], h["off_sdtab"] = int(u64[16]), int(u64[17]), int(u64[18])
-    return h
-
-
-def _view(prepared: torch.Tensor, off: int, nbytes: int, dtype) -> np.ndarray:
-    return np.frombuffer(prepared[off:off + nbytes].cpu().numpy().tobytes(), dtype=dtype)
-
-
-def _records(recs: torch.Tensor, C: int):
-    raw = recs.cpu().numpy()
-    T = raw.shape[0]
-    keys = np.frombuffer(raw[:, :8 * C].tobytes(), dtype=np.uint64).reshape(T, C)
-    zs = np.frombuffer(raw[:, 8 * C:12 * C].tobytes(), dtype=np.float32).reshape(T, C)
-    hi = (keys >> np.uint64(32)).astype(np.uint32)
-    bits = np.where(hi & np.uint32(0x80000000), hi & np.uint32(0x7FFFFFFF), ~hi).astype(np.uint32)
-    u = bits.view(np.float32)
-    feat = (0x7FFFFFFF - (keys & np.uint64(0xFFFFFFFF)).astype(np.int64)).astype(np.int64)
-    return keys != 0, u, feat, zs
-
-
-def _emulate(x: torch.Tensor, bd: torch.Tensor, tab: np.ndarray, F: int):
-    """quant_x_kernel<SD> restated: -> (a f32 [T, d], Aq int64 [T, d], sx f32 [T], m int [T], E int64 [T])."""
-    a = (x.float().cpu() - bd.cpu()).numpy().astype(np.float32)
-    T, d = a.shape
-    colmax = np.abs(a).max(axis=0)
-    thr = np.float32(8.0) * colmax.sum(dtype=np.float32) / np.float32(d)
-    out = colmax > thr
-    assert out.sum() <= 128
-    hx = (tab >> 16).astype(np.int64)
-    hw = (tab & 0xFFFF).astype(np.int64)
-    rx = ((2 * hx + 1).astype(np.float32) * np.float32(1.0 / 131072.0))
-    gw = 2 * hw + 1 - 65536
-    gx = 2 * hx + 1 - 65536
-    aa = np.abs(a)
-    m_in = np.where(out[None, :], 0, aa).max(axis=1)
-    m_out = np.where(out[None, :], aa, 0).max(axis=1) if out.any() else np.zeros(T, np.float32)
-    scale = np.where(m_in > 0, m_in / np.float32(127.0), np.where(m_out > 0, m_out / np.float32(127.0), np.float32(1.0))).astype(np.float32)
-    m = np.maximum(np.ceil(m_out / (np.float32(127.0) * scale)).astype(np.int64), 1)
-    inv = (np.float32(1.0) / scale).astype(np.float32)
-    inv_o = (np.float32(1.0) / (scale * m.astype(np.float32))).astype(np.float32)
-    sv = (a * inv[:, None]).astype(np.float32)
-    hi = np.where(out[None, :], np.rint((a * inv_o[:, None]).astype(np.float32)), 0).astype(np.float32)
-    rem = np.where(out[None, :], (sv - (m.astype(np.float32)[:, None] * hi).astype(np.float32)).astype(np.float32), sv)
-    q = np.clip(np.floor((rem + rx[None, :]).astype(np.float32)), -127, 127).astype(np.int64)
-    Aq = q + m[:, None] * hi.astype(np.int64)
-    E = np.rint((Aq @ gw).astype(np.float64) / 131072.0 - float(F) / 131072.0 ** 2).astype(np.int64)
-    return a, Aq, scale, m, E, gx, out
 
 
 @pytest.mark.parametrize("T,d", [(512, 512), (200, 1024)], ids=["mfma-tiles", "weight-stream"])
@@ -115,7 +57,7 @@ def test_subtractive_dither_band_is_the_elementwise_bound(dev, T, d):
     wstat = _view(prepared, h["off_wstat"], N * 16, np.float32).reshape(N, 4)
     ds = _view(prepared, h["off_ds"], N * 4, np.float32)
     sw = wstat[:, 0].astype(np.float64)
-    a, Aq, sx, m, E, gx, out = _emulate(x, bd, tab, F)
+    a, Aq, sx, m, E, gx, out = _emulate(x, bd, tab, F)     # (the outlier remainder restated exactly: candidate_ref.py)
     assert 1 <= out.sum() <= 4 and int(m.max()) <= 252 and int(m.max()) > 1
 
     # the weights' side of the tables: Wq = floor(W / sw + r_w) and Ds = sw D

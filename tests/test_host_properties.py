@@ -112,3 +112,42 @@ def test_subtractive_dither_identities_and_residual_distribution():
     assert 0.9 < ratio.std() < 1.1 and np.abs(ratio).max() < 5.0
     # non-subtractive stochastic rounding of the SAME adversarial token: variance 1/4 per element, three times as much
     assert abs((q[0] - A[0]).var() - 0.25) < 0.01
+
+
+def test_outlier_remainder_restatements():
+    """The remainder plane of quant_x_kernel<SD>: an outlier dim's A = v / scale is split into m hi (the outlier tile) and
+    lo = floor(A - m hi + r_x) in its own column.  Evaluated as (v * inv) - m hi in f32, A - m hi carries the rounding of
+    v * inv at |A| up to 127 m: about 1e-3 step, and floor() picks the wrong integer for a few 1e-4 of the elements.  With ONE
+    rounding, fmaf(-(m hi), scale, v) * inv, the error drops to ~1e-5 step and floor() agrees with the exact remainder except
+    right next to an integer (tests/candidate_ref.py accepts either neighbour there)."""
+    import numpy as np
+
+    import candidate_ref as cr
+
+    rng = np.random.default_rng(11)
+    n = 1_000_000
+    for lo, hi_, f32_flips in ((2, 127, (3e-5, 5e-4)), (128, 252, (1.5e-4, 8e-4))):
+        m = rng.integers(lo, hi_ + 1, n)
+        scale = (np.float32(2.0) ** rng.uniform(-12, 6, n)).astype(np.float32)
+        v = (rng.uniform(-127, 127, n) * m * scale).astype(np.float32)
+        inv_o = (np.float32(1.0) / (scale * m.astype(np.float32))).astype(np.float32)
+        h = np.rint((v * inv_o).astype(np.float32))
+        r = ((2 * rng.integers(0, 1 << 16, n) + 1) / 131072.0).astype(np.float32)
+        exact = cr.remainder_exact(v, scale, m, h)
+        assert np.abs(exact).max() <= m.max() / 2 + 1                # |lo| <= m / 2 + 1 <= 127: the column holds it
+        q_ex, amb = cr.floor_exact(exact, r)
+        assert 5e-5 < amb.mean() < 2e-4                             # 2 x 2^-14 of the elements sit in the undecidable band
+        old = cr.remainder_f32(v, scale, m, h)
+        q_old = np.floor((old + r).astype(np.float32)).astype(np.int64)
+        assert np.abs(old - exact).max() > 5e-4, "the f32 evaluation's error this test exists for"
+        assert f32_flips[0] < (q_old != q_ex).mean() < f32_flips[1]
+        new = cr.remainder_fma(v, scale, m, h)
+        q_new = np.floor((new + r).astype(np.float32)).astype(np.int64)
+        assert np.abs(new - exact).max() < 3e-5
+        assert not ((q_new != q_ex) & ~amb).any(), "one rounding: floor() agrees away from the boundary"
+        assert (q_new != q_ex).mean() < 1e-5
+    # the outlier set: 8 x the mean column max, the threshold raised by 1.5 until at most 128 dims qualify
+    a = rng.normal(0, 1, (64, 4096)).astype(np.float32)
+    a[3, :200] = np.float32(1e3) * (1 + np.arange(200, dtype=np.float32) / 100)
+    out = cr.outlier_dims(a)
+    assert out.sum() <= cr.MAX_OUT and out[:200].sum() == out.sum() and out[199]
