@@ -74,8 +74,9 @@ namespace {
 // ---- MFMA GEMM: gemm_mfma.h.  Tile choice from tools/gemm_sweep on MI355X (T=8192, d=4096,
 // N=131072): 256x256 tiles of 128-B k-rows, 2-slot ring, 8 waves as 2x4.
 using GemmBf16 = GemmCfg<256, 256, 2, 2, 4, false>;
-using GemmI8 = GemmCfg<256, 256, 2, 2, 4, true>;
-using GemmI8Cert = GemmCfg<256, 256, 2, 2, 4, true, 32>;   // msae_options::certified (encode_cert.h)
+constexpr int kGemmI8Shape = MSAE_GEMM_MF == 16 ? 128 : 0;  // GemmCfg bit 7: 16x16x64 int8 MFMAs (tuning.h)
+using GemmI8 = GemmCfg<256, 256, 2, 2, 4, true, kGemmI8Shape>;
+using GemmI8Cert = GemmCfg<256, 256, 2, 2, 4, true, 32 | kGemmI8Shape>;   // msae_options::certified (encode_cert.h)
 using GemmF8 = GemmCfg<256, 256, 2, 2, 4, false, 64>;      // MSAE_COARSE_FP8: e4m3 operands (BASELINE configs[4])
 constexpr int G_BM = GemmBf16::BM;
 

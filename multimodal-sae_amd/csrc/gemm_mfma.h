@@ -118,6 +118,7 @@ struct GemmOperands {
 //   bit 4 ABL_NOMFMA   issue no MFMA
 //   bit 5 CERT         the certified three-segment pass (encode_cert.h); I8 only
 //   bit 6 F8           fp8 (e4m3) operands, f32 accumulate (I8 = false)
+//   bit 7 MF16         int8 through v_mfma_i32_16x16x64_i8 instead of 32x32x32 (I8 only; tuning.h MSAE_GEMM_MF)
 template <int BM_, int BN_, int STAGES_, int WM_, int WN_, bool I8_ = false, int FLAGS_ = 0>
 struct GemmCfg {
   static constexpr int BM = BM_, BN = BN_, STAGES = STAGES_, WM = WM_, WN = WN_;
@@ -131,10 +132,25 @@ struct GemmCfg {
   static constexpr bool F8 = FLAGS_ & 64;
   static_assert(!(I8_ && (FLAGS_ & 64)), "fp8 accumulates in f32");
   static constexpr bool SCALED = I8_ || F8;       // value = acc * sx[t] * sw[n] + bias (else: acc + bias)
+  // The 16x16x64 int8 shape: the same MACs per cycle as 32x32x32, but under the package power cap it holds a higher clock on the
+  // product's operands (tools/mfma_rate.hip: 1.14x the sustained rate, profiles/gemm_mfma_shape.txt).  Tile, waves, ring, LDS
+  // image and staging are unchanged; a 16-VGPR accumulator block then holds four 16x16 blocks stacked in rows (64 x 16).
+  static constexpr bool MF16 = FLAGS_ & 128;
+  static_assert(!(FLAGS_ & 128) || I8_, "16x16x64 is an int8 shape");
+  static_assert(!(FLAGS_ & 128) || !(FLAGS_ & 28), "the ablation paths are written for 32x32 blocks");
+  static constexpr int BR = MF16 ? 64 : 32, BC = MF16 ? 16 : 32;   // rows x columns of one accumulator block (16 VGPRs)
   static constexpr int NWAVES = WM * WN, NT = NWAVES * 64;
-  static constexpr int TM = BM / WM, TN = BN / WN, MI = TM / 32, NI = TN / 32;
+  static constexpr int TM = BM / WM, TN = BN / WN, MI = TM / BR, NI = TN / BC;
+  static constexpr int FA = MF16 ? TM / 16 : MI, FB = MF16 ? TN / 16 : NI;   // A / B fragments of one k-step
   static constexpr int ROWB = 128;               // bytes per tile row: 64 bf16 or 128 int8
-  static constexpr int KS = 4;                   // MFMA k-steps per tile (32 B per lane-half each)
+  static constexpr int KS = MF16 ? 2 : 4;        // MFMA k-steps per tile (32 B per lane-half each; 16x16x64: 16 B per lane-quarter)
+  // row / column inside the wave tile of register e of accumulator block (i, j) in lane `lane`:
+  //   32x32: C[r][n] with n = lane & 31, r = (e & 3) + 8 (e >> 2) + 4 (lane >> 5)
+  //   16x16: register group e >> 2 is the 16x16 block of rows 16 (e >> 2) ..; in it n = lane & 15, r = (e & 3) + 4 (lane >> 4)
+  static __device__ __forceinline__ int acc_row(int i, int e, int lane) {
+    return i * BR + (MF16 ? 16 * (e >> 2) + 4 * (lane >> 4) + (e & 3) : (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5));
+  }
+  static __device__ __forceinline__ int acc_col(int j, int lane) { return j * BC + (lane & (BC - 1)); }
   static constexpr int A_BYTES = BM * ROWB, B_BYTES = BN * ROWB, STAGE_BYTES = A_BYTES + B_BYTES;
   static constexpr int LDS_RING_BYTES = STAGES * STAGE_BYTES;
   // behind the ring: side buffer of epilogue constants, then the THRESH epilogue's candidate queue.
@@ -151,7 +167,7 @@ struct GemmCfg {
   static constexpr int PIECES = STAGE_BYTES / 1024, PPW = PIECES / NWAVES;  // 1-KiB pieces per wave
   static constexpr int A_PIECES = A_BYTES / 1024;
   static_assert(PIECES % NWAVES == 0, "stage must split evenly over the waves");
-  static_assert(TM % 32 == 0 && TN % 32 == 0, "tile shape");
+  static_assert(TM % BR == 0 && TN % BC == 0 && TM % 32 == 0 && TN % 16 == 0, "tile shape");
   static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 };
 
@@ -276,9 +292,24 @@ __device__ __forceinline__ void wait_vmcnt() {
 }
 
 // one k-tile of MFMAs out of the LDS images sA / sB
+// 16x16x64 int8 on register group s (registers 4s .. 4s+3) of a 16-VGPR accumulator block
+__device__ __forceinline__ void gemm_mfma16(f32x16 &acc, int s, const i32x4 &a, const i32x4 &b) {
+  i32x16 v = __builtin_bit_cast(i32x16, acc);
+  i32x4 c = {v[4 * s], v[4 * s + 1], v[4 * s + 2], v[4 * s + 3]};
+  c = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, c, 0, 0, 0);
+  v[4 * s] = c[0]; v[4 * s + 1] = c[1]; v[4 * s + 2] = c[2]; v[4 * s + 3] = c[3];
+  acc = __builtin_bit_cast(f32x16, v);
+}
 template <class C>
-__device__ __forceinline__ void gemm_mfma_step(f32x16 (&acc)[C::MI][C::NI], const i32x4 (&a)[C::MI],
-                                               const i32x4 (&b)[C::NI]) {
+__device__ __forceinline__ void gemm_mfma_step(f32x16 (&acc)[C::MI][C::NI], const i32x4 (&a)[C::FA],
+                                               const i32x4 (&b)[C::FB]) {
+  if constexpr (C::MF16) {   // A fragment f = rows 16 f .. of the wave tile: block f / 4, register group f % 4
+#pragma unroll
+    for (int f = 0; f < C::FA; ++f)
+#pragma unroll
+      for (int j = 0; j < C::FB; ++j) gemm_mfma16(acc[f >> 2][j], f & 3, a[f], b[j]);
+    return;
+  }
   // (issue order: i outer -- consecutive MFMAs share the A fragment; j outer, four in a row on one B fragment, measured the same:
   // 3.84-3.86 vs 3.82-3.87 ms, NOTEBOOK.md)
 #pragma unroll
@@ -330,8 +361,8 @@ __device__ __forceinline__ void gemm_read_frags(i32x4 (&a)[C::MI], i32x4 (&b)[C:
 // that k-step (the next reads in flight across it).  The waves that issue the next k-tile's LDS-DMA inside the compute phase
 // instead of before their first MFMA do it at position MSAE_GEMM_STAGGER_AT (gemm_kernel: stagger)
 template <class C, class F>
-__device__ __forceinline__ void gemm_compute_asm(f32x16 (&acc)[C::MI][C::NI], const unsigned char *sA,
-                                                 int wr, int wc, int l31, int kh, F &&mid) {
+__device__ __forceinline__ void gemm_compute_asm32(f32x16 (&acc)[C::MI][C::NI], const unsigned char *sA,
+                                                   int wr, int wc, int l31, int kh, F &&mid) {
   static_assert(C::KS == 4, "four k-steps per tile");
   const unsigned base = (unsigned)(size_t)(const __attribute__((address_space(3))) unsigned char *)sA;
   const unsigned rowA = base + (unsigned)(wr * C::TM + l31) * 128u;
@@ -357,6 +388,94 @@ __device__ __forceinline__ void gemm_compute_asm(f32x16 (&acc)[C::MI][C::NI], co
   mid(2);
   lgkm_wait_tied<0, C>(a1, b1);
   gemm_mfma_step<C>(acc, a1, b1);
+}
+
+// ---- the same k-tile with 16x16x64 MFMAs (C::MF16) ----
+// A k-step (64 B of k) is 8 A and 4 B fragments of 16 rows (lane l: row l % 16, 16-B chunk 4 ks + l / 16 -- with the LDS image's
+// swizzle (r >> 1) & 7 every ds_read_b128 is conflict-free) and 32 MFMAs.  A whole k-step of fragments is 48 VGPRs, so the tile runs
+// in half-steps: A rows 0-63 (block 0) then 64-127 (block 1), each against the 4 B fragments held in registers, B-outer (one B
+// fragment across four consecutive MFMAs).  Three 16-VGPR groups: ga = A low half, gc = A high half, gb = B.  Each group is
+// refilled for the next k-step as soon as its last MFMA has issued: the A high half of k-step ks in front of half-step (ks, 0), the
+// A low half of ks + 1 in front of half-step (ks, 1), B of ks + 1 piecewise behind the four MFMAs of each B fragment in half-step
+// (ks, 1).  lgkmcnt counts the wave's outstanding LDS reads in issue order; the "+v" ties make each MFMA depend on the wait that
+// covers its operands.  They do not stop MFMAs from moving BELOW a later wait: the compiled order differs from the written one
+// (the waits of a half-step come ahead of its first MFMA, and the wait for the A high half of k-step 1 ahead of half-step (1, 0)),
+// so a read does not always have 16 MFMAs to land behind; the partner wave on the SIMD covers the rest.  Correctness does not
+// depend on the order.
+template <int N>
+__device__ __forceinline__ void lgkm_wait_tie4(i32x4 (&g)[4]) {
+  asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(g[0]), "+v"(g[1]), "+v"(g[2]), "+v"(g[3]) : "n"(N) : "memory");
+}
+template <int N>
+__device__ __forceinline__ void lgkm_wait_tie1(i32x4 &g) {
+  asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(g) : "n"(N) : "memory");
+}
+template <int IMM>
+__device__ __forceinline__ void gemm_read4(i32x4 (&g)[4], unsigned addr) {   // four fragments 16 rows (2 KiB) apart
+  g[0] = lds_read_b128<IMM + 0 * 2048>(addr); g[1] = lds_read_b128<IMM + 1 * 2048>(addr);
+  g[2] = lds_read_b128<IMM + 2 * 2048>(addr); g[3] = lds_read_b128<IMM + 3 * 2048>(addr);
+}
+// half-step on A block h (held in g) against the 4 B fragments; B fragment j is waited for right before its MFMAs
+template <class C>
+__device__ __forceinline__ void gemm_half_wait_b(f32x16 (&acc)[C::MI][C::NI], int h, i32x4 (&ga)[4], i32x4 (&gb)[4]) {
+  lgkm_wait_tie4<7>(ga);   // outstanding in issue order: ga, gb[0..3], the next A group (4)
+  lgkm_wait_tie1<7>(gb[0]);
+#pragma unroll
+  for (int s = 0; s < 4; ++s) gemm_mfma16(acc[h][0], s, ga[s], gb[0]);
+  lgkm_wait_tie1<6>(gb[1]);
+#pragma unroll
+  for (int s = 0; s < 4; ++s) gemm_mfma16(acc[h][1], s, ga[s], gb[1]);
+  lgkm_wait_tie1<5>(gb[2]);
+#pragma unroll
+  for (int s = 0; s < 4; ++s) gemm_mfma16(acc[h][2], s, ga[s], gb[2]);
+  lgkm_wait_tie1<4>(gb[3]);
+#pragma unroll
+  for (int s = 0; s < 4; ++s) gemm_mfma16(acc[h][3], s, ga[s], gb[3]);
+}
+template <class C, class F>
+__device__ __forceinline__ void gemm_compute_asm16(f32x16 (&acc)[C::MI][C::NI], const unsigned char *sA, int wr, int wc,
+                                                   int lane, F &&mid) {
+  static_assert(C::KS == 2 && C::MI == 2 && C::NI == 4 && C::FA == 8 && C::FB == 4, "written for a 128x64 wave tile");
+  const int l15 = lane & 15, kq = lane >> 4;
+  const unsigned base = (unsigned)(size_t)(const __attribute__((address_space(3))) unsigned char *)sA;
+  const unsigned rowA = base + (unsigned)(wr * C::TM + l15) * 128u;
+  const unsigned rowB = base + (unsigned)C::A_BYTES + (unsigned)(wc * C::TN + l15) * 128u;
+  const unsigned sw = (unsigned)gemm_swz(l15);       // same swizzle for every 16-row block of A and B
+  const unsigned off0 = ((unsigned)kq ^ sw) << 4, off1 = ((unsigned)(4 + kq) ^ sw) << 4;
+  const unsigned a0 = rowA + off0, b0 = rowB + off0, a1 = rowA + off1, b1 = rowB + off1;
+  i32x4 ga[4], gb[4], gc[4];
+  gemm_read4<0>(ga, a0);                             // A rows 0-63, k-step 0
+  gemm_read4<0>(gb, b0);                             // B, k-step 0
+  mid(-1);
+  gemm_read4<8192>(gc, a0);                          // A rows 64-127, k-step 0
+  gemm_half_wait_b<C>(acc, 0, ga, gb);
+  mid(0);
+  gemm_read4<0>(ga, a1);                             // A rows 0-63, k-step 1
+  lgkm_wait_tie4<4>(gc);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) gemm_mfma16(acc[1][j], s, gc[s], gb[j]);
+    if (j == 0) gb[0] = lds_read_b128<0 * 2048>(b1);   // B fragment j of k-step 1, once its last MFMA of k-step 0 has issued
+    if (j == 1) gb[1] = lds_read_b128<1 * 2048>(b1);
+    if (j == 2) gb[2] = lds_read_b128<2 * 2048>(b1);
+    if (j == 3) gb[3] = lds_read_b128<3 * 2048>(b1);
+  }
+  mid(1);
+  gemm_read4<8192>(gc, a1);                          // A rows 64-127, k-step 1
+  gemm_half_wait_b<C>(acc, 0, ga, gb);
+  mid(2);
+  lgkm_wait_tie4<0>(gc);
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int s = 0; s < 4; ++s) gemm_mfma16(acc[1][j], s, gc[s], gb[j]);
+}
+template <class C, class F>
+__device__ __forceinline__ void gemm_compute_asm(f32x16 (&acc)[C::MI][C::NI], const unsigned char *sA,
+                                                 int wr, int wc, int l31, int kh, F &&mid) {
+  if constexpr (C::MF16) gemm_compute_asm16<C>(acc, sA, wr, wc, l31 + 32 * kh, mid);
+  else gemm_compute_asm32<C>(acc, sA, wr, wc, l31, kh, mid);
 }
 template <class C>
 __device__ __forceinline__ void gemm_compute_asm(f32x16 (&acc)[C::MI][C::NI], const unsigned char *sA,
@@ -390,26 +509,50 @@ template <class C>
 __device__ __forceinline__ void gemm_compute_lead_compact(f32x16 (&acc)[C::MI][C::NI], const unsigned char *sA,
                                                           int wr, int wc, int l31, int kh) {
   const unsigned char *sB = sA + C::BM * 32;
-  i32x4 a[C::MI], b[C::NI];
+  if constexpr (C::MF16) {   // a fragment spans 64 B of k, the image 32: lanes 32-63 (chunks 2, 3) feed zeros
+    const int lane = l31 + 32 * kh, l15 = lane & 15, kq = lane >> 4;
+    i32x4 a[C::FA], b[C::FB];
 #pragma unroll
-  for (int i = 0; i < C::MI; ++i) a[i] = *reinterpret_cast<const i32x4 *>(sA + (wr * C::TM + i * 32 + l31) * 32 + kh * 16);
+    for (int f = 0; f < C::FA; ++f)
+      a[f] = kh ? i32x4{} : *reinterpret_cast<const i32x4 *>(sA + (wr * C::TM + f * 16 + l15) * 32 + kq * 16);
 #pragma unroll
-  for (int j = 0; j < C::NI; ++j) b[j] = *reinterpret_cast<const i32x4 *>(sB + (wc * C::TN + j * 32 + l31) * 32 + kh * 16);
-  gemm_mfma_step<C>(acc, a, b);
+    for (int j = 0; j < C::FB; ++j)
+      b[j] = kh ? i32x4{} : *reinterpret_cast<const i32x4 *>(sB + (wc * C::TN + j * 16 + l15) * 32 + kq * 16);
+    gemm_mfma_step<C>(acc, a, b);
+  } else {
+    i32x4 a[C::MI], b[C::NI];
+#pragma unroll
+    for (int i = 0; i < C::MI; ++i) a[i] = *reinterpret_cast<const i32x4 *>(sA + (wr * C::TM + i * 32 + l31) * 32 + kh * 16);
+#pragma unroll
+    for (int j = 0; j < C::NI; ++j) b[j] = *reinterpret_cast<const i32x4 *>(sB + (wc * C::TN + j * 32 + l31) * 32 + kh * 16);
+    gemm_mfma_step<C>(acc, a, b);
+  }
 }
 
 // the outlier k-tile: only its first `nks` k-steps hold data (32 outlier dims per k-step), the rest is zero
 template <class C>
 __device__ __forceinline__ void gemm_compute_lead(f32x16 (&acc)[C::MI][C::NI], const unsigned char *sA,
                                                   const unsigned char *sB, int wr, int wc, int l31, int kh, int nks) {
-  for (int ks = 0; ks < nks; ++ks) {
-    const int chunk = ks * 2 + kh;
-    i32x4 a[C::MI], b[C::NI];
+  if constexpr (C::MF16) {   // 64 outlier dims per k-step
+    const int lane = l31 + 32 * kh, l15 = lane & 15, kq = lane >> 4;
+    for (int ks = 0; ks < (nks + 1) >> 1; ++ks) {
+      i32x4 a[C::FA], b[C::FB];
 #pragma unroll
-    for (int i = 0; i < C::MI; ++i) a[i] = gemm_frag(sA, wr * C::TM + i * 32 + l31, chunk);
+      for (int f = 0; f < C::FA; ++f) a[f] = gemm_frag(sA, wr * C::TM + f * 16 + l15, 4 * ks + kq);
 #pragma unroll
-    for (int j = 0; j < C::NI; ++j) b[j] = gemm_frag(sB, wc * C::TN + j * 32 + l31, chunk);
-    gemm_mfma_step<C>(acc, a, b);
+      for (int j = 0; j < C::FB; ++j) b[j] = gemm_frag(sB, wc * C::TN + j * 16 + l15, 4 * ks + kq);
+      gemm_mfma_step<C>(acc, a, b);
+    }
+  } else {
+    for (int ks = 0; ks < nks; ++ks) {
+      const int chunk = ks * 2 + kh;
+      i32x4 a[C::MI], b[C::NI];
+#pragma unroll
+      for (int i = 0; i < C::MI; ++i) a[i] = gemm_frag(sA, wr * C::TM + i * 32 + l31, chunk);
+#pragma unroll
+      for (int j = 0; j < C::NI; ++j) b[j] = gemm_frag(sB, wc * C::TN + j * 32 + l31, chunk);
+      gemm_mfma_step<C>(acc, a, b);
+    }
   }
 }
 
@@ -494,7 +637,6 @@ template <class C, bool DENSE, class F>
 __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[C::MI][C::NI], const GemmEpilogue &ep, int T,
                                               int m0, int n0, int wr, int wc, int lane,
                                               unsigned char *smem, const float *side, F &&after_barrier, int tl_tile = 0) {
-  const int l31 = lane & 31, kh = lane >> 5;
   constexpr int QCAP = C::QCAP;
   unsigned *q_count = reinterpret_cast<unsigned *>(smem + C::LDS_RING_BYTES + C::SIDE_BYTES);
   unsigned long long *queue = reinterpret_cast<unsigned long long *>(smem + C::LDS_RING_BYTES + C::SIDE_BYTES + 16);
@@ -514,7 +656,7 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[C::MI][C::NI], const
   bool c_live[C::NI];
 #pragma unroll
   for (int j = 0; j < C::NI; ++j) {
-    const int col = wc * C::TN + j * 32 + l31;         // column inside the tile
+    const int col = wc * C::TN + C::acc_col(j, lane);  // column inside the tile
     c_bias[j] = col_c[col];
     c_sw[j] = col_c[C::NT + col];
     if constexpr (C::I8 && !C::CERT) c_ds[j] = -col_c[6 * C::NT + col];
@@ -522,7 +664,7 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[C::MI][C::NI], const
     const int feat = gemm_feature(ep, n0 + col);
     c_live[j] = (feat != ep.skip_a) && (feat != ep.skip_b);
   }
-  // C[i][n] of a 32x32 block: n = lane&31, i = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
+  // row / column of register e of block (i, j): GemmCfg::acc_row / acc_col
   if (msae_tuning::ABL_NOEPI && !DENSE && ep.cap != -12345) { asm volatile("" ::"v"(acc[0][0][0])); } else   // (tuning builds: skip the element loop)
   // THRESH.  One pass over the wave's MI x NI blocks without any LDS round trip: the value v replaces the accumulator in its register,
   // the sign of (v + h_n B_t) - tau goes through a 1-instruction shift register (v_alignbit) into a 16-bit hit mask per block.
@@ -530,12 +672,63 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[C::MI][C::NI], const
   // by a select tree on the hit's position).
   if constexpr (!DENSE) {
     unsigned hits[C::MI][C::NI];
+    if constexpr (C::MF16) {
+      // 16x16 blocks: a lane holds 4 column sets (NI = 4) instead of 2, so the 48 row constants of a whole block do not fit beside
+      // them.  The rows of register group g (e = 4g .. 4g+3) are the same in all four column blocks: hold 12 row constants at a
+      // time, with a scheduling fence per group so that the compiler does not hoist the next groups' LDS loads.
+#pragma unroll
+      for (int i = 0; i < C::MI; ++i) {
+        unsigned mj[C::NI];
+#pragma unroll
+        for (int j = 0; j < C::NI; ++j) mj[j] = 0u;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          __builtin_amdgcn_sched_barrier(0);
+          float tau[4], rs[4], bt[4];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int row = wr * C::TM + C::acc_row(i, 4 * g + r, lane);
+            tau[r] = row_c[row];
+            rs[r] = row_c[C::NT + row];
+            bt[r] = row_c[5 * C::NT + row];
+          }
+#pragma unroll
+          for (int j = 0; j < C::NI; ++j) {
+            unsigned m = mj[j];
+#pragma unroll
+            for (int r = 0; r < 4; r += 2) {
+              typedef float f32x2 __attribute__((ext_vector_type(2)));
+              const int e = 4 * g + r;
+              const f32x2 tau2 = {tau[r], tau[r + 1]}, rs2 = {rs[r], rs[r + 1]}, bt2 = {bt[r], bt[r + 1]};
+              const f32x2 a = {(float)__builtin_bit_cast(i32x16, acc[i][j])[e], (float)__builtin_bit_cast(i32x16, acc[i][j])[e + 1]};
+              f32x2 v;
+              if constexpr (!C::CERT) {   // as below
+                const f32x2 sw2 = {c_sw[j], c_sw[j]}, ds2 = {c_ds[j], c_ds[j]}, b2 = {c_bias[j], c_bias[j]};
+                v = __builtin_elementwise_fma(__builtin_elementwise_fma(a, sw2, ds2), rs2, b2);
+              } else {
+                v = a * (rs2 * c_sw[j]) + c_bias[j];
+              }
+              acc[i][j][e] = v.x;
+              acc[i][j][e + 1] = v.y;
+              const f32x2 ch2 = {c_h[j], c_h[j]};
+              const f32x2 dlt = __builtin_elementwise_fma(ch2, bt2, v) - tau2;
+              m = __builtin_amdgcn_alignbit(m, __float_as_uint(dlt.x), 31);
+              m = __builtin_amdgcn_alignbit(m, __float_as_uint(dlt.y), 31);
+            }
+            mj[j] = m;
+          }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < C::NI; ++j) hits[i][j] = c_live[j] ? (~mj[j] & 0xFFFFu) : 0u;   // bit 15 - e: output e is a hit
+      }
+    } else
 #pragma unroll
     for (int i = 0; i < C::MI; ++i) {
       float tau[16], rs[16], bt[16];
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int row = wr * C::TM + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * kh;
+        const int row = wr * C::TM + C::acc_row(i, e, lane);
         tau[e] = row_c[row];
         rs[e] = C::SCALED ? row_c[C::NT + row] : 0.f;
         bt[e] = row_c[5 * C::NT + row];
@@ -588,7 +781,7 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[C::MI][C::NI], const
 #pragma unroll
         for (int j = 0; j < C::NI; ++j) {
           unsigned h = hits[i][j];
-          const int col = wc * C::TN + j * 32 + l31;
+          const int col = wc * C::TN + C::acc_col(j, lane);
           while (h) {
             const int p = 31 - __builtin_clz(h);                                // highest set bit first = lowest e first
             h &= ~(1u << p);
@@ -604,7 +797,7 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[C::MI][C::NI], const
 #pragma unroll
             for (int q = 0; q < 2; ++q) s2[q] = sel(b2, s4[2 * q + 1], s4[2 * q]);
             const float v = __uint_as_float(sel(b3, s2[1], s2[0]));
-            const int row = wr * C::TM + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * kh;
+            const int row = wr * C::TM + C::acc_row(i, e, lane);
             if (slot < QCAP) {
               queue[slot] = ((unsigned long long)__float_as_uint(v) << 32) | (unsigned)(row << 16 | col);
             } else {                                                            // queue full: slow path
@@ -621,15 +814,15 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[C::MI][C::NI], const
       }
     }
   } else {
-    // DENSE: every value + its band, C[i][n] of a 32x32 block: n = lane&31, i = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
+    // DENSE: every value + its band (32x32 blocks: 128-B runs per 32 lanes; 16x16: 64-B runs per 16 lanes)
 #pragma unroll
     for (int i = 0; i < C::MI; ++i) {
 #pragma unroll
       for (int j = 0; j < C::NI; ++j) {
-        const int col = wc * C::TN + j * 32 + l31;
+        const int col = wc * C::TN + C::acc_col(j, lane);
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-          const int row = wr * C::TM + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * kh, t = m0 + row;
+          const int row = wr * C::TM + C::acc_row(i, e, lane), t = m0 + row;
           float v;
           if constexpr (C::I8 && !C::CERT)
             v = __builtin_fmaf(__builtin_fmaf((float)__builtin_bit_cast(i32x16, acc[i][j])[e], c_sw[j], c_ds[j]), row_c[C::NT + row], c_bias[j]);
@@ -866,7 +1059,7 @@ __global__ __launch_bounds__(C::NT) void gemm_kernel(GemmOperands op, int T, int
     for (int i = 0; i < C::MI; ++i)
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int row = wr * C::TM + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * kh;
+        const int row = wr * C::TM + C::acc_row(i, e, tid_ & 63);
         const int m = side_m[row];
         int ee = 0;
         if constexpr (C::I8 && !C::CERT) ee = side_e[row];     // -E (0 without the subtractive dither): one v_mad_i32_i24 per accumulator either way

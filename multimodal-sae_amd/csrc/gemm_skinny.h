@@ -24,6 +24,10 @@ struct SkinnyCfg {
   // 150 us pass.
   static constexpr int BM = BM_, NWAVES = NW_, BN = 32 * NW_, WM = 1, WN = NW_, NT = 64 * NW_;
   static constexpr int TM = BM, TN = 32, MI = BM / 32, NI = 1;
+  // 32x32 accumulator blocks: gemm_mfma.h's shared epilogue reads MF16 (its THRESH loop) and acc_row / acc_col
+  static constexpr bool MF16 = false;
+  static __device__ __forceinline__ int acc_row(int i, int e, int lane) { return i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5); }
+  static __device__ __forceinline__ int acc_col(int j, int lane) { return j * 32 + (lane & 31); }
   static constexpr bool I8 = true, F8 = false, CERT = false, SCALED = true;   // (gemm_mfma.h's epilogue reads these)
   static constexpr int KC = (NW_ == 4 ? 32768 : 65536) / BM;   // bytes of k per A chunk
   // ADMA (the 256-token tile): the token rows travel L2 -> LDS by LDS-DMA (global_load_lds, as gemm_mfma.h's operands) instead of

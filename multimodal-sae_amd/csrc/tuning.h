@@ -18,6 +18,10 @@
 #define MSAE_GEMM_GM 8         // x GN column tiles, GM * GN = 32.  8 x 4 fetches 12 operand blocks per k-step for 32 tiles; 4 x 8 the same with the
 #define MSAE_GEMM_GN 4         // roles swapped, 16 x 2 / 2 x 16 fetch 18 (profiles/r05_ab_supertile.txt)
 #endif
+#ifndef MSAE_GEMM_MF           // int8 candidate GEMM (GemmI8, GemmI8Cert): MFMA shape, 16 = v_mfma_i32_16x16x64_i8, 32 = v_mfma_i32_32x32x32_i8.
+#define MSAE_GEMM_MF 16        // Equal MACs per cycle; 16x16x64 holds a higher clock under the power cap (profiles/gemm_mfma_shape.txt)
+#endif
+static_assert(MSAE_GEMM_MF == 16 || MSAE_GEMM_MF == 32, "MSAE_GEMM_MF: 16 or 32");
 #ifndef MSAE_SK_UN             // weight-stream kernel: 64-B k-steps per B batch at 64 tokens (halved per doubling of the tile)
 #define MSAE_SK_UN 4
 #endif

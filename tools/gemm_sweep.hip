@@ -114,6 +114,7 @@ int main(int argc, char **argv) {
     if (which < 0 || which == 4) RUN(256, 256, 2, 2, 4, true, 4);       // no staging (MFMA + reads + barriers)
     if (which == 5) RUN(256, 256, 2, 2, 4, true, 8);                    // no fragment reads (staging + MFMA on constant registers)
     if (which == 6) RUN(256, 256, 2, 2, 4, true, 16);                   // no MFMA (staging + fragment reads)
+    if (which == 7) RUN(256, 256, 2, 2, 4, true, 128);                  // int8 on 16x16x64 MFMAs (GemmCfg bit 7, MSAE_GEMM_MF = 16)
   }
   return 0;
 }

@@ -1,25 +1,51 @@
 // mfma_rate.hip -- probe (not part of the product): sustained matrix rate of one MFMA flavour with every SIMD busy and nothing
 // else in the loop (8 independent accumulators per wave, 2 waves per SIMD), i.e. the rate the package power cap allows.
 // int8 32x32x32 against the f8f6f4 32x32x64 instruction with fp8 / fp6 / fp4 operands (would an MXFP6
-// candidate pass really run twice as fast as the int8 one?).
+// candidate pass really run twice as fast as the int8 one?), and int8 32x32x32 against int8 16x16x64 (same cycles per MAC:
+// does the smaller shape hold a higher clock under the power cap on the product's operands?  DESIGN.md section 8 (2)).
 //   hipcc --offload-arch=gfx950 -O3 tools/mfma_rate.hip -o tools/bin/mfma_rate && tools/bin/mfma_rate
+//   MFMA_RATE_ONLY=i8_32 | i8_16: one flavour alone (MFMA_RATE_REPS launches back to back), for power sampling per flavour
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
+#include <cstring>
+#include <vector>
+#include <algorithm>
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at %s:%d\n", hipGetErrorString(e), __FILE__, __LINE__); exit(1); } } while (0)
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 typedef int i32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-template <int FMT>   // -1: int8 32x32x32;  0 fp8 (e4m3), 2 fp6 (e2m3), 4 fp4 (e2m1) through v_mfma_scale_f32_32x32x64_f8f6f4
+template <int FMT>   // -1: int8 32x32x32;  -2: int8 16x16x64;  0 fp8 (e4m3), 2 fp6 (e2m3), 4 fp4 (e2m1) through v_mfma_scale_f32_32x32x64_f8f6f4
 __global__ __launch_bounds__(512) void rate_kernel(const int *__restrict__ src, float *__restrict__ out, int iters, int rot) {
   const int tid = blockIdx.x * 512 + threadIdx.x;
   i32x8 a, b;
 #pragma unroll
   for (int i = 0; i < 8; ++i) { a[i] = src[(tid * 8 + i) & 0xFFFF]; b[i] = src[(tid * 8 + i + 4096) & 0xFFFF]; }
-  if constexpr (FMT < 0) {
+  if constexpr (FMT == -2) {
+    // same MACs per iteration as the 32x32x32 loop: 16 MFMAs of half the MACs, 16 independent accumulators (64 VGPRs), the
+    // same four operand register sets rotated over consecutive MFMAs
+    i32x4 acc[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) acc[j] = i32x4{};
+    i32x4 a4[4], b4[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int o = rot ? q : 0;
+      a4[q] = i32x4{a[o & 7], a[(o + 1) & 7], a[(o + 2) & 7], a[(o + 3) & 7]};
+      b4[q] = i32x4{b[(o + 4) & 7], b[(o + 5) & 7], b[(o + 6) & 7], b[(o + 7) & 7]};
+    }
+    for (int it = 0; it < iters; ++it) {
+#pragma unroll
+      for (int j = 0; j < 16; ++j) acc[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a4[j & 3], b4[j & 3], acc[j], 0, 0, 0);
+    }
+    int s = 0;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) s += acc[j][0] + acc[j][3];
+    out[tid] = (float)s;
+  } else if constexpr (FMT < 0) {
     i32x16 acc[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[j] = i32x16{};
@@ -66,17 +92,31 @@ __global__ __launch_bounds__(512) void rate_kernel(const int *__restrict__ src, 
 template <int FMT>
 void run(const char *name, const int *src, float *out, double ops_per_mfma) {
   const int grid = 256, iters = 20000;    // one 8-wave workgroup per CU: 2 waves per SIMD
-  hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
-  float best = 1e30f;
   const int reps = getenv("MFMA_RATE_REPS") ? atoi(getenv("MFMA_RATE_REPS")) : 4;   // many: long enough for the SMU's power average
+  const int vary = getenv("MFMA_RATE_VARY") ? 1 : 0;
+  // one event between consecutive launches and no host sync until the end: the launches run back to back
+  std::vector<hipEvent_t> ev(reps + 1);
+  for (auto &h : ev) CK(hipEventCreate(&h));
+  CK(hipEventRecord(ev[0], 0));
   for (int rep = 0; rep < reps; ++rep) {
-    CK(hipEventRecord(e0, 0));
-    rate_kernel<FMT><<<grid, 512>>>(src, out, iters, getenv("MFMA_RATE_VARY") ? 1 : 0);
-    CK(hipEventRecord(e1, 0)); CK(hipEventSynchronize(e1));
-    float ms; CK(hipEventElapsedTime(&ms, e0, e1)); if (rep && ms < best) best = ms;
+    rate_kernel<FMT><<<grid, 512>>>(src, out, iters, vary);
+    CK(hipEventRecord(ev[rep + 1], 0));
   }
-  const double ops = (double)grid * 8 * iters * 8 * ops_per_mfma;
-  printf("%-34s %8.3f ms  %6.2f P(FL)OP/s\n", name, best, ops / (best * 1e-3) / 1e15);
+  CK(hipEventSynchronize(ev[reps]));
+  std::vector<float> ms(reps);
+  for (int rep = 0; rep < reps; ++rep) CK(hipEventElapsedTime(&ms[rep], ev[rep], ev[rep + 1]));
+  float total = 0.f, tail = 0.f;
+  for (int rep = 0; rep < reps; ++rep) { total += ms[rep]; if (rep >= reps / 2) tail += ms[rep]; }
+  tail /= (float)(reps - reps / 2);                                          // mean of the second half: the sustained rate
+  std::sort(ms.begin() + (reps > 1), ms.end());
+  const float best = ms[reps > 1];                                           // best, the first (cold) launch excluded
+  const double ops = (double)grid * 8 * iters * (FMT == -2 ? 16 : 8) * ops_per_mfma;
+  printf("%-34s %8.3f ms  %6.2f P(FL)OP/s", name, best, ops / (best * 1e-3) / 1e15);
+  if (reps >= 8)
+    printf("   sustained (2nd half of %d launches, %.2f s): %8.3f ms  %6.2f P(FL)OP/s", reps, total * 1e-3f, tail,
+           ops / (tail * 1e-3) / 1e15);
+  printf("\n");
+  for (auto &h : ev) CK(hipEventDestroy(h));
 }
 
 int main() {
@@ -118,8 +158,15 @@ int main() {
   if (gs) printf("operands: Gaussian, %s\n", gs[0] == 'i' ? "int8 round(N(0, 32))" : "e4m3 of N(0, 1) * 112");
   else if (sg) printf("operands: random signs, %s\n", sg[0] == 'i' ? "two's complement" : "sign bit");
   float *out; CK(hipMalloc(&out, 256 * 512 * 4));
+  if (const char *only = getenv("MFMA_RATE_ONLY")) {
+    if (!strcmp(only, "i8_32")) run<-1>("int8 32x32x32", src, out, 2.0 * 32 * 32 * 32);
+    else if (!strcmp(only, "i8_16")) run<-2>("int8 16x16x64", src, out, 2.0 * 16 * 16 * 64);
+    else { printf("MFMA_RATE_ONLY: i8_32 or i8_16\n"); return 1; }
+    return 0;
+  }
   if (getenv("MFMA_RATE_ONLY_FP8")) { run<0>("f8f6f4 32x32x64, fp8 e4m3", src, out, 2.0 * 32 * 32 * 64); return 0; }
   run<-1>("int8 32x32x32", src, out, 2.0 * 32 * 32 * 32);
+  run<-2>("int8 16x16x64", src, out, 2.0 * 16 * 16 * 64);
   if (getenv("MFMA_RATE_ONLY_I8")) return 0;
   run<0>("f8f6f4 32x32x64, fp8 e4m3", src, out, 2.0 * 32 * 32 * 64);
   run<2>("f8f6f4 32x32x64, fp6 e2m3", src, out, 2.0 * 32 * 32 * 64);
