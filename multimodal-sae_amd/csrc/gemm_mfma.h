@@ -1,7 +1,8 @@
 // gemm_mfma.h -- candidate-pass GEMM  C[T][N] = A[T][K] * B[N][K]^T  on the gfx950 matrix cores, with
 // the SAE epilogues.  Two operand types share one tile / pipeline structure:
 //   bf16 : v_mfma_f32_32x32x16_bf16, f32 accumulate          (2.5 PFLOP/s dense peak)
-//   int8 : v_mfma_i32_32x32x32_i8,  i32 accumulate, per-token x per-feature scales applied in the
+//   int8 : v_mfma_i32_16x16x64_i8 (the default; v_mfma_i32_32x32x32_i8 behind MSAE_GEMM_MF=32, tuning.h),
+//          i32 accumulate, per-token x per-feature scales applied in the
 //          epilogue; a leading "outlier" k-tile carries the few massive activation dims at a
 //          coarser per-token scale (acc *= m[t] after it)   (~2x the bf16 rate, half the bytes)
 // This is the dominant kernel of the fused encoder (encode_fused.hip): 2*d*N FLOP per token.  Both
@@ -9,7 +10,8 @@
 //
 // Structure (template parameters BM, BN, STAGES, WM, WN; a k-tile is always 128 B per row):
 //   * a workgroup of WM x WN waves computes a BM x BN tile; each wave owns (BM/WM) x (BN/WN) as
-//     MI x NI blocks of 32x32 (16 accumulator VGPRs each);
+//     MI x NI accumulator blocks of 16 VGPRs each: one 32x32 MFMA result, or (int8 16x16x64) four 16x16
+//     results stacked in rows, 64 x 16 (GemmEpiCfg);
 //   * operand tiles travel L2 -> LDS by global_load_lds (16 B per lane, 1 KiB per wave instruction,
 //     no VGPR round trip) into a ring of STAGES slots; counted s_waitcnt vmcnt + ONE raw s_barrier
 //     per k-tile, so loads stay in flight across barriers;
@@ -18,8 +20,9 @@
 //     (SQ_LDS_BANK_CONFLICT = 0 measured).  global_load_lds writes lane-linear, so the permutation
 //     is applied to the per-lane SOURCE address and again on the read;
 //   * the fragment reads of a k-tile are inline-asm ds_read_b128 with COUNTED lgkmcnt waits (the
-//     compiler waits lgkmcnt(0) after every group of reads): the 6 reads of k-step ks+1 are in
-//     flight while the 8 MFMAs of ks execute (-5 % on the int8 pass);
+//     compiler waits lgkmcnt(0) after every group of reads): the reads of the next (half) k-step are in
+//     flight while the MFMAs of this one execute -- 32x32: 6 reads behind 8 MFMAs, 16x16x64: 4-fragment
+//     groups behind 16 (-5 % on the int8 pass; gemm_compute_asm32 / gemm_compute_asm16);
 //   * workgroups are persistent (one per CU) and walk their tiles as one flat k-sequence: the last
 //     k-iteration of a tile already stages the first k-tile of the next one;
 //   * tile -> workgroup map is XCD-aware: the 32 workgroups resident on one XCD's 32 CUs form an
@@ -111,39 +114,18 @@ struct GemmOperands {
   int cert;
 };
 
-// FLAGS:
-//   (tuning only; results invalid when an ABL bit is set)
-//   bit 2 ABL_NOSTAGE  skip the LDS-DMA staging in the loop
-//   bit 3 ABL_NOREAD   read the fragments once and reuse them
-//   bit 4 ABL_NOMFMA   issue no MFMA
-//   bit 5 CERT         the certified three-segment pass (encode_cert.h); I8 only
-//   bit 6 F8           fp8 (e4m3) operands, f32 accumulate (I8 = false)
-//   bit 7 MF16         int8 through v_mfma_i32_16x16x64_i8 instead of 32x32x32 (I8 only; tuning.h MSAE_GEMM_MF)
-template <int BM_, int BN_, int STAGES_, int WM_, int WN_, bool I8_ = false, int FLAGS_ = 0>
-struct GemmCfg {
-  static constexpr int BM = BM_, BN = BN_, STAGES = STAGES_, WM = WM_, WN = WN_;
-  static constexpr bool I8 = I8_;
-  static constexpr bool ABL_NOSTAGE = FLAGS_ & 4, ABL_NOREAD = FLAGS_ & 8, ABL_NOMFMA = FLAGS_ & 16;
-  static constexpr bool CERT = FLAGS_ & 32;       // certified pass (GemmOperands::cert): its own instantiation, the product kernel is untouched
-  // fp8 candidate pass (BASELINE configs[4]: "fp8 MFMA encoder path"): one byte per operand element exactly like int8 -- the SAME
-  // tile-major operands, LDS image, ring and hand-scheduled fragment reads -- multiplied by v_mfma_f32_32x32x16_fp8_fp8 (two per
-  // 16-byte fragment pair: the low and the high 8 bytes of the lanes) into f32 accumulators; per-token / per-feature scales in
-  // the epilogue as on the int8 path, the error band of the bf16 path's form (relative roundings).  I8_ must be false.
-  static constexpr bool F8 = FLAGS_ & 64;
-  static_assert(!(I8_ && (FLAGS_ & 64)), "fp8 accumulates in f32");
-  static constexpr bool SCALED = I8_ || F8;       // value = acc * sx[t] * sw[n] + bias (else: acc + bias)
-  // The 16x16x64 int8 shape: the same MACs per cycle as 32x32x32, but under the package power cap it holds a higher clock on the
-  // product's operands (tools/mfma_rate.hip: 1.14x the sustained rate, profiles/gemm_mfma_shape.txt).  Tile, waves, ring, LDS
-  // image and staging are unchanged; a 16-VGPR accumulator block then holds four 16x16 blocks stacked in rows (64 x 16).
-  static constexpr bool MF16 = FLAGS_ & 128;
-  static_assert(!(FLAGS_ & 128) || I8_, "16x16x64 is an int8 shape");
-  static_assert(!(FLAGS_ & 128) || !(FLAGS_ & 28), "the ablation paths are written for 32x32 blocks");
+constexpr int gemm_side_bytes(int nt) { return 7 * nt * 4; }   // the LDS side buffer of nt threads (GemmSide)
+
+// What gemm_epilogue and GemmSide require of a config C, stated once.  From this base: the operand kind (I8 / F8 / CERT -> SCALED)
+// and the accumulator block shape (MF16, BR x BC, acc_row / acc_col).  From the config itself: BM, BN, NT (threads, >= BM + BN),
+// the wave tile TM x TN = MI x NI blocks, and the LDS map LDS_RING_BYTES | SIDE_BYTES = gemm_side_bytes(NT) | 16 | QCAP * 8.
+template <bool I8_, bool F8_, bool CERT_, bool MF16_>
+struct GemmEpiCfg {
+  static constexpr bool I8 = I8_, F8 = F8_, CERT = CERT_, MF16 = MF16_;
+  static_assert(!(I8 && F8), "fp8 accumulates in f32");
+  static_assert(!MF16 || I8, "16x16x64 is an int8 shape");
+  static constexpr bool SCALED = I8 || F8;       // value = acc * sx[t] * sw[n] + bias (else: acc + bias)
   static constexpr int BR = MF16 ? 64 : 32, BC = MF16 ? 16 : 32;   // rows x columns of one accumulator block (16 VGPRs)
-  static constexpr int NWAVES = WM * WN, NT = NWAVES * 64;
-  static constexpr int TM = BM / WM, TN = BN / WN, MI = TM / BR, NI = TN / BC;
-  static constexpr int FA = MF16 ? TM / 16 : MI, FB = MF16 ? TN / 16 : NI;   // A / B fragments of one k-step
-  static constexpr int ROWB = 128;               // bytes per tile row: 64 bf16 or 128 int8
-  static constexpr int KS = MF16 ? 2 : 4;        // MFMA k-steps per tile (32 B per lane-half each; 16x16x64: 16 B per lane-quarter)
   // row / column inside the wave tile of register e of accumulator block (i, j) in lane `lane`:
   //   32x32: C[r][n] with n = lane & 31, r = (e & 3) + 8 (e >> 2) + 4 (lane >> 5)
   //   16x16: register group e >> 2 is the 16x16 block of rows 16 (e >> 2) ..; in it n = lane & 15, r = (e & 3) + 4 (lane >> 4)
@@ -151,16 +133,41 @@ struct GemmCfg {
     return i * BR + (MF16 ? 16 * (e >> 2) + 4 * (lane >> 4) + (e & 3) : (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5));
   }
   static __device__ __forceinline__ int acc_col(int j, int lane) { return j * BC + (lane & (BC - 1)); }
+};
+
+// FLAGS:
+//   (tuning only; results invalid when an ABL bit is set)
+//   bit 2 ABL_NOSTAGE  skip the LDS-DMA staging in the loop
+//   bit 3 ABL_NOREAD   read the fragments once and reuse them
+//   bit 4 ABL_NOMFMA   issue no MFMA
+//   bit 5 CERT         the certified three-segment pass (encode_cert.h); I8 only: its own instantiation, the product kernel is untouched
+//   bit 6 F8           fp8 (e4m3) operands, f32 accumulate (I8 = false)
+//   bit 7 MF16         int8 through v_mfma_i32_16x16x64_i8 instead of 32x32x32 (I8 only; tuning.h MSAE_GEMM_MF)
+// fp8 candidate pass (BASELINE configs[4]: "fp8 MFMA encoder path"): one byte per operand element exactly like int8 -- the SAME
+// tile-major operands, LDS image, ring and hand-scheduled fragment reads -- multiplied by v_mfma_f32_32x32x16_fp8_fp8 (two per
+// 16-byte fragment pair: the low and the high 8 bytes of the lanes) into f32 accumulators; per-token / per-feature scales in
+// the epilogue as on the int8 path, the error band of the bf16 path's form (relative roundings).  I8_ must be false.
+// The 16x16x64 int8 shape: the same MACs per cycle as 32x32x32, but under the package power cap it holds a higher clock on the
+// product's operands (tools/mfma_rate.hip: 1.14x the sustained rate, profiles/gemm_mfma_shape.txt).  Tile, waves, ring, LDS
+// image and staging are unchanged; a 16-VGPR accumulator block then holds four 16x16 blocks stacked in rows (64 x 16).
+template <int BM_, int BN_, int STAGES_, int WM_, int WN_, bool I8_ = false, int FLAGS_ = 0>
+struct GemmCfg : GemmEpiCfg<I8_, (FLAGS_ & 64) != 0, (FLAGS_ & 32) != 0, (FLAGS_ & 128) != 0> {
+  using GemmCfg::GemmEpiCfg::MF16;
+  using GemmCfg::GemmEpiCfg::BR;
+  using GemmCfg::GemmEpiCfg::BC;
+  static constexpr int BM = BM_, BN = BN_, STAGES = STAGES_, WM = WM_, WN = WN_;
+  static constexpr bool ABL_NOSTAGE = FLAGS_ & 4, ABL_NOREAD = FLAGS_ & 8, ABL_NOMFMA = FLAGS_ & 16;
+  static constexpr int NWAVES = WM * WN, NT = NWAVES * 64;
+  static constexpr int TM = BM / WM, TN = BN / WN, MI = TM / BR, NI = TN / BC;
+  static constexpr int FA = MF16 ? TM / 16 : MI, FB = MF16 ? TN / 16 : NI;   // A / B fragments of one k-step
+  static constexpr int ROWB = 128;               // bytes per tile row: 64 bf16 or 128 int8
+  static constexpr int KS = MF16 ? 2 : 4;        // MFMA k-steps per tile (32 B per lane-half each; 16x16x64: 16 B per lane-quarter)
   static constexpr int A_BYTES = BM * ROWB, B_BYTES = BN * ROWB, STAGE_BYTES = A_BYTES + B_BYTES;
   static constexpr int LDS_RING_BYTES = STAGES * STAGE_BYTES;
-  // behind the ring: side buffer of epilogue constants, then the THRESH epilogue's candidate queue.
+  // behind the ring: side buffer of epilogue constants (GemmSide), then the THRESH epilogue's candidate queue.
   // Neither overlaps the ring: the next tile's first k-tile is already landing in it meanwhile.
-  // side buffer, one float per thread and slot: tau|bias, sx|sw, m (int, parked early)|Q, P|Si, m|So, B|h
-  // (row threads | column threads)
-  // slot 6 (round 6): E (int) | Ds
-  static constexpr int SIDE_SLOTS = 7;
-  static constexpr int SIDE_BYTES = SIDE_SLOTS * NT * 4;
-  static constexpr int QCAP = 2296;              // (2304 before slot 6: the budget below is the CU's whole LDS)
+  static constexpr int SIDE_BYTES = gemm_side_bytes(NT);
+  static constexpr int QCAP = 2296;              // (2304 before the dither's slot of the side buffer: the budget below is the CU's whole LDS)
   static constexpr int LDS_BYTES = LDS_RING_BYTES + SIDE_BYTES + 16 + QCAP * 8;
   static_assert(STAGES == 2, "the flat cross-tile k-sequence below is written for a 2-slot ring");
   static_assert(BM + BN <= NT, "one thread per tile row and column fetches the epilogue constants");
@@ -362,8 +369,9 @@ __device__ __forceinline__ void gemm_read_frags(i32x4 (&a)[C::MI], i32x4 (&b)[C:
 // instead of before their first MFMA do it at position MSAE_GEMM_STAGGER_AT (gemm_kernel: stagger)
 template <class C, class F>
 __device__ __forceinline__ void gemm_compute_asm32(f32x16 (&acc)[C::MI][C::NI], const unsigned char *sA,
-                                                   int wr, int wc, int l31, int kh, F &&mid) {
+                                                   int wr, int wc, int lane, F &&mid) {
   static_assert(C::KS == 4, "four k-steps per tile");
+  const int l31 = lane & 31, kh = lane >> 5;
   const unsigned base = (unsigned)(size_t)(const __attribute__((address_space(3))) unsigned char *)sA;
   const unsigned rowA = base + (unsigned)(wr * C::TM + l31) * 128u;
   const unsigned rowB = base + (unsigned)C::A_BYTES + (unsigned)(wc * C::TN + l31) * 128u;
@@ -473,14 +481,22 @@ __device__ __forceinline__ void gemm_compute_asm16(f32x16 (&acc)[C::MI][C::NI], 
 }
 template <class C, class F>
 __device__ __forceinline__ void gemm_compute_asm(f32x16 (&acc)[C::MI][C::NI], const unsigned char *sA,
-                                                 int wr, int wc, int l31, int kh, F &&mid) {
-  if constexpr (C::MF16) gemm_compute_asm16<C>(acc, sA, wr, wc, l31 + 32 * kh, mid);
-  else gemm_compute_asm32<C>(acc, sA, wr, wc, l31, kh, mid);
+                                                 int wr, int wc, int lane, F &&mid) {
+  if constexpr (C::MF16) gemm_compute_asm16<C>(acc, sA, wr, wc, lane, mid);
+  else gemm_compute_asm32<C>(acc, sA, wr, wc, lane, mid);
 }
-template <class C>
-__device__ __forceinline__ void gemm_compute_asm(f32x16 (&acc)[C::MI][C::NI], const unsigned char *sA,
-                                                 int wr, int wc, int l31, int kh) {
-  gemm_compute_asm<C>(acc, sA, wr, wc, l31, kh, [](int) {});
+
+// The fragments of k-step ks of the wave tile, compiler-scheduled (outlier tile, ablations): fragment f of A / B is FR = 16 or 32
+// tile rows, lane l holds row l % FR and the 16-B chunk l / FR of the k-step's 64 / FR; frag(tile, row, chunk) reads one.
+template <class C, class F>
+__device__ __forceinline__ void gemm_load_frags(i32x4 (&a)[C::FA], i32x4 (&b)[C::FB], const unsigned char *tA,
+                                                const unsigned char *tB, int wr, int wc, int lane, int ks, F &&frag) {
+  constexpr int FR = C::MF16 ? 16 : 32;
+  const int lr = lane & (FR - 1), chunk = ks * (64 / FR) + lane / FR;
+#pragma unroll
+  for (int f = 0; f < C::FA; ++f) a[f] = frag(tA, wr * C::TM + f * FR + lr, chunk);
+#pragma unroll
+  for (int f = 0; f < C::FB; ++f) b[f] = frag(tB, wc * C::TN + f * FR + lr, chunk);
 }
 
 // Compact outlier tile (at most 32 outlier dims: one k-step).  The k-loop is bound by the L2 -> LDS delivery, and a
@@ -507,109 +523,54 @@ __device__ __forceinline__ void gemm_stage_lead_compact(const unsigned char *__r
 }
 template <class C>
 __device__ __forceinline__ void gemm_compute_lead_compact(f32x16 (&acc)[C::MI][C::NI], const unsigned char *sA,
-                                                          int wr, int wc, int l31, int kh) {
-  const unsigned char *sB = sA + C::BM * 32;
-  if constexpr (C::MF16) {   // a fragment spans 64 B of k, the image 32: lanes 32-63 (chunks 2, 3) feed zeros
-    const int lane = l31 + 32 * kh, l15 = lane & 15, kq = lane >> 4;
-    i32x4 a[C::FA], b[C::FB];
-#pragma unroll
-    for (int f = 0; f < C::FA; ++f)
-      a[f] = kh ? i32x4{} : *reinterpret_cast<const i32x4 *>(sA + (wr * C::TM + f * 16 + l15) * 32 + kq * 16);
-#pragma unroll
-    for (int j = 0; j < C::FB; ++j)
-      b[j] = kh ? i32x4{} : *reinterpret_cast<const i32x4 *>(sB + (wc * C::TN + j * 16 + l15) * 32 + kq * 16);
-    gemm_mfma_step<C>(acc, a, b);
-  } else {
-    i32x4 a[C::MI], b[C::NI];
-#pragma unroll
-    for (int i = 0; i < C::MI; ++i) a[i] = *reinterpret_cast<const i32x4 *>(sA + (wr * C::TM + i * 32 + l31) * 32 + kh * 16);
-#pragma unroll
-    for (int j = 0; j < C::NI; ++j) b[j] = *reinterpret_cast<const i32x4 *>(sB + (wc * C::TN + j * 32 + l31) * 32 + kh * 16);
-    gemm_mfma_step<C>(acc, a, b);
-  }
+                                                          int wr, int wc, int lane) {
+  i32x4 a[C::FA], b[C::FB];   // (16x16x64: a fragment spans 64 B of k, the image 32: lanes 32-63 -- chunks 2, 3 -- feed zeros)
+  gemm_load_frags<C>(a, b, sA, sA + C::BM * 32, wr, wc, lane, 0, [](const unsigned char *t, int row, int chunk) {
+    return chunk < 2 ? *reinterpret_cast<const i32x4 *>(t + row * 32 + chunk * 16) : i32x4{};
+  });
+  gemm_mfma_step<C>(acc, a, b);
 }
 
-// the outlier k-tile: only its first `nks` k-steps hold data (32 outlier dims per k-step), the rest is zero
+// the outlier k-tile: only its first `nks` k-steps of 32 B hold data (32 outlier dims each), the rest is zero
 template <class C>
 __device__ __forceinline__ void gemm_compute_lead(f32x16 (&acc)[C::MI][C::NI], const unsigned char *sA,
-                                                  const unsigned char *sB, int wr, int wc, int l31, int kh, int nks) {
-  if constexpr (C::MF16) {   // 64 outlier dims per k-step
-    const int lane = l31 + 32 * kh, l15 = lane & 15, kq = lane >> 4;
-    for (int ks = 0; ks < (nks + 1) >> 1; ++ks) {
-      i32x4 a[C::FA], b[C::FB];
-#pragma unroll
-      for (int f = 0; f < C::FA; ++f) a[f] = gemm_frag(sA, wr * C::TM + f * 16 + l15, 4 * ks + kq);
-#pragma unroll
-      for (int j = 0; j < C::FB; ++j) b[j] = gemm_frag(sB, wc * C::TN + j * 16 + l15, 4 * ks + kq);
-      gemm_mfma_step<C>(acc, a, b);
-    }
-  } else {
-    for (int ks = 0; ks < nks; ++ks) {
-      const int chunk = ks * 2 + kh;
-      i32x4 a[C::MI], b[C::NI];
-#pragma unroll
-      for (int i = 0; i < C::MI; ++i) a[i] = gemm_frag(sA, wr * C::TM + i * 32 + l31, chunk);
-#pragma unroll
-      for (int j = 0; j < C::NI; ++j) b[j] = gemm_frag(sB, wc * C::TN + j * 32 + l31, chunk);
-      gemm_mfma_step<C>(acc, a, b);
-    }
+                                                  const unsigned char *sB, int wr, int wc, int lane, int nks) {
+  for (int ks = 0; ks < (C::MF16 ? (nks + 1) >> 1 : nks); ++ks) {   // (16x16x64: 64 dims per k-step)
+    i32x4 a[C::FA], b[C::FB];
+    gemm_load_frags<C>(a, b, sA, sB, wr, wc, lane, ks, [](const unsigned char *t, int row, int chunk) { return gemm_frag(t, row, chunk); });
+    gemm_mfma_step<C>(acc, a, b);
   }
 }
 
 template <class C>
 __device__ __forceinline__ void gemm_compute(f32x16 (&acc)[C::MI][C::NI], const unsigned char *sA,
-                                             const unsigned char *sB, int wr, int wc, int l31, int kh,
-                                             i32x4 (&abl_a)[C::MI], i32x4 (&abl_b)[C::NI]) {
+                                             const unsigned char *sB, int wr, int wc, int lane,
+                                             i32x4 (&abl_a)[C::FA], i32x4 (&abl_b)[C::FB]) {
   if constexpr (!C::ABL_NOREAD && !C::ABL_NOMFMA) {
-    gemm_compute_asm<C>(acc, sA, wr, wc, l31, kh);
+    gemm_compute_asm<C>(acc, sA, wr, wc, lane, [](int) {});
     return;
   }
   // ablation builds only (tools/gemm_sweep): compiler-scheduled reads / no reads / no MFMA
 #pragma unroll
   for (int ks = 0; ks < C::KS; ++ks) {
-    const int chunk = ks * 2 + kh;
-    i32x4 a[C::MI], b[C::NI];
+    i32x4 a[C::FA], b[C::FB];
     if constexpr (C::ABL_NOREAD) {
 #pragma unroll
-      for (int i = 0; i < C::MI; ++i) { a[i] = abl_a[i]; asm volatile("" : "+v"(a[i])); }
+      for (int f = 0; f < C::FA; ++f) { a[f] = abl_a[f]; asm volatile("" : "+v"(a[f])); }
 #pragma unroll
-      for (int j = 0; j < C::NI; ++j) { b[j] = abl_b[j]; asm volatile("" : "+v"(b[j])); }
+      for (int f = 0; f < C::FB; ++f) { b[f] = abl_b[f]; asm volatile("" : "+v"(b[f])); }
     } else {
-#pragma unroll
-      for (int i = 0; i < C::MI; ++i) a[i] = gemm_frag(sA, wr * C::TM + i * 32 + l31, chunk);
-#pragma unroll
-      for (int j = 0; j < C::NI; ++j) b[j] = gemm_frag(sB, wc * C::TN + j * 32 + l31, chunk);
+      gemm_load_frags<C>(a, b, sA, sB, wr, wc, lane, ks, [](const unsigned char *t, int row, int chunk) { return gemm_frag(t, row, chunk); });
     }
     if constexpr (C::ABL_NOMFMA) {
 #pragma unroll
-      for (int i = 0; i < C::MI; ++i) asm volatile("" ::"v"(a[i]));
+      for (int f = 0; f < C::FA; ++f) asm volatile("" ::"v"(a[f]));
 #pragma unroll
-      for (int j = 0; j < C::NI; ++j) asm volatile("" ::"v"(b[j]));
+      for (int f = 0; f < C::FB; ++f) asm volatile("" ::"v"(b[f]));
     } else {
       gemm_mfma_step<C>(acc, a, b);
     }
   }
-}
-
-// Epilogue.  DENSE stores every value.  THRESH compares with the per-token threshold; survivors are
-// rare (~1 per 200 outputs pass the hot loop's separable bound) but each needs a slot in its token's
-// candidate list, i.e. a RETURNING global atomic (~2 us round trip).  Doing that inline serialises ~30
-// round trips per wave -- as long as the whole k-loop.  So survivors are first queued in LDS (its own
-// region behind the ring) and then flushed, one queue entry per lane: the global atomics of the whole
-// workgroup are in flight together.  The hot loop itself touches no LDS queue: hit masks per 32x32
-// block first (4.5 VALU per output), then ONE queue reservation per lane and tile, then the pushes
-// (round 3; 15.4k -> 7.8k cycles per tile on the tile timeline, profiles/r03_epilogue_batch.txt --
-// worth 0-1 % of wall time only, because the kernel runs at the package power limit: the clock drops
-// as the cycle count does, profiles/r03_power.txt).
-// z^2 sigma^2 of pair (row, col) from the side buffer (same expression as band_sq in encode_fused.hip)
-template <class C>
-__device__ __forceinline__ float gemm_band_sq(const float *side, int row, int col, float zz12) {
-  const float *row_c = side, *col_c = side + C::BM;
-  const float pz = row_c[3 * C::NT + row];
-  if constexpr (!C::I8 && !C::F8) return pz * col_c[2 * C::NT + col];
-  const float rs = row_c[C::NT + row], mf = row_c[4 * C::NT + row];
-  const float rz = rs * rs * zz12;
-  return __builtin_fmaf(pz, col_c[2 * C::NT + col], __builtin_fmaf(rz * mf * mf, col_c[4 * C::NT + col], rz * col_c[3 * C::NT + col]));
 }
 
 // append one candidate key to token t's list (segment of this workgroup)
@@ -633,38 +594,214 @@ __device__ __forceinline__ int gemm_feature(const GemmEpilogue &ep, int n) {
   return n * ep.bias_stride + ep.bias_off;
 }
 
-template <class C, bool DENSE, class F>
+// ---- the LDS side buffer: the epilogue constants of one output tile ----------------------------------------------------------
+// Seven slots of NT floats behind the ring.  Thread tid < BM owns row tid of the tile, thread BM + c its column c, and slot s
+// keeps one word for each of them: [s * NT + row] | [s * NT + BM + col].  Only these two structs know the slot numbers:
+//   slot   row t (token)                      column n (feature)
+//    0     tau   threshold (THRESH)           bias
+//    1     sx    scale                        sw    scale
+//    2     m as int             EARLY         Q  \
+//    3     P   \  of the band                 Si  } of the band: z^2 sigma^2 = P Q + R (Si + M So)   (gemm_band_sq)
+//    4     m as float (M = m^2) /             So /
+//    5     B   = z sigma against the reference feature   h  >= sqrt of every ratio to it             (THRESH; file header)
+//    6     -E as int            EARLY         Ds = sw_n D_n                                           (subtractive dither, int8)
+// GemmSideView is what the epilogue gets: it can name every value above except the two EARLY ones.
+template <class C>
+class GemmSideView {
+ public:
+  __device__ __forceinline__ float tau(int row) const { return s[row]; }
+  __device__ __forceinline__ float sx(int row) const { return s[C::NT + row]; }
+  __device__ __forceinline__ float P(int row) const { return s[3 * C::NT + row]; }
+  __device__ __forceinline__ float m(int row) const { return s[4 * C::NT + row]; }
+  __device__ __forceinline__ float B(int row) const { return s[5 * C::NT + row]; }
+  __device__ __forceinline__ float bias(int col) const { return s[C::BM + col]; }
+  __device__ __forceinline__ float sw(int col) const { return s[C::NT + C::BM + col]; }
+  __device__ __forceinline__ float Q(int col) const { return s[2 * C::NT + C::BM + col]; }
+  __device__ __forceinline__ float Si(int col) const { return s[3 * C::NT + C::BM + col]; }
+  __device__ __forceinline__ float So(int col) const { return s[4 * C::NT + C::BM + col]; }
+  __device__ __forceinline__ float h(int col) const { return s[5 * C::NT + C::BM + col]; }
+  __device__ __forceinline__ float Ds(int col) const { return s[6 * C::NT + C::BM + col]; }
+
+ protected:
+  __device__ __forceinline__ explicit GemmSideView(unsigned char *side) : s((__attribute__((address_space(3))) float *)side) {}
+  __attribute__((address_space(3))) float *s;   // (typed as LDS: left to address-space inference the THRESH loop took 20 VGPRs more)
+};
+
+// The kernels' side: fetch a tile's constants into registers in front of the k-loop, park them behind it (so the epilogue
+// never waits on global memory), and the EARLY pair.
+template <class C>
+class GemmSide : public GemmSideView<C> {
+  using GemmSideView<C>::s;
+  static constexpr bool DITHER = C::I8 && !C::CERT;   // GemmEpilogue::row_e / col_ds may be set
+  static_assert(C::SIDE_BYTES == gemm_side_bytes(C::NT) && C::BM + C::BN <= C::NT, "row part | column part of every slot");
+  static_assert(C::LDS_BYTES == C::LDS_RING_BYTES + 7 * C::NT * 4 + 16 + C::QCAP * 8, "ring | side buffer | queue count | queue");
+  __device__ __forceinline__ __attribute__((address_space(3))) int *words() const { return (__attribute__((address_space(3))) int *)s; }
+
+ public:
+  __device__ __forceinline__ explicit GemmSide(unsigned char *smem) : GemmSideView<C>(smem + C::LDS_RING_BYTES) {}
+
+  // This thread's word of slots 0-4 and 6, and the reference feature (Qr, Sir, Sor) of slot 5
+  struct Regs {
+    float c0 = 0.f, c1 = 0.f, c3 = 0.f, c4 = 0.f;
+    int c2 = 1, c6 = 0;                             // rows: m, +E; columns: the float bits of Q, Ds
+    float ref0 = 1.f, ref1 = 1.f, ref2 = 1.f;
+  };
+  // tile at (m0, n0); rows from T on are padding; has_out: the launch has an outlier tile (int8)
+  template <bool DENSE>
+  static __device__ __forceinline__ Regs fetch(const GemmEpilogue &ep, int tid, int m0, int n0, int T, bool has_out) {
+    Regs r;
+    if constexpr (!DENSE) { r.ref0 = ep.refs[0]; r.ref1 = ep.refs[1]; r.ref2 = ep.refs[2]; }
+    if (tid < C::BM) {
+      const int t = m0 + tid;
+      if constexpr (!DENSE) {
+        const float v = (t < T) ? ep.tau_vals[(size_t)t * ep.tau_ld + ep.tau_col] : 0.f;
+        r.c0 = (v > 0.f) ? v : __builtin_inff();     // degenerate / padded token: emit nothing
+      }
+      if (t < T) {
+        const f32x4 rc = ep.rowc[t];
+        r.c1 = rc[0];
+        r.c3 = rc[2];
+        r.c4 = 1.f;
+        if (has_out) { r.c2 = (int)rc[1]; r.c4 = rc[1]; }
+        if constexpr (C::CERT || C::F8) r.c4 = rc[1];
+        if constexpr (DITHER) {
+          if (ep.row_e) { const int2 em = ep.row_e[t]; r.c6 = em.x; r.c2 = em.y; }
+        }
+      }
+    } else if (tid < C::BM + C::BN) {
+      const int n = n0 + tid - C::BM;
+      r.c0 = ep.bias ? ep.bias[gemm_feature(ep, n)] : 0.f;
+      const f32x4 cc = ep.colc[n];
+      r.c1 = cc[0];
+      r.c2 = __float_as_int(cc[1]);
+      r.c3 = cc[2];
+      r.c4 = cc[3];
+      if constexpr (DITHER) {
+        if (ep.col_ds) r.c6 = __float_as_int(ep.col_ds[n]);
+      }
+    }
+    return r;
+  }
+
+  // EARLY: m and -E of the rows (acc = acc * m - E right behind the outlier tile) are parked in front of the tile's first barrier,
+  // while slower waves of a persistent workgroup may still run the PREVIOUS tile's epilogue.  So they live where no epilogue
+  // reads -- the row parts of slots 2 and 6, which GemmSideView cannot name -- and never beside an epilogue input (d74ff0c: as
+  // int2 across slot 2 they overwrote Q_n under the slow waves' band computations; verified-and-wrong tokens at N = 262144).
+  __device__ __forceinline__ void park_early(int tid, const Regs &r) const {
+    if (tid < C::BM) { words()[2 * C::NT + tid] = r.c2; if constexpr (DITHER) words()[6 * C::NT + tid] = -r.c6; }
+  }
+  __device__ __forceinline__ int early_m(int row) const { return words()[2 * C::NT + row]; }
+  __device__ __forceinline__ int early_neg_e(int row) const { return DITHER ? words()[6 * C::NT + row] : 0; }   // (0 without the dither)
+
+  // behind the k-loop: everything the epilogue reads.  Slot 5 is computed only now: the loads it needs had the whole k-loop to land.
+  template <bool DENSE>
+  __device__ __forceinline__ void park(int tid, const Regs &r, float zz12) const {
+    const bool col = tid >= C::BM;                  // (the row parts of slots 2 and 6 are the EARLY pair's)
+    s[tid] = r.c0;
+    s[C::NT + tid] = r.c1;
+    if (col) words()[2 * C::NT + tid] = r.c2;
+    s[3 * C::NT + tid] = r.c3;
+    s[4 * C::NT + tid] = r.c4;
+    if constexpr (DITHER) { if (col) words()[6 * C::NT + tid] = r.c6; }
+    if constexpr (!DENSE) {
+      float c5 = 0.f;
+      if (tid < C::BM) {          // B_t: z sigma of this token against the reference feature
+        float b2 = r.c3 * r.ref0;
+        if constexpr (C::SCALED) {
+          const float rz = r.c1 * r.c1 * zz12;
+          b2 = __builtin_fmaf(rz * r.c4 * r.c4, r.ref2, __builtin_fmaf(rz, r.ref1, b2));
+        }
+        c5 = __builtin_sqrtf(b2) * 1.00001f;
+      } else if (tid < C::BM + C::BN) {   // h_n >= sqrt of every ratio to the reference feature (0/0 counts as 0)
+        const float q = __int_as_float(r.c2);
+        float h2 = q / r.ref0;
+        if constexpr (C::SCALED) {
+          h2 = fmaxf(h2, r.c3 / r.ref1);
+          if (r.c4 > 0.f) h2 = fmaxf(h2, r.c4 / r.ref2);
+        }
+        c5 = (q > 0.f || r.c3 > 0.f || r.c4 > 0.f) ? __builtin_sqrtf(h2) * 1.00001f : 0.f;
+      }
+      s[5 * C::NT + tid] = c5;
+    }
+  }
+};
+
+// z^2 sigma^2 of pair (row, col) from the side buffer (same expression as band_sq in encode_fused.hip)
+template <class C>
+__device__ __forceinline__ float gemm_band_sq(const GemmSideView<C> &side, int row, int col, float zz12) {
+  const float pz = side.P(row);
+  if constexpr (!C::SCALED) return pz * side.Q(col);
+  const float rs = side.sx(row), mf = side.m(row);
+  const float rz = rs * rs * zz12;
+  return __builtin_fmaf(pz, side.Q(col), __builtin_fmaf(rz * mf * mf, side.So(col), rz * side.Si(col)));
+}
+
+// The coarse pre-activation v of accumulator register e (V = float) or registers e, e + 1 (V = f32x2: packed-f32 instructions) of
+// one block, for the operand kind of C.  THE definition of v: the candidate audit pins it to a fraction of an f32 rounding.
+//   int8            v = (acc sw_n - sw_n D_n) sx_t + b_n   two fmas; nds = -sw_n D_n (0 without the subtractive dither)
+//   certified, fp8  v = acc (sx_t sw_n) + b_n
+//   bf16            v = acc + b_n
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+template <class V>
+__device__ __forceinline__ V gemm_splat(float x) {
+  if constexpr (sizeof(V) == sizeof(float)) return x;
+  else return V{x, x};
+}
+template <class C, class V>
+__device__ __forceinline__ V gemm_value(const f32x16 &blk, int e, V sx, float sw, float nds, float bias) {
+  V a;
+  if constexpr (sizeof(V) == sizeof(float)) {
+    if constexpr (C::I8) a = (float)__builtin_bit_cast(i32x16, blk)[e]; else a = blk[e];
+  } else {
+    if constexpr (C::I8) a = V{(float)__builtin_bit_cast(i32x16, blk)[e], (float)__builtin_bit_cast(i32x16, blk)[e + 1]};
+    else a = V{blk[e], blk[e + 1]};
+  }
+  if constexpr (C::I8 && !C::CERT)
+    return __builtin_elementwise_fma(__builtin_elementwise_fma(a, gemm_splat<V>(sw), gemm_splat<V>(nds)), sx, gemm_splat<V>(bias));
+  else if constexpr (C::SCALED) return a * (sx * sw) + bias;
+  else return a + bias;
+}
+
+// Epilogue.  DENSE stores every value.  THRESH compares with the per-token threshold; survivors are
+// rare (~1 per 200 outputs pass the hot loop's separable bound) but each needs a slot in its token's
+// candidate list, i.e. a RETURNING global atomic (~2 us round trip).  Doing that inline serialises ~30
+// round trips per wave -- as long as the whole k-loop.  So survivors are first queued in LDS (its own
+// region behind the ring) and then flushed, one queue entry per lane: the global atomics of the whole
+// workgroup are in flight together.  The hot loop itself touches no LDS queue: hit masks per accumulator
+// block first (4.5 VALU per output), then ONE queue reservation per lane and tile, then the pushes
+// (round 3; 15.4k -> 7.8k cycles per tile on the tile timeline, profiles/r03_epilogue_batch.txt --
+// worth 0-1 % of wall time only, because the kernel runs at the package power limit: the clock drops
+// as the cycle count does, profiles/r03_power.txt).
+// Called by every wave of the workgroup with its accumulators, behind GemmSide::park (its first barrier orders the two).
+template <class C, bool DENSE>
 __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[C::MI][C::NI], const GemmEpilogue &ep, int T,
                                               int m0, int n0, int wr, int wc, int lane,
-                                              unsigned char *smem, const float *side, F &&after_barrier, int tl_tile = 0) {
+                                              unsigned char *smem, const GemmSideView<C> side, int tl_tile = 0) {
   constexpr int QCAP = C::QCAP;
   unsigned *q_count = reinterpret_cast<unsigned *>(smem + C::LDS_RING_BYTES + C::SIDE_BYTES);
   unsigned long long *queue = reinterpret_cast<unsigned long long *>(smem + C::LDS_RING_BYTES + C::SIDE_BYTES + 16);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();                        // side[] written; previous tile's flush done
-  after_barrier();
+  __builtin_amdgcn_s_barrier();                        // side buffer written; previous tile's flush done
   if constexpr (!DENSE) {
     if (threadIdx.x == 0) *q_count = 0u;
     __syncthreads();
   }
   MSAE_TL(7);
-  // side[s*NT + tid]: slot s of row tid (tid < BM) or of column tid - BM
-  const float *row_c = side, *col_c = side + C::BM;
   // column constants of this lane's NI columns stay in registers across the row loops
   float c_bias[C::NI], c_sw[C::NI], c_h[C::NI];
-  [[maybe_unused]] float c_ds[C::NI];                  // -sw_n D_n (subtractive dither; 0 otherwise)
+  float c_ds[C::NI];                                   // -sw_n D_n (subtractive dither; 0 otherwise)
   bool c_live[C::NI];
 #pragma unroll
   for (int j = 0; j < C::NI; ++j) {
     const int col = wc * C::TN + C::acc_col(j, lane);  // column inside the tile
-    c_bias[j] = col_c[col];
-    c_sw[j] = col_c[C::NT + col];
-    if constexpr (C::I8 && !C::CERT) c_ds[j] = -col_c[6 * C::NT + col];
-    c_h[j] = col_c[5 * C::NT + col];
+    c_bias[j] = side.bias(col);
+    c_sw[j] = side.sw(col);
+    c_ds[j] = (C::I8 && !C::CERT) ? -side.Ds(col) : 0.f;
+    c_h[j] = side.h(col);
     const int feat = gemm_feature(ep, n0 + col);
     c_live[j] = (feat != ep.skip_a) && (feat != ep.skip_b);
   }
-  // row / column of register e of block (i, j): GemmCfg::acc_row / acc_col
+  // row / column of register e of block (i, j): C::acc_row / acc_col
   if (msae_tuning::ABL_NOEPI && !DENSE && ep.cap != -12345) { asm volatile("" ::"v"(acc[0][0][0])); } else   // (tuning builds: skip the element loop)
   // THRESH.  One pass over the wave's MI x NI blocks without any LDS round trip: the value v replaces the accumulator in its register,
   // the sign of (v + h_n B_t) - tau goes through a 1-instruction shift register (v_alignbit) into a 16-bit hit mask per block.
@@ -672,97 +809,48 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[C::MI][C::NI], const
   // by a select tree on the hit's position).
   if constexpr (!DENSE) {
     unsigned hits[C::MI][C::NI];
-    if constexpr (C::MF16) {
-      // 16x16 blocks: a lane holds 4 column sets (NI = 4) instead of 2, so the 48 row constants of a whole block do not fit beside
-      // them.  The rows of register group g (e = 4g .. 4g+3) are the same in all four column blocks: hold 12 row constants at a
-      // time, with a scheduling fence per group so that the compiler does not hoist the next groups' LDS loads.
-#pragma unroll
-      for (int i = 0; i < C::MI; ++i) {
-        unsigned mj[C::NI];
-#pragma unroll
-        for (int j = 0; j < C::NI; ++j) mj[j] = 0u;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          __builtin_amdgcn_sched_barrier(0);
-          float tau[4], rs[4], bt[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int row = wr * C::TM + C::acc_row(i, 4 * g + r, lane);
-            tau[r] = row_c[row];
-            rs[r] = row_c[C::NT + row];
-            bt[r] = row_c[5 * C::NT + row];
-          }
-#pragma unroll
-          for (int j = 0; j < C::NI; ++j) {
-            unsigned m = mj[j];
-#pragma unroll
-            for (int r = 0; r < 4; r += 2) {
-              typedef float f32x2 __attribute__((ext_vector_type(2)));
-              const int e = 4 * g + r;
-              const f32x2 tau2 = {tau[r], tau[r + 1]}, rs2 = {rs[r], rs[r + 1]}, bt2 = {bt[r], bt[r + 1]};
-              const f32x2 a = {(float)__builtin_bit_cast(i32x16, acc[i][j])[e], (float)__builtin_bit_cast(i32x16, acc[i][j])[e + 1]};
-              f32x2 v;
-              if constexpr (!C::CERT) {   // as below
-                const f32x2 sw2 = {c_sw[j], c_sw[j]}, ds2 = {c_ds[j], c_ds[j]}, b2 = {c_bias[j], c_bias[j]};
-                v = __builtin_elementwise_fma(__builtin_elementwise_fma(a, sw2, ds2), rs2, b2);
-              } else {
-                v = a * (rs2 * c_sw[j]) + c_bias[j];
-              }
-              acc[i][j][e] = v.x;
-              acc[i][j][e + 1] = v.y;
-              const f32x2 ch2 = {c_h[j], c_h[j]};
-              const f32x2 dlt = __builtin_elementwise_fma(ch2, bt2, v) - tau2;
-              m = __builtin_amdgcn_alignbit(m, __float_as_uint(dlt.x), 31);
-              m = __builtin_amdgcn_alignbit(m, __float_as_uint(dlt.y), 31);
-            }
-            mj[j] = m;
-          }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int j = 0; j < C::NI; ++j) hits[i][j] = c_live[j] ? (~mj[j] & 0xFFFFu) : 0u;   // bit 15 - e: output e is a hit
-      }
-    } else
+    // The constants of RG rows are held at a time.  32x32 blocks: all 16 rows of a block.  16x16 blocks: a lane holds 4 column
+    // sets (NI = 4) instead of 2, so the 48 row constants of a whole block do not fit beside them; the rows of register group g
+    // (e = 4g .. 4g+3) are the same in all four column blocks: 12 row constants at a time, with a scheduling fence per group so
+    // that the compiler does not hoist the next groups' LDS loads.
+    constexpr int RG = C::MF16 ? 4 : 16;
 #pragma unroll
     for (int i = 0; i < C::MI; ++i) {
-      float tau[16], rs[16], bt[16];
+      unsigned mj[C::NI];
 #pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int row = wr * C::TM + C::acc_row(i, e, lane);
-        tau[e] = row_c[row];
-        rs[e] = C::SCALED ? row_c[C::NT + row] : 0.f;
-        bt[e] = row_c[5 * C::NT + row];
-      }
+      for (int j = 0; j < C::NI; ++j) mj[j] = 0u;
 #pragma unroll
-      for (int j = 0; j < C::NI; ++j) {
-        unsigned m = 0;
+      for (int g = 0; g < 16 / RG; ++g) {
+        if constexpr (RG < 16) __builtin_amdgcn_sched_barrier(0);
+        float tau[RG], rs[RG], bt[RG];
 #pragma unroll
-        for (int e = 0; e < 16; e += 2) {                                      // two outputs per packed-f32 instruction
-          typedef float f32x2 __attribute__((ext_vector_type(2)));
-          const f32x2 tau2 = {tau[e], tau[e + 1]}, rs2 = {rs[e], rs[e + 1]}, bt2 = {bt[e], bt[e + 1]};
-          f32x2 v;
-          if constexpr (C::I8 && !C::CERT) {
-            // v = (acc sw_n - sw_n D_n) sx_t + b_n: two packed fmas, as many instructions as acc (sx sw) + b
-            const f32x2 a = {(float)__builtin_bit_cast(i32x16, acc[i][j])[e], (float)__builtin_bit_cast(i32x16, acc[i][j])[e + 1]};
-            const f32x2 sw2 = {c_sw[j], c_sw[j]}, ds2 = {c_ds[j], c_ds[j]}, b2 = {c_bias[j], c_bias[j]};
-            v = __builtin_elementwise_fma(__builtin_elementwise_fma(a, sw2, ds2), rs2, b2);
-          } else if constexpr (C::I8) {
-            const f32x2 a = {(float)__builtin_bit_cast(i32x16, acc[i][j])[e], (float)__builtin_bit_cast(i32x16, acc[i][j])[e + 1]};
-            v = a * (rs2 * c_sw[j]) + c_bias[j];
-          } else if constexpr (C::F8) {
-            v = f32x2{acc[i][j][e], acc[i][j][e + 1]} * (rs2 * c_sw[j]) + c_bias[j];
-          } else {
-            v = f32x2{acc[i][j][e], acc[i][j][e + 1]} + c_bias[j];
-          }
-          acc[i][j][e] = v.x;
-          acc[i][j][e + 1] = v.y;
-          const f32x2 ch2 = {c_h[j], c_h[j]};
-          const f32x2 dlt = __builtin_elementwise_fma(ch2, bt2, v) - tau2;      // >= +0 iff the bound reaches tau (NaN: either)
-          m = __builtin_amdgcn_alignbit(m, __float_as_uint(dlt.x), 31);        // m = m << 1 | sign(dlt)
-          m = __builtin_amdgcn_alignbit(m, __float_as_uint(dlt.y), 31);
+        for (int r = 0; r < RG; ++r) {
+          const int row = wr * C::TM + C::acc_row(i, RG * g + r, lane);
+          tau[r] = side.tau(row);
+          rs[r] = C::SCALED ? side.sx(row) : 0.f;
+          bt[r] = side.B(row);
         }
-        hits[i][j] = c_live[j] ? (~m & 0xFFFFu) : 0u;                          // bit 15 - e: output e is a hit
+#pragma unroll
+        for (int j = 0; j < C::NI; ++j) {
+          unsigned m = mj[j];
+#pragma unroll
+          for (int r = 0; r < RG; r += 2) {                                      // two outputs per packed-f32 instruction
+            const int e = RG * g + r;
+            const f32x2 tau2 = {tau[r], tau[r + 1]}, rs2 = {rs[r], rs[r + 1]}, bt2 = {bt[r], bt[r + 1]};
+            const f32x2 v = gemm_value<C, f32x2>(acc[i][j], e, rs2, c_sw[j], c_ds[j], c_bias[j]);
+            acc[i][j][e] = v.x;
+            acc[i][j][e + 1] = v.y;
+            const f32x2 ch2 = {c_h[j], c_h[j]};
+            const f32x2 dlt = __builtin_elementwise_fma(ch2, bt2, v) - tau2;      // >= +0 iff the bound reaches tau (NaN: either)
+            m = __builtin_amdgcn_alignbit(m, __float_as_uint(dlt.x), 31);        // m = m << 1 | sign(dlt)
+            m = __builtin_amdgcn_alignbit(m, __float_as_uint(dlt.y), 31);
+          }
+          mj[j] = m;
+          // bit 15 - e: output e is a hit  (taken here, not in a loop of its own behind the groups: that form spills on 32x32 blocks)
+          if (g == 16 / RG - 1) hits[i][j] = c_live[j] ? (~m & 0xFFFFu) : 0u;
+        }
       }
+      if constexpr (RG < 16) __builtin_amdgcn_sched_barrier(0);
     }
     unsigned total = 0;
 #pragma unroll
@@ -802,7 +890,7 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[C::MI][C::NI], const
               queue[slot] = ((unsigned long long)__float_as_uint(v) << 32) | (unsigned)(row << 16 | col);
             } else {                                                            // queue full: slow path
               const float u = v + __builtin_sqrtf(gemm_band_sq<C>(side, row, col, ep.zz12));
-              if (u > row_c[row]) {
+              if (u > side.tau(row)) {
                 const int t = m0 + row;
                 const int feat = gemm_feature(ep, n0 + col);
                 gemm_push_candidate(ep, t, ((unsigned long long)f32_order_key(u) << 32) | (unsigned)(0x7FFFFFFF - feat));
@@ -823,12 +911,7 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[C::MI][C::NI], const
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
           const int row = wr * C::TM + C::acc_row(i, e, lane), t = m0 + row;
-          float v;
-          if constexpr (C::I8 && !C::CERT)
-            v = __builtin_fmaf(__builtin_fmaf((float)__builtin_bit_cast(i32x16, acc[i][j])[e], c_sw[j], c_ds[j]), row_c[C::NT + row], c_bias[j]);
-          else if constexpr (C::I8) v = (float)__builtin_bit_cast(i32x16, acc[i][j])[e] * (row_c[C::NT + row] * c_sw[j]) + c_bias[j];
-          else if constexpr (C::F8) v = acc[i][j][e] * (row_c[C::NT + row] * c_sw[j]) + c_bias[j];
-          else v = acc[i][j][e] + c_bias[j];
+          const float v = gemm_value<C, float>(acc[i][j], e, C::SCALED ? side.sx(row) : 0.f, c_sw[j], c_ds[j], c_bias[j]);
           if (t < T) ep.dense[(size_t)t * ep.ld_dense + n0 + col] = v + __builtin_sqrtf(gemm_band_sq<C>(side, row, col, ep.zz12));
         }
       }
@@ -843,7 +926,7 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[C::MI][C::NI], const
       const int row = (int)((e >> 16) & 0xFFFFu), col = (int)(e & 0xFFFFu);
       const float v = __uint_as_float((unsigned)(e >> 32));
       const float u = v + __builtin_sqrtf(gemm_band_sq<C>(side, row, col, ep.zz12));   // the exact upper value
-      if (!(u > row_c[row])) continue;
+      if (!(u > side.tau(row))) continue;
       const int t = m0 + row;
       const int feat = gemm_feature(ep, n0 + col);
       gemm_push_candidate(ep, t, ((unsigned long long)f32_order_key(u) << 32) | (unsigned)(0x7FFFFFFF - feat));
@@ -873,7 +956,6 @@ __global__ __launch_bounds__(C::NT) void gemm_kernel(GemmOperands op, int T, int
   const int lane = tid_ & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid_ >> 6);
   const int wr = wave / C::WN, wc = wave % C::WN;
-  const int l31 = lane & 31, kh = lane >> 5;
   int tm, tn;
   gemm_map_tile(tile_id, nM, nN, tm, tn);
   const int m0 = tm * C::BM, n0 = tn * C::BN;
@@ -888,47 +970,9 @@ __global__ __launch_bounds__(C::NT) void gemm_kernel(GemmOperands op, int T, int
   // after the k-loop, so the epilogue never waits on global memory.  (Issuing these loads behind the
   // tile's first barrier instead -- so that the first vmcnt(0) does not wait for them -- measured 5 %
   // SLOWER: their address arithmetic then sits between the DMA issue and the first MFMAs of the tile.)
-  //   threads [0, BM)      : tau (THRESH) and (sx, m, P) of row m0 + tid
-  //   threads [BM, BM+BN)  : bias and (sw, Q, Si, So) of column n0 + tid - BM
-  float side0 = 0.f, side1 = 0.f, side3 = 0.f, side4 = 0.f;
-  int side2 = 1;
-  [[maybe_unused]] int side6 = 0;                // E_t (rows, int) | Ds_n (columns, float bits)
-  float ref0 = 1.f, ref1 = 1.f, ref2 = 1.f;
-  {
-    if constexpr (!DENSE) { ref0 = ep.refs[0]; ref1 = ep.refs[1]; ref2 = ep.refs[2]; }   // consumed after the k-loop
-    const int tid = tid_;
-    if (tid < C::BM) {
-      const int t = m0 + tid;
-      if constexpr (!DENSE) {
-        const float v = (t < T) ? ep.tau_vals[(size_t)t * ep.tau_ld + ep.tau_col] : 0.f;
-        side0 = (v > 0.f) ? v : __builtin_inff();     // degenerate / padded token: emit nothing
-      }
-      if (t < T) {
-        const f32x4 rc = ep.rowc[t];
-        side1 = rc[0];
-        side3 = rc[2];
-        side4 = 1.f;
-        if (C::I8 && op.Ao != nullptr) { side2 = (int)rc[1]; side4 = rc[1]; }
-        if constexpr (C::CERT || C::F8) side4 = rc[1];
-        if constexpr (C::I8 && !C::CERT) {
-          if (ep.row_e) { const int2 em = ep.row_e[t]; side6 = em.x; side2 = em.y; }
-        }
-      }
-    } else if (tid < C::BM + C::BN) {
-      const int n = n0 + tid - C::BM;
-      const int feat = gemm_feature(ep, n);
-      side0 = ep.bias ? ep.bias[feat] : 0.f;
-      const f32x4 cc = ep.colc[n];
-      side1 = cc[0];
-      side2 = __float_as_int(cc[1]);
-      side3 = cc[2];
-      side4 = cc[3];
-      if constexpr (C::I8 && !C::CERT) {
-        if (ep.col_ds) side6 = __float_as_int(ep.col_ds[n]);
-      }
-    }
-  }
   const bool has_out = C::I8 && op.Ao != nullptr;
+  const GemmSide<C> side(smem);
+  const typename GemmSide<C>::Regs side_regs = GemmSide<C>::template fetch<DENSE>(ep, tid_, m0, n0, T, has_out);
   [[maybe_unused]] const bool sub_e = C::I8 && !C::CERT && ep.row_e != nullptr;   // wave-uniform
   int lead_ks = 4;
   if (has_out && op.n_out != nullptr) lead_ks = (*op.n_out + 31) >> 5;    // wave-uniform scalar load
@@ -941,13 +985,10 @@ __global__ __launch_bounds__(C::NT) void gemm_kernel(GemmOperands op, int T, int
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;   // all-zero bits: also i32 zero
 
-  i32x4 abl_a[C::MI], abl_b[C::NI];
-  if constexpr (C::ABL_NOREAD) {
-#pragma unroll
-    for (int i = 0; i < C::MI; ++i) abl_a[i] = *reinterpret_cast<const i32x4 *>(op.A + (size_t)(m0 + i * 32 + l31) * op.ldA + kh * 16);
-#pragma unroll
-    for (int j = 0; j < C::NI; ++j) abl_b[j] = *reinterpret_cast<const i32x4 *>(op.B + (size_t)(n0 + j * 32 + l31) * op.ldB + kh * 16);
-  }
+  i32x4 abl_a[C::FA], abl_b[C::FB];
+  if constexpr (C::ABL_NOREAD)   // any fragments: the first ones of the tile's rows, straight from global memory
+    gemm_load_frags<C>(abl_a, abl_b, op.A + (size_t)m0 * op.ldA, op.B + (size_t)n0 * op.ldB, 0, 0, lane, 0,
+                       [&](const unsigned char *t, int row, int chunk) { return *reinterpret_cast<const i32x4 *>(t + (size_t)row * op.ldA + chunk * 16); });
 
   // tile sequence: [outlier tile (int8, optional)] then the nk main k-tiles
   const int lead = has_out ? 1 : 0;
@@ -999,21 +1040,12 @@ __global__ __launch_bounds__(C::NT) void gemm_kernel(GemmOperands op, int T, int
     stage(m0, n0, 0, 0);
   }
 
-  // m and -E of the tile's rows are parked EARLY (in front of the tile's first barrier), i.e. while slower waves of this persistent
-  // workgroup may still be in the PREVIOUS tile's epilogue: they may only go where that epilogue does not read -- the ROW parts of
-  // slots 2 and 6 (its rows' m comes from slot 4, E is not an epilogue input; the COLUMN part of slot 2 is Q_n, read by every
-  // gemm_band_sq).  Round 6 first packed the two as int2 across the whole of slot 2: a fast wave's next-tile pairs overwrote Q_n under
-  // the slow waves' band computations -- sample features' upper values went wrong at N = 262144 (four sample tiles per workgroup;
-  // 0.23 % of the tokens verified-and-wrong in tools/soak_fused.py, all missing features = 13 mod 32), found by the wide soak.
-  int *side_m = reinterpret_cast<int *>(smem + C::LDS_RING_BYTES) + 2 * C::NT;
-  [[maybe_unused]] int *side_e = reinterpret_cast<int *>(smem + C::LDS_RING_BYTES) + 6 * C::NT;
-  static_assert(C::BM + C::BN <= C::NT, "row part | column part of a side slot");
   auto iteration = [&](int kt, bool park_m = false) {
     MSAE_TLK(kt == 8, 0);
     MSAE_TLK(kt == 9, 5);
     wait_vmcnt<0>();               // this wave's pieces of k-tile kt (and the side constants) landed
-    if (park_m) {                  // outlier multipliers of the tile's rows -> LDS (read after this k-tile)
-      if (tid_ < C::BM) { side_m[tid_] = side2; if constexpr (C::I8 && !C::CERT) side_e[tid_] = -side6; }
+    if (park_m) {                  // outlier multipliers (and -E) of the tile's rows -> LDS (read after this k-tile)
+      side.park_early(tid_, side_regs);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
     MSAE_TLK(kt == 8, 1);
@@ -1040,14 +1072,14 @@ __global__ __launch_bounds__(C::NT) void gemm_kernel(GemmOperands op, int T, int
     MSAE_TLK(kt == 8, 3);
     const unsigned char *sA = smem + (seq & 1) * C::STAGE_BYTES;
     if (park_m) {
-      if (lead_compact) { if (lead_ks > 0) { if constexpr (C::I8) gemm_compute_lead_compact<C>(acc, sA, wr, wc, l31, kh); } }
-      else gemm_compute_lead<C>(acc, sA, sA + C::A_BYTES, wr, wc, l31, kh, lead_ks);
+      if (lead_compact) { if (lead_ks > 0) { if constexpr (C::I8) gemm_compute_lead_compact<C>(acc, sA, wr, wc, lane); } }
+      else gemm_compute_lead<C>(acc, sA, sA + C::A_BYTES, wr, wc, lane, lead_ks);
     }
     else if constexpr (!C::ABL_NOREAD && !C::ABL_NOMFMA && !C::ABL_NOSTAGE)
-      gemm_compute_asm<C>(acc, sA, wr, wc, l31, kh, [&](int pos) {
+      gemm_compute_asm<C>(acc, sA, wr, wc, lane, [&](int pos) {
         if (late && pos == MSAE_GEMM_STAGGER_AT) stage_next();
       });
-    else gemm_compute<C>(acc, sA, sA + C::A_BYTES, wr, wc, l31, kh, abl_a, abl_b);
+    else gemm_compute<C>(acc, sA, sA + C::A_BYTES, wr, wc, lane, abl_a, abl_b);
     MSAE_TLK(kt == 8, 4);
     ++seq;
   };
@@ -1060,9 +1092,7 @@ __global__ __launch_bounds__(C::NT) void gemm_kernel(GemmOperands op, int T, int
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         const int row = wr * C::TM + C::acc_row(i, e, tid_ & 63);
-        const int m = side_m[row];
-        int ee = 0;
-        if constexpr (C::I8 && !C::CERT) ee = side_e[row];     // -E (0 without the subtractive dither): one v_mad_i32_i24 per accumulator either way
+        const int m = side.early_m(row), ee = side.early_neg_e(row);   // one v_mad_i32_i24 per accumulator with or without -E
 #pragma unroll
         for (int j = 0; j < C::NI; ++j) {
           i32x16 v = __builtin_bit_cast(i32x16, acc[i][j]);
@@ -1098,39 +1128,10 @@ __global__ __launch_bounds__(C::NT) void gemm_kernel(GemmOperands op, int T, int
   }
 
   MSAE_TL(3);
-  // park the epilogue constants in LDS (side buffer behind the ring)
-  float *side = reinterpret_cast<float *>(smem + C::LDS_RING_BYTES);
-  side[tid_] = side0;
-  side[C::NT + tid_] = side1;
-  reinterpret_cast<int *>(side)[2 * C::NT + tid_] = side2;
-  side[3 * C::NT + tid_] = side3;
-  side[4 * C::NT + tid_] = side4;
-  if constexpr (C::I8 && !C::CERT) reinterpret_cast<int *>(side)[6 * C::NT + tid_] = side6;
-  if constexpr (!DENSE) {
-    // slot 5 of the separable bound, computed only now: the loads it needs had the whole k-loop to land
-    float side5 = 0.f;
-    if (tid_ < C::BM) {          // B_t: z sigma of this token against the reference feature
-      float b2 = side3 * ref0;
-      if constexpr (C::I8 || C::F8) {
-        const float rz = side1 * side1 * ep.zz12;
-        b2 = __builtin_fmaf(rz * side4 * side4, ref2, __builtin_fmaf(rz, ref1, b2));
-      }
-      side5 = __builtin_sqrtf(b2) * 1.00001f;
-    } else if (tid_ < C::BM + C::BN) {   // h_n >= sqrt of every ratio to the reference feature (0/0 counts as 0)
-      const float q = __int_as_float(side2);
-      float h2 = q / ref0;
-      if constexpr (C::I8 || C::F8) {
-        h2 = fmaxf(h2, side3 / ref1);
-        if (side4 > 0.f) h2 = fmaxf(h2, side4 / ref2);
-      }
-      side5 = (q > 0.f || side3 > 0.f || side4 > 0.f) ? __builtin_sqrtf(h2) * 1.00001f : 0.f;
-    }
-    side[5 * C::NT + tid_] = side5;
-  }
+  side.template park<DENSE>(tid_, side_regs, ep.zz12);
   // behind the epilogue's first barrier every wave is done with the last k-tile's slot: the next tile's first main
   // k-tile lands there while the epilogue runs (its outlier tile is already in the other slot)
-  gemm_epilogue<C, DENSE>(acc, ep, T, m0, n0, wr, wc, lane, smem, side,
-                          [] {}, tl_tile);
+  gemm_epilogue<C, DENSE>(acc, ep, T, m0, n0, wr, wc, lane, smem, side, tl_tile);
   MSAE_TL(6);
   }
 }

@@ -17,18 +17,13 @@
 #include "gemm_mfma.h"
 
 template <int BM_, int NW_ = 4>
-struct SkinnyCfg {
+struct SkinnyCfg : GemmEpiCfg<true, false, false, false> {   // int8, handed to gemm_epilogue as 32x32 accumulator blocks
   // NW waves per workgroup, 32 features each.  NW = 4: two workgroups share a CU (80 KB of LDS, 2 waves per SIMD at ~200
   // VGPRs each), so one's prologue / epilogue (~12 us each: dependent loads of the side constants, the outlier tile,
   // the queue flush's atomics) runs beside the other's stream; with ONE 8-wave workgroup per CU they were 50 us of a
   // 150 us pass.
   static constexpr int BM = BM_, NWAVES = NW_, BN = 32 * NW_, WM = 1, WN = NW_, NT = 64 * NW_;
   static constexpr int TM = BM, TN = 32, MI = BM / 32, NI = 1;
-  // 32x32 accumulator blocks: gemm_mfma.h's shared epilogue reads MF16 (its THRESH loop) and acc_row / acc_col
-  static constexpr bool MF16 = false;
-  static __device__ __forceinline__ int acc_row(int i, int e, int lane) { return i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5); }
-  static __device__ __forceinline__ int acc_col(int j, int lane) { return j * 32 + (lane & 31); }
-  static constexpr bool I8 = true, F8 = false, CERT = false, SCALED = true;   // (gemm_mfma.h's epilogue reads these)
   static constexpr int KC = (NW_ == 4 ? 32768 : 65536) / BM;   // bytes of k per A chunk
   // ADMA (the 256-token tile): the token rows travel L2 -> LDS by LDS-DMA (global_load_lds, as gemm_mfma.h's operands) instead of
   // through 32 registers per lane, which buys the B stream a second k-step in flight (UN = 2: 64 KB of weights in flight per CU
@@ -38,8 +33,7 @@ struct SkinnyCfg {
   static constexpr int PITCH = ADMA ? KC : KC + 16;     // row pitch of the LDS image (16 B pad: rows spread over the banks)
   static constexpr int A_BUF = BM * PITCH;
   static constexpr int LDS_RING_BYTES = 2 * A_BUF;
-  static constexpr int SIDE_SLOTS = 7;                  // (slot 6: gemm_mfma.h's subtractive-dither corrections)
-  static constexpr int SIDE_BYTES = SIDE_SLOTS * NT * 4;
+  static constexpr int SIDE_BYTES = gemm_side_bytes(NT);
   static constexpr int QCAP = 128 * NW_;                // ~0.5 % of BM x BN outputs pass the hot loop's bound
   static constexpr int LDS_BYTES = LDS_RING_BYTES + SIDE_BYTES + 16 + QCAP * 8;
   // k-steps (64 B of k each) per B batch (registers: 8 UN per batch; the accumulators take BM / 2 of the wave's budget)
@@ -64,43 +58,13 @@ __global__ __launch_bounds__(64 * NW) void gemm_skinny_kernel(GemmOperands op, i
   op.A += (size_t)m0 * op.ldA;
   if (op.Ao) op.Ao += (size_t)m0 * 128;
 
-  // ---- epilogue constants of this tile's rows / columns (registers now, LDS after the k-loop; as gemm_kernel)
-  float side0 = 0.f, side1 = 0.f, side3 = 0.f, side4 = 0.f;
-  int side2 = 1;
-  int side6 = 0;                                       // subtractive dither (gemm_mfma.h): E_t (rows) | float bits of Ds_n (columns)
-  float ref0 = 1.f, ref1 = 1.f, ref2 = 1.f;
-  if constexpr (!DENSE) { ref0 = ep.refs[0]; ref1 = ep.refs[1]; ref2 = ep.refs[2]; }
+  // ---- epilogue constants of this tile's rows / columns (registers now, LDS after the k-loop; as gemm_kernel), and (m, -E) of
+  // the rows, parked at once for acc = acc * m - E behind the outlier tile.  (One tile per workgroup: no previous epilogue can be
+  // running here, but the pair sits in GemmSide's EARLY locations all the same -- one layout, no precondition.)
   const bool has_out = op.Ao != nullptr;
-  if (tid < C::BM) {
-    const int t = tid;
-    if constexpr (!DENSE) {
-      const float v = (t < T) ? ep.tau_vals[(size_t)(m0 + t) * ep.tau_ld + ep.tau_col] : 0.f;
-      side0 = (v > 0.f) ? v : __builtin_inff();       // degenerate / padded token: emit nothing
-    }
-    if (t < T) {
-      const f32x4 rc = ep.rowc[m0 + t];
-      side1 = rc[0];
-      side3 = rc[2];
-      side4 = 1.f;
-      if (has_out) { side2 = (int)rc[1]; side4 = rc[1]; }
-      if (ep.row_e) { const int2 em = ep.row_e[m0 + t]; side6 = em.x; side2 = em.y; }
-    }
-  } else if (tid < C::BM + C::BN) {
-    const int n = n0 + tid - C::BM;
-    const int feat = gemm_feature(ep, n);
-    side0 = ep.bias ? ep.bias[feat] : 0.f;
-    const f32x4 cc = ep.colc[n];
-    side1 = cc[0];
-    side2 = __float_as_int(cc[1]);
-    side3 = cc[2];
-    side4 = cc[3];
-    if (ep.col_ds) side6 = __float_as_int(ep.col_ds[n]);
-  }
-  float *side = reinterpret_cast<float *>(smem + C::LDS_RING_BYTES);
-  // (m, -E) of the rows as int2 in slot 2 (free until the constants are parked behind the k-loop): acc = acc * m - E below
-  int2 *side_me = reinterpret_cast<int2 *>(reinterpret_cast<int *>(side) + 2 * C::NT);
-  static_assert(2 * C::BM <= C::NT, "the (m, -E) pairs fit one side slot");
-  if (tid < C::BM) side_me[tid] = int2{side2, -side6};
+  const GemmSide<C> side(smem);
+  const typename GemmSide<C>::Regs side_regs = GemmSide<C>::template fetch<DENSE>(ep, tid, m0, n0, m0 + T, has_out);
+  side.park_early(tid, side_regs);
   const bool sub_e = ep.row_e != nullptr;              // (wave-uniform)
 
   // v_mfma_i32_16x16x64_i8: A = 16 tokens x 64 B of k, B = 16 features x 64 B of k (lane l: row l % 16, bytes 16 (l / 16) ..),
@@ -214,15 +178,15 @@ __global__ __launch_bounds__(64 * NW) void gemm_skinny_kernel(GemmOperands op, i
       for (int tg = 0; tg < TG; ++tg)
         mfma(tg, *reinterpret_cast<const i32x4 *>(op.Ao + (size_t)(tg * 16 + l15) * 128 + ks * 64 + lg * 16), b);
     }
-    __syncthreads();                                   // side_me written
+    __syncthreads();                                   // (m, -E) parked
     if (lead_ks > 0 || sub_e) {                        // |acc| < 2^21 and m <= 1040 (quant_x_kernel: larger multipliers send the token to the exact path): the product fits int32
 #pragma unroll
       for (int tg = 0; tg < TG; ++tg)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int2 me = side_me[tg * 16 + lg * 4 + r];
-          acc16[tg][0][r] = __mul24(acc16[tg][0][r], me.x) + me.y;
-          acc16[tg][1][r] = __mul24(acc16[tg][1][r], me.x) + me.y;
+          const int row = tg * 16 + lg * 4 + r, m = side.early_m(row), ne = side.early_neg_e(row);
+          acc16[tg][0][r] = __mul24(acc16[tg][0][r], m) + ne;
+          acc16[tg][1][r] = __mul24(acc16[tg][1][r], m) + ne;
         }
     }
   }
@@ -308,27 +272,8 @@ __global__ __launch_bounds__(64 * NW) void gemm_skinny_kernel(GemmOperands op, i
   }
 
   // ---- epilogue constants -> LDS, then gemm_mfma.h's epilogue
-  side[tid] = side0;
-  side[C::NT + tid] = side1;
-  reinterpret_cast<int *>(side)[2 * C::NT + tid] = side2;
-  side[3 * C::NT + tid] = side3;
-  side[4 * C::NT + tid] = side4;
-  reinterpret_cast<int *>(side)[6 * C::NT + tid] = side6;
-  if constexpr (!DENSE) {
-    float side5 = 0.f;
-    if (tid < C::BM) {          // B_t: z sigma of this token against the reference feature
-      const float rz = side1 * side1 * ep.zz12;
-      const float b2 = __builtin_fmaf(rz * side4 * side4, ref2, __builtin_fmaf(rz, ref1, side3 * ref0));
-      side5 = __builtin_sqrtf(b2) * 1.00001f;
-    } else if (tid < C::BM + C::BN) {   // h_n >= sqrt of every ratio to the reference feature (0/0 counts as 0)
-      const float q = __int_as_float(side2);
-      float h2 = fmaxf(q / ref0, side3 / ref1);
-      if (side4 > 0.f) h2 = fmaxf(h2, side4 / ref2);
-      side5 = (q > 0.f || side3 > 0.f || side4 > 0.f) ? __builtin_sqrtf(h2) * 1.00001f : 0.f;
-    }
-    side[5 * C::NT + tid] = side5;
-  }
-  gemm_epilogue<C, DENSE>(acc, ep, m0 + T, m0, n0, 0, wave, lane, smem, side, [] {});
+  side.template park<DENSE>(tid, side_regs, ep.zz12);
+  gemm_epilogue<C, DENSE>(acc, ep, m0 + T, m0, n0, 0, wave, lane, smem, side);
 }
 
 // Host launcher: A = xq row-major [>= BM rows][d]; B = Wq fragment-major (op.packed = 3); optional

@@ -8,7 +8,8 @@ import sys
 
 src, dst = sys.argv[1], sys.argv[2]
 d = json.load(open(src))
-KEYS = {"gemm_kernel<int8,THRESH>": ("gemm_kernel<GemmCfg<256, 256, 2, 2, 4, true, 0>, false>",),
+KEYS = {"gemm_kernel<int8,THRESH>": ("gemm_kernel<GemmCfg<256, 256, 2, 2, 4, true, 128>, false>",   # 16x16x64 MFMAs (the default)
+                                     "gemm_kernel<GemmCfg<256, 256, 2, 2, 4, true, 0>, false>"),    # 32x32x32 (MSAE_GEMM_MF=32)
         "gemm_kernel<bf16,THRESH>": ("gemm_kernel<GemmCfg<256, 256, 2, 2, 4, false, 0>, false>",),
         # the re-score of the bench batch since round 4: PHASE 1 | counting sort | fm_dot_kernel (the row reads) | PHASE 2
         "fm_dot_kernel": ("fm_dot_kernel",), "select_rescore_kernel<PHASE 1>": ("select_rescore_kernel<1, false, false, 1>",),
