@@ -1,6 +1,6 @@
 // encode_cert.h -- the CERTIFIED candidate pass of the fused encoder (msae_options::certified; round-4 verdict, item 1b): both
 // operands as TWO int8 planes (15 bits), three MFMA segments, a DETERMINISTIC error band.  Host dispatch: encode_fused.hip
-// (run_cert); the GEMM is gemm_mfma.h's kernel with GemmOperands::cert set.
+// (run_cert fills a CandidatePass for run_candidate_pipeline); the GEMM is gemm_mfma.h's kernel with GemmOperands::cert set.
 //
 // Operands.  a_c = sxf (X_c + dx_c),  X_c = 128 xh_c + xl_c  (xh in [-127, 127], xl in [-64, 63], |dx_c| <= 1/2 + 2e-3)
 //            w_c = swf (W_c + dw_c),  W_c = 128 wh_c + wl_c  likewise, per feature row,

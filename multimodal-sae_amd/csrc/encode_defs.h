@@ -55,6 +55,9 @@ constexpr unsigned PREP_I8 = 2u;     // Wq row-major, tile-major (+ sample copie
 constexpr unsigned PREP_FRAG = 4u;   // Wq fragment-major (+ sample copy): the weight-stream kernels of <= 128 tokens
 constexpr unsigned PREP_F8 = 8u;     // fp8 (e4m3) operands, tile-major: ALL rows in the row-major int8 region (off_wq), the sample rows in off_wqsp
                                      // -- they overwrite int8 operands, so PREP_I8 / PREP_FRAG and PREP_F8 exclude each other
+// What a prepare / refresh is asked to REBUILD (prepare_impl's request; the PREP_* bits above say what a buffer then holds)
+constexpr int REQ_BF16 = 1, REQ_I8 = 2, REQ_F8 = 8;
+constexpr int REQ_NO_FRAG = 4;       // ... the int8 operands WITHOUT their fragment-major copies (a batch of > 256 tokens follows)
 
 __host__ __device__ inline bool fast_shape_ok(int N, int d) {
   return N % (SAMPLE_STRIDE * 256) == 0 && d % 64 == 0;  // sample width N/32 must tile by BN = 256

@@ -289,28 +289,28 @@ __global__ __launch_bounds__(256) void gather_wo_fp8_kernel(const float *__restr
   }
 }
 
-// pointers into a prepared buffer for the operand groups `modes` rebuilds (bit 1: int8 operands, bit 2: without the
-// fragment-major copies); stats are rebuilt by every mode
-inline RowQuantOut row_quant_out(unsigned char *base, const Prepared &p, int modes, bool i8) {
+// pointers into a prepared buffer for the operand groups the request `req` (REQ_* bits) rebuilds; stats are rebuilt by every request
+inline RowQuantOut row_quant_out(unsigned char *base, const Prepared &p, int req, bool i8) {
   RowQuantOut o{};
   o.wstat = reinterpret_cast<f32x4 *>(base + p.off_wstat); o.wstat_s = reinterpret_cast<f32x4 *>(base + p.off_wstat_s);
   o.colbf = reinterpret_cast<f32x4 *>(base + p.off_colbf); o.colbf_s = reinterpret_cast<f32x4 *>(base + p.off_colbf_s);
   o.layout = 1;
-  if ((modes & 2) && i8) {
+  if ((req & REQ_I8) && i8) {
     o.wq = reinterpret_cast<signed char *>(base + p.off_wq); o.wqs = reinterpret_cast<signed char *>(base + p.off_wqs);
     o.wqp = reinterpret_cast<signed char *>(base + p.off_wqp); o.wqsp = reinterpret_cast<signed char *>(base + p.off_wqsp);
     o.ds = reinterpret_cast<float *>(base + p.off_ds);
     o.sdtab = reinterpret_cast<const int *>(base + p.off_sdtab);
-    if (!(modes & 4)) {
+    if (!(req & REQ_NO_FRAG)) {
       o.wqf = reinterpret_cast<signed char *>(base + p.off_wqf); o.wqsf = reinterpret_cast<signed char *>(base + p.off_wqsf);
     }
   }
   return o;
 }
-// which operand groups a prepare / refresh of `modes` leaves valid (Prepared::valid)
-inline unsigned prep_valid_bits(int modes, int N, int d) {
-  if ((modes & 8) && i8_shape_ok(N, d)) return ((modes & 1) ? PREP_BF16 : 0u) | PREP_F8;   // (fp8 operands sit where int8 ones would)
-  return ((modes & 1) ? PREP_BF16 : 0u) | (((modes & 2) && i8_shape_ok(N, d)) ? (PREP_I8 | ((modes & 4) ? 0u : PREP_FRAG)) : 0u);
+// which operand groups a prepare / refresh of `req` leaves valid (Prepared::valid)
+inline unsigned prep_valid_bits(int req, int N, int d) {
+  const unsigned bf = (req & REQ_BF16) ? PREP_BF16 : 0u;
+  if ((req & REQ_F8) && i8_shape_ok(N, d)) return bf | PREP_F8;   // (fp8 operands sit where int8 ones would)
+  return bf | (((req & REQ_I8) && i8_shape_ok(N, d)) ? (PREP_I8 | ((req & REQ_NO_FRAG) ? 0u : PREP_FRAG)) : 0u);
 }
 
 // x side (every call).  Massive-activation dims would dictate the per-token scale and wipe out
@@ -435,7 +435,7 @@ __global__ __launch_bounds__(256) void quant_x_kernel(const void *__restrict__ x
     return;
   }
   // (SD: the buffer's seed; 0 = operands rounded to nearest behind a dithering call -- the stale-operand bit below sends the
-  // call to the exact path in that case, see run_fast)
+  // call to the exact path in that case, see prep_i8 in encode_fused.hip)
   [[maybe_unused]] const unsigned long long dseed = SD ? *dseed_p : 0ull;
   [[maybe_unused]] int e1 = 0;                     // 16 dims' share of sum g_w Aq over the token's own columns (2^-17 units; flushed per iteration)
   [[maybe_unused]] long long e1_64 = 0;

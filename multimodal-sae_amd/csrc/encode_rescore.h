@@ -173,7 +173,7 @@ __device__ __forceinline__ int count_ge(const unsigned long long *keys, int n, f
 // order, so each pair of them is a full lgkmcnt(0) round trip (128 per pass), which nothing hides when a token's
 // waves are alone on their SIMDs.
 //
-// PHASE (feature-major first round, run_fast): when a feature is a candidate of many tokens of the batch (k = 256 at 8192 tokens:
+// PHASE (feature-major first round, rescore_stage): when a feature is a candidate of many tokens of the batch (k = 256 at 8192 tokens:
 // 347 rows per token = 22 tokens per feature), the token-major first round reads every row of W_enc ~22 times from HBM.  PHASE 1
 // stops behind the choice of the first round and hands its (token, feature) pairs to a counting sort by feature; fm_dot_kernel
 // computes the same exact chains feature-major (W_enc once, the activations out of the Infinity Cache); PHASE 2 picks the
@@ -991,7 +991,7 @@ inline bool fm_pays(int T, int k, int N, int d, int esize) {
 }
 // lanes per feature group of fm_dot_kernel: 16 when a feature has >= ~12 pairs (k = 256 at 8192 tokens: 22), else 4
 inline int fm_group_lanes(int T, int k, int N) { return 1.36 * (double)T * k >= 12.0 * N ? 16 : 4; }
-// the plan's side (no activation type there: the workspace is sized for the 16-bit case, run_fast asks fm_pays() again)
+// the plan's side (no activation type there: the workspace is sized for the 16-bit case, rescore_stage asks fm_pays() again)
 inline bool fm_shape_ok(int T, int k, int N, int d, int r_max) {
   int nw, lpr;
   rescore_shape(T, k, nw, lpr);

@@ -11,7 +11,7 @@ HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 NAME="${MSAE_DBG_NAME:-libmsae_dbg.so}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -munsafe-fp-atomics -Wno-unused-function ${MSAE_DBG_FLAGS-}"
 OBJS=""
-for f in capi decode topk sparsify encode_f32 encode_fused train; do
+for f in capi decode topk sparsify feature_stats encode_f32 probe encode_fused train; do
   "$HIPCC" $FLAGS -c "$SRC/$f.hip" -o "$OBJ/$f.o" &
   OBJS="$OBJS $OBJ/$f.o"
 done
