@@ -222,6 +222,14 @@ __device__ __forceinline__ float band_sq(const f32x4 rc, const f32x4 cc, float z
   const float rz = rc[0] * rc[0] * zz12;
   return __builtin_fmaf(rc[2], cc[1], __builtin_fmaf(rz * rc[1] * rc[1], cc[3], rz * cc[2]));
 }
+// Model check of one re-scored pair: does the exact pre-activation `pre` contradict the coarse value (= upper - z sigma)?
+// |pre - coarse| <= sqrt(zc2) sigma  <=>  (pre - coarse)^2 z^2 <= zc2 (z sigma)^2;  zs2 = (z sigma)^2 of the pair, z2 = z^2.
+__device__ __forceinline__ bool contradicts_model(float pre, float upper, float zs2, float z2, float zc2) {
+  const float diff = pre - (upper - __builtin_sqrtf(zs2));
+  return diff * diff * z2 > zc2 * zs2 * 1.0001f + 1e-30f;
+}
+// result key of feature f with the exact pre-activation `pre`: its activation relu(pre) above the feature
+__device__ __forceinline__ unsigned long long result_key(float pre, int f) { return rank_key(pre > 0.f ? pre : 0.f, f); }
 
 // Dither of the activations (quant_x_kernel, prep_small_kernel): one 32-bit hash per element, keyed per token.
 //   key  = low word of mix64(seed + golden * (t + 1))      (once per thread and token)

@@ -420,34 +420,33 @@ int run_small(const EncodeCall &c, const FusedCtx &fx) {
 // select + exact re-score of the candidate lists (RescoreArgs filled by the caller): token-major, or with the FEATURE-major first
 // round where the plan has it and the cost model says it pays (encode_rescore.h)
 template <int DT>
-int rescore_stage(RescoreArgs &ra, const EncodeCall &c, unsigned char *ws, const FusedPlan &pl) {
+int rescore_stage(RescoreArgs &ra, const float *a32, const EncodeCall &c, unsigned char *ws, const FusedPlan &pl) {
   const int T = c.T, d = c.d, N = c.N, k = c.k;
   hipStream_t s = c.s;
-  const int nrp = next_pow2(pl.r_max + 1);
-  const size_t smem = ((size_t)pl.cap + nrp) * 8 + 64;
   // (fm_dot_kernel reads x in 16-B pieces; the entry points ask 8 B of a 16-bit x)
   if (!(pl.fm && msae_aligned(c.x, 16) && fm_pays(T, k, N, d, DT == MSAE_F32 ? 4 : 2)))
-    return launch_select_rescore<false>(ra, T, k, smem, ra.a32, c.W_enc, s);
+    return launch_select_rescore<false>(ra, a32, c.W_enc, s);
   int *fcount = at<int>(ws, pl.off_fmcount);
   int2 *pairs = at<int2>(ws, pl.off_fmpairs);
   float *fpre = at<float>(ws, pl.off_fmpre);
-  ra.fm_count = fcount; ra.fm_target = at<int>(ws, pl.off_fmtarget);
-  ra.fm_keys = at<u64>(ws, pl.off_fmkeys); ra.fm_pre = fpre; ra.fm_rcap = pl.r_max; ra.fm_cand = at<u64>(ws, pl.off_cand);
-  ra.fm_rank = reinterpret_cast<int *>(fpre);
-  ra.fm_defer = at<int>(ws, pl.off_fmdefer);
-  MSAE_HIP_TRY(hipMemsetAsync(ra.fm_defer, 0, (size_t)T * 2 * 4, s));
+  RescoreFm &fm = ra.fm;
+  fm.count = fcount; fm.target = at<int>(ws, pl.off_fmtarget);
+  fm.keys = at<u64>(ws, pl.off_fmkeys); fm.pre = fpre; fm.rcap = pl.r_max; fm.cand = at<u64>(ws, pl.off_cand);
+  fm.rank = reinterpret_cast<int *>(fpre);
+  fm.defer = at<int>(ws, pl.off_fmdefer);
+  MSAE_HIP_TRY(hipMemsetAsync(fm.defer, 0, (size_t)T * 2 * 4, s));
   MSAE_HIP_TRY(hipMemsetAsync(fcount, 0, ((size_t)N + 1) * 4, s));
-  const int lrc = launch_select_rescore<false, 1>(ra, T, k, smem, ra.a32, c.W_enc, s);
+  const int lrc = launch_select_rescore<false, 1>(ra, a32, c.W_enc, s);
   if (lrc) return lrc;
   const int scan_blocks = (N + FM_SCAN_BLOCK - 1) / FM_SCAN_BLOCK, G = fm_group_lanes(T, k, N);
   hipLaunchKernelGGL(fm_blocksum_kernel, dim3(scan_blocks), dim3(256), 0, s, fcount, N, G, fcount + N + 64);
   hipLaunchKernelGGL(fm_scan_kernel, dim3(scan_blocks), dim3(256), 0, s, fcount, N, G, fcount + N + 64, pairs);
-  hipLaunchKernelGGL(fm_scatter_kernel, dim3(T), dim3(256), 0, s, ra.fm_target, ra.fm_keys, ra.fm_rank, pl.r_max, fcount, pairs);
+  hipLaunchKernelGGL(fm_scatter_kernel, dim3(T), dim3(256), 0, s, fm.target, fm.keys, fm.rank, pl.r_max, fcount, pairs);
   const long max_slots = (long)T * pl.r_max + (long)N * (G - 1);
   const dim3 dgrid((unsigned)((max_slots + 63) / 64));
   if (G == 16) hipLaunchKernelGGL((fm_dot_kernel<DT, 16>), dgrid, dim3(64), 0, s, c.x, c.b_dec, c.W_enc, c.b_enc, pairs, fcount + N, d, pl.r_max, fpre);
   else hipLaunchKernelGGL((fm_dot_kernel<DT, 4>), dgrid, dim3(64), 0, s, c.x, c.b_dec, c.W_enc, c.b_enc, pairs, fcount + N, d, pl.r_max, fpre);
-  return launch_select_rescore<false, 2>(ra, T, k, smem, ra.a32, c.W_enc, s);
+  return launch_select_rescore<false, 2>(ra, a32, c.W_enc, s);
 }
 
 // ---- the candidate pipeline (stages 2 to 6 of the header) ------------------------------------------------------------------
@@ -578,17 +577,17 @@ int run_candidate_pipeline(const EncodeCall &c, unsigned char *ws, const FusedPl
   }
   {
     RescoreArgs ra{};
-    ra.a32 = a32; ra.W_enc = c.W_enc; ra.b_enc = c.b_enc;
+    ra.b_enc = c.b_enc;
     ra.tau_vals = tauv; ra.tau_ld = pl.r; ra.tau_col = pl.r - 1;
     ra.cnt = cnt; ra.cand = cand; ra.cap = pl.cap;
-    ra.T = T; ra.d = c.d; ra.N = N; ra.k = c.k; ra.r_max = pl.r_max;
+    ra.T = T; ra.d = c.d; ra.k = c.k; ra.r_max = pl.r_max;
     ra.rowc = rowc; ra.colc = cp.colc; ra.zz12 = cp.zzx; ra.z2 = cp.z2; ra.i8 = cp.i8; ra.zc2 = cp.zc2;
-    ra.set_feature = c.set_feature; ra.set_value = c.set_value; ra.zero_feature = c.zero_feature;
+    ra.set_feature = c.set_feature; ra.set_value = c.set_value;
     ra.vals = c.vals; ra.idx = c.idx.i32; ra.idx64 = c.idx.i64; ra.status = c.status;
     ra.flagged = pl.fb.flagged(ws); ra.n_flagged = pl.fb.n_flagged(ws, T);
     ra.fb_cap = T;
     ra.rows_out = co.rows_out;
-    const int lrc = rescore_stage<DT>(ra, c, ws, pl);
+    const int lrc = rescore_stage<DT>(ra, a32, c, ws, pl);
     if (lrc) return lrc;
   }
   prof_mark(co.prof, 5, s);
@@ -1112,21 +1111,19 @@ int run_rescore_ext(const EncodeCall &c, const ShardRecords &sr, unsigned char *
   hipLaunchKernelGGL(prep_x_kernel<DT>, dim3(2048), dim3(256), 0, c.s, c.x, c.b_dec, T_valid, T_valid, c.d,
                      (unsigned short *)nullptr, a32);
   RescoreArgs ra{};
-  ra.a32 = a32; ra.W_enc = c.W_enc; ra.b_enc = c.b_enc;
+  ra.b_enc = c.b_enc;
   ra.cap = xp.cap;
-  ra.T = T_valid; ra.d = c.d; ra.N = c.N; ra.k = c.k; ra.r_max = xp.r_max;
+  ra.T = T_valid; ra.d = c.d; ra.k = c.k; ra.r_max = xp.r_max;
   ra.zz12 = z * z / 12.f; ra.z2 = z * z; ra.i8 = 0;
   // (the records' z sigma came from shards running with the same options; large batches subtract the dither there -- actual
   // sigma --, small ones carry Hoeffding's proxy: 6 of either is the net under operands edited behind the API)
   ra.zc2 = guard_z_check2(false);
-  ra.set_feature = c.set_feature; ra.set_value = c.set_value; ra.zero_feature = c.zero_feature;
+  ra.set_feature = c.set_feature; ra.set_value = c.set_value;
   ra.vals = c.vals; ra.idx = nullptr; ra.idx64 = c.idx.i64; ra.status = c.status;
   ra.flagged = flagged; ra.n_flagged = xp.fb.n_flagged(ws, T);
   ra.fb_cap = T;
-  ra.ext = sr.recs; ra.ext_G = sr.G; ra.ext_C = sr.C; ra.ext_T = T; ra.ext_stride = shard_record_bytes(sr.C); ra.ext_valid = T_valid;
-  const int nrp = next_pow2(xp.r_max + 1);
-  const size_t smem = ((size_t)xp.cap + nrp) * 8 + (size_t)xp.cap * 8 + 64;
-  const int lrc = launch_select_rescore<true>(ra, T_valid, c.k, smem, (const float *)a32, c.W_enc, c.s);
+  ra.ext = RescoreExt{sr.recs, sr.G, sr.C, T, shard_record_bytes(sr.C), T_valid};
+  const int lrc = launch_select_rescore<true>(ra, a32, c.W_enc, c.s);
   if (lrc) return lrc;
   const int rc = run_exact_fallback(c, ws, xp.fb, co.detail);
   return rc ? rc : msae_launch_status();

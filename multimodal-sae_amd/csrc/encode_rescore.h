@@ -1,41 +1,48 @@
 // encode_rescore.h -- behind the candidate GEMM: per-token candidate select + exact f32 re-score + verification
 // (select_rescore_kernel), the feature-sharded group's record packing (pack_candidates_kernel), and their launchers.
-// Host dispatch: encode_fused.hip.
+// Sort / select primitives: encode_sortsel.h.  Host dispatch: encode_fused.hip.
 #pragma once
 #include <type_traits>
 
 #include "encode_defs.h"
+#include "encode_sortsel.h"
 
 namespace {
 
 // ---- candidate select + exact re-score ----------------------------------------------------------
 static_assert(MSAE_RESCORE_U * 4 == 64, "one re-scoring batch must be the 64 floats fast_shape_ok() guarantees");
+// EXT (feature-sharded group, msae_rescore_candidates): the candidate lists come as the shards' records instead of
+// cnt / cand / tau_vals / rowc / colc: record (g, t) at recs + ((size_t)g * T + t) * stride; the first `valid` token rows hold tokens
+struct RescoreExt { const unsigned char *recs; int G, C, T, stride, valid; };
+// FEATURE-MAJOR first round (PHASE 1 / 2 of select_rescore_kernel, fm_* kernels below): per-feature pair counts [N + 1],
+// first-round size per token (| FM_SORTED), the first-round keys [T][rcap], their exact pre-activations [T][rcap]
+struct RescoreFm {
+  int *count; int *target; unsigned long long *keys; const float *pre; int rcap;
+  unsigned long long *cand;           // = RescoreArgs::cand, writable: PHASE 1 leaves a fully sorted list there for PHASE 2
+  int *rank;                          // = pre's storage: a pair's rank inside its feature, between PHASE 1 and the scatter
+  // LEAN / full pairs of PHASE kernels: defer[(PHASE - 1) * T + t] != 0 <=> the LEAN launch left token t to the full one;
+  // all != 0: this (full) launch takes every token (no LEAN launch ran for the phase)
+  int *defer; int all;
+};
+// (the activations a32 [T][d] and W_enc are kernel parameters of their own: __restrict__ there is what makes the loads of the
+// activations scalar)
 struct RescoreArgs {
-  const float *a32; const float *W_enc, *b_enc;
+  const float *b_enc;
   const float *tau_vals; int tau_ld, tau_col;
   const int *cnt; const unsigned long long *cand; int cap;
-  int T, d, N, k, r_max;
-  int set_feature; float set_value; int zero_feature;
+  int T, d, k, r_max;
+  int set_feature; float set_value;
   const f32x4 *rowc, *colc;           // error-band constants per token / per feature
   float zz12, z2; int i8;
   float zc2;                          // (model check) a re-scored pair further than sqrt(zc2) sigma from its coarse value flags the token
   float *vals; int32_t *idx; int64_t *idx64; int32_t *status;   // idx / idx64: either may be null
   int *flagged; int *n_flagged; int fb_cap;
   int32_t *rows_out;                  // optional diagnostics (msae_options::rows_rescored)
-  // EXT (feature-sharded group, msae_rescore_candidates): the candidate lists come as the shards' records
-  // instead of cnt / cand / tau_vals / rowc / colc: record (g, t) at ext + ((size_t)g * ext_T + t) * ext_stride
-  const unsigned char *ext; int ext_G, ext_C, ext_T, ext_stride, ext_valid;
   int lpr;   // lanes per row in the first round (1, 2, 4): small batches need the extra bytes in flight (rescore_shape)
-  // FEATURE-MAJOR first round (PHASE 1 / 2 of select_rescore_kernel, fm_* kernels below): per-feature pair counts [N + 1],
-  // first-round size per token (| FM_SORTED), the first-round keys [T][fm_rcap], their exact pre-activations [T][fm_rcap]
-  int *fm_count; int *fm_target; unsigned long long *fm_keys; const float *fm_pre; int fm_rcap;
-  unsigned long long *fm_cand;        // = cand, writable: PHASE 1 leaves a fully sorted list there for PHASE 2
-  int *fm_rank;                       // = fm_pre's storage: a pair's rank inside its feature, between PHASE 1 and the scatter
-  // LEAN / full pairs of PHASE kernels: fm_defer[(PHASE - 1) * T + t] != 0 <=> the LEAN launch left token t to the full one;
-  // fm_all != 0: this (full) launch takes every token (no LEAN launch ran for the phase)
-  int *fm_defer; int fm_all;
+  RescoreExt ext;
+  RescoreFm fm;
 };
-// fm_target[t] = first-round size (12 bits) | sorted prefix saved in fm_keys (8 bits, PHASE 1's preselect) << 12 | FM_SORTED
+// fm.target[t] = first-round size (12 bits) | sorted prefix saved in fm.keys (8 bits, PHASE 1's preselect) << 12 | FM_SORTED
 constexpr int FM_SORTED = 1 << 30;   // the token's whole list was written back to cand in sorted order
 constexpr int FM_TARGET_MASK = 0xFFF, FM_PREFIX_SHIFT = 12, FM_PREFIX_MASK = 0xFF;
 
@@ -44,110 +51,391 @@ constexpr int FM_TARGET_MASK = 0xFFF, FM_PREFIX_SHIFT = 12, FM_PREFIX_MASK = 0xF
 // the shard NOT in the record can have (+inf: the shard could not bound it -> the token is recomputed exactly).
 __host__ __device__ inline int shard_record_bytes(int C) { return C * 12 + 8; }
 
-// Wave-wide bitonic sort (descending) of n = power-of-two u64 keys in LDS by ONE 64-lane wave.
-template <int NT>
-__device__ __forceinline__ void wave_sort_desc_u64(unsigned long long *s, int n, int lane) {
-  for (int size = 2; size <= n; size <<= 1)
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      __syncthreads();
-      for (int i = lane; i < (n >> 1); i += NT) {
-        const int lo = (i / stride) * (stride << 1) + (i % stride), hi = lo + stride;
-        const bool desc = ((lo & size) == 0);
-        const unsigned long long x = s[lo], y = s[hi];
-        if ((x < y) == desc) { s[lo] = y; s[hi] = x; }
-      }
-    }
-  __syncthreads();
+// Key slots of a LEAN launch (the 4-wave PHASE 1 sorts whole lists of up to 2048 keys in registers and needs the slots as its
+// exchange buffer only)
+__host__ __device__ constexpr int lean_key_slots(int nw, int phase) { return nw == 1 ? 256 : (phase == 1 ? 2048 : 512); }
+
+// The dynamic LDS of select_rescore_kernel, byte offsets: keys[key_slots] u64 | res[nrp] u64 | ezs[ext_cap] f32 |
+// ef[ext_cap] i32 | a[a_floats] f32 | 64 bytes of slack.  The kernel takes its pointers from it, the launcher its sizes.
+struct RescoreLds {
+  int key_slots, nrp;
+  unsigned keys, res, ezs, ef, a, total;
+  __host__ __device__ RescoreLds(int key_slots_, int nrp_, int ext_cap, int a_floats)
+      : key_slots(key_slots_), nrp(nrp_), keys(0u), res(8u * key_slots_), ezs(res + 8u * nrp_), ef(ezs + 4u * ext_cap),
+        a(ef + 4u * ext_cap), total(a + 4u * a_floats + 64u) {}
+};
+// ... of one launch: a LEAN one has lean_key_slots() instead of the list's cap; the results are r_max + 1 keys rounded up to a
+// power of two (a LEAN PHASE 1 has none: it ends before the first result); ext: the EXT kernels' lookup arrays; a_floats: d
+// for the LDSA kernels, else 0
+__host__ __device__ inline RescoreLds rescore_lds(int nw, int phase, bool lean, int cap, int r_max, bool ext, int a_floats) {
+  return RescoreLds(lean ? lean_key_slots(nw, phase) : cap, lean && phase == 1 ? 0 : next_pow2(r_max + 1), ext ? cap : 0, a_floats);
 }
 
-// The same order for <= 64 R keys by ONE wave in registers: key i = r * 64 + lane sits in v[r]; partners 64 or more apart are
-// the lane's own registers, closer ones another lane's (two 32-bit shuffles).  No LDS traffic, no barriers: a 64-key sort is
-// 21 compare-exchange steps of ~10 instructions (the LDS version: 21 barriers, ~10 k cycles for a wave that is alone).
-template <int R>
-__device__ __forceinline__ void wave_sort_desc_u64_regs(unsigned long long (&v)[R], int lane) {
-#pragma unroll
-  for (int size = 2; size <= 64 * R; size <<= 1)
-#pragma unroll
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      if (stride >= 64) {
-        constexpr int dummy = 0; (void)dummy;
-        const int rs = stride >> 6;
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-          if ((r & rs) == 0) {
-            const bool desc = (((r * 64 + lane) & size) == 0);
-            const unsigned long long a = v[r], b = v[r | rs];
-            if ((a < b) == desc) { v[r] = b; v[r | rs] = a; }
-          }
-        }
-      } else {
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-          const int i = r * 64 + lane;
-          const unsigned lo = __shfl_xor((unsigned)v[r], stride, 64), hi = __shfl_xor((unsigned)(v[r] >> 32), stride, 64);
-          const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-          // the lower index of a pair keeps the larger key where the block sorts descending
-          const bool lower = (lane & stride) == 0, desc = ((i & size) == 0);
-          const bool take_max = lower == desc;
-          v[r] = take_max ? (v[r] > o ? v[r] : o) : (v[r] < o ? v[r] : o);
-        }
-      }
-    }
+template <int NW_, bool EXT_, bool LDSA_, int PHASE_, bool LEAN_>
+struct RescoreCfg {
+  static constexpr int NW = NW_, PHASE = PHASE_, NT = 64 * NW_, LEAN_KEYS = lean_key_slots(NW_, PHASE_);
+  static constexpr bool EXT = EXT_, LDSA = LDSA_, LEAN = LEAN_;
+  static_assert(!LEAN || (PHASE != 0 && !EXT && !LDSA), "LEAN: the PHASE kernels of the single-GPU path");
+};
+
+// What one workgroup works on: its token, its regions of the dynamic LDS (RescoreLds), the token's candidate list (load_list)
+struct RescoreToken {
+  __device__ __forceinline__ RescoreToken(unsigned char *smem, const RescoreLds &lds)
+      : t(blockIdx.x), lane(threadIdx.x), keys(reinterpret_cast<unsigned long long *>(smem + lds.keys)),
+        res(reinterpret_cast<unsigned long long *>(smem + lds.res)), ezs(reinterpret_cast<float *>(smem + lds.ezs)),
+        ef(reinterpret_cast<int *>(smem + lds.ef)), a_lds(reinterpret_cast<float *>(smem + lds.a)), kcap(lds.key_slots), nrp(lds.nrp) {}
+  int t, lane;                          // token; thread index within the token's workgroup
+  unsigned long long *keys, *res;       // the list's keys [kcap] (the sorted prefix, KeyPrefix); the result keys [nrp]
+  float *ezs; int *ef;                  // EXT only: [cap] z sigma / global feature by list position
+  float *a_lds;                         // LDSA only: [d] the token's activations
+  int kcap, nrp;
+  int cnt, n, np;                       // candidates found; of them in the list (<= cap); n rounded up to a power of two
+  float tau;                            // no feature outside the list has an upper value above tau
+  f32x4 rc = {0.f, 0.f, 0.f, 0.f};      // the token's error-band constants (local lists)
+};
+
+// LDSA: the token's activations -> LDS (no barrier: the caller publishes them)
+template <class C>
+__device__ __forceinline__ void stage_activations(const RescoreToken &tk, const float *__restrict__ a, int d) {
+  for (int i = 4 * tk.lane; i < d; i += 4 * C::NT)
+    *reinterpret_cast<f32x4 *>(tk.a_lds + i) = *reinterpret_cast<const f32x4 *>(a + i);
 }
 
-// ... and for 64 NW R keys by a WORKGROUP of NW waves: key i = tid * R + r sits in v[r] of thread tid.  Partners closer than R
-// are the thread's own registers, up to 32 R apart another lane's (shuffles), farther another wave's: those few steps
-// (3 of 66 for 2048 keys) go through `xch` (LDS, 64 NW R keys) behind barriers.  All threads call.
-template <int NW, int R>
-__device__ __forceinline__ void wg_sort_desc_u64_regs(unsigned long long (&v)[R], int tid, unsigned long long *xch) {
-  constexpr int M = 64 * NW * R;
-#pragma unroll
-  for (int size = 2; size <= M; size <<= 1)
-#pragma unroll
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      if (stride < R) {
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-          if ((r & stride) == 0) {
-            const bool desc = (((tid * R + r) & size) == 0);
-            const unsigned long long a = v[r], b = v[r | stride];
-            if ((a < b) == desc) { v[r] = b; v[r | stride] = a; }
-          }
-        }
-      } else {
-        const int pt = stride / R;                         // partner thread = tid ^ pt
-        const bool lower = (tid & pt) == 0;
-        if (pt >= 64) {
-          __syncthreads();
-#pragma unroll
-          for (int r = 0; r < R; ++r) xch[tid * R + r] = v[r];
-          __syncthreads();
-        }
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-          unsigned long long o;
-          if (pt >= 64) o = xch[(tid ^ pt) * R + r];
-          else o = ((unsigned long long)__shfl_xor((unsigned)(v[r] >> 32), pt, 64) << 32) | __shfl_xor((unsigned)v[r], pt, 64);
-          const bool desc = (((tid * R + r) & size) == 0);
-          const bool take_max = lower == desc;
-          v[r] = take_max ? (v[r] > o ? v[r] : o) : (v[r] < o ? v[r] : o);
+// Step 1: the token's candidate list, tau and row constants -- from the local buffers (the keys stay in cand[]: KeyPrefix fetches
+// them) or (EXT) from the shards' records: keys[] = the union of the records, zero-padded to np, the list POSITION in the low word;
+// published by the barrier at the end.  No side effects outside LDS.
+template <class C>
+__device__ __forceinline__ void load_list(const RescoreArgs &p, RescoreToken &tk) {
+  const int t = tk.t, lane = tk.lane;
+  if constexpr (C::EXT) {
+    __shared__ int s_n;
+    __shared__ unsigned s_tau;
+    const RescoreExt &x = p.ext;
+    const int M = x.G * x.C;
+    tk.np = next_pow2(M > 2 ? M : 2);
+    if (lane == 0) { s_n = 0; s_tau = 0u; }
+    __syncthreads();
+    int mine = 0;
+    for (int i = lane; i < tk.np; i += C::NT) {
+      unsigned long long kv = 0ull;
+      if (i < M) {
+        const int g = i / x.C, j = i - g * x.C;
+        const unsigned char *rec = x.recs + ((size_t)g * x.T + t) * x.stride;
+        const unsigned long long key = reinterpret_cast<const unsigned long long *>(rec)[j];
+        if (key != 0ull) {
+          kv = (key & 0xFFFFFFFF00000000ull) | (unsigned)(0x7FFFFFFF - i);
+          tk.ef[i] = rank_key_index(key);
+          tk.ezs[i] = reinterpret_cast<const float *>(rec + (size_t)x.C * 8)[j];
+          ++mine;
         }
       }
+      tk.keys[i] = kv;
     }
-}
-
-// number of keys (sorted descending, value in the upper 32 bits as an order key) whose value is >= v
-__device__ __forceinline__ int count_ge(const unsigned long long *keys, int n, float v) {
-  const unsigned tk = f32_order_key(v);
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if ((unsigned)(keys[mid] >> 32) >= tk) lo = mid + 1; else hi = mid;
+    if (mine) atomicAdd(&s_n, mine);
+    for (int g = lane; g < x.G; g += C::NT) {   // tau = the largest bound of ALL shards (order keys: +inf dominates, NaN never enters)
+      const unsigned char *rec = x.recs + ((size_t)g * x.T + t) * x.stride;
+      atomicMax(&s_tau, f32_order_key(*reinterpret_cast<const float *>(rec + (size_t)x.C * 12)));
+    }
+    __syncthreads();
+    tk.n = tk.cnt = s_n;
+    tk.tau = f32_from_order_key(s_tau);
+  } else {
+    tk.cnt = p.cnt[t];
+    tk.n = tk.cnt < p.cap ? tk.cnt : p.cap;
+    tk.tau = p.tau_vals[(size_t)t * p.tau_ld + p.tau_col];
+    tk.rc = p.rowc[t];
+    tk.np = next_pow2(tk.n > 2 ? tk.n : 2);
   }
-  return lo;
 }
 
-// ONE WAVE per token (64-thread workgroup; 4 waves for k > 64).  dynamic LDS: keys[cap] u64 | res[nrp] u64.
+// Step 2: the sorted prefix of the list.  keys[0, n_sorted) hold the n_sorted largest keys in descending order (upper value desc,
+// index asc on ties).  PARTIAL: of a list of ~650 candidates a token uses the first 40-60, so the prefix is usually not the whole
+// list; whoever then needs a candidate behind it (count_needed, the target check of a round: need_full) gets the full sort after
+// all -- the prefix is the same keys in the same places.  A LEAN launch has no room for the whole list of most tokens: there the
+// token is DEFERRED to the full-size launch instead (the caller leaves; nothing here has a side effect outside LDS).
+// Every member is wave-uniform, so the barriers of the sorts are not in divergent code.
+template <class C>
+struct KeyPrefix {
+  // preselect: a list of PRE_MIN < n <= 64 PRE_PK keys gives a prefix of PRE_LO..PRE_HI
+  static constexpr int PRE_LO = 96, PRE_HI = 128, PRE_MIN = 192, PRE_PK = 32;
+  int n_sorted;
+  bool partial = false;                  // n_sorted < n: keys[] does not hold the whole list
+  bool presorted = false;                // PHASE 2: PHASE 1 left the whole list sorted in cand[]
+  bool deferred = false;                 // LEAN: this token needs the full-size launch
+
+  __device__ __forceinline__ KeyPrefix(const RescoreArgs &p, const RescoreToken &tk) : n_sorted(tk.n) {
+    if constexpr (C::PHASE == 2) presorted = (p.fm.target[tk.t] & FM_SORTED) != 0;
+  }
+
+  // the whole list sorted in keys[0, np): four waves sort up to 2048 keys in registers (half of the k = 256 tokens have <= 1024
+  // candidates: 4 keys per thread; else 8, keys[] being the exchange buffer)
+  __device__ __forceinline__ void full_sort(const RescoreArgs &p, const RescoreToken &tk) {
+    if constexpr (C::LEAN) { if (tk.np > C::LEAN_KEYS) { deferred = true; return; } }
+    if constexpr (!C::EXT) {               // (EXT: load_list put them there)
+      __syncthreads();
+      for (int i = tk.lane; i < tk.np; i += C::NT) tk.keys[i] = (i < tk.n) ? p.cand[(size_t)tk.t * p.cap + i] : 0ull;
+    }
+    if (presorted) __syncthreads();
+    else lds_sort_desc_u64<C::NW, (C::NW == 4 && !C::EXT) ? 8 : 0>(tk.keys, tk.np, tk.kcap, tk.lane);
+    partial = false;
+    n_sorted = tk.n;
+  }
+  __device__ __forceinline__ void need_full(const RescoreArgs &p, const RescoreToken &tk) {
+    if constexpr (C::LEAN) deferred = true; else full_sort(p, tk);
+  }
+  // candidates with u >= v (over the whole list)
+  __device__ __forceinline__ int count_needed(const RescoreArgs &p, const RescoreToken &tk, float v) {
+    int c = count_ge(tk.keys, n_sorted, v);
+    if (partial && c >= n_sorted) { need_full(p, tk); if (!deferred) c = count_ge(tk.keys, tk.n, v); }
+    return c;
+  }
+
+  // The three ways a partial prefix comes to exist (`partial` says whether it did; the keys are published).
+  // PHASE 2: a prefix that is sorted already -- `have` keys at src, zero-padded to `slots`
+  __device__ __forceinline__ void adopt(const RescoreToken &tk, const unsigned long long *src, int have, int slots) {
+    for (int i = tk.lane; i < slots; i += C::NT) tk.keys[i] = i < have ? src[i] : 0ull;
+    __syncthreads();
+    partial = true;
+    n_sorted = have;
+  }
+  // One wave, local lists: SELECT the PRE_LO..PRE_HI largest (keys in registers, bisection on the value word with ballot
+  // counts, a handful of steps) and sort only those PRE_HI slots.  Ties across the window: no such threshold -> no prefix.
+  __device__ __forceinline__ void preselect(const RescoreArgs &p, const RescoreToken &tk) {
+    static_assert(C::NW == 1 && !C::EXT, "one wave holds the list in registers");
+    const int n = tk.n, lane = tk.lane;
+    if (!(msae_tuning::RESCORE_PRESELECT && !presorted && n > PRE_MIN && n <= 64 * PRE_PK && p.k + 4 <= 64)) return;
+    const int nj = (n + 63) >> 6;
+    unsigned long long kreg[PRE_PK];
+    wave_load_keys<PRE_PK>(kreg, p.cand + (size_t)tk.t * p.cap, n, nj, lane);
+    unsigned lo = 0u, hi = 0xFFFFFFFFu;     // count(value word >= lo) > PRE_HI, count(>= hi) < PRE_LO
+    int c_sel = -1;
+    unsigned thr = 0u;
+    while (hi - lo > 1u) {
+      const unsigned mid = lo + ((hi - lo) >> 1);
+      const int c = wave_count_if<PRE_PK>(kreg, nj, [mid](unsigned long long key) { return (unsigned)(key >> 32) >= mid; });
+      if (c > PRE_HI) lo = mid;
+      else if (c < PRE_LO) hi = mid;
+      else { c_sel = c; thr = mid; break; }
+    }
+    if (c_sel <= 0) return;
+    wave_compact_if<PRE_PK>(kreg, nj, lane, [thr](unsigned long long key) { return (unsigned)(key >> 32) >= thr; },
+                            [&tk](unsigned long long key, bool take, int pos) { if (take) tk.keys[pos] = key; });
+    for (int i = c_sel + lane; i < PRE_HI; i += C::NT) tk.keys[i] = 0ull;
+    lds_sort_desc_u64<1, 2>(tk.keys, PRE_HI, tk.kcap, lane);     // two keys per lane, in registers
+    partial = true;
+    n_sorted = c_sel;
+  }
+};
+
+// Step 3: size of the first round: the candidates with u >= (k-th largest coarse value among the first mt) - zeta * (their median
+// sigma), at least k + 4, at most lim.  May need the whole list (count_needed): the caller checks pre.deferred.
+template <class C>
+__device__ __forceinline__ int first_round_target(const RescoreArgs &p, const RescoreToken &tk, KeyPrefix<C> &pre, int has_set, int lim) {
+  __shared__ float s_cc[C::NT], s_zs[C::NT], s_pick[2];
+  const int lane = tk.lane;
+  int target = lim;
+  const int mt_max = p.k <= 64 ? 64 : C::NT;       // the same statistic whatever the number of waves per token
+  const int mt = tk.n < mt_max ? tk.n : mt_max;
+  float my_cc = -__builtin_inff(), my_zs = 0.f;
+  if (lane < mt) {
+    const unsigned long long key = tk.keys[lane];
+    if constexpr (C::EXT) my_zs = tk.ezs[rank_key_index(key)];
+    else my_zs = __builtin_sqrtf(band_sq(tk.rc, p.colc[rank_key_index(key)], p.zz12, p.i8 != 0));
+    my_cc = f32_from_order_key((unsigned)(key >> 32)) - my_zs;
+  }
+  s_cc[lane] = my_cc;
+  s_zs[lane] = my_zs;
+  if (lane < 2) s_pick[lane] = lane == 0 ? -__builtin_inff() : 0.f;
+  __syncthreads();
+  const int kk = p.k - has_set;
+  if (lane < mt && kk >= 1 && kk <= mt) {
+    int rank_c = 0, rank_z = 0;
+    for (int j = 0; j < mt; ++j) {
+      const float cj = s_cc[j], zj = s_zs[j];
+      rank_c += (cj > my_cc || (cj == my_cc && j < lane)) ? 1 : 0;
+      rank_z += (zj < my_zs || (zj == my_zs && j < lane)) ? 1 : 0;
+    }
+    if (rank_c == kk - 1) s_pick[0] = my_cc;
+    if (rank_z == mt / 2) s_pick[1] = my_zs;
+  }
+  __syncthreads();
+  if (kk >= 1 && kk <= mt && p.z2 > 0.f) {
+    const float thr1 = s_pick[0] - GUARD_ZETA * s_pick[1] * __builtin_amdgcn_rsqf(p.z2);
+    int n1 = pre.count_needed(p, tk, thr1);
+    if (n1 < p.k + 4) n1 = p.k + 4;
+    target = n1 < lim ? n1 : lim;
+  }
+  if constexpr (C::LDSA && C::PHASE == 0) {   // small batch: one pass reads 64 NW / lpr rows whatever the target -- fill it (fewer second rounds)
+    const int rpp = p.lpr > 0 ? C::NT / p.lpr : C::NT;
+    const int fill = rpp < lim ? rpp : lim;
+    if (target < fill) target = fill;
+  }
+  return target;
+}
+
+// Step 4 (PHASE 1, SIDE EFFECTS: the atomicAdd on fm.count and global stores -- a LEAN launch defers a token before it, never
+// behind): the first round's keys (the counting sort reads them), behind them the rest of a preselected prefix for PHASE 2, and
+// the whole list in sorted order where it was sorted.
+template <class C>
+__device__ __forceinline__ void phase1_emit(const RescoreArgs &p, const RescoreToken &tk, const KeyPrefix<C> &pre, int target) {
+  const int t = tk.t;
+  const int save = pre.partial && pre.n_sorted <= p.fm.rcap && pre.n_sorted <= FM_PREFIX_MASK ? pre.n_sorted : 0;
+  for (int c = tk.lane; c < (target > save ? target : save); c += C::NT) {
+    const unsigned long long key = tk.keys[c];
+    p.fm.keys[(size_t)t * p.fm.rcap + c] = key;
+    // the count's old value is this pair's rank among its feature's pairs: the scatter needs no second atomic (the rank
+    // waits in the pair's slot of fm.pre, which fm_dot_kernel fills later)
+    if (c < target) p.fm.rank[(size_t)t * p.fm.rcap + c] = atomicAdd(p.fm.count + rank_key_index(key), 1);
+  }
+  if (!pre.partial)
+    for (int i = tk.lane; i < tk.n; i += C::NT) p.fm.cand[(size_t)t * p.cap + i] = tk.keys[i];
+  if (tk.lane == 0) p.fm.target[t] = target | (save << FM_PREFIX_SHIFT) | (pre.partial ? 0 : FM_SORTED);
+}
+
+// Step 5: exact pre-activations of the candidates [done, target) into res[], token-major.  Returns whether a pair of this lane
+// contradicted the error model.
+// LPR = 1: lane c streams row c (16 B per lane and instruction).  LPR = 4: four lanes share a row, lane q loading bytes
+// [16 q, 16 q + 16) of every 64-B piece -- four times fewer cache lines per instruction, but only 16 rows per pass, i.e. three
+// row-streaming latencies per round instead of one.  The chain stays one serial ascending-k sequence: sub-step q multiplies the
+// group's lane-q piece (every lane executes it on its own registers; only lane q's is the true partial sum) and a quad rotate
+// hands the accumulator on.  The activations are wave-uniform scalar operands (a[], SGPRs) or, LDSA, this lane's own piece
+// from LDS.
+template <class C, int LPR>
+__device__ __forceinline__ int rescore_pass(const RescoreArgs &p, const RescoreToken &tk, const float *__restrict__ a,
+                                            const float *__restrict__ W_enc, int has_set, int done, int target) {
+  constexpr int RPP = C::NT / LPR;                 // rows per pass
+  constexpr int RS_B = 4 * MSAE_RESCORE_U * LPR;   // floats of a row per batch
+  const int rq = tk.lane / LPR, q = tk.lane % LPR;
+  int my_viol = 0;
+  for (int c0 = done; c0 < target; c0 += RPP) {
+    const int c = c0 + rq;
+    const bool active = c < target;
+    const unsigned long long key = active ? tk.keys[c] : tk.keys[c0];
+    int f = rank_key_index(key);
+    float ext_zs = 0.f;
+    f32x4 cc = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (C::EXT) { ext_zs = tk.ezs[f]; f = tk.ef[f]; }     // list position -> (z sigma, global feature)
+    else cc = p.colc[f];
+    const float upper = f32_from_order_key((unsigned)(key >> 32));
+    const float *__restrict__ w = W_enc + (size_t)f * p.d + 4 * q;
+    float acc = 0.f;
+    // two batches of MSAE_RESCORE_U x 16 B per lane, software-pipelined: while one batch is consumed the
+    // other is in flight, so the lane never drains its loads
+    f32x4 wa[MSAE_RESCORE_U], wb[MSAE_RESCORE_U];
+    auto fetch = [&](f32x4 (&dst)[MSAE_RESCORE_U], int kk) {
+#pragma unroll
+      for (int u = 0; u < MSAE_RESCORE_U; ++u) dst[u] = *reinterpret_cast<const f32x4 *>(w + kk + 4 * LPR * u);
+    };
+    auto consume = [&](const f32x4 (&src)[MSAE_RESCORE_U], int kk) {
+#pragma unroll
+      for (int u = 0; u < MSAE_RESCORE_U; ++u) {
+        [[maybe_unused]] f32x4 av;                   // LDSA: the activations of this lane's own piece
+        if constexpr (C::LDSA) av = *reinterpret_cast<const f32x4 *>(tk.a_lds + kk + 4 * LPR * u + 4 * q);
+#pragma unroll
+        for (int qq = 0; qq < LPR; ++qq) {
+          [[maybe_unused]] const int k0 = kk + 4 * LPR * u + 4 * qq;
+          if constexpr (C::LDSA) {                   // only sub-step qq == q carries the true partial sum
+            acc = __builtin_fmaf(av[0], src[u][0], acc);
+            acc = __builtin_fmaf(av[1], src[u][1], acc);
+            acc = __builtin_fmaf(av[2], src[u][2], acc);
+            acc = __builtin_fmaf(av[3], src[u][3], acc);
+          } else {
+            acc = __builtin_fmaf(a[k0 + 0], src[u][0], acc);   // a[] is wave-uniform: SGPRs
+            acc = __builtin_fmaf(a[k0 + 1], src[u][1], acc);
+            acc = __builtin_fmaf(a[k0 + 2], src[u][2], acc);
+            acc = __builtin_fmaf(a[k0 + 3], src[u][3], acc);
+          }
+          if constexpr (LPR == 4)   // quad_perm:[3,0,1,2] -- lane i takes lane i - 1's value, lane 0 lane 3's
+            acc = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc), 0x93, 0xF, 0xF, false));
+          if constexpr (LPR == 2)   // quad_perm:[1,0,3,2] -- the two lanes of a pair swap
+            acc = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc), 0xB1, 0xF, 0xF, false));
+        }
+      }
+    };
+    fetch(wa, 0);
+    for (int kk = 0; kk < p.d; kk += 2 * RS_B) {     // d % RS_B == 0 (fast_shape_ok / the caller's choice of LPR)
+      const bool has_b = kk + RS_B < p.d;
+      if (has_b) fetch(wb, kk + RS_B);
+      consume(wa, kk);
+      if (kk + 2 * RS_B < p.d) fetch(wa, kk + 2 * RS_B);
+      if (has_b) consume(wb, kk + RS_B);
+    }
+    const float pre = acc + (p.b_enc ? p.b_enc[f] : 0.f);
+    if (active && q == 0) {                          // whole pieces done: the sum is back in the group's lane 0
+      tk.res[has_set + c] = result_key(pre, f);      // slots past the sorted prefix are 0
+      const float zs2 = C::EXT ? ext_zs * ext_zs : band_sq(tk.rc, cc, p.zz12, p.i8 != 0);
+      if (contradicts_model(pre, upper, zs2, p.z2, p.zc2)) my_viol = 1;
+    }
+  }
+  return my_viol;
+}
+// PHASE 2's first round: fm_dot_kernel computed the values
+template <class C>
+__device__ __forceinline__ int fm_pickup(const RescoreArgs &p, const RescoreToken &tk, int has_set, int target) {
+  int my_viol = 0;
+  for (int c = tk.lane; c < target; c += C::NT) {
+    const unsigned long long key = tk.keys[c];
+    const int f = rank_key_index(key);
+    const float upper = f32_from_order_key((unsigned)(key >> 32));
+    const float pre = p.fm.pre[(size_t)tk.t * p.fm.rcap + c];
+    tk.res[has_set + c] = result_key(pre, f);
+    if (contradicts_model(pre, upper, band_sq(tk.rc, p.colc[f], p.zz12, p.i8 != 0), p.z2, p.zc2)) my_viol = 1;
+  }
+  return my_viol;
+}
+
+// Step 6: what the sorted results say: v_k = the exact k-th value so far, needed = the candidates with u >= v_k.  The token
+// VERIFIES (returns true) when all of those are re-scored, v_k > tau and nothing contradicted the model; the rounds end (last)
+// with that, or when no further round can help.  May need the whole list (count_needed): the caller checks pre.deferred.
+template <class C>
+__device__ __forceinline__ bool verify(const RescoreArgs &p, const RescoreToken &tk, KeyPrefix<C> &pre, int has_set, int done,
+                                       int lim, bool viol, bool guarded, int &needed, bool &last) {
+  const bool have_k = done + has_set >= p.k;
+  const float v_k = f32_from_order_key((unsigned)(tk.res[p.k - 1] >> 32));
+  const bool list_ok = tk.cnt <= p.cap && tk.tau > 0.f;
+  needed = have_k ? pre.count_needed(p, tk, v_k) : tk.n;
+  const bool ok = list_ok && have_k && !viol && needed <= done && v_k > tk.tau * 1.000001f && !guarded;
+  last = ok || viol || guarded || done >= lim || !list_ok;
+  return ok;
+}
+
+// LEAN: the token is left to the full-size launch (the only store of a token that is given up)
+template <class C>
+__device__ __forceinline__ void defer_token(const RescoreArgs &p, const RescoreToken &tk) {
+  if (tk.lane == 0) p.fm.defer[(size_t)(C::PHASE - 1) * p.T + tk.t] = 1;
+}
+
+// Step 7 (SIDE EFFECTS: global stores, the atomicAdd on n_flagged): the token's outputs, status word, rows_rescored word, and
+// its place in the flagged list if it did not verify.
+template <class C>
+__device__ __forceinline__ void write_token(const RescoreArgs &p, const RescoreToken &tk, bool ok, bool viol, bool guarded,
+                                            int has_set, int done, int rounds, int first_target) {
+  const int t = tk.t;
+  for (int j = tk.lane; j < p.k; j += C::NT) {
+    const unsigned long long key = tk.res[j];
+    const int fi = key ? rank_key_index(key) : 0;
+    if (p.idx) p.idx[(size_t)t * p.k + j] = fi;
+    if (p.idx64) p.idx64[(size_t)t * p.k + j] = fi;
+    p.vals[(size_t)t * p.k + j] = key ? f32_from_order_key((unsigned)(key >> 32)) : 0.f;
+  }
+  if (tk.lane == 0) {
+    // not verified: 2 | reason bits (4 list overflow, 8 tau <= 0, 16 fewer than k candidates,
+    // 32 more than r_max rows needed / v_k not above tau, 64 a re-scored pair contradicted the error
+    // model); the exact fallback rewrites it to 1 once it has recomputed t
+    const int reason = 2 | (tk.cnt > p.cap ? 4 : 0) | (!(tk.tau > 0.f) ? 8 : 0) |
+                       (done + has_set < p.k ? 16 : 0) | (guarded ? 128 : (viol ? 64 : 32));
+    if (p.status) p.status[t] = ok ? 0 : reason;
+    // msae_options::rows_rescored: [1 << 30: first round feature-major] | rounds << 24 | first-round rows << 12 | rows of W_enc
+    // this token read (0: not verified here)
+    if (p.rows_out) p.rows_out[t] = ok ? (C::PHASE == 2 ? 1 << 30 : 0) | ((rounds & 0x3F) << 24) | ((first_target < 0xFFF ? first_target : 0xFFF) << 12) | (done < 0xFFF ? done : 0xFFF) : 0;   // (12-bit fields saturate)
+    if (!ok) {
+      const int slot = atomicAdd(p.n_flagged, 1);
+      if (slot < p.fb_cap) p.flagged[slot] = t;
+    }
+  }
+}
+
+// ONE WAVE per token (64-thread workgroup; 4 waves for k > 64).  Dynamic LDS: RescoreLds.
 //
 // The candidate list is ordered by the UPPER value u = coarse + z*sigma; lane c re-scores candidate c
 // with the exact ascending-k f32 chain: it walks row f of W_enc with two software-pipelined batches
@@ -182,444 +470,94 @@ __device__ __forceinline__ int count_ge(const unsigned long long *keys, int n, f
 // tokens a CU works on at a time is set by the LDS a workgroup claims, and that is sized for the worst token (the whole list:
 // 16-32 KB) although nearly every token is done with a sorted prefix of 128-512 keys.  A LEAN launch claims the prefix only
 // (6 KB at k = 32: 28 tokens per CU instead of 4-7) and LEAVES a token to the full-size launch behind it -- before any side
-// effect -- the moment it would need the whole list (a full sort, a candidate behind the prefix) or a follow-up round.
+// effect -- the moment it would need the whole list (a full sort, a candidate behind the prefix) or a follow-up round: every
+// `if constexpr (LEAN) { ... defer_token(); return; }` below stands in front of the steps with side effects (phase1_emit, write_token).
 template <int NW, bool EXT = false, bool LDSA = false, int PHASE = 0, bool LEAN = false>   // NW waves per token: 1 for k <= 64, 4 for larger k (longer lists)
 __global__ __launch_bounds__(64 * NW) void select_rescore_kernel(RescoreArgs p, const float *__restrict__ a32,
                                                             const float *__restrict__ W_enc) {
+  using C = RescoreCfg<NW, EXT, LDSA, PHASE, LEAN>;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  unsigned long long *keys = reinterpret_cast<unsigned long long *>(smem);
-  const int nrp = next_pow2(p.r_max + 1);
-  static_assert(!LEAN || (PHASE != 0 && !EXT && !LDSA), "LEAN: the PHASE kernels of the single-GPU path");
-  // key slots of a LEAN launch (the 4-wave PHASE 1 sorts whole lists of up to 2048 keys in registers and needs the slots as
-  // its exchange buffer only; PHASE 1 has no results: no res[] behind the keys)
-  constexpr int LEAN_KEYS = NW == 1 ? 256 : (PHASE == 1 ? 2048 : 512);
-  const int kcap = LEAN ? LEAN_KEYS : p.cap;
-  unsigned long long *res = keys + kcap;
-  [[maybe_unused]] float *ezs = reinterpret_cast<float *>(res + nrp);     // EXT only: [cap] z sigma by list position
-  [[maybe_unused]] int *ef = reinterpret_cast<int *>(ezs + p.cap);        // EXT only: [cap] global feature by position
-  [[maybe_unused]] float *a_lds = EXT ? reinterpret_cast<float *>(ef + p.cap) : ezs;   // LDSA only: [d]
-  constexpr int NT = 64 * NW;
-  __shared__ float s_cc[NT], s_zs[NT], s_pick[2];
-  __shared__ int s_n;
-  __shared__ unsigned s_tau;
-  const int lane = threadIdx.x;   // thread index within the token's workgroup
-  const int t = blockIdx.x;
-  if constexpr (EXT) { if (t >= p.ext_valid) return; }
-  if constexpr (PHASE != 0 && !LEAN) { if (!p.fm_all && p.fm_defer[(size_t)(PHASE - 1) * p.T + t] == 0) return; }   // the LEAN launch did it
-  [[maybe_unused]] bool deferred = false;             // LEAN: this token needs the full-size launch (wave-uniform)
-#define MSAE_LEAN_BAIL()                                                                   \
-  do {                                                                                     \
-    if constexpr (LEAN) {                                                                  \
-      if (deferred) {                                                                      \
-        if (lane == 0) p.fm_defer[(size_t)(PHASE - 1) * p.T + t] = 1;                      \
-        return;                                                                            \
-      }                                                                                    \
-    }                                                                                      \
-  } while (0)
-  int cnt, n;
-  float tau;
+  RescoreToken tk(smem, rescore_lds(NW, PHASE, LEAN, p.cap, p.r_max, EXT, LDSA ? p.d : 0));
+  const int t = tk.t, lane = tk.lane;
+  if constexpr (EXT) { if (t >= p.ext.valid) return; }
+  if constexpr (PHASE != 0 && !LEAN) { if (!p.fm.all && p.fm.defer[(size_t)(PHASE - 1) * p.T + t] == 0) return; }   // the LEAN launch did it
   MSAE_RTL(0);
   const float *__restrict__ a = a32 + (size_t)t * p.d;  // noalias kernel arg + uniform address: s_load
-  auto stage_a = [&]() {
-    for (int i = 4 * (int)threadIdx.x; i < p.d; i += 4 * 64 * NW)
-      *reinterpret_cast<f32x4 *>(a_lds + i) = *reinterpret_cast<const f32x4 *>(a + i);
-  };
   // (PHASE 2 stages them when a token gets a follow-up round: its first round read no row here)
-  if constexpr (LDSA && PHASE == 0) stage_a();            // published by the barriers of the list sort below
-  f32x4 rc = {0.f, 0.f, 0.f, 0.f};
-  const bool i8 = p.i8 != 0;
-  int np;
-  if constexpr (EXT) {
-    const int M = p.ext_G * p.ext_C;
-    np = next_pow2(M > 2 ? M : 2);
-    if (lane == 0) { s_n = 0; s_tau = 0u; }
-    __syncthreads();
-    int mine = 0;
-    for (int i = lane; i < np; i += NT) {
-      unsigned long long kv = 0ull;
-      if (i < M) {
-        const int g = i / p.ext_C, j = i - g * p.ext_C;
-        const unsigned char *rec = p.ext + ((size_t)g * p.ext_T + t) * p.ext_stride;
-        const unsigned long long key = reinterpret_cast<const unsigned long long *>(rec)[j];
-        if (key != 0ull) {
-          kv = (key & 0xFFFFFFFF00000000ull) | (unsigned)(0x7FFFFFFF - i);
-          ef[i] = rank_key_index(key);
-          ezs[i] = reinterpret_cast<const float *>(rec + (size_t)p.ext_C * 8)[j];
-          ++mine;
-        }
-      }
-      keys[i] = kv;
-    }
-    if (mine) atomicAdd(&s_n, mine);
-    for (int g = lane; g < p.ext_G; g += NT) {   // tau = the largest bound of ALL shards (order keys: +inf dominates, NaN never enters)
-      const unsigned char *rec = p.ext + ((size_t)g * p.ext_T + t) * p.ext_stride;
-      atomicMax(&s_tau, f32_order_key(*reinterpret_cast<const float *>(rec + (size_t)p.ext_C * 12)));
-    }
-    __syncthreads();
-    n = cnt = s_n;
-    tau = f32_from_order_key(s_tau);
-  } else {
-    cnt = p.cnt[t];
-    n = cnt < p.cap ? cnt : p.cap;
-    tau = p.tau_vals[(size_t)t * p.tau_ld + p.tau_col];
-    rc = p.rowc[t];
-    np = next_pow2(n > 2 ? n : 2);
-  }
-  if constexpr (PHASE != 1) { for (int i = lane; i < nrp; i += NT) res[i] = 0ull; }
+  if constexpr (LDSA && PHASE == 0) stage_activations<C>(tk, a, p.d);   // published by the barriers of the list sort below
+  load_list<C>(p, tk);
+  if constexpr (PHASE != 1) { for (int i = lane; i < tk.nrp; i += C::NT) tk.res[i] = 0ull; }
   MSAE_RTL(1);
-  // keys[0, n_sorted) hold the n_sorted largest keys in descending order (upper value desc, index asc on ties).
-  // PARTIAL: of a list of ~650 candidates a token uses the first 40-60, so one wave first SELECTS its PRE_LO..PRE_HI
-  // largest (keys in registers, bisection on the value word with ballot counts, a handful of steps) and sorts only
-  // those 128 slots; whoever then needs a candidate behind them (count_needed, the target check of a round) gets the
-  // full sort after all -- the presorted prefix is the same keys in the same places.
-  constexpr int PRE_LO = 96, PRE_HI = 128, PRE_MIN = 192, PRE_PK = 32;
-  int n_sorted = n;
-  bool partial = false;
-  bool presorted = false;                      // PHASE 2: PHASE 1 left the list sorted in place
-  if constexpr (PHASE == 2) presorted = (p.fm_target[t] & FM_SORTED) != 0;
-  bool have_keys = false;                      // keys[0, n_sorted) already hold a sorted prefix of the list
-  auto full_sort = [&]() {
-    if constexpr (LEAN) { if (np > LEAN_KEYS) { deferred = true; return; } }
-    if constexpr (!EXT) {
-      __syncthreads();
-      for (int i = lane; i < np; i += NT) keys[i] = (i < n) ? p.cand[(size_t)t * p.cap + i] : 0ull;
-    }
-    if (presorted) { __syncthreads(); return; }
-    if constexpr (NW == 4 && !EXT) {
-      if (np <= 1024 && kcap >= 1024) {                    // (round 6) half of the k = 256 tokens have <= 1024 candidates: 4 keys per thread, 55 stages instead of 66
-        __syncthreads();
-        unsigned long long v4[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v4[r] = lane * 4 + r < np ? keys[lane * 4 + r] : 0ull;
-        wg_sort_desc_u64_regs<4, 4>(v4, lane, keys);
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < 4; ++r) keys[lane * 4 + r] = v4[r];
-        __syncthreads();
-        return;
-      }
-      if (np <= 2048 && kcap >= 2048) {                    // wave-uniform: 8 keys per thread, sorted in registers (keys[] = the exchange buffer: 2048 slots)
-        __syncthreads();
-        unsigned long long v8[8];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) v8[r] = lane * 8 + r < np ? keys[lane * 8 + r] : 0ull;
-        wg_sort_desc_u64_regs<4, 8>(v8, lane, keys);
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < 8; ++r) keys[lane * 8 + r] = v8[r];
-        __syncthreads();
-        return;
-      }
-    }
-    wave_sort_desc_u64<NT>(keys, np, lane);
-  };
-  if constexpr (PHASE == 2 && NW == 1) {      // PHASE 1's preselected + sorted prefix, as it left it
-    const int saved = (p.fm_target[t] >> FM_PREFIX_SHIFT) & FM_PREFIX_MASK;
-    if (!presorted && saved > 0) {
-      for (int i = lane; i < PRE_HI; i += NT) keys[i] = i < saved ? p.fm_keys[(size_t)t * p.fm_rcap + i] : 0ull;
-      __syncthreads();
-      partial = true;
-      n_sorted = saved;
-      have_keys = true;
-    }
+
+  KeyPrefix<C> pre(p, tk);
+  if constexpr (PHASE == 2 && NW == 1) {       // PHASE 1's preselected + sorted prefix, as it left it in fm.keys
+    const int saved = (p.fm.target[t] >> FM_PREFIX_SHIFT) & FM_PREFIX_MASK;
+    if (!pre.presorted && saved > 0) pre.adopt(tk, p.fm.keys + (size_t)t * p.fm.rcap, saved, pre.PRE_HI);
   }
   if constexpr (PHASE == 2 && LEAN) {          // ... or the first LEAN_KEYS of the list PHASE 1 sorted in place
-    if (presorted && n > LEAN_KEYS) {
-      for (int i = lane; i < LEAN_KEYS; i += NT) keys[i] = p.cand[(size_t)t * p.cap + i];
-      __syncthreads();
-      partial = true;
-      n_sorted = LEAN_KEYS;
-      have_keys = true;
-    }
+    if (pre.presorted && tk.n > C::LEAN_KEYS) pre.adopt(tk, p.cand + (size_t)t * p.cap, C::LEAN_KEYS, C::LEAN_KEYS);
   }
-  if constexpr (!EXT && NW == 1) {
-    if (msae_tuning::RESCORE_PRESELECT && !presorted && !partial && n > PRE_MIN && n <= 64 * PRE_PK && p.k + 4 <= 64) {          // wave-uniform
-      const int nj = (n + 63) >> 6;
-      unsigned long long kreg[PRE_PK];
-#pragma unroll
-      for (int j = 0; j < PRE_PK; ++j) {
-        const int i = j * 64 + lane;
-        kreg[j] = (j < nj && i < n) ? p.cand[(size_t)t * p.cap + i] : 0ull;
-      }
-      unsigned lo = 0u, hi = 0xFFFFFFFFu;     // count(value word >= lo) > PRE_HI, count(>= hi) < PRE_LO
-      int c_sel = -1;
-      unsigned thr = 0u;
-      while (hi - lo > 1u) {
-        const unsigned mid = lo + ((hi - lo) >> 1);
-        int c = 0;
-#pragma unroll
-        for (int jb = 0; jb < PRE_PK; jb += 8) {             // one branch per eight key slots (empty slots hold 0)
-          if (jb < nj) {
-#pragma unroll
-            for (int j = jb; j < jb + 8; ++j)
-              c += __builtin_popcountll(__builtin_amdgcn_ballot_w64((unsigned)(kreg[j] >> 32) >= mid));
-          }
-        }
-        if (c > PRE_HI) lo = mid;
-        else if (c < PRE_LO) hi = mid;
-        else { c_sel = c; thr = mid; break; }
-      }
-      if (c_sel > 0) {                                       // (ties across the window: no such threshold -> full sort)
-        int base = 0;
-#pragma unroll
-        for (int j = 0; j < PRE_PK; ++j) {
-          if (j < nj) {
-            const bool take = (unsigned)(kreg[j] >> 32) >= thr;
-            const unsigned long long m = __builtin_amdgcn_ballot_w64(take);
-            if (take) keys[base + __builtin_popcountll(m & ((1ull << lane) - 1ull))] = kreg[j];
-            base += __builtin_popcountll(m);
-          }
-        }
-        for (int i = c_sel + lane; i < PRE_HI; i += NT) keys[i] = 0ull;
-        {   // the PRE_HI = 128 slots: two keys per lane, sorted in registers
-          static_assert(PRE_HI == 2 * NT, "two key slots per lane");
-          __syncthreads();
-          unsigned long long v2[2] = {keys[lane], keys[64 + lane]};
-          wave_sort_desc_u64_regs<2>(v2, lane);
-          keys[lane] = v2[0]; keys[64 + lane] = v2[1];
-          __syncthreads();
-        }
-        partial = true;
-        n_sorted = c_sel;
-        have_keys = true;
-      }
-    }
-  }
-  if (!have_keys) full_sort();
-  MSAE_LEAN_BAIL();
-  auto need_full = [&]() {
-    if constexpr (LEAN) { deferred = true; return; }
-    full_sort(); partial = false; n_sorted = n;
-  };
-  auto count_needed = [&](float v) {         // candidates with u >= v (over the whole list)
-    int c = count_ge(keys, n_sorted, v);
-    if (partial && c >= n_sorted) { need_full(); if (!deferred) c = count_ge(keys, n, v); }
-    return c;
-  };
+  if constexpr (!EXT && NW == 1) { if (!pre.partial) pre.preselect(p, tk); }
+  if (!pre.partial) pre.full_sort(p, tk);
+  if constexpr (LEAN) { if (pre.deferred) { defer_token<C>(p, tk); return; } }
   MSAE_RTL(2);
   const int has_set = p.set_feature >= 0 ? 1 : 0;
-  if constexpr (PHASE != 1) { if (lane == 0 && has_set) res[0] = rank_key(p.set_value, p.set_feature); }
+  if constexpr (PHASE != 1) { if (lane == 0 && has_set) tk.res[0] = rank_key(p.set_value, p.set_feature); }
 
-  // ---- size of the first round ------------------------------------------------------------------
-  const int lim = n < p.r_max ? n : p.r_max;
-  int target = lim;
-  if constexpr (PHASE == 2) {
-    target = p.fm_target[t] & FM_TARGET_MASK;
-  } else {
-    const int mt_max = p.k <= 64 ? 64 : NT;       // the same statistic whatever the number of waves per token
-    const int mt = n < mt_max ? n : mt_max;
-    float my_cc = -__builtin_inff(), my_zs = 0.f;
-    if (lane < mt) {
-      const unsigned long long key = keys[lane];
-      if constexpr (EXT) my_zs = ezs[rank_key_index(key)];
-      else my_zs = __builtin_sqrtf(band_sq(rc, p.colc[rank_key_index(key)], p.zz12, i8));
-      my_cc = f32_from_order_key((unsigned)(key >> 32)) - my_zs;
-    }
-    s_cc[lane] = my_cc;
-    s_zs[lane] = my_zs;
-    if (lane < 2) s_pick[lane] = lane == 0 ? -__builtin_inff() : 0.f;
-    __syncthreads();
-    const int kk = p.k - has_set;
-    if (lane < mt && kk >= 1 && kk <= mt) {
-      int rank_c = 0, rank_z = 0;
-      for (int j = 0; j < mt; ++j) {
-        const float cj = s_cc[j], zj = s_zs[j];
-        rank_c += (cj > my_cc || (cj == my_cc && j < lane)) ? 1 : 0;
-        rank_z += (zj < my_zs || (zj == my_zs && j < lane)) ? 1 : 0;
-      }
-      if (rank_c == kk - 1) s_pick[0] = my_cc;
-      if (rank_z == mt / 2) s_pick[1] = my_zs;
-    }
-    __syncthreads();
-    if (kk >= 1 && kk <= mt && p.z2 > 0.f) {
-      const float thr1 = s_pick[0] - GUARD_ZETA * s_pick[1] * __builtin_amdgcn_rsqf(p.z2);
-      int n1 = count_needed(thr1);
-      MSAE_LEAN_BAIL();
-      if (n1 < p.k + 4) n1 = p.k + 4;
-      target = n1 < lim ? n1 : lim;
-    }
-  }
-  if constexpr (LDSA && PHASE == 0) {   // small batch: one pass reads 64 NW / lpr rows whatever the target -- fill it (fewer second rounds)
-    const int rpp = p.lpr > 0 ? NT / p.lpr : NT;
-    const int fill = rpp < lim ? rpp : lim;
-    if (target < fill) target = fill;
-  }
-
+  const int lim = tk.n < p.r_max ? tk.n : p.r_max;
+  int target;
+  if constexpr (PHASE == 2) target = p.fm.target[t] & FM_TARGET_MASK;
+  else target = first_round_target<C>(p, tk, pre, has_set, lim);
+  if constexpr (LEAN) { if (pre.deferred) { defer_token<C>(p, tk); return; } }
   MSAE_RTL(3);
-  const float zc2 = p.zc2;
-  const bool guarded = !EXT && rc[3] != 0.f;     // the token's shape is outside the noise model (quant_x_kernel): exact path
+  const bool guarded = !EXT && tk.rc[3] != 0.f;  // the token's shape is outside the noise model (quant_x_kernel): exact path
   if (guarded) target = 0;                       // (no row is read for it here)
   if constexpr (PHASE == 1) {
-    if (partial && target > n_sorted) need_full();          // wave-uniform
-    MSAE_LEAN_BAIL();
-    // the first round's keys (the counting sort reads them), and behind them the rest of a preselected prefix for PHASE 2
-    const int save = partial && n_sorted <= p.fm_rcap && n_sorted <= FM_PREFIX_MASK ? n_sorted : 0;
-    for (int c = lane; c < (target > save ? target : save); c += NT) {
-      const unsigned long long key = keys[c];
-      p.fm_keys[(size_t)t * p.fm_rcap + c] = key;
-      // the count's old value is this pair's rank among its feature's pairs: the scatter needs no second atomic (the rank
-      // waits in the pair's slot of fm_pre, which fm_dot_kernel fills later)
-      if (c < target) p.fm_rank[(size_t)t * p.fm_rcap + c] = atomicAdd(p.fm_count + rank_key_index(key), 1);
-    }
-    if (!partial)
-      for (int i = lane; i < n; i += NT) p.fm_cand[(size_t)t * p.cap + i] = keys[i];
-    if (lane == 0) p.fm_target[t] = target | (save << FM_PREFIX_SHIFT) | (partial ? 0 : FM_SORTED);
+    if (pre.partial && target > pre.n_sorted) pre.need_full(p, tk);          // wave-uniform
+    if constexpr (LEAN) { if (pre.deferred) { defer_token<C>(p, tk); return; } }
+    phase1_emit<C>(p, tk, pre, target);
     return;
   }
-  int done = 0;                                  // candidates re-scored so far (wave-uniform)
+
+  int done = 0, rounds = 0;                      // candidates re-scored so far (wave-uniform)
   bool ok = false, viol = false;
-  int rounds = 0;
   const int first_target = target;
   for (;;) {
     ++rounds;
+    if (pre.partial && target > pre.n_sorted) pre.need_full(p, tk);          // wave-uniform
+    if constexpr (LEAN) { if (pre.deferred) { defer_token<C>(p, tk); return; } }
     int my_viol = 0;
-    // LPR = 1: lane c streams row c (16 B per lane and instruction).  LPR = 4 (tuning builds): four lanes share a
-    // row, lane q loading bytes [16 q, 16 q + 16) of every 64-B piece -- four times fewer cache lines per
-    // instruction, but only 16 rows per pass, i.e. three row-streaming latencies per round instead of one.  The
-    // chain stays one serial ascending-k sequence: sub-step q multiplies the group's lane-q piece (every lane
-    // executes it on its own registers; only lane q's is the true partial sum) and a quad rotate hands the
-    // accumulator on.  The activations are wave-uniform scalar operands either way.
-    auto run_pass = [&](auto lpr_tag) {
-      constexpr int LPR = decltype(lpr_tag)::value;
-      constexpr int RPP = NT / LPR;                  // rows per pass
-      constexpr int RS_U = MSAE_RESCORE_U, RS_B = 4 * RS_U * LPR;   // floats of a row per batch
-      const int rq = lane / LPR, q = lane % LPR;
-      for (int c0 = done; c0 < target; c0 += RPP) {
-        const int c = c0 + rq;
-        const bool active = c < target;
-        const unsigned long long key = active ? keys[c] : keys[c0];
-        int f = rank_key_index(key);
-        float ext_zs = 0.f;
-        f32x4 cc = {0.f, 0.f, 0.f, 0.f};
-        if constexpr (EXT) { ext_zs = ezs[f]; f = ef[f]; }     // list position -> (z sigma, global feature)
-        else cc = p.colc[f];
-        const float upper = f32_from_order_key((unsigned)(key >> 32));
-        const float *__restrict__ w = W_enc + (size_t)f * p.d + 4 * q;
-        float acc = 0.f;
-        // two batches of RS_U x 16 B per lane, software-pipelined: while one batch is consumed the
-        // other is in flight, so the lane never drains its loads
-        f32x4 wa[RS_U], wb[RS_U];
-        auto fetch = [&](f32x4 (&dst)[RS_U], int kk) {
-#pragma unroll
-          for (int u = 0; u < RS_U; ++u) dst[u] = *reinterpret_cast<const f32x4 *>(w + kk + 4 * LPR * u);
-        };
-        auto consume = [&](const f32x4 (&src)[RS_U], int kk) {
-#pragma unroll
-          for (int u = 0; u < RS_U; ++u) {
-            [[maybe_unused]] f32x4 av;                   // LDSA: the activations of this lane's own piece
-            if constexpr (LDSA) av = *reinterpret_cast<const f32x4 *>(a_lds + kk + 4 * LPR * u + 4 * q);
-#pragma unroll
-            for (int qq = 0; qq < LPR; ++qq) {
-              const int k0 = kk + 4 * LPR * u + 4 * qq;
-              if constexpr (LDSA) {                      // only sub-step qq == q carries the true partial sum
-                acc = __builtin_fmaf(av[0], src[u][0], acc);
-                acc = __builtin_fmaf(av[1], src[u][1], acc);
-                acc = __builtin_fmaf(av[2], src[u][2], acc);
-                acc = __builtin_fmaf(av[3], src[u][3], acc);
-              } else {
-                acc = __builtin_fmaf(a[k0 + 0], src[u][0], acc);   // a[] is wave-uniform: SGPRs
-                acc = __builtin_fmaf(a[k0 + 1], src[u][1], acc);
-                acc = __builtin_fmaf(a[k0 + 2], src[u][2], acc);
-                acc = __builtin_fmaf(a[k0 + 3], src[u][3], acc);
-              }
-              if constexpr (LPR == 4)   // quad_perm:[3,0,1,2] -- lane i takes lane i - 1's value, lane 0 lane 3's
-                acc = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc), 0x93, 0xF, 0xF, false));
-              if constexpr (LPR == 2)   // quad_perm:[1,0,3,2] -- the two lanes of a pair swap
-                acc = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc), 0xB1, 0xF, 0xF, false));
-            }
-          }
-        };
-        fetch(wa, 0);
-        for (int kk = 0; kk < p.d; kk += 2 * RS_B) {     // d % RS_B == 0 (fast_shape_ok / the caller's choice of LPR)
-          const bool has_b = kk + RS_B < p.d;
-          if (has_b) fetch(wb, kk + RS_B);
-          consume(wa, kk);
-          if (kk + 2 * RS_B < p.d) fetch(wa, kk + 2 * RS_B);
-          if (has_b) consume(wb, kk + RS_B);
-        }
-        const float pre = acc + (p.b_enc ? p.b_enc[f] : 0.f);
-        if (active && q == 0) {                          // whole pieces done: the sum is back in the group's lane 0
-          res[has_set + c] = rank_key(pre > 0.f ? pre : 0.f, f);  // slots past the sorted prefix are 0
-          // model check: |p - coarse| <= 6 sigma  <=>  (p - coarse)^2 z^2 <= 36 (z sigma)^2
-          const float zs2 = EXT ? ext_zs * ext_zs : band_sq(rc, cc, p.zz12, i8);
-          const float diff = pre - (upper - __builtin_sqrtf(zs2));
-          if (diff * diff * p.z2 > zc2 * zs2 * 1.0001f + 1e-30f) my_viol = 1;
-        }
-      }
-    };
-    // A follow-up round re-scores a handful of rows: with a lane per row each of them is a latency chain (16 KB at
-    // 512 B in flight = 32 round trips, ~60 us whatever the load); four lanes per row carry 2 KB in flight each.
-    // The first round of a SMALL batch (too few tokens to fill the chip with a lane per row) does the same with
-    // p.lpr lanes per row and as many waves per token.
-    if (partial && target > n_sorted) need_full();          // wave-uniform
-    MSAE_LEAN_BAIL();
     bool from_fm = false;
     if constexpr (PHASE == 2) {
-      if (rounds == 1) {                                     // the first round's values: fm_dot_kernel computed them
-        from_fm = true;
-        for (int c = lane; c < target; c += NT) {
-          const unsigned long long key = keys[c];
-          const int f = rank_key_index(key);
-          const float upper = f32_from_order_key((unsigned)(key >> 32));
-          const float pre = p.fm_pre[(size_t)t * p.fm_rcap + c];
-          res[has_set + c] = rank_key(pre > 0.f ? pre : 0.f, f);
-          const float zs2 = band_sq(rc, p.colc[f], p.zz12, i8);
-          const float diff = pre - (upper - __builtin_sqrtf(zs2));
-          if (diff * diff * p.z2 > zc2 * zs2 * 1.0001f + 1e-30f) my_viol = 1;
-        }
-      }
+      if (rounds == 1) { my_viol = fm_pickup<C>(p, tk, has_set, target); from_fm = true; }
     }
     if (!from_fm) {
       // PHASE 2: a follow-up round's wave is alone on its SIMD -- the scalar loads of the activations would be one exposed round
       // trip per pair of them (~130 k cycles per pass, the kernel's tail); LDSA reads them from LDS
-      if constexpr (LDSA && PHASE == 2) { if (rounds == 2) { stage_a(); __syncthreads(); } }
-      const bool few = rounds > 1 && target - done <= NT / 4;
+      if constexpr (LDSA && PHASE == 2) { if (rounds == 2) { stage_activations<C>(tk, a, p.d); __syncthreads(); } }
+      // A follow-up round re-scores a handful of rows: with a lane per row each of them is a latency chain (16 KB at 512 B in
+      // flight = 32 round trips, ~60 us whatever the load); four lanes per row carry 2 KB in flight each.  The first round of a
+      // SMALL batch (too few tokens to fill the chip with a lane per row) does the same with p.lpr lanes per row.
+      const bool few = rounds > 1 && target - done <= C::NT / 4;
       int lpr = few ? 4 : (MSAE_RESCORE_LPR == 4 ? 4 : p.lpr);
       while (lpr > 1 && p.d % (4 * MSAE_RESCORE_U * lpr) != 0) lpr >>= 1;      // a batch is 64 lpr floats of a row
-      if (lpr == 4) run_pass(std::integral_constant<int, 4>());
-      else if (lpr == 2) run_pass(std::integral_constant<int, 2>());
-      else run_pass(std::integral_constant<int, 1>());
+      if (lpr == 4) my_viol = rescore_pass<C, 4>(p, tk, a, W_enc, has_set, done, target);
+      else if (lpr == 2) my_viol = rescore_pass<C, 2>(p, tk, a, W_enc, has_set, done, target);
+      else my_viol = rescore_pass<C, 1>(p, tk, a, W_enc, has_set, done, target);
     }
     done = target;
     viol = viol || (__syncthreads_or(my_viol) != 0);
     MSAE_RTL(2 + 2 * rounds);
-    {   // res[] is zero (= empty, the smallest key) behind the slots written so far: sort the filled prefix only
-      const int filled = next_pow2(done + has_set > 2 ? done + has_set : 2);
-      bool in_regs = false;
-      if constexpr (NW == 1) {
-        if (filled <= 64 && nrp >= 64) {                     // wave-uniform: one key per lane, sorted in registers
-          in_regs = true;
-          __syncthreads();
-          unsigned long long v1[1] = {res[lane]};
-          wave_sort_desc_u64_regs<1>(v1, lane);
-          res[lane] = v1[0];
-          __syncthreads();
-        }
-      }
-      if constexpr (NW == 4) {
-        if (filled <= 1024 && nrp >= 1024) {                // wave-uniform: 4 keys per thread (k = 256: ~350 results)
-          in_regs = true;
-          __syncthreads();
-          unsigned long long v4[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v4[r] = res[lane * 4 + r];
-          wg_sort_desc_u64_regs<4, 4>(v4, lane, res);
-          __syncthreads();
-#pragma unroll
-          for (int r = 0; r < 4; ++r) res[lane * 4 + r] = v4[r];
-          __syncthreads();
-        }
-      }
-      if (!in_regs) wave_sort_desc_u64<NT>(res, filled < nrp ? filled : nrp, lane);
-    }
+    // res[] is zero (= empty, the smallest key) behind the slots written so far: sort the filled prefix only -- in registers where
+    // one key per lane / four per thread of four waves (k = 256: ~350 results) hold it
+    lds_sort_desc_u64<NW, NW == 1 ? 1 : 4>(tk.res, next_pow2(done + has_set > 2 ? done + has_set : 2), tk.nrp, lane);
     MSAE_RTL(3 + 2 * rounds);
-    const bool have_k = done + has_set >= p.k;
-    const float v_k = f32_from_order_key((unsigned)(res[p.k - 1] >> 32));
-    const int needed = have_k ? count_needed(v_k) : n;          // candidates with u >= v_k
-    MSAE_LEAN_BAIL();
-    ok = (cnt <= p.cap) && (tau > 0.f) && have_k && !viol && needed <= done && v_k > tau * 1.000001f && !guarded;
-    if (ok || viol || guarded || done >= lim || !(tau > 0.f) || cnt > p.cap) break;
-    if constexpr (LEAN) { deferred = true; MSAE_LEAN_BAIL(); }   // a follow-up round: the full-size launch (rows token-major, activations in LDS)
+    int needed;
+    bool last;
+    ok = verify<C>(p, tk, pre, has_set, done, lim, viol, guarded, needed, last);
+    if constexpr (LEAN) { if (pre.deferred) { defer_token<C>(p, tk); return; } }
+    if (last) break;
+    if constexpr (LEAN) { defer_token<C>(p, tk); return; }   // a follow-up round: the full-size launch (rows token-major, activations in LDS)
     target = needed > done ? needed : done + 1;
     if (target > lim) target = lim;
     __syncthreads();
@@ -627,31 +565,8 @@ __global__ __launch_bounds__(64 * NW) void select_rescore_kernel(RescoreArgs p, 
 
   MSAE_RTL(14);
   MSAE_RTL_VALUE(15, ((unsigned long long)rounds << 32) | (unsigned)done);
-  for (int j = lane; j < p.k; j += NT) {
-    const unsigned long long key = res[j];
-    const int fi = key ? rank_key_index(key) : 0;
-    if (p.idx) p.idx[(size_t)t * p.k + j] = fi;
-    if (p.idx64) p.idx64[(size_t)t * p.k + j] = fi;
-    p.vals[(size_t)t * p.k + j] = key ? f32_from_order_key((unsigned)(key >> 32)) : 0.f;
-  }
-  if (lane == 0) {
-    // not verified: 2 | reason bits (4 list overflow, 8 tau <= 0, 16 fewer than k candidates,
-    // 32 more than r_max rows needed / v_k not above tau, 64 a re-scored pair contradicted the error
-    // model); the exact fallback rewrites it to 1 once it has recomputed t
-    const int reason = 2 | (cnt > p.cap ? 4 : 0) | (!(tau > 0.f) ? 8 : 0) |
-                       (done + has_set < p.k ? 16 : 0) | (guarded ? 128 : (viol ? 64 : 32));
-    if (p.status) p.status[t] = ok ? 0 : reason;
-    // msae_options::rows_rescored: [1 << 30: first round feature-major] | rounds << 24 | first-round rows << 12 | rows of W_enc
-    // this token read (0: not verified here)
-    if (p.rows_out) p.rows_out[t] = ok ? (PHASE == 2 ? 1 << 30 : 0) | ((rounds & 0x3F) << 24) | ((first_target < 0xFFF ? first_target : 0xFFF) << 12) | (done < 0xFFF ? done : 0xFFF) : 0;   // (12-bit fields saturate)
-    if (!ok) {
-      const int slot = atomicAdd(p.n_flagged, 1);
-      if (slot < p.fb_cap) p.flagged[slot] = t;
-    }
-  }
+  write_token<C>(p, tk, ok, viol, guarded, has_set, done, rounds, first_target);
 }
-
-#undef MSAE_LEAN_BAIL
 
 // ---- feature-major first round -------------------------------------------------------------------
 // The pairs of a feature occupy whole GROUPS of G lanes (G = 4 or 16: fm_group_lanes) of fm_dot_kernel's waves, so a feature's
@@ -838,23 +753,12 @@ __global__ __launch_bounds__(64) void pack_candidates_kernel(PackArgs p) {
   const bool bounded = cnt <= p.cap && tau > 0.f && p.rowc[t][3] == 0.f;
   const int nj = bounded ? (n + 63) >> 6 : 0;            // key slots in use (wave-uniform)
   unsigned long long kreg[PK];
-#pragma unroll
-  for (int j = 0; j < PK; ++j) {
-    const int i = j * 64 + lane;
-    kreg[j] = (j < nj && i < n) ? p.cand[(size_t)t * p.cap + i] : 0ull;
-  }
+  wave_load_keys<PK>(kreg, p.cand + (size_t)t * p.cap, n, nj, lane);
   unsigned long long lo = 0ull, hi = ~0ull;              // count(key >= lo) >= C  (or everything is taken), count(>= hi) < C
   if (n > p.C) {
     while (hi - lo > 1ull) {
       const unsigned long long mid = lo + ((hi - lo) >> 1);
-      int c = 0;
-#pragma unroll
-      for (int jb = 0; jb < PK; jb += 8) {               // one branch per eight key slots (empty slots hold 0 < mid)
-        if (jb < nj) {
-#pragma unroll
-          for (int j = jb; j < jb + 8; ++j) c += __builtin_popcountll(__builtin_amdgcn_ballot_w64(kreg[j] >= mid));
-        }
-      }
+      const int c = wave_count_if<PK>(kreg, nj, [mid](unsigned long long key) { return key >= mid; });
       if (c >= p.C) lo = mid; else hi = mid;
     }
   } else {
@@ -864,26 +768,19 @@ __global__ __launch_bounds__(64) void pack_candidates_kernel(PackArgs p) {
   unsigned long long *okeys = reinterpret_cast<unsigned long long *>(rec);
   float *ozs = reinterpret_cast<float *>(rec + (size_t)p.C * 8);
   const f32x4 rc = p.rowc[t];
-  int base = 0;
   unsigned long long below = 0ull;                       // largest key NOT taken
-#pragma unroll
-  for (int j = 0; j < PK; ++j) {
-    if (j < nj) {
-      const unsigned long long key = kreg[j];
-      const bool take = key >= lo && key != 0ull;
-      const unsigned long long m = __builtin_amdgcn_ballot_w64(take);
-      if (take) {
-        const int pos = base + __builtin_popcountll(m & ((1ull << lane) - 1ull));
-        const int f = rank_key_index(key);
-        okeys[pos] = (key & 0xFFFFFFFF00000000ull) | (unsigned)(0x7FFFFFFF - (f + p.row_offset));
-        ozs[pos] = __builtin_sqrtf(band_sq(rc, p.colc[f], p.zz12, p.i8 != 0));
-      } else {
-        below = key > below ? key : below;
-      }
-      base += __builtin_popcountll(m);
-    }
-  }
-  for (int jj = base + lane; jj < p.C; jj += 64) { okeys[jj] = 0ull; ozs[jj] = 0.f; }
+  const int taken = wave_compact_if<PK>(
+      kreg, nj, lane, [lo](unsigned long long key) { return key >= lo && key != 0ull; },
+      [&](unsigned long long key, bool take, int pos) {
+        if (take) {
+          const int f = rank_key_index(key);
+          okeys[pos] = (key & 0xFFFFFFFF00000000ull) | (unsigned)(0x7FFFFFFF - (f + p.row_offset));
+          ozs[pos] = __builtin_sqrtf(band_sq(rc, p.colc[f], p.zz12, p.i8 != 0));
+        } else {
+          below = key > below ? key : below;
+        }
+      });
+  for (int jj = taken + lane; jj < p.C; jj += 64) { okeys[jj] = 0ull; ozs[jj] = 0.f; }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     const unsigned long long o = __shfl_xor(below, off, 64);
@@ -911,61 +808,55 @@ inline void rescore_shape(int T, int k, int &nw, int &lpr) {
   lpr = 1;
   if (k <= 64) {
     const long lanes = (long)T * (k + 13);
-    // Round 6 (profiles/r06_ab_rescore_lpr.txt): a workgroup of lpr waves per token is alone on its CU up to 256 tokens; one token
+    // profiles/r06_ab_rescore_lpr.txt: a workgroup of lpr waves per token is alone on its CU up to 256 tokens; one token
     // more and the kernel ends with the CU that holds TWO four-wave workgroups (0.078 -> 0.135 ms from 256 to 257 tokens) -- two
     // waves per token then beat four up to ~640 tokens (257: 0.099, 512: 0.123 against 0.152), a lane per row beyond (768: 0.157
-    // against 0.235 / 0.207, 1024: 0.189 against 0.297 / 0.230).  The old rule asked only whether the lanes fill the chip.
+    // against 0.235 / 0.207, 1024: 0.189 against 0.297 / 0.230).  (Asking only whether the lanes fill the chip is not enough.)
     if (T <= 256 && lanes * 4 <= 131072) lpr = 4;
     else if (T <= 640 && lanes * 2 <= 131072) lpr = 2;
     if (const char *e = getenv("MSAE_LPR")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4) lpr = v; }   // (A/B runs)
     nw = lpr;
   }
 }
-// bytes of the results array behind the keys in select_rescore_kernel's dynamic LDS (smem = (cap + nrp) * 8 + 64)
-inline size_t full_minus_keys(size_t smem, int cap) { return smem - 64 - (size_t)cap * 8; }
+
+// one launch of select_rescore_kernel<NW, EXT, LDSA, PHASE, LEAN> with the dynamic LDS `lds` describes, a workgroup per token
+template <int NW, bool EXT, bool LDSA, int PHASE, bool LEAN>
+inline int launch_rescore_kernel(const RescoreArgs &ra, const RescoreLds &lds, const float *a32, const float *W_enc, hipStream_t s) {
+  const auto kernel = select_rescore_kernel<NW, EXT, LDSA, PHASE, LEAN>;
+  MSAE_HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds.total));
+  hipLaunchKernelGGL(kernel, dim3(ra.T), dim3(64 * NW), lds.total, s, ra, a32, W_enc);
+  return 0;
+}
+// Which kernels run for ra.T tokens (sets ra.lpr and, PHASE 1 / 2, ra.fm.all).  a32: the tokens' f32 activations [T][d].
 template <bool EXT, int PHASE = 0>
-inline int launch_select_rescore(RescoreArgs &ra, int T, int k, size_t smem, const float *a32, const float *W_enc,
-                                 hipStream_t s) {
+inline int launch_select_rescore(RescoreArgs &ra, const float *a32, const float *W_enc, hipStream_t s) {
   int nw;
-  rescore_shape(T, k, nw, ra.lpr);
-  const bool ldsa = PHASE == 0 && ra.lpr > 1 && smem + (size_t)ra.d * 4 <= 96 * 1024;      // small batch: activations in LDS
-  if (ldsa) smem += (size_t)ra.d * 4;
-#define MSAE_RS_LAUNCH(NWV, LDSAV, PH)                                                                                   \
-  do {                                                                                                                   \
-    MSAE_HIP_TRY(hipFuncSetAttribute((const void *)select_rescore_kernel<NWV, EXT, LDSAV, PH>,                           \
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));                            \
-    hipLaunchKernelGGL((select_rescore_kernel<NWV, EXT, LDSAV, PH>), dim3(T), dim3(64 * NWV), smem, s, ra, a32, W_enc);  \
-  } while (0)
-#define MSAE_RS_LAUNCH_L(NWV, PH)                                                                                       \
-  do {                                                                                                                   \
-    MSAE_HIP_TRY(hipFuncSetAttribute((const void *)select_rescore_kernel<NWV, EXT, false, PH, true>,                     \
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));                            \
-    hipLaunchKernelGGL((select_rescore_kernel<NWV, EXT, false, PH, true>), dim3(T), dim3(64 * NWV), smem, s, ra, a32, W_enc); \
-  } while (0)
+  rescore_shape(ra.T, ra.k, nw, ra.lpr);
+  auto lds = [&](bool lean, bool with_a) { return rescore_lds(nw, PHASE, lean, ra.cap, ra.r_max, EXT, with_a ? ra.d : 0); };
+  const RescoreLds full = lds(false, false), full_a = lds(false, true);
   if constexpr (PHASE != 0) {                 // feature-major first round: large batches only (fm_shape_ok: a lane per row)
     // a LEAN launch (prefix-sized LDS) in front of the full-size one, which then takes the tokens the LEAN one left to it
-    const size_t nres = PHASE == 1 ? 0 : full_minus_keys(smem, ra.cap);           // PHASE 1 has no results
-    const size_t full = smem, lean = (size_t)(nw == 1 ? 256 : (PHASE == 1 ? 2048 : 512)) * 8 + nres + 64;
-    const bool has_lean = ra.fm_defer != nullptr && lean < full && (nw == 1 || PHASE == 2 || ra.cap >= 2048);
-    ra.fm_all = has_lean ? 0 : 1;
+    const RescoreLds lean = lds(true, false);
+    const bool has_lean = ra.fm.defer != nullptr && lean.total < full.total && (nw == 1 || PHASE == 2 || ra.cap >= 2048);
+    ra.fm.all = has_lean ? 0 : 1;
     if (has_lean) {
-      smem = lean;
-      if (nw == 1) MSAE_RS_LAUNCH_L(1, PHASE); else MSAE_RS_LAUNCH_L(4, PHASE);
-      smem = full;
+      const int rc = nw == 1 ? launch_rescore_kernel<1, EXT, false, PHASE, true>(ra, lean, a32, W_enc, s)
+                             : launch_rescore_kernel<4, EXT, false, PHASE, true>(ra, lean, a32, W_enc, s);
+      if (rc) return rc;
     }
-    const bool lds2 = PHASE == 2 && nw == 1 && smem + (size_t)ra.d * 4 <= 64 * 1024;   // follow-up rounds: activations in LDS
-    if (lds2) { smem += (size_t)ra.d * 4; MSAE_RS_LAUNCH(1, true, PHASE); }
-    else if (nw == 1) MSAE_RS_LAUNCH(1, false, PHASE);
-    else MSAE_RS_LAUNCH(4, false, PHASE);
+    if constexpr (PHASE == 2) {               // one wave per token: the follow-up rounds read the activations from LDS where they fit
+      if (nw == 1 && full_a.total <= 64 * 1024) return launch_rescore_kernel<1, EXT, true, 2, false>(ra, full_a, a32, W_enc, s);
+    }
+    if (nw == 1) return launch_rescore_kernel<1, EXT, false, PHASE, false>(ra, full, a32, W_enc, s);
+    return launch_rescore_kernel<4, EXT, false, PHASE, false>(ra, full, a32, W_enc, s);
   } else {
-    if (ldsa) { if (nw == 2) MSAE_RS_LAUNCH(2, true, 0); else MSAE_RS_LAUNCH(4, true, 0); }
-    else if (nw == 1) MSAE_RS_LAUNCH(1, false, 0);
-    else if (nw == 2) MSAE_RS_LAUNCH(2, false, 0);
-    else MSAE_RS_LAUNCH(4, false, 0);
+    const bool ldsa = ra.lpr > 1 && full_a.total <= 96 * 1024;       // small batch: activations in LDS
+    if (ldsa && nw == 2) return launch_rescore_kernel<2, EXT, true, 0, false>(ra, full_a, a32, W_enc, s);
+    if (ldsa) return launch_rescore_kernel<4, EXT, true, 0, false>(ra, full_a, a32, W_enc, s);
+    if (nw == 1) return launch_rescore_kernel<1, EXT, false, 0, false>(ra, full, a32, W_enc, s);
+    if (nw == 2) return launch_rescore_kernel<2, EXT, false, 0, false>(ra, full, a32, W_enc, s);
+    return launch_rescore_kernel<4, EXT, false, 0, false>(ra, full, a32, W_enc, s);
   }
-#undef MSAE_RS_LAUNCH
-#undef MSAE_RS_LAUNCH_L
-  return 0;
 }
 
 // The feature-major first round pays when a row of W_enc is a candidate of several tokens of the batch -- m = ~1.36 k T / N tokens
@@ -981,7 +872,7 @@ inline bool fm_pays(int T, int k, int N, int d, int esize) {
   if (force >= 0) return force != 0;
   const double m = 1.36 * (double)T * k / N;
   if (m < 0.6) return false;
-  // Round 6 (tools/fm_midsize.py, profiles/r06_fm_midsize.txt): below ~2 tokens per feature the batch is small enough for the
+  // tools/fm_midsize.py, profiles/r06_fm_midsize.txt: below ~2 tokens per feature the batch is small enough for the
   // token-major kernel to be latency-bound -- it reaches ~4.2 TB/s, not the 6.2 of a full batch -- and the feature-major route
   // already wins from ~1 token per feature: T = 2880 (one anyres image, m = 0.96) 2.11 -> 2.05 ms, 4096 (m = 1.36) 2.67 -> 2.56;
   // T = 2048 (m = 0.68) is a tie, 1024 stays token-major.

@@ -479,12 +479,11 @@ __global__ __launch_bounds__(64) void rescore_small_kernel(const float *__restri
     }
     if (lane == 0) {                                   // after whole chunks the true sum is back in lane 0
       const float pre = acc + (b_enc ? b_enc[f] : 0.f);
-      exact[(size_t)t * 128 + r] = rank_key(pre > 0.f ? pre : 0.f, f);
+      exact[(size_t)t * 128 + r] = result_key(pre, f);
       if (upper > -__builtin_inff()) {
         const f32x4 rc = rowc[t], st = wstat[f];
         const float zs2 = __builtin_fmaf(rc[2], st[1], rc[0] * rc[0] * zz12 * st[2]);
-        const float diff = pre - (upper - __builtin_sqrtf(zs2));
-        if (diff * diff * z2 > zc2 * zs2 * 1.0001f + 1e-30f) atomicOr(viol + t, 1);
+        if (contradicts_model(pre, upper, zs2, z2, zc2)) atomicOr(viol + t, 1);
       }
     }
   } else if (lane == 0) {
