@@ -26,6 +26,8 @@
  *   msae_decode_bwd_wdec_f32 TritonDecoder.backward (W)    sae/kernels.py:417-419,10-175
  *   msae_sparsify_*          scatter_ + Cache.add/get_nonzeros  features/cache.py:214-217,42-92
  *   msae_feature_stats_*     per-feature counts + top examples  features/loader.py:103-106, constructors.py:28-141
+ *   msae_rows_topk_f32       cos + get_neighbors; logits   features/stats.py:76-120; stats.py:12-47
+ *   msae_row_inv_norms_f32   F.normalize's norms in cos    features/stats.py:80-81
  *
  * Numerics contract: all dot products are ascending-k f32 fused
  * multiply-add chains (v_mfma_f32_32x32x2_f32 / v_fma_f32), bit-identical to oracle/sae_oracle.c.
@@ -415,6 +417,39 @@ int msae_pooled_acts_f32(const void *x, int x_dtype, const float *W_enc, const f
                          void *stream);
 int msae_probe_maps_f32(const void *x, int x_dtype, const float *W_enc, const float *b_enc, const float *b_dec, int T,
                         int d, int N, const int32_t *seg, int S, const int32_t *idx, int k, float *maps, void *stream);
+
+/* ---- neighbours and top logits: fused f32 GEMM + per-row top-k (Sae.neighbors, Sae.top_logits) ----------------------
+ * Replaces sae_auto_interp/features/stats.py:76-120 (cos + get_neighbors: normalise, torch.mm, torch.topk) and
+ * stats.py:12-47 (logits: torch.matmul, torch.topk) without materialising the [M][N] product.  Both calls are asynchronous
+ * on `stream`; neither allocates nor reads anything back to the host.
+ * msae_rows_topk_f32: queries are the rows q_rows[m] of Q[Qn][d] (q_rows NULL: row m, M <= Qn), keys K[N][d];
+ *   vals[M][k] f32, idx[M][k] int32 key indices.  Numerics contract:
+ *   1. dot[m][n] is the ascending-k f32 fma chain from +0 of Q[q_rows[m]][c] * K[n][c] -- msae_pre_acts_f32's tile with
+ *      b_dec = NULL and rows = q_rows, bit-identical to oracle.pre_acts(Q[q_rows], K, 0, 0, relu=False).
+ *   2. value = dot, then * q_scale[m] if given, then * k_scale[n] if given: each its own rounded f32 multiply.
+ *   3. Ranking: the canonical top-k of row m over all n -- value descending, index ascending, by the library's rank key, so
+ *      +-0 and non-finite values rank exactly as msae_topk_f32 ranks them.  n == exclude[m] is left out (exclude[m] < 0:
+ *      nothing).  k > N - (exclude != NULL ? 1 : 0) returns MSAE_EINVAL.  Values are decoded from the rank key, as
+ *      msae_merge_topk's are: a value of -0 is returned as +0.
+ *   4. The result does not depend on `chunks`, on the grid, or on which other queries are in the call.
+ *   Envelope: any d (d % 4 != 0 and unaligned pointers take the tile's generic staging path), any N (N % 128 != 0
+ *   included), any M >= 0, 1 <= k <= 64.  q_rows may be unsorted and hold repeats; an entry outside [0, Qn) is clamped
+ *   into it, never faults.  chunks: 0 = chosen by the library (the smallest count that gives two workgroups per CU over
+ *   the 128-query tiles, at most the 128-key strips and 8192 / k), > 0 = forced (tests; capped at the strips,
+ *   MSAE_EINVAL beyond 8192 / k).  ws: msae_rows_topk_ws_bytes(M, N, k, chunks) bytes (the clamped row list, the merge
+ *   mask of the int64 variant, then the per-chunk lists [chunks][2][M][k] in msae_merge_topk's `gathered` layout, merged by one msae_merge_topk call).
+ * msae_row_inv_norms_f32: inv[n] = the f32 nearest to 1 / max(||W_n||_2, 1e-12) (F.normalize's clamp) evaluated in f64
+ *   (fixed summation order, no atomics: bit-reproducible; <= 1 f32 ulp from numpy f64).  The cosine is defined from the
+ *   arrays the caller passes as q_scale / k_scale, so points 1-4 hold whatever order the norms were summed in. */
+int msae_row_inv_norms_f32(const float *W, int N, int d, float *inv, void *stream);
+size_t msae_rows_topk_ws_bytes(int M, int N, int k, int chunks);
+int msae_rows_topk_f32(const float *Q, int Qn, const int32_t *q_rows, int M, const float *K, int N, int d,
+                       const float *q_scale, const float *k_scale, const int32_t *exclude, int k, int chunks,
+                       float *vals, int32_t *idx, void *ws, size_t ws_bytes, void *stream);
+/* the same with int64 indices (Tensor.topk's index type) written directly: no widening pass, no int32 copy */
+int msae_rows_topk_i64_f32(const float *Q, int Qn, const int32_t *q_rows, int M, const float *K, int N, int d,
+                           const float *q_scale, const float *k_scale, const int32_t *exclude, int k, int chunks,
+                           float *vals, int64_t *idx, void *ws, size_t ws_bytes, void *stream);
 
 /* ---- merge of per-shard results (feature-sharded encode; no reference counterpart) ----
  * gathered: int32 [G][2][T][kl], the all-gather of each rank's packed block [2][T][kl]

@@ -162,3 +162,63 @@ class FeatureStats:
         st.tokens_seen = int(meta["tokens_seen"])
         st.windows_per_row = json.loads(meta["windows_per_row"])
         return st
+
+
+# ---- neighbours and top logits (sae_auto_interp/features/stats.py:12-47,76-120) ----------------------------------------
+def cos(matrix: Tensor, selected_features=(0,)) -> Tensor:
+    """Dense cosine similarities [M, N] of the selected rows of `matrix` against all of its rows (stats.py:76-85), for
+    small selections.  matrix is [N, d] -- one row per feature, as `Sae.W_dec` and `Sae.encoder.weight` are here (the
+    reference's decoder.weight is its transpose).  Same arithmetic as `Sae.neighbors`: the exact f32 dot, then
+    * inv[m], then * inv[n]."""
+    ops._no_grad_inputs("features.cos", matrix)
+    W = matrix.detach().to(torch.float32).contiguous()
+    sel = torch.as_tensor(list(selected_features) if not isinstance(selected_features, Tensor) else selected_features,
+                          dtype=torch.int64).to(W.device)
+    inv = ops.row_inv_norms(W)
+    dots = ops._dense_gemm_nt(W.index_select(0, sel), W)
+    return dots * inv.index_select(0, sel)[:, None] * inv[None, :]
+
+
+def get_neighbors(sae_dict, feature_filter, k: int = 10):
+    """The reference's get_neighbors (stats.py:88-120) over {module name: Sae}: for every module with selected features in
+    `feature_filter`, the top k decoder cosines of each selected feature INCLUDING itself with rank 0 dropped, so each
+    entry holds k - 1 neighbours -> (neighbors_dict {module: {i: {"indices", "values"}}}, per_layer_features {module:
+    sorted unique indices of the full top k}).  As in the reference, with exact duplicate decoder rows the dropped rank 0
+    may be the twin rather than the feature itself; `Sae.neighbors(exclude_self=True)` skips the
+    feature by index instead."""
+    from collections import defaultdict
+
+    neighbors_dict, per_layer_features = defaultdict(dict), {}
+    for module_path, sae in sae_dict.items():
+        selected = feature_filter.get(module_path, False)
+        if selected is None or selected is False or len(selected) == 0:
+            continue
+        values, indices = sae.neighbors(selected, k=k, matrix="decoder", exclude_self=False)
+        values, indices = values.cpu(), indices.cpu()
+        for i in range(indices.shape[0]):
+            neighbors_dict[module_path][i] = {"indices": indices[i].tolist()[1:], "values": values[i].tolist()[1:]}
+        per_layer_features[module_path] = torch.unique(indices).tolist()
+    return neighbors_dict, per_layer_features
+
+
+def logits(records, W_U: Tensor, W_dec, k: int = 10, tokenizer=None):
+    """Direct logit attribution of a list of feature records (stats.py:12-47): sets `record.top_logits` to the decoded
+    top-k tokens of `W_U @ W_dec[feature]` and returns the list.  W_U: the unembedding [V, d]; W_dec: an `Sae`, or its
+    decoder as [N, d] (a [d, N] matrix, the reference's layout, is transposed)."""
+    from ..sae import Sae
+
+    feats = [int(r.feature.feature_index) for r in records]
+    if isinstance(W_dec, Sae):
+        _, top = W_dec.top_logits(W_U, feats, k=k)
+    else:
+        if W_dec.shape[-1] != W_U.shape[-1] and W_dec.shape[0] == W_U.shape[-1]:
+            W_dec = W_dec.t()
+        rows = torch.tensor(feats, dtype=torch.int32).to(W_dec.device)
+        _, top = ops.rows_topk(W_dec.detach(), W_U.detach(), k, q_rows=rows)     # (token strings carry no gradient)
+    top = top.cpu()
+    decoded_top_logits = []
+    for i, record in enumerate(records):
+        decoded = tokenizer.batch_decode(top[i])
+        decoded_top_logits.append(decoded)
+        record.top_logits = decoded
+    return decoded_top_logits

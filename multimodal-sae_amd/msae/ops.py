@@ -10,6 +10,8 @@ These are the operators the drop-in ``Sae`` module (msae/sae/sae.py) and the fea
     msae::sparsify      scatter_ + Cache.get_nonzeros/add    features/cache.py:214-217,42-92
     msae::pooled_acts   pre_acts(h).mean(0) per segment      tools/probe_activations.py:109-126
     msae::probe_maps    latents[:, :, idx]                   tools/probe_activations.py:126
+    msae::row_inv_norms F.normalize's 1 / max(norm, eps)     features/stats.py:80-81
+    msae::rows_topk     torch.mm + torch.topk, fused         features/stats.py:35-37,83,107
 
 All ops run on the tensor's device on the current stream, never synchronise (``sparsify`` reads one
 int64 back, as ``torch.nonzero`` does), and raise on CPU tensors.
@@ -438,6 +440,95 @@ def probe_maps(x: Tensor, W_enc: Tensor, b_enc: Optional[Tensor], b_dec: Optiona
 @probe_maps.register_fake
 def _(x, W_enc, b_enc, b_dec, segments, indices):
     return x.new_empty(x.shape[0], indices.shape[1], dtype=torch.float32)
+
+
+# ---- neighbours / top logits (features/stats.py:12-47,76-120) -----------------------------------------------------------
+ROWS_TOPK_MAX_K = 64
+
+
+def _no_grad_inputs(what: str, *tensors: Optional[Tensor]) -> None:
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise RuntimeError(f"{what} is an inference path: call it under torch.no_grad() or on detached inputs")
+
+
+@torch.library.custom_op("msae::row_inv_norms", mutates_args=())
+def _row_inv_norms(W: Tensor) -> Tensor:
+    dev = _hip.require_device(W)
+    lib = _hip.load()
+    Wc = _f32c(W)
+    assert Wc.dim() == 2, f"W must be [N, d], got {tuple(Wc.shape)}"
+    N, d = Wc.shape
+    inv = torch.empty(N, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.msae_row_inv_norms_f32(_hip.ptr(Wc), N, d, _hip.ptr(inv), _hip.stream_of(Wc)),
+                   "msae_row_inv_norms_f32")
+    return inv
+
+
+@_row_inv_norms.register_fake
+def _(W):
+    return W.new_empty(W.shape[0], dtype=torch.float32)
+
+
+def row_inv_norms(W: Tensor) -> Tensor:
+    """inv[n] = the f32 nearest to 1 / max(||W[n]||_2, 1e-12) (F.normalize's clamp), norms summed in f64 in a fixed order
+    (bit-reproducible) -> [N] f32.  Inference only."""
+    _no_grad_inputs("ops.row_inv_norms", W)
+    return _row_inv_norms(W)
+
+
+@torch.library.custom_op("msae::rows_topk", mutates_args=())
+def _rows_topk(Q: Tensor, K: Tensor, k: int, q_rows: Optional[Tensor], q_scale: Optional[Tensor],
+               k_scale: Optional[Tensor], exclude: Optional[Tensor], chunks: int) -> Tuple[Tensor, Tensor]:
+    dev = _hip.require_device(Q, K, q_rows, q_scale, k_scale, exclude)
+    lib = _hip.load()
+    # (a view whose storage offset breaks the 16-B alignment stays a view: the kernel takes its generic staging path)
+    Qc = Q.detach() if (Q.dtype == torch.float32 and Q.is_contiguous()) else _f32c(Q)
+    Kc = K.detach() if (K.dtype == torch.float32 and K.is_contiguous()) else _f32c(K)
+    assert Qc.dim() == 2 and Kc.dim() == 2 and Qc.shape[1] == Kc.shape[1], \
+        f"Q [Qn, d] and K [N, d] must share d, got {tuple(Qc.shape)} and {tuple(Kc.shape)}"
+    (Qn, d), N = Qc.shape, Kc.shape[0]
+    rows = None if q_rows is None else q_rows.detach().to(torch.int32).contiguous()
+    M = Qn if rows is None else rows.numel()
+    qs, ks = _f32c(q_scale), _f32c(k_scale)
+    ex = None if exclude is None else exclude.detach().to(torch.int32).contiguous()
+    if not 1 <= k <= ROWS_TOPK_MAX_K or k > N - (0 if ex is None else 1):
+        raise ValueError(f"k must be in [1, min({ROWS_TOPK_MAX_K}, keys{' - 1' if ex is not None else ''})], got k = {k} "
+                         f"with {N} keys")
+    assert qs is None or qs.numel() == M, f"q_scale has {qs.numel()} entries for {M} queries"
+    assert ks is None or ks.numel() == N, f"k_scale has {ks.numel()} entries for {N} keys"
+    assert ex is None or ex.numel() == M, f"exclude has {ex.numel()} entries for {M} queries"
+    vals = torch.empty(M, k, dtype=torch.float32, device=dev)
+    idx = torch.empty(M, k, dtype=torch.int64, device=dev)      # written directly: no widening pass
+    if M == 0:
+        return vals, idx
+    nbytes = lib.msae_rows_topk_ws_bytes(M, N, k, chunks)
+    if nbytes == 0:
+        raise ValueError(f"rows_topk: chunks = {chunks} is out of range for k = {k} (chunks * k <= 8192)")
+    ws = _workspace(dev, nbytes)
+    with torch.cuda.device(dev):
+        _hip.check(lib.msae_rows_topk_i64_f32(_hip.ptr(Qc), Qn, _hip.ptr(rows), M, _hip.ptr(Kc), N, d, _hip.ptr(qs),
+                                              _hip.ptr(ks), _hip.ptr(ex), k, chunks, _hip.ptr(vals), _hip.ptr(idx),
+                                              _hip.ptr(ws), ws.numel(), _hip.stream_of(Qc)), "msae_rows_topk_i64_f32")
+    return vals, idx
+
+
+@_rows_topk.register_fake
+def _(Q, K, k, q_rows, q_scale, k_scale, exclude, chunks):
+    M = Q.shape[0] if q_rows is None else q_rows.numel()
+    return Q.new_empty(M, k, dtype=torch.float32), Q.new_empty(M, k, dtype=torch.int64)
+
+
+def rows_topk(Q: Tensor, K: Tensor, k: int, q_rows: Optional[Tensor] = None, q_scale: Optional[Tensor] = None,
+              k_scale: Optional[Tensor] = None, exclude: Optional[Tensor] = None, chunks: int = 0) -> Tuple[Tensor, Tensor]:
+    """The canonical top-k (value descending, index ascending) of every row of (Q[q_rows] @ K.T) * q_scale[:, None] *
+    k_scale[None, :] without the dense [M, N] product -> (vals f32 [M, k], idx int64 [M, k]).  Q [Qn, d], K [N, d] f32;
+    q_rows int [M] (None: every row of Q; entries outside [0, Qn) are clamped); q_scale [M], k_scale [N] f32 or None;
+    exclude int [M]: a key index each query skips (< 0: none); 1 <= k <= 64; chunks: 0 = chosen by the library.  The bits are
+    include/msae.h's contract ("neighbours"): the dots are pre_acts's, the two scales separate f32 multiplies, and the
+    result does not depend on `chunks` or on the other queries of the call.  Inference only."""
+    _no_grad_inputs("ops.rows_topk", Q, K, q_scale, k_scale)
+    return _rows_topk(Q, K, k, q_rows, q_scale, k_scale, exclude, chunks)
 
 
 def set_coarse_mode(mode: str) -> None:

@@ -12,6 +12,8 @@ unchanged.  What differs is underneath:
 * `decode`        -> torch.ops.msae.decode     (coalesced gather-matmul over W_dec rows, autograd)
 * `probe`         -> torch.ops.msae.pooled_acts + topk + probe_maps (tools/probe_activations.py:109-126 without the
                      dense latents: new)
+* `neighbors`, `top_logits` -> torch.ops.msae.row_inv_norms + rows_topk (features/stats.py:12-47,76-120 as one fused
+                     f32 GEMM + per-row top-k: DESIGN.md section 7c)
 
 SAE math is f32 whatever dtype the LLM hands over, as in the reference (sae.py:140,174).
 There is no CPU implementation: calling a compute method with CPU tensors raises.
@@ -307,6 +309,61 @@ class Sae(nn.Module):
             values, indices = ops.topk(pooled, k)
             m = ops.probe_maps(flat, self.encoder.weight, self.encoder.bias, self.b_dec, seg, indices) if maps else None
         return ProbeOutput(values, indices, m)
+
+    # ---- neighbours and top logits (features/stats.py:12-47,76-120) -----------------------------------------
+    def _feature_rows(self, features, what: str) -> Optional[Tensor]:
+        """`features` (None, a list or a tensor of indices) -> int32 device tensor [M] or None (all), no host sync."""
+        if features is None:
+            return None
+        dev = self.encoder.weight.device
+        if isinstance(features, Tensor):
+            if features.dtype not in (torch.int32, torch.int64) or features.dim() != 1:
+                raise ValueError(f"Sae.{what}: features must be a 1-d int tensor, got {features.dtype} {tuple(features.shape)}")
+            return features.to(dev, torch.int32).clamp(0, self.num_latents - 1)
+        host = torch.tensor([int(f) for f in features], dtype=torch.int32)
+        if host.numel() and not (0 <= int(host.min()) and int(host.max()) < self.num_latents):
+            raise ValueError(f"Sae.{what}: feature indices must lie in [0, {self.num_latents})")
+        return host.pin_memory().to(dev, non_blocking=True) if dev.type == "cuda" else host
+
+    def neighbors(self, features=None, k: int = 10, matrix: str = "decoder", exclude_self: bool = True):
+        """The k nearest features of each selected feature by cosine similarity of the decoder (or encoder) rows
+        (features/stats.py:76-120) -> (values f32 [M, k], indices int64 [M, k]), value descending, ties by ascending
+        index.  features: a list or 1-d int tensor of indices, or None for all N; matrix: "decoder" (W_dec) or "encoder"
+        (encoder.weight), both [N, d]; exclude_self skips the feature's own index (rank 0 is NOT dropped: with duplicated
+        rows the feature itself need not rank first).  One fused GEMM + top-k: the [M, N] cosines are never stored.
+        cos = dot * inv[m] * inv[n] with inv = ops.row_inv_norms (include/msae.h, "neighbours")."""
+        if matrix not in ("decoder", "encoder"):
+            raise ValueError(f"matrix must be 'decoder' or 'encoder', got {matrix!r}")
+        W = self.W_dec if matrix == "decoder" else self.encoder.weight
+        if W is None:
+            raise ValueError("this Sae has no decoder: use matrix='encoder'")
+        lim = min(ops.ROWS_TOPK_MAX_K, self.num_latents - (1 if exclude_self else 0))
+        if not 1 <= k <= lim:
+            raise ValueError(f"k must be in [1, {lim}], got {k}")
+        rows = self._feature_rows(features, "neighbors")
+        with torch.no_grad():
+            W = W.detach()
+            inv = ops.row_inv_norms(W)
+            if rows is None:                       # every feature: the scales are one array, the exclusion is the row number
+                own = torch.arange(self.num_latents, dtype=torch.int32, device=W.device) if exclude_self else None
+                return ops.rows_topk(W, W, k, q_scale=inv, k_scale=inv, exclude=own)
+            return ops.rows_topk(W, W, k, q_rows=rows, q_scale=torch.index_select(inv, 0, rows.long()), k_scale=inv,
+                                 exclude=rows if exclude_self else None)
+
+    def top_logits(self, W_U: Tensor, features=None, k: int = 10):
+        """Direct logit attribution (features/stats.py:12-47): the k tokens each selected feature's decoder row pushes
+        hardest -> (values f32 [M, k], token ids int64 [M, k]).  W_U: the unembedding [V, d] in f32, bf16 or f16 (up-cast
+        to f32 once); no scales, no exclusion."""
+        if self.W_dec is None:
+            raise ValueError("this Sae has no decoder")
+        if W_U.dim() != 2 or W_U.shape[1] != self.d_in:
+            raise ValueError(f"W_U must be [V, {self.d_in}], got {tuple(W_U.shape)}")
+        lim = min(ops.ROWS_TOPK_MAX_K, W_U.shape[0])
+        if not 1 <= k <= lim:
+            raise ValueError(f"k must be in [1, {lim}], got {k}")
+        rows = self._feature_rows(features, "top_logits")
+        with torch.no_grad():
+            return ops.rows_topk(self.W_dec.detach(), W_U.detach(), k, q_rows=rows)
 
     def forward(self, x: Tensor, dead_mask: Union[Tensor, None] = None) -> ForwardOutput:
         """Training forward (sae.py:193-247): reconstruction, FVU, AuxK and Multi-TopK terms, fully
