@@ -28,6 +28,7 @@
  *   msae_feature_stats_*     per-feature counts + top examples  features/loader.py:103-106, constructors.py:28-141
  *   msae_rows_topk_f32       cos + get_neighbors; logits   features/stats.py:76-120; stats.py:12-47
  *   msae_row_inv_norms_f32   F.normalize's norms in cos    features/stats.py:80-81
+ *   msae_edit_topk_f32       hook edits with a feature LIST features/steering.py:113-114, patching/utils.py:43-48
  *
  * Numerics contract: all dot products are ascending-k f32 fused
  * multiply-add chains (v_mfma_f32_32x32x2_f32 / v_fma_f32), bit-identical to oracle/sae_oracle.c.
@@ -450,6 +451,42 @@ int msae_rows_topk_f32(const float *Q, int Qn, const int32_t *q_rows, int M, con
 int msae_rows_topk_i64_f32(const float *Q, int Qn, const int32_t *q_rows, int M, const float *K, int N, int d,
                            const float *q_scale, const float *k_scale, const int32_t *exclude, int k, int chunks,
                            float *vals, int64_t *idx, void *ws, size_t ws_bytes, void *stream);
+
+/* ---- set-valued hook edits on a top-k list (Sae.encode(edits=...)) -------------------------------
+ * The reference's hooks edit the dense latents with torch indexing, so the edited feature may be a LIST or tensor:
+ * latents[:, :, f] = clamp (features/steering.py:113-114), mask[:, off_features] = 0 (features/patching/utils.py:43-48).
+ * msae_encode_topk takes one feature of each kind; a set of E distinct features is applied AFTER an unedited encode that
+ * over-fetched kk >= k + E entries per token:
+ *   vals_in / idx_in [T][kk]  msae_encode_topk's output for k' = kk with no edit (canonical order; idx in [0, N))
+ *   edit_feat int32 [E]       the edited features, STRICTLY ASCENDING, each in [0, N)
+ *   edit_val f32 [E]          the value of a SET edit (ignored for a ZERO edit)
+ *   edit_kind int32 [E]       MSAE_EDIT_SET or MSAE_EDIT_ZERO
+ *   vals / idx [T][k]         outputs; must not overlap the inputs
+ * Asynchronous on `stream`; allocates nothing, never synchronises, needs no workspace (the sort of a token's at most
+ * 8192 keys is LDS-resident, one workgroup per token).  MSAE_EINVAL: E < 1, k < 1, kk < k + E, k + E > N,
+ * k + E > 4096 (msae_encode_topk's own limit on k), T < 0, a null pointer.  T == 0 does nothing.
+ * Contract (L = msae_pre_acts_f32's latents of the encode that produced the list):
+ *   1. The output is the canonical top-k (value descending, index ascending) of L' with L'[:, f] = edit_val for a SET
+ *      edit and L'[:, f] = +0 for a ZERO edit -- bit-identical to msae_topk_f32 on the edited dense latents for finite
+ *      pre-activations.  A feature has ONE entry in the table: the host layer (msae.features.FeatureEdits) gives ZERO
+ *      precedence where a feature is named in both lists (the oracle applies set, then zero).
+ *   2. With E = 1 it is bit-identical to msae_encode_topk's scalar set_feature / zero_feature arguments.
+ *   3. A SET value <= 0 ranks by the same key rule as msae_topk_f32 (+-0 tie with the zero fill by index, negatives below
+ *      every zero); because k + E <= N a negative value is never selected.  Values are decoded from the rank key: a
+ *      value of -0 is returned as +0.
+ *   4. A non-finite pre-activation AT AN EDITED FEATURE: the result holds the set value or +0, where the reference's
+ *      mask multiply would produce NaN from NaN * 0 (a flagged quirk).
+ *   5. Only the first k + E entries of a row are read: the result does not depend on kk beyond kk >= k + E, nor on T or
+ *      on the other tokens of the call.
+ *   6. The `status` of the underlying encode describes the result unchanged (the kernel does not touch it). */
+enum { MSAE_EDIT_SET = 0, MSAE_EDIT_ZERO = 1 };
+int msae_edit_topk_f32(const float *vals_in, const int32_t *idx_in, int T, int kk, const int32_t *edit_feat,
+                       const float *edit_val, const int32_t *edit_kind, int E, int N, int k, float *vals, int32_t *idx,
+                       void *stream);
+/* the same reading and writing 64-bit indices (msae_encode_topk_i64's output type) */
+int msae_edit_topk_i64_f32(const float *vals_in, const int64_t *idx_in, int T, int kk, const int32_t *edit_feat,
+                           const float *edit_val, const int32_t *edit_kind, int E, int N, int k, float *vals,
+                           int64_t *idx, void *stream);
 
 /* ---- merge of per-shard results (feature-sharded encode; no reference counterpart) ----
  * gathered: int32 [G][2][T][kl], the all-gather of each rank's packed block [2][T][kl]

@@ -1,0 +1,162 @@
+"""FeatureEdits -- a set of latent edits for one encode: clamp some features to values, ablate others.
+
+The reference's hooks edit the dense latents with torch indexing, so the feature may be a list or tensor:
+
+    steering     latents[:, :, f] = clamp            features/steering.py:113-114
+    attribution  mask[:, off_features] = 0           features/patching/utils.py:43-48
+
+`Sae.encode(x, edits=FeatureEdits(...))` applies such a set without the dense [T, N] latents: the unedited fused encode
+over-fetches k + E entries per token and `ops.edit_topk` (csrc/edit_topk.hip) drops the edited features from each list,
+adds the edits' own (value, feature) pairs and re-ranks -- exact, DESIGN.md section 7d.
+
+Everything host-side happens ONCE, here: range checks, duplicates, the merge of the two lists (a feature in both is
+zeroed: the oracle applies set, then zero), the sort, and one upload of the three device arrays.  Afterwards nothing is
+read back, so an encode with a prebuilt object is stream-ordered like every other op.
+"""
+from __future__ import annotations
+
+from typing import Iterable, Mapping, Optional, Tuple, Union
+
+import numpy as np
+import torch
+from torch import Tensor
+
+EDIT_SET, EDIT_ZERO = 0, 1          # include/msae.h: MSAE_EDIT_SET / MSAE_EDIT_ZERO
+MAX_SELECTED = 4096                 # k + E: msae_encode_topk's own limit on k
+
+
+def _int_list(features, what: str) -> list:
+    if isinstance(features, Tensor):
+        if features.dtype.is_floating_point or features.dtype == torch.bool:
+            raise ValueError(f"FeatureEdits: {what} features must be integers, got {features.dtype}")
+        features = features.detach().reshape(-1).cpu().tolist()
+    elif isinstance(features, np.ndarray):
+        if features.dtype.kind not in "iu":
+            raise ValueError(f"FeatureEdits: {what} features must be integers, got {features.dtype}")
+        features = features.reshape(-1).tolist()
+    elif isinstance(features, (int, np.integer)):
+        features = [features]
+    out = []
+    for f in features:
+        if isinstance(f, (bool, float)) or not isinstance(f, (int, np.integer)):
+            raise ValueError(f"FeatureEdits: {what} features must be integers, got {f!r}")
+        out.append(int(f))
+    return out
+
+
+def _float_list(values) -> list:
+    if isinstance(values, Tensor):
+        values = values.detach().reshape(-1).float().cpu().tolist()
+    elif isinstance(values, np.ndarray):
+        values = values.reshape(-1).tolist()
+    return [float(v) for v in values]
+
+
+class FeatureEdits:
+    """FeatureEdits(num_latents, set=None, zero=None, device="cuda")
+
+    set   a mapping feature -> value, or a (features, values) pair of equal-length sequences / tensors
+    zero  an int, or any iterable / tensor of features
+    A feature named in both is zeroed.  Errors (ValueError): a feature outside [0, num_latents), a feature twice in `set`,
+    a non-finite set value, nothing to edit, more than 4095 distinct features.  Duplicates inside `zero` are harmless (the
+    reference's `mask[:, off_features] = 0` accepts them) and collapse.
+
+    Attributes: E (distinct edited features), features (their sorted tuple), num_latents, device; the device arrays
+    feat / val / kind [E] that ops.edit_topk takes; mask (bool [num_latents], True at every edited feature, built on the
+    device at first use: the backward of the differentiable encode masks those latents' gradients)."""
+
+    def __init__(self, num_latents: int, set: Union[Mapping, Tuple, None] = None, zero: Optional[Iterable] = None,
+                 device: Union[str, torch.device] = "cuda"):
+        self.num_latents = int(num_latents)
+        table = {}
+        if set is not None:
+            if isinstance(set, Mapping):
+                feats, vals = _int_list(list(set.keys()), "set"), _float_list(list(set.values()))
+            else:
+                try:
+                    f_in, v_in = set
+                except (TypeError, ValueError):
+                    raise ValueError("FeatureEdits: set must be a mapping feature -> value or a (features, values) pair") from None
+                feats, vals = _int_list(f_in, "set"), _float_list(v_in)
+            if len(feats) != len(vals):
+                raise ValueError(f"FeatureEdits: set has {len(feats)} features and {len(vals)} values")
+            for f, v in zip(feats, vals):
+                if f in table:
+                    raise ValueError(f"FeatureEdits: feature {f} appears twice in set")
+                if not np.isfinite(v):
+                    raise ValueError(f"FeatureEdits: set value of feature {f} is not finite ({v})")
+                table[f] = (EDIT_SET, v)
+        if zero is not None:
+            for f in _int_list(zero, "zero"):
+                table[f] = (EDIT_ZERO, 0.0)                      # ZERO over SET
+        if not table:
+            raise ValueError("FeatureEdits: nothing to edit (set and zero are both empty)")
+        bad = [f for f in table if not 0 <= f < self.num_latents]
+        if bad:
+            raise ValueError(f"FeatureEdits: features must lie in [0, {self.num_latents}), got {sorted(bad)[:8]}")
+        if len(table) >= MAX_SELECTED:
+            raise ValueError(f"FeatureEdits: {len(table)} edited features; k + E <= {MAX_SELECTED} is the encoder's limit")
+        self.features = tuple(sorted(table))
+        self.E = len(self.features)
+        self.kinds = tuple(table[f][0] for f in self.features)       # host copies: tests, repr
+        self.values = tuple(table[f][1] for f in self.features)
+        # one buffer, one copy: int32 [3, E] = features, value bits, kinds
+        host = np.empty((3, self.E), dtype=np.int32)
+        host[0] = self.features
+        host[1] = np.asarray(self.values, dtype=np.float32).view(np.int32)
+        host[2] = self.kinds
+        self.device = torch.device(device)
+        buf = torch.from_numpy(host)
+        if self.device.type == "cuda":
+            buf = buf.pin_memory().to(self.device, non_blocking=True)
+        self._buf = buf
+        self.feat, self.val, self.kind = buf[0], buf[1].view(torch.float32), buf[2]
+        self._mask: Optional[Tensor] = None
+
+    @property
+    def mask(self) -> Tensor:
+        if self._mask is None:
+            m = torch.zeros(self.num_latents, dtype=torch.bool, device=self.device)
+            m[self.feat.long()] = True
+            self._mask = m
+        return self._mask
+
+    def check(self, num_latents: int, k: int, device=None) -> None:
+        """Raise ValueError unless this object fits an encode of `num_latents` features selecting k."""
+        if self.num_latents != num_latents:
+            raise ValueError(f"FeatureEdits was built for num_latents = {self.num_latents}, the Sae has {num_latents}")
+        if k + self.E > min(num_latents, MAX_SELECTED):
+            raise ValueError(f"k + E = {k} + {self.E} exceeds min(num_latents, {MAX_SELECTED}) = "
+                             f"{min(num_latents, MAX_SELECTED)}")
+        if device is not None:
+            want, have = torch.device(device), self.feat.device
+            if want.type != have.type or (want.index is not None and have.index is not None and want.index != have.index):
+                raise ValueError(f"FeatureEdits lives on {have}, the encode runs on {want}")
+
+    def __len__(self) -> int:
+        return self.E
+
+    def __repr__(self) -> str:
+        n_zero = sum(1 for kd in self.kinds if kd == EDIT_ZERO)
+        return f"FeatureEdits(num_latents={self.num_latents}, E={self.E}: {self.E - n_zero} set, {n_zero} zero)"
+
+
+def as_off_features(off_features, sae) -> Tuple[int, Optional[FeatureEdits]]:
+    """The attribution hooks' `off_features` (None, an int, a sequence or a tensor: what `mask[:, off_features] = 0`
+    takes) -> (zero_feature for the in-kernel scalar route, or -1; FeatureEdits on `sae`'s device for the list route, or
+    None).  `sae` is only looked at for a list: a feature-sharded engine takes the scalar route alone."""
+    if off_features is None:
+        return -1, None
+    if isinstance(off_features, FeatureEdits):
+        return -1, off_features
+    if isinstance(off_features, (int, np.integer)) and not isinstance(off_features, bool):
+        return int(off_features), None
+    if isinstance(off_features, Tensor) and off_features.dim() == 0:
+        return int(off_features), None
+    feats = _int_list(off_features, "zero")
+    if not feats:                                   # `mask[:, []] = 0` edits nothing
+        return -1, None
+    if not hasattr(sae, "encoder"):
+        raise NotImplementedError("ablating a set of features runs on the single-GPU msae.Sae only: a feature-sharded "
+                                  "engine takes one feature")
+    return -1, FeatureEdits(sae.num_latents, zero=feats, device=sae.encoder.weight.device)

@@ -5,33 +5,37 @@ Reference hooks replaced (behaviour identical, dense `[T, N]` latents never mate
         latents = pre_acts(h); if S != 1: latents[:, :, f] = clamp; topk; decode(top[0]) -> fp16
   * attribution  features/patching/utils.py:33-58:
         latents = pre_acts(h.flatten(0,1)); latents[:, off] *= 0; topk; decode -> fp16 view(B,S,d)
-The latent edits are arguments of the fused encode kernel (`set_feature`, `zero_feature`).
+The latent edits are arguments of the fused encode kernel (`set_feature`, `zero_feature`); a LIST of features -- the
+reference's indexing takes one -- goes through `FeatureEdits`: an over-fetching encode and the list edit kernel
+(msae/features/edits.py).
 """
 from __future__ import annotations
 
-from typing import Callable, Dict, Optional
+from typing import Callable, Dict, Mapping, Optional
 
 import torch
 from torch import Tensor
 
 from ..sae import Sae
+from .edits import FeatureEdits, as_off_features
 
 
 def sae_reconstruct(sae, hidden: Tensor, *, set_feature: int = -1, set_value: float = 0.0,
                     zero_feature: int = -1, out_dtype: Optional[torch.dtype] = None,
-                    differentiable: Optional[bool] = None) -> Tensor:
+                    differentiable: Optional[bool] = None, edits: Optional[FeatureEdits] = None) -> Tensor:
     """[..., d] hidden states -> SAE reconstruction of the same shape.  `sae` is an `Sae` module or a
     feature-sharded engine (msae.parallel.ShardedSae over an N/G slice of the encoder per rank, SURVEY 8f rank 4:
     "N-sharded across 8 GPUs"; every rank must hold the same hidden states): same edits, by GLOBAL feature id, same
-    bits out."""
+    bits out.  `edits`: a set of edits instead of the scalar arguments (single-GPU `Sae` only)."""
     flat = hidden.reshape(-1, hidden.shape[-1])
     if isinstance(sae, Sae):
         top = sae.encode(flat, set_feature=set_feature, set_value=set_value, zero_feature=zero_feature,
-                         differentiable=differentiable)
+                         differentiable=differentiable, edits=edits)
         out = sae.decode(top.top_acts, top.top_indices)
     else:   # engine interface: encode -> (acts, global ids, status), decode(acts, ids)
+        ed = {} if edits is None else {"edits": edits}      # (an engine raises NotImplementedError on a set of edits)
         acts, idx, _ = sae.encode(flat.contiguous(), set_feature=set_feature, set_value=set_value,
-                                  zero_feature=zero_feature)
+                                  zero_feature=zero_feature, **ed)
         out = sae.decode(acts, idx)
     return out.to(out_dtype or hidden.dtype).view(hidden.shape)
 
@@ -108,9 +112,29 @@ class _DecodeStepGraph:
         self.keep = (sae._prepared_weights(), ops._WS.get((h.device, side.cuda_stream)), side)
 
 
-def clamp_features_max(sae, feature: int, hooked_module: torch.nn.Module, k: float = 10, graph_step: Optional[bool] = None):
+def _steering_edits(sae, feature, k: float):
+    """`feature` of clamp_features_max -> (set_feature for the in-kernel scalar route or -1, FeatureEdits or None)."""
+    if isinstance(feature, FeatureEdits):
+        return -1, feature
+    if isinstance(feature, Mapping):
+        table = feature
+    elif isinstance(feature, Tensor) and feature.dim() > 0:
+        table = {int(f): float(k) for f in feature.reshape(-1).tolist()}
+    elif isinstance(feature, (list, tuple, range)) or (hasattr(feature, "__iter__") and not isinstance(feature, Tensor)):
+        table = {int(f): float(k) for f in feature}
+    else:
+        return int(feature), None                   # today's path, unchanged
+    if not isinstance(sae, Sae):
+        raise NotImplementedError("clamping a set of features runs on the single-GPU msae.Sae only: a feature-sharded "
+                                  "engine takes one feature")
+    return -1, FeatureEdits(sae.num_latents, set=table, device=sae.device)
+
+
+def clamp_features_max(sae, feature, hooked_module: torch.nn.Module, k: float = 10, graph_step: Optional[bool] = None):
     """Register the steering hook (steering.py:102-128): on prefill (S != 1) the feature's latent
     is set to `k` before TopK; every call replaces the layer output by the fp16 reconstruction.
+    `feature`: an int (the in-kernel edit), a sequence or tensor of ints (`latents[:, :, f] = k` with a list: all
+    clamped to `k`), or a mapping feature -> value; a set is uploaded once, here, as a FeatureEdits.
     `sae`: an `Sae`, or a `ShardedSae` engine (the S = 1 decode steps then stream N/G rows of the encoder per rank
     and exchange 8 k_loc bytes; the decode of so few tokens is local on every rank).
     `graph_step`: replay the S = 1 step from a captured HIP graph (_DecodeStepGraph); default: on for a single-GPU `Sae`
@@ -120,6 +144,7 @@ def clamp_features_max(sae, feature: int, hooked_module: torch.nn.Module, k: flo
     if graph_step is None:
         graph_step = os.environ.get("MSAE_HOOK_GRAPH", "1") not in ("0", "")
     step_graph = _DecodeStepGraph() if (graph_step and isinstance(sae, Sae)) else None
+    set_feature, edits = _steering_edits(sae, feature, k)
 
     def hook(module, _, outputs):
         h = outputs[0] if isinstance(outputs, tuple) else outputs
@@ -129,8 +154,8 @@ def clamp_features_max(sae, feature: int, hooked_module: torch.nn.Module, k: flo
             out = step_graph(sae, h[0])
             if out is not None:
                 return _replace_first(outputs, out.unsqueeze(0))
-        out = sae_reconstruct(sae, h[0], set_feature=feature if prefill else -1, set_value=float(k),
-                              out_dtype=torch.float16).unsqueeze(0)
+        out = sae_reconstruct(sae, h[0], set_feature=set_feature if prefill else -1, set_value=float(k),
+                              out_dtype=torch.float16, edits=edits if prefill else None).unsqueeze(0)
         return _replace_first(outputs, out)
 
     handle = hooked_module.register_forward_hook(hook)
@@ -139,13 +164,19 @@ def clamp_features_max(sae, feature: int, hooked_module: torch.nn.Module, k: flo
 
 
 def attribution_sae_hook(sae_dict: Dict[str, Sae], module_to_name: Dict[torch.nn.Module, str],
-                         cache: Dict[str, Tensor], off_features: Optional[int] = None) -> Callable:
-    """Hook body of get_model_forward_cache_with_sae (patching/utils.py:33-58)."""
+                         cache: Dict[str, Tensor], off_features=None) -> Callable:
+    """Hook body of get_model_forward_cache_with_sae (patching/utils.py:33-58).  `off_features`: None, an int, or a
+    sequence / tensor of ints (`mask[:, off_features] = 0` takes any of them)."""
+    per_module: dict = {}         # a list of features becomes one FeatureEdits per hooked Sae, built at its first call
 
     def hook(module, inputs, outputs):
         h = outputs[0] if isinstance(outputs, tuple) else outputs
         name = module_to_name[module]
-        out = sae_reconstruct(sae_dict[name], h, zero_feature=-1 if off_features is None else off_features,
+        sae = sae_dict[name]
+        if name not in per_module:
+            per_module[name] = as_off_features(off_features, sae)
+        zero, edits = per_module[name]
+        out = sae_reconstruct(sae, h, zero_feature=zero, edits=edits,
                               out_dtype=torch.float16, differentiable=torch.is_grad_enabled())
         cache[name] = out
         return _replace_first(outputs, out)

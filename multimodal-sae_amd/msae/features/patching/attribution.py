@@ -97,10 +97,17 @@ class Attribution:
         return torch.arange(sae.num_latents)      # (the reference reads a misspelt cfg field here, attribution.py:121)
 
     def get_attribution(self, indices: Union[List[int], Tensor, None] = None, method: str = "exact"):
-        """-> {module name: [fp16 CPU tensor [B, S] per requested feature]} (attribution.py:116-189)."""
+        """-> {module name: [fp16 CPU tensor [B, S] per requested feature]} (attribution.py:116-189).  With
+        method="exact" an element of `indices` may itself be a list of features: the group is ablated together
+        (`mask[:, off_features] = 0` with a list) and yields one result; "batched" linearises per feature and takes
+        plain indices only."""
         if indices is None:
             indices = self._default_indices()
-        indices = [int(i) for i in (indices.tolist() if isinstance(indices, Tensor) else indices)]
+        indices = [[int(j) for j in i] if isinstance(i, (list, tuple)) else int(i)
+                   for i in (indices.tolist() if isinstance(indices, Tensor) else indices)]
+        if method == "batched" and any(isinstance(i, list) for i in indices):
+            raise ValueError("method='batched' scores one feature at a time (its linearisation is per feature): "
+                             "ablate a group of features with method='exact'")
         if method == "batched":
             out = self._batched(indices)
         elif method == "exact":
@@ -111,7 +118,7 @@ class Attribution:
             dist.barrier()
         return out
 
-    def _per_feature(self, indices: List[int]):
+    def _per_feature(self, indices: list):
         attribution_dict = collections.defaultdict(list)
         with torch.no_grad():    # the clean run does not depend on the feature and is never differentiated
             _, clean_cache = get_model_forward_cache_with_sae(self.model, self.inputs, self.sae_dict,

@@ -20,6 +20,7 @@ import torch
 from torch import Tensor
 
 from ...sae import Sae
+from ..edits import as_off_features
 
 
 def get_logit_diff(logits: Tensor, answer_token_indices: Tensor) -> Tensor:
@@ -32,12 +33,16 @@ def get_logit_diff(logits: Tensor, answer_token_indices: Tensor) -> Tensor:
 
 
 def sae_splice_hook(sae_dict: Dict[str, Sae], module_to_name: Dict[torch.nn.Module, str],
-                    cache: Dict[str, Tensor], off_features: Optional[int] = None,
+                    cache: Dict[str, Tensor], off_features=None,
                     keep_latents: Optional[Dict[str, Tuple[Tensor, Tensor]]] = None, extra_k: int = 0) -> Callable:
-    """Forward-hook body of get_model_forward_cache_with_sae (utils.py:33-58).  `keep_latents`
+    """Forward-hook body of get_model_forward_cache_with_sae (utils.py:33-58).  `off_features`: None, an int (the edit
+    inside the fused kernel), or a sequence / tensor of ints as `mask[:, off_features] = 0` takes (one FeatureEdits per
+    hooked Sae, built at its first call: over-fetching encode + list edit).  `keep_latents`
     (optional) receives the (top_acts, top_indices) of every hooked module -- the batched
     attribution needs them; `extra_k` asks the encoder for that many latents beyond k (the
     reconstruction still uses the first k)."""
+
+    per_module: dict = {}
 
     def hook(module, inputs, outputs):
         unpacked = list(outputs) if isinstance(outputs, tuple) else [outputs]
@@ -45,18 +50,26 @@ def sae_splice_hook(sae_dict: Dict[str, Sae], module_to_name: Dict[torch.nn.Modu
         sae = sae_dict[name]
         bs, seq_len, dim = unpacked[0].shape
         flat = unpacked[0].flatten(0, 1)
-        zero = -1 if off_features is None else int(off_features)
+        if name not in per_module:
+            per_module[name] = as_off_features(off_features, sae)
+        zero, edits = per_module[name]
         if extra_k:
             from ... import ops
 
             with torch.no_grad():
-                va, ia, _ = ops.encode_topk(flat, sae.encoder.weight, sae.encoder.bias, sae.b_dec,
-                                            sae._prepared_weights(), sae.cfg.k + extra_k, -1, 0.0, zero)
+                if edits is not None:
+                    edits.check(sae.num_latents, sae.cfg.k + extra_k, sae.device)
+                    va, ia, _ = ops.encode_topk(flat, sae.encoder.weight, sae.encoder.bias, sae.b_dec,
+                                                sae._prepared_weights(), sae.cfg.k + extra_k + edits.E)
+                    va, ia = ops.edit_topk(va, ia, edits.feat, edits.val, edits.kind, sae.num_latents, sae.cfg.k + extra_k)
+                else:
+                    va, ia, _ = ops.encode_topk(flat, sae.encoder.weight, sae.encoder.bias, sae.b_dec,
+                                                sae._prepared_weights(), sae.cfg.k + extra_k, -1, 0.0, zero)
             if keep_latents is not None:
                 keep_latents[name] = (va, ia)
         # the reference's graph is differentiable wherever autograd is on (the SAE's parameters require grad even under
         # a frozen LLM): keep that, rather than Sae.encode's default of following x.requires_grad
-        top = sae.encode(flat, zero_feature=zero, differentiable=torch.is_grad_enabled())
+        top = sae.encode(flat, zero_feature=zero, edits=edits, differentiable=torch.is_grad_enabled())
         if keep_latents is not None and not extra_k:
             keep_latents[name] = (top.top_acts.detach(), top.top_indices)
         sae_out = sae.decode(top.top_acts, top.top_indices).to(torch.float16).view(bs, seq_len, dim)
@@ -69,9 +82,10 @@ def sae_splice_hook(sae_dict: Dict[str, Sae], module_to_name: Dict[torch.nn.Modu
 
 
 def get_model_forward_cache_with_sae(model: torch.nn.Module, inputs: Dict[str, Any], sae_dict: Dict[str, Sae],
-                                     module_to_name: Dict[torch.nn.Module, str], off_features: int = None,
+                                     module_to_name: Dict[torch.nn.Module, str], off_features=None,
                                      keep_latents: Optional[dict] = None, extra_k: int = 0):
     """Run the model with every hooked module's output replaced by its SAE reconstruction.
+    `off_features`: None, an int, or a sequence / tensor of features zeroed together.
     -> (logits, {module name: fp16 reconstruction [B, S, d]})   (utils.py:21-71)."""
     cache: Dict[str, Tensor] = {}
     hook = sae_splice_hook(sae_dict, module_to_name, cache, off_features, keep_latents, extra_k)

@@ -784,6 +784,57 @@ def _(x, W_enc, b_enc, b_dec, prepared, k, set_feature=-1, set_value=0.0, zero_f
             x.new_empty(x.shape[:-1], dtype=torch.int32))
 
 
+# ---- set-valued hook edits on the top-k list (csrc/edit_topk.hip) ------------------------------------
+EDIT_TOPK_MAX_SELECTED = 4096       # k + E: msae_encode_topk's own limit on k
+
+
+@torch.library.custom_op("msae::edit_topk", mutates_args=())
+def _edit_topk(vals_in: Tensor, idx_in: Tensor, edit_feat: Tensor, edit_val: Tensor, edit_kind: Tensor,
+               num_latents: int, k: int) -> Tuple[Tensor, Tensor]:
+    dev = _hip.require_device(vals_in, idx_in, edit_feat, edit_val, edit_kind)
+    lib = _hip.load()
+    assert vals_in.shape == idx_in.shape and vals_in.dim() >= 1, \
+        f"vals_in and idx_in must share a shape [..., kk], got {tuple(vals_in.shape)} and {tuple(idx_in.shape)}"
+    assert idx_in.dtype in (torch.int32, torch.int64), f"idx_in must be int32 or int64, got {idx_in.dtype}"
+    E, kk = edit_feat.numel(), vals_in.shape[-1]
+    assert edit_val.numel() == E and edit_kind.numel() == E, "the edit table's three arrays must have one length"
+    v_in = _f32c(vals_in)
+    i_in = idx_in.detach().contiguous()
+    ef = edit_feat.detach().to(torch.int32).contiguous()
+    ev = _f32c(edit_val)
+    ek = edit_kind.detach().to(torch.int32).contiguous()
+    T = v_in.numel() // max(kk, 1)
+    vals = torch.empty(*v_in.shape[:-1], k, dtype=torch.float32, device=dev)
+    idx = torch.empty(*v_in.shape[:-1], k, dtype=i_in.dtype, device=dev)
+    wide = i_in.dtype == torch.int64
+    fn, name = (lib.msae_edit_topk_i64_f32, "msae_edit_topk_i64_f32") if wide else (lib.msae_edit_topk_f32, "msae_edit_topk_f32")
+    with torch.cuda.device(dev):
+        _hip.check(fn(_hip.ptr(v_in), _hip.ptr(i_in), T, kk, _hip.ptr(ef), _hip.ptr(ev), _hip.ptr(ek), E, num_latents, k,
+                      _hip.ptr(vals), _hip.ptr(idx), _hip.stream_of(v_in)), name)
+    return vals, idx
+
+
+@_edit_topk.register_fake
+def _(vals_in, idx_in, edit_feat, edit_val, edit_kind, num_latents, k):
+    return (vals_in.new_empty(*vals_in.shape[:-1], k, dtype=torch.float32),
+            idx_in.new_empty(*idx_in.shape[:-1], k))
+
+
+def edit_topk(vals_in: Tensor, idx_in: Tensor, edit_feat: Tensor, edit_val: Tensor, edit_kind: Tensor, num_latents: int,
+              k: int) -> Tuple[Tensor, Tensor]:
+    """The canonical top-k of the EDITED latents from an unedited top-kk list -> (vals f32 [..., k], idx [..., k] in
+    idx_in's dtype, int32 or int64).  vals_in / idx_in [..., kk]: encode_topk's output for kk >= k + E without edits;
+    edit_feat int [E] strictly ascending in [0, num_latents), edit_val f32 [E], edit_kind int [E] (0 set, 1 zero) -- the
+    arrays of a msae.features.FeatureEdits.  Exact: include/msae.h, "set-valued hook edits".  Nothing is read back; the
+    arguments the library would refuse (kk < k + E, k + E > num_latents, k + E > 4096, E < 1) raise ValueError here."""
+    E, kk = edit_feat.numel(), vals_in.shape[-1]
+    if E < 1 or k < 1 or kk < k + E or k + E > num_latents or k + E > EDIT_TOPK_MAX_SELECTED:
+        raise ValueError(f"edit_topk: need E >= 1, k >= 1, kk >= k + E and k + E <= min(num_latents, {EDIT_TOPK_MAX_SELECTED}); "
+                         f"got kk = {kk}, k = {k}, E = {E}, num_latents = {num_latents}")
+    _no_grad_inputs("ops.edit_topk", vals_in, edit_val)
+    return _edit_topk(vals_in, idx_in, edit_feat, edit_val, edit_kind, num_latents, k)
+
+
 def shard_candidates(x: Tensor, b_enc_shard: Optional[Tensor], b_dec: Optional[Tensor], prepared_shard: Tensor,
                      N_shard: int, k: int, row_offset: int, C: int, set_feature: int = -1,
                      zero_feature: int = -1) -> Tensor:
@@ -1066,11 +1117,20 @@ class _SparseEncode(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, W_enc, b_enc, b_dec, k, dead_mask, k_aux, k_multi, prepared=None, set_feature=-1,
-                set_value=0.0, zero_feature=-1):
+                set_value=0.0, zero_feature=-1, edit_set=None):
         vals, idxs = [], []
-        edits = set_feature >= 0 or zero_feature >= 0
+        edits = set_feature >= 0 or zero_feature >= 0 or edit_set is not None
         assert not (edits and (k_aux > 0 or k_multi > 0)), "hook edits apply to the plain top-k only"
-        if k_aux == 0 and max(k, k_multi) <= 256:
+        if edit_set is not None:
+            # a SET of edits (msae.features.FeatureEdits): the unedited encode over-fetches k + E entries, edit_topk re-ranks
+            # each list with the edits applied (exact: DESIGN.md section 7d) -- the same two steps as the inference path
+            assert set_feature < 0 and zero_feature < 0, "edits= and the scalar edit arguments are mutually exclusive"
+            v, i, _ = encode_topk(x, W_enc, b_enc, b_dec,
+                                  prepared if prepared is not None else _refresh_train_operands(W_enc, x.shape[0]),
+                                  k + edit_set.E)
+            v, i = edit_topk(v, i, edit_set.feat, edit_set.val, edit_set.kind, W_enc.shape[0], k)
+            vals.append(v); idxs.append(i)
+        elif k_aux == 0 and max(k, k_multi) <= 256:
             # no AuxK term: the fused encoder gives the canonical top-max(k, 4k); the top-k is its
             # prefix (same order), and the dense [T, N] latents are never built.  `prepared`: operands
             # of a weight that does not change between calls (inference hooks); None = training step
@@ -1099,6 +1159,7 @@ class _SparseEncode(torch.autograd.Function):
         ctx.save_for_backward(x, W_enc, b_dec, torch.cat(idxs, -1), torch.cat(vals, -1))
         ctx.splits = [t.shape[-1] for t in vals]
         ctx.set_feature = set_feature
+        ctx.edit_mask = None if edit_set is None else edit_set.mask
         ctx.has_b_enc = b_enc is not None
         out = []
         for v, i in zip(vals, idxs):
@@ -1115,6 +1176,8 @@ class _SparseEncode(torch.autograd.Function):
         g_cat = torch.cat(g, -1).float() * (val_cat > 0)           # relu'
         if ctx.set_feature >= 0:                                   # a latent overwritten by a constant carries no gradient
             g_cat = g_cat * (idx_cat != ctx.set_feature)
+        if ctx.edit_mask is not None:                              # ... and neither does one of a set of edited latents
+            g_cat = g_cat * ~ctx.edit_mask[idx_cat]
         a = x.float() - b_dec
         need_x, need_W, need_be, need_bd = ctx.needs_input_grad[:4]
         g_x = g_W = g_be = g_bd = None
@@ -1138,19 +1201,20 @@ class _SparseEncode(torch.autograd.Function):
             da = decode(idx_cat, g_cat, W_enc, None)
             g_x = da.to(x.dtype) if need_x else None
             g_bd = -da.sum(0) if need_bd else None
-        return g_x, g_W, g_be, g_bd, None, None, None, None, None, None, None, None
+        return g_x, g_W, g_be, g_bd, None, None, None, None, None, None, None, None, None
 
 
 def sparse_encode(x: Tensor, W_enc: Tensor, b_enc: Tensor, b_dec: Tensor, k: int,
                   dead_mask: Optional[Tensor] = None, k_aux: int = 0, k_multi: int = 0, *,
                   prepared: Optional[Tensor] = None, set_feature: int = -1, set_value: float = 0.0,
-                  zero_feature: int = -1):
+                  zero_feature: int = -1, edits=None):
     """-> [(acts, idx)] for the top-k, (optional) AuxK and (optional) Multi-TopK selections.
     Differentiable w.r.t. x, W_enc, b_enc, b_dec through the selected latents (the graph of the
-    reference's pre_acts -> [mask] -> topk, sae.py:172-185, patching/utils.py:43-49)."""
+    reference's pre_acts -> [mask] -> topk, sae.py:172-185, patching/utils.py:43-49).  `edits`: a
+    msae.features.FeatureEdits instead of the scalar edit arguments; an edited latent carries no gradient."""
     lead = x.shape[:-1]
     out = _SparseEncode.apply(x.reshape(-1, x.shape[-1]), W_enc, b_enc, b_dec, k, dead_mask, k_aux, k_multi, prepared,
-                              set_feature, float(set_value), zero_feature)        # the node works on [T, d]
+                              set_feature, float(set_value), zero_feature, edits)  # the node works on [T, d]
     if len(lead) != 1:
         out = tuple(o.reshape(*lead, o.shape[-1]) for o in out)
     return [(out[2 * j], out[2 * j + 1]) for j in range(len(out) // 2)]

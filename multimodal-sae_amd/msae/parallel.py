@@ -358,10 +358,13 @@ class ShardedSae:
 
         return join, (vals[: hi - lo], idx[: hi - lo]), pack
 
-    def encode(self, x: Tensor, set_feature: int = -1, set_value: float = 0.0, zero_feature: int = -1):
+    def encode(self, x: Tensor, set_feature: int = -1, set_value: float = 0.0, zero_feature: int = -1, edits=None):
         """-> (top_acts [T,k] f32, top_indices [T,k] int64 GLOBAL feature ids, status [T]).  The optional edits are
         the hooks' (`latents[:, set_feature] = set_value`, `latents[:, zero_feature] = 0` before the TopK), by global
-        feature id."""
+        feature id.  A SET of edits (`edits=`, msae.features.FeatureEdits) is not implemented on sharded engines."""
+        if edits is not None:
+            raise NotImplementedError("edits= (a set of edited features) runs on the single-GPU msae.Sae only: a feature-sharded "
+                                      "engine takes the scalar set_feature / zero_feature arguments")
         ed = {}
         if set_feature >= 0:
             ed.update(set_feature=set_feature, set_value=set_value)
@@ -596,7 +599,10 @@ class EmulatedShardGroup:
         self.mode, self.world = mode, world
         self._second_round = None
 
-    def encode(self, x: Tensor, set_feature: int = -1, set_value: float = 0.0, zero_feature: int = -1):
+    def encode(self, x: Tensor, set_feature: int = -1, set_value: float = 0.0, zero_feature: int = -1, edits=None):
+        if edits is not None:
+            raise NotImplementedError("edits= (a set of edited features) runs on the single-GPU msae.Sae only: a feature-sharded "
+                                      "engine takes the scalar set_feature / zero_feature arguments")
         ed = {}
         if set_feature >= 0:
             ed.update(set_feature=set_feature, set_value=set_value)

@@ -203,10 +203,13 @@ class Sae(nn.Module):
 
     def encode(self, x: Tensor, *, set_feature: int = -1, set_value: float = 0.0,
                zero_feature: int = -1, return_status: bool = False, resolve: bool = True,
-               differentiable: Optional[bool] = None, exact: bool = False, certified: bool = False):
+               differentiable: Optional[bool] = None, exact: bool = False, certified: bool = False, edits=None):
         """Fused encode + TopK (sae.py:183-185).  `set_feature/set_value` and `zero_feature` apply
         the steering / attribution hooks' edits of the dense latents (steering.py:113-114,
-        patching/utils.py:43-48) inside the kernel, before TopK.
+        patching/utils.py:43-48) inside the kernel, before TopK.  `edits` (a msae.features.FeatureEdits) applies a SET of
+        such edits -- the reference's indexing takes a list or tensor of features: the unedited encode over-fetches
+        k + E entries per token and ops.edit_topk re-ranks each list with the edits applied; exact, bit-identical to the
+        scalar arguments for E = 1.  It is mutually exclusive with the scalar arguments (ValueError).
 
         The kernel verifies every token and recomputes the ones it cannot verify (degenerate
         activations: all-zero rows, fewer than k positive latents, tokens the error model of the
@@ -223,6 +226,10 @@ class Sae(nn.Module):
         hooks: the LLM's hidden states do), or the module is in TRAINING mode and a parameter requires grad (a loaded module is,
         as in the reference, until `.eval()` / `.requires_grad_(False)`), or `differentiable=True` is passed.  The detached fast
         path is what runs under `torch.no_grad()` (the cache and steering hooks) and in `eval()` mode."""
+        if edits is not None:
+            if set_feature >= 0 or zero_feature >= 0:
+                raise ValueError("Sae.encode: pass either edits= or the scalar set_feature / zero_feature arguments, not both")
+            edits.check(self.num_latents, self.cfg.k, self.encoder.weight.device)
         if differentiable is None:
             params = self.encoder.weight.requires_grad or self.encoder.bias.requires_grad or self.b_dec.requires_grad
             differentiable = x.requires_grad or (self.training and params and not (exact or certified or return_status))
@@ -238,12 +245,18 @@ class Sae(nn.Module):
             # same kernel, as one autograd node with the sparse backward
             (acts, idx), = ops.sparse_encode(x, self.encoder.weight, self.encoder.bias, self.b_dec, self.cfg.k,
                                              prepared=self._prepared_weights(), set_feature=set_feature,
-                                             set_value=set_value, zero_feature=zero_feature)
+                                             set_value=set_value, zero_feature=zero_feature, edits=edits)
             return EncoderOutput(acts, idx)
         with torch.no_grad():      # (a custom op without an autograd formula would hang a raising node on the outputs)
-            acts, idx, status = ops.encode_topk(x, self.encoder.weight, self.encoder.bias, self.b_dec,
-                                                self._prepared_weights(), self.cfg.k, set_feature,
-                                                float(set_value), zero_feature, exact=exact, certified=certified)
+            if edits is not None:  # over-fetch, then edit: `exact` / `certified` only change the first call
+                acts, idx, status = ops.encode_topk(x, self.encoder.weight, self.encoder.bias, self.b_dec,
+                                                    self._prepared_weights(), self.cfg.k + edits.E, exact=exact,
+                                                    certified=certified)
+                acts, idx = ops.edit_topk(acts, idx, edits.feat, edits.val, edits.kind, self.num_latents, self.cfg.k)
+            else:
+                acts, idx, status = ops.encode_topk(x, self.encoder.weight, self.encoder.bias, self.b_dec,
+                                                    self._prepared_weights(), self.cfg.k, set_feature,
+                                                    float(set_value), zero_feature, exact=exact, certified=certified)
         out = EncoderOutput(acts, idx)
         return (out, status) if return_status else out
 
