@@ -962,10 +962,17 @@ def decode_bwd(top_indices: Tensor, top_acts: Tensor, W_dec: Tensor, grad_out: T
             ws = _workspace(dev, lib.msae_decode_bwd_wdec_ws_bytes(A, k, N))
             rowsq = torch.empty(N, dtype=torch.float32, device=dev) if _WGRAD_COLLECT is not None else None
             rowsum = torch.empty(N, dtype=torch.float32, device=dev) if _WGRAD_ROWSUM is not None else None
-            _hip.check(lib.msae_decode_bwd_wdec_f32(_hip.ptr(idx), _hip.ptr(acts), _hip.ptr(g), A, k, N,
-                                                    d, _hip.ptr(g_w), _hip.ptr(rowsq), _hip.ptr(rowsum), _hip.ptr(flag),
+            # the weight-gradient kernel works on whole f32x4 columns: a width that is no multiple of four runs zero-padded to
+            # the next one (columns are independent fma chains, the zero columns add exactly 0 to the row's squared norm)
+            d4 = (d + 3) // 4 * 4
+            g4 = g if d4 == d else torch.nn.functional.pad(g.reshape(-1, d), (0, d4 - d))
+            g_w4 = g_w if d4 == d else torch.empty(N, d4, dtype=torch.float32, device=dev)
+            _hip.check(lib.msae_decode_bwd_wdec_f32(_hip.ptr(idx), _hip.ptr(acts), _hip.ptr(g4), A, k, N,
+                                                    d4, _hip.ptr(g_w4), _hip.ptr(rowsq), _hip.ptr(rowsum), _hip.ptr(flag),
                                                     _hip.ptr(ws), ws.numel(), st),
                        "msae_decode_bwd_wdec_f32")
+            if d4 != d:
+                g_w.copy_(g_w4[:, :d])
             if rowsum is not None:
                 _WGRAD_ROWSUM.append(rowsum)
             if rowsq is not None:
