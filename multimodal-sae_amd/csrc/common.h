@@ -80,12 +80,19 @@ __device__ __forceinline__ float f32_from_order_key(unsigned k) {
   unsigned b = (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k;
   return __uint_as_float(b);
 }
-// 64-bit rank key of (value, index): value desc, then index asc  <=>  key desc
-__device__ __forceinline__ unsigned long long rank_key(float v, int idx) {
-  return ((unsigned long long)f32_order_key(v) << 32) | (unsigned)(0x7FFFFFFF - idx);
+// 64-bit rank key of (value, index): value desc, then index asc  <=>  key desc.  The order key of the value in the upper word,
+// 0x7FFFFFFF - index in the lower; key 0 (no pair produces it) ranks last and stands for "empty".  The layout lives HERE only.
+__device__ __forceinline__ unsigned long long rank_key_from_order(unsigned order_key, int idx) {
+  return ((unsigned long long)order_key << 32) | (unsigned)(0x7FFFFFFF - idx);
 }
+__device__ __forceinline__ unsigned long long rank_key(float v, int idx) { return rank_key_from_order(f32_order_key(v), idx); }
 __device__ __forceinline__ int rank_key_index(unsigned long long k) {
   return 0x7FFFFFFF - (int)(unsigned)(k & 0xFFFFFFFFull);
+}
+__device__ __forceinline__ float rank_key_value(unsigned long long k) { return f32_from_order_key((unsigned)(k >> 32)); }
+// the same value word, index word of idx
+__device__ __forceinline__ unsigned long long rank_key_with_index(unsigned long long k, int idx) {
+  return (k & 0xFFFFFFFF00000000ull) | (unsigned)(0x7FFFFFFF - idx);
 }
 
 // optional outputs of the row top-k launch (exact fallback of the fused encoder): 64-bit indices beside or
@@ -99,7 +106,7 @@ struct TopkExtra {
 };
 
 // optional second output of the threshold select (msae_kth_value_launch): every value of the row ABOVE the threshold found is
-// appended to its row's candidate list as (order key << 32 | 0x7FFFFFFF - feature), feature of column j = j*stride + off
+// appended to its row's candidate list as rank_key_from_order(order key, feature), feature of column j = j*stride + off
 struct KthPush {
   int *cnt = nullptr;                // [T] list lengths (atomically advanced); null: no push
   unsigned long long *cand = nullptr;
@@ -107,26 +114,6 @@ struct KthPush {
   int cnt_stride = 1;                // row t's counter is cnt[t * cnt_stride] ...
   int row_stride = 0;                // ... and its list starts at cand[t * row_stride] (0: cap) -- segmented lists: segment 0
 };
-
-// Bitonic sort of n (power of two) 64-bit keys in LDS, DESCENDING; all threads of the block call.
-__device__ __forceinline__ void bitonic_sort_desc_u64(unsigned long long *s, int n) {
-  for (int size = 2; size <= n; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      __syncthreads();
-      for (int i = threadIdx.x; i < (n >> 1); i += blockDim.x) {
-        int lo = (i / stride) * (stride << 1) + (i % stride);
-        int hi = lo + stride;
-        bool desc = ((lo & size) == 0);
-        unsigned long long a = s[lo], b = s[hi];
-        if ((a < b) == desc) {
-          s[lo] = b;
-          s[hi] = a;
-        }
-      }
-    }
-  }
-  __syncthreads();
-}
 
 __host__ __device__ static inline int next_pow2(int v) {
   int p = 1;

@@ -10,6 +10,7 @@
 // independent 16-B loads per lane are in flight; the f32 fma chain runs in j order so the result
 // is bit-identical to oracle/sae_oracle.c:msae_oracle_decode.
 #include "common.h"
+#include "wave_ops.h"
 
 namespace {
 
@@ -168,7 +169,8 @@ __global__ __launch_bounds__(256) void wgrad_count_kernel(const int32_t *__restr
 // single workgroup: offsets[n] = exclusive prefix of counts; cursor = copy; offsets[N] = total.  Tiles of 8192 counts: a thread
 // owns 8 CONSECUTIVE counts (two coalesced 16-B loads, its local prefix in registers), one wave scan of the thread totals, one
 // LDS hop across the 16 waves, coalesced 16-B stores: 16 iterations at N = 131072 (the 1024-wide scan of round 3 took 128
-// iterations = 137 us; a chunk-per-thread scan, tried first in round 4, 265 us: 4-byte accesses 512 B apart).
+// iterations = 137 us; a chunk-per-thread scan, tried first in round 4, 265 us: 4-byte accesses 512 B apart).  The carry stays
+// in LDS behind its two barriers: on wave_ops.h's block_excl_scan with a register carry the kernel took 34.1 us against 29.0.
 __global__ __launch_bounds__(1024) void wgrad_scan_kernel(const int *__restrict__ counts, int N,
                                                           int *__restrict__ offsets,
                                                           int *__restrict__ cursor) {
@@ -190,12 +192,7 @@ __global__ __launch_bounds__(1024) void wgrad_scan_kernel(const int *__restrict_
     int tot = 0;
 #pragma unroll
     for (int e = 0; e < 8; ++e) { const int t = v[e]; v[e] = tot; tot += t; }   // v[e] = exclusive prefix inside the thread
-    int incl = tot;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int o = __shfl_up(incl, off, 64);
-      if (lane >= off) incl += o;
-    }
+    const int incl = wave_incl_scan(tot, lane);
     if (lane == 63) wave_tot[wave] = incl;
     __syncthreads();
     int pre = carry;

@@ -16,13 +16,14 @@
 //   2. list entry j < k + E binary-searches them; a hit drops the entry (its feature's value is the edit's)
 //   3. survivors and the E edit entries become 64-bit rank keys (common.h: msae_topk_f32's / msae_merge_topk's key)
 //   4. the n_sort = next_pow2(k + 2 E) keys (padding: key 0, which no (value, index) pair produces) are sorted in LDS,
-//      bitonic, descending
+//      bitonic, descending (sortsel.h)
 //   5. the first k are decoded: value from the order key (a value of -0 comes back as +0, as msae_merge_topk's does), index
 // LDS per workgroup: 8 n_sort + 4 E bytes (2.2 KiB at k = 32, E = 50; 80 KiB at the envelope k + E = 4096, E = 4095).
 // The kernel never indexes memory by a list entry's feature, so a hostile index cannot fault it.
 #include <algorithm>
 
 #include "common.h"
+#include "sortsel.h"
 
 namespace {
 
@@ -63,10 +64,10 @@ __global__ __launch_bounds__(ET_MAX_THREADS) void edit_topk_kernel(
     }
     keys[j] = key;
   }
-  bitonic_sort_desc_u64(keys, n_sort);                              // (barriers before and after)
+  bitonic_sort_desc_u64<0>(keys, n_sort, threadIdx.x);              // run-time thread count (barriers before and after)
   for (int j = threadIdx.x; j < k; j += blockDim.x) {
     const unsigned long long key = keys[j];
-    vals[t * k + j] = f32_from_order_key((unsigned)(key >> 32));
+    vals[t * k + j] = rank_key_value(key);
     idx[t * k + j] = (IDX)rank_key_index(key);
   }
 }

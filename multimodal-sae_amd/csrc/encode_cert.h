@@ -78,8 +78,7 @@ __global__ __launch_bounds__(256) void cert_prepare_rows_kernel(const float *__r
     const f32x4 v = *reinterpret_cast<const f32x4 *>(row + c);
     m = fmaxf(fmaxf(m, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+  m = wave_max(m);
   if ((threadIdx.x & 63) == 0) red[0][threadIdx.x >> 6] = m;
   __syncthreads();
   m = fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3]));
@@ -164,8 +163,7 @@ __global__ __launch_bounds__(256) void cert_quant_x_kernel(const float *__restri
     const f32x4 v = *reinterpret_cast<const f32x4 *>(row + c);
     m = fmaxf(fmaxf(m, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+  m = wave_max(m);
   if ((threadIdx.x & 63) == 0) red[0][threadIdx.x >> 6] = m;
   __syncthreads();
   m = fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3]));

@@ -9,6 +9,7 @@
 
 #include "common.h"
 #include "tuning.h"
+#include "wave_ops.h"
 
 namespace {
 

@@ -698,7 +698,7 @@ __global__ __launch_bounds__(256) void sample_push_kernel(const float *__restric
       const int feat = (j + e) * SAMPLE_STRIDE + SAMPLE_OFF;
       if (feat == skip_a || feat == skip_b) continue;
       const int slot = atomicAdd(cnt + (size_t)t * cnt_stride, 1);
-      if (slot < cap) cand[(size_t)t * row_stride + slot] = ((unsigned long long)f32_order_key(u[e]) << 32) | (unsigned)(0x7FFFFFFF - feat);
+      if (slot < cap) cand[(size_t)t * row_stride + slot] = rank_key(u[e], feat);
     }
   }
 }

@@ -1,11 +1,11 @@
 // encode_rescore.h -- behind the candidate GEMM: per-token candidate select + exact f32 re-score + verification
 // (select_rescore_kernel), the feature-sharded group's record packing (pack_candidates_kernel), and their launchers.
-// Sort / select primitives: encode_sortsel.h.  Host dispatch: encode_fused.hip.
+// Sort / select primitives: sortsel.h.  Host dispatch: encode_fused.hip.
 #pragma once
 #include <type_traits>
 
 #include "encode_defs.h"
-#include "encode_sortsel.h"
+#include "sortsel.h"
 
 namespace {
 
@@ -123,7 +123,7 @@ __device__ __forceinline__ void load_list(const RescoreArgs &p, RescoreToken &tk
         const unsigned char *rec = x.recs + ((size_t)g * x.T + t) * x.stride;
         const unsigned long long key = reinterpret_cast<const unsigned long long *>(rec)[j];
         if (key != 0ull) {
-          kv = (key & 0xFFFFFFFF00000000ull) | (unsigned)(0x7FFFFFFF - i);
+          kv = rank_key_with_index(key, i);
           tk.ef[i] = rank_key_index(key);
           tk.ezs[i] = reinterpret_cast<const float *>(rec + (size_t)x.C * 8)[j];
           ++mine;
@@ -241,7 +241,7 @@ __device__ __forceinline__ int first_round_target(const RescoreArgs &p, const Re
     const unsigned long long key = tk.keys[lane];
     if constexpr (C::EXT) my_zs = tk.ezs[rank_key_index(key)];
     else my_zs = __builtin_sqrtf(band_sq(tk.rc, p.colc[rank_key_index(key)], p.zz12, p.i8 != 0));
-    my_cc = f32_from_order_key((unsigned)(key >> 32)) - my_zs;
+    my_cc = rank_key_value(key) - my_zs;
   }
   s_cc[lane] = my_cc;
   s_zs[lane] = my_zs;
@@ -316,7 +316,7 @@ __device__ __forceinline__ int rescore_pass(const RescoreArgs &p, const RescoreT
     f32x4 cc = {0.f, 0.f, 0.f, 0.f};
     if constexpr (C::EXT) { ext_zs = tk.ezs[f]; f = tk.ef[f]; }     // list position -> (z sigma, global feature)
     else cc = p.colc[f];
-    const float upper = f32_from_order_key((unsigned)(key >> 32));
+    const float upper = rank_key_value(key);
     const float *__restrict__ w = W_enc + (size_t)f * p.d + 4 * q;
     float acc = 0.f;
     // two batches of MSAE_RESCORE_U x 16 B per lane, software-pipelined: while one batch is consumed the
@@ -376,7 +376,7 @@ __device__ __forceinline__ int fm_pickup(const RescoreArgs &p, const RescoreToke
   for (int c = tk.lane; c < target; c += C::NT) {
     const unsigned long long key = tk.keys[c];
     const int f = rank_key_index(key);
-    const float upper = f32_from_order_key((unsigned)(key >> 32));
+    const float upper = rank_key_value(key);
     const float pre = p.fm.pre[(size_t)tk.t * p.fm.rcap + c];
     tk.res[has_set + c] = result_key(pre, f);
     if (contradicts_model(pre, upper, band_sq(tk.rc, p.colc[f], p.zz12, p.i8 != 0), p.z2, p.zc2)) my_viol = 1;
@@ -391,7 +391,7 @@ template <class C>
 __device__ __forceinline__ bool verify(const RescoreArgs &p, const RescoreToken &tk, KeyPrefix<C> &pre, int has_set, int done,
                                        int lim, bool viol, bool guarded, int &needed, bool &last) {
   const bool have_k = done + has_set >= p.k;
-  const float v_k = f32_from_order_key((unsigned)(tk.res[p.k - 1] >> 32));
+  const float v_k = rank_key_value(tk.res[p.k - 1]);
   const bool list_ok = tk.cnt <= p.cap && tk.tau > 0.f;
   needed = have_k ? pre.count_needed(p, tk, v_k) : tk.n;
   const bool ok = list_ok && have_k && !viol && needed <= done && v_k > tk.tau * 1.000001f && !guarded;
@@ -416,7 +416,7 @@ __device__ __forceinline__ void write_token(const RescoreArgs &p, const RescoreT
     const int fi = key ? rank_key_index(key) : 0;
     if (p.idx) p.idx[(size_t)t * p.k + j] = fi;
     if (p.idx64) p.idx64[(size_t)t * p.k + j] = fi;
-    p.vals[(size_t)t * p.k + j] = key ? f32_from_order_key((unsigned)(key >> 32)) : 0.f;
+    p.vals[(size_t)t * p.k + j] = key ? rank_key_value(key) : 0.f;
   }
   if (tk.lane == 0) {
     // not verified: 2 | reason bits (4 list overflow, 8 tau <= 0, 16 fewer than k candidates,
@@ -598,8 +598,7 @@ __global__ __launch_bounds__(256) void fm_scan_kernel(int *__restrict__ counts, 
   __syncthreads();
   if (tid < 64) {
     int v = part[tid] + part[tid + 64] + part[tid + 128] + part[tid + 192];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    v = wave_sum(v);
     if (tid == 0) s_base = v;
   }
   __syncthreads();
@@ -774,23 +773,19 @@ __global__ __launch_bounds__(64) void pack_candidates_kernel(PackArgs p) {
       [&](unsigned long long key, bool take, int pos) {
         if (take) {
           const int f = rank_key_index(key);
-          okeys[pos] = (key & 0xFFFFFFFF00000000ull) | (unsigned)(0x7FFFFFFF - (f + p.row_offset));
+          okeys[pos] = rank_key_with_index(key, f + p.row_offset);
           ozs[pos] = __builtin_sqrtf(band_sq(rc, p.colc[f], p.zz12, p.i8 != 0));
         } else {
           below = key > below ? key : below;
         }
       });
   for (int jj = taken + lane; jj < p.C; jj += 64) { okeys[jj] = 0ull; ozs[jj] = 0.f; }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const unsigned long long o = __shfl_xor(below, off, 64);
-    below = o > below ? o : below;
-  }
+  below = wave_max(below);
   if (lane == 0) {
     // what the shard's other features can reach: the best candidate left behind, else the threshold every
     // non-candidate stayed below; +inf when the shard cannot tell (overflowed list, degenerate token)
     float b = __builtin_inff();
-    if (bounded) b = below != 0ull ? f32_from_order_key((unsigned)(below >> 32)) : tau;
+    if (bounded) b = below != 0ull ? rank_key_value(below) : tau;
     float *tail = reinterpret_cast<float *>(rec + (size_t)p.C * 12);
     tail[0] = b;
     tail[1] = 0.f;

@@ -411,15 +411,15 @@ __device__ __forceinline__ void finalize_small(unsigned long long *keys, const u
     else if (has_set) kv = rank_key(set_value, set_feature);
     keys[i] = kv;
   }
-  wave_sort_desc_u64<64>(keys, 128, lane);
-  const float v_k = f32_from_order_key((unsigned)(keys[k - 1] >> 32));
+  bitonic_sort_desc_u64<64>(keys, 128, lane);
+  const float v_k = rank_key_value(keys[k - 1]);
   const bool ok = (v_k > tau * 1.000001f) && (v_k > 0.f) && (viol == 0);
   for (int j = lane; j < k; j += 64) {
     const unsigned long long key = keys[j];
     const int fi = key ? rank_key_index(key) : 0;
     if (idx.i32) idx.i32[(size_t)t * k + j] = fi;
     if (idx.i64) idx.i64[(size_t)t * k + j] = fi;
-    vals[(size_t)t * k + j] = key ? f32_from_order_key((unsigned)(key >> 32)) : 0.f;
+    vals[(size_t)t * k + j] = key ? rank_key_value(key) : 0.f;
   }
   if (lane == 0) {
     if (status) status[t] = ok ? 0 : (2 | (viol ? 64 : 32));
@@ -452,7 +452,7 @@ __global__ __launch_bounds__(64) void rescore_small_kernel(const float *__restri
   const unsigned long long ck = cand[(size_t)t * 128 + r];
   if (ck != 0ull) {                                    // wave-uniform
     const int f = rank_key_index(ck);
-    const float upper = f32_from_order_key((unsigned)(ck >> 32));
+    const float upper = rank_key_value(ck);
     const float *__restrict__ w = W_enc + (size_t)f * d + lane * 4;
     const float *__restrict__ a = a32 + (size_t)t * d + lane * 4;
     float acc = 0.f;

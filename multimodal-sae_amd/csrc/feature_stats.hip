@@ -22,6 +22,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "common.h"
+#include "wave_ops.h"
 
 namespace {
 
@@ -145,8 +146,7 @@ __global__ __launch_bounds__(64) void fs_merge_kernel(const unsigned long long *
       ai[0][j] = ti[j];
       tn += ti[j] >= 0;                             // valid entries sit at the front
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) tn += __shfl_xor(tn, off, 64);
+    tn = wave_sum(tn);
     int cur = 0;
     bool changed = false;
     __syncthreads();

@@ -893,7 +893,7 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[C::MI][C::NI], const
               if (u > side.tau(row)) {
                 const int t = m0 + row;
                 const int feat = gemm_feature(ep, n0 + col);
-                gemm_push_candidate(ep, t, ((unsigned long long)f32_order_key(u) << 32) | (unsigned)(0x7FFFFFFF - feat));
+                gemm_push_candidate(ep, t, rank_key(u, feat));
               }
             }
             ++slot;
@@ -929,7 +929,7 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[C::MI][C::NI], const
       if (!(u > side.tau(row))) continue;
       const int t = m0 + row;
       const int feat = gemm_feature(ep, n0 + col);
-      gemm_push_candidate(ep, t, ((unsigned long long)f32_order_key(u) << 32) | (unsigned)(0x7FFFFFFF - feat));
+      gemm_push_candidate(ep, t, rank_key(u, feat));
     }
   }
   MSAE_TL(5);

@@ -25,6 +25,7 @@
 #include <algorithm>
 
 #include "f32_tile.h"
+#include "wave_ops.h"
 
 namespace {
 
@@ -146,7 +147,7 @@ __global__ __launch_bounds__(F_THREADS, KMAX <= NB_K_SMALL ? 2 : 1) void rows_to
 #pragma unroll
     for (int j = 0; j < KMAX; ++j)
       if (j < k) {
-        plane0[off0 + j] = (int32_t)__float_as_uint(f32_from_order_key((unsigned)(list[j] >> 32)));
+        plane0[off0 + j] = (int32_t)__float_as_uint(rank_key_value(list[j]));
         if (wide) reinterpret_cast<int64_t *>(plane1)[off1 + j] = rank_key_index(list[j]);   // (one chunk, int64 output)
         else plane1[off1 + j] = rank_key_index(list[j]);
       }
@@ -164,8 +165,7 @@ __global__ __launch_bounds__(IN_THREADS) void row_inv_norms_kernel(const float *
       const double v = (double)w[i];
       s = __builtin_fma(v, v, s);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    s = wave_sum(s);
     if (lane == 0) {
       const double nrm = __builtin_sqrt(s);
       inv[n] = (float)(1.0 / (nrm > 1e-12 ? nrm : 1e-12));    // F.normalize's clamp (stats.py:80-81)

@@ -1,18 +1,24 @@
-// encode_sortsel.h -- sort and select primitives on 64-bit rank keys (value word above, index word below; 0 = empty, the
-// smallest key) for the stages behind the candidate GEMM (encode_rescore.h): bitonic sorts of an LDS array by one wave or one
-// workgroup, in LDS or in registers; a lookup in a sorted array; ballot counts and compaction of keys held in registers.
+// sortsel.h -- sort and select primitives on 64-bit keys that rank by descending value (common.h's rank keys: value word above,
+// index word below; 0 = empty, the smallest key) for every kernel that orders a list: the stages behind the candidate GEMM
+// (encode_rescore.h, encode_small.h), the row top-k and the shard merge (topk.hip), the cache records (sparsify.hip) and the
+// list edits (edit_topk.hip).  Bitonic sorts of an LDS array by one wave or one workgroup, in LDS or in registers; a lookup in
+// a sorted array; ballot counts and compaction of keys held in registers.
 #pragma once
 #include "common.h"
 
 namespace {
 
-// Wave-wide bitonic sort (descending) of n = power-of-two u64 keys in LDS by the NT threads of the workgroup.  Ends with a barrier.
+// Bitonic sort (descending) of the n = power-of-two u64 keys of the LDS array s by ALL threads of the workgroup: NT of them, or
+// blockDim.x where NT = 0 (a launch that sizes the workgroup at run time); tid = the caller's index among them.  The one LDS
+// compare-exchange loop of the library.  Barriers: one in front of every step -- so whoever filled s[] needs none of their own
+// -- and one behind the last: the sorted keys are visible to every thread.  n must be uniform over the workgroup.
 template <int NT>
-__device__ __forceinline__ void wave_sort_desc_u64(unsigned long long *s, int n, int lane) {
+__device__ __forceinline__ void bitonic_sort_desc_u64(unsigned long long *s, int n, int tid) {
+  const int nt = NT ? NT : (int)blockDim.x;
   for (int size = 2; size <= n; size <<= 1)
     for (int stride = size >> 1; stride > 0; stride >>= 1) {
       __syncthreads();
-      for (int i = lane; i < (n >> 1); i += NT) {
+      for (int i = tid; i < (n >> 1); i += nt) {
         const int lo = (i / stride) * (stride << 1) + (i % stride), hi = lo + stride;
         const bool desc = ((lo & size) == 0);
         const unsigned long long x = s[lo], y = s[hi];
@@ -126,7 +132,7 @@ __device__ __forceinline__ void lds_sort_desc_u64(unsigned long long *s, int n, 
   if constexpr (NW == 1 && RMAX >= 2) { if (n <= 128 && slots >= 128) { lds_sort_desc_u64_regs<1, 2>(s, n, tid); return; } }
   if constexpr (NW == 4 && RMAX >= 4) { if (n <= 1024 && slots >= 1024) { lds_sort_desc_u64_regs<4, 4>(s, n, tid); return; } }
   if constexpr (NW == 4 && RMAX >= 8) { if (n <= 2048 && slots >= 2048) { lds_sort_desc_u64_regs<4, 8>(s, n, tid); return; } }
-  wave_sort_desc_u64<64 * NW>(s, n < slots ? n : slots, tid);
+  bitonic_sort_desc_u64<64 * NW>(s, n < slots ? n : slots, tid);
 }
 
 // number of keys (sorted descending, value in the upper 32 bits as an order key) whose value is >= v

@@ -12,6 +12,8 @@
 // and an LDS bitonic sort puts them in canonical order.  HBM-bound: the row is streamed once from
 // HBM and re-read from L2 by the later passes (N*4 B = 512 KiB at N = 131072).
 #include "common.h"
+#include "sortsel.h"
+#include "wave_ops.h"
 
 namespace {
 
@@ -27,34 +29,6 @@ struct TkShared {
   unsigned base_gt;
   unsigned base_eq;
 };
-
-__device__ __forceinline__ unsigned wave_incl_scan(unsigned v, int lane) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    unsigned n = __shfl_up(v, off, 64);
-    if (lane >= off) v += n;
-  }
-  return v;
-}
-
-// Block-wide exclusive prefix sum of `v` in thread order; returns the exclusive prefix and
-// writes the block total to *total.  Uses sh.wave_tot; contains two barriers.
-__device__ __forceinline__ unsigned block_excl_scan(unsigned v, TkShared &sh, unsigned *total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  unsigned incl = wave_incl_scan(v, lane);
-  __syncthreads();  // previous users of wave_tot are done
-  if (lane == 63) sh.wave_tot[wave] = incl;
-  __syncthreads();
-  unsigned base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < TK_WAVES; ++w) {
-    unsigned t = sh.wave_tot[w];
-    if (w < wave) base += t;
-    tot += t;
-  }
-  *total = tot;
-  return base + incl - v;
-}
 
 template <bool VEC>
 __device__ __forceinline__ void load4(const float *row, int i, int N, float (&v)[4]) {
@@ -182,7 +156,7 @@ __global__ __launch_bounds__(TK_THREADS) void topk_rows_kernel(const float *__re
     const unsigned packed = c_gt | (c_eq << 16);
     if (__syncthreads_or((int)packed) == 0) continue;
     unsigned total;
-    const unsigned ex = block_excl_scan(packed, sh, &total);
+    const unsigned ex = block_excl_scan<TK_WAVES>(packed, sh.wave_tot, &total);
     unsigned p_gt = sh.base_gt + (ex & 0xFFFFu);
     unsigned p_eq = sh.base_eq + (ex >> 16);
 #pragma unroll
@@ -207,7 +181,7 @@ __global__ __launch_bounds__(TK_THREADS) void topk_rows_kernel(const float *__re
   __syncthreads();
 
   // ---- canonical order ---------------------------------------------------------------------
-  bitonic_sort_desc_u64(keys, kp);
+  bitonic_sort_desc_u64<TK_THREADS>(keys, kp, threadIdx.x);
   const int orow = ex.row_map ? ex.row_map[rowi] : rowi;
   for (int j = threadIdx.x; j < k; j += TK_THREADS) {
     const unsigned long long kk = keys[j];
@@ -301,7 +275,7 @@ __global__ __launch_bounds__(256) void kth_value_kernel(const float *__restrict_
         // 64-bit store for the whole kernel (2 x VPL VGPRs: half the occupancy)
         unsigned kk;
         asm volatile("v_mov_b32 %0, %1" : "=v"(kk) : "v"(key[i]));
-        if (slot < push.cap) list[slot] = ((unsigned long long)kk << 32) | (unsigned)(0x7FFFFFFF - (j * push.stride + push.off));
+        if (slot < push.cap) list[slot] = rank_key_from_order(kk, j * push.stride + push.off);
       }
       base += __builtin_popcountll(m);
       if ((i & 7) == 7) asm volatile("" : "+s"(base));
@@ -312,16 +286,24 @@ __global__ __launch_bounds__(256) void kth_value_kernel(const float *__restrict_
 // ---- merge of per-shard top-k_loc lists (feature-sharded encode, msae/parallel.py) ---------------
 // gathered: int32 [G][2][T][kl] exactly as all_gather_into_tensor lays out each rank's packed
 // [2][T][kl] block (plane 0 = f32 activation bits, plane 1 = GLOBAL feature index).
-// One wave per token: G*kl rank keys into LDS, bitonic sort, canonical top-k out.  flagged[t] = 1
-// when some shard's LAST gathered latent ranks inside the merged top-k (that shard may own more
-// members than it sent; the host redoes those tokens with k_loc = k).
-__global__ __launch_bounds__(64) void merge_topk_kernel(const int32_t *__restrict__ gathered, int T,
-                                                        int G, int kl, int k,
-                                                        float *__restrict__ vals,
-                                                        int32_t *__restrict__ idx,
-                                                        int32_t *__restrict__ flagged) {
+// One wave per token: G*kl rank keys into LDS, bitonic sort, canonical top-k out.  One body, two instantiations with the
+// outputs of their round:
+//   first round:  every token; flagged[t] (optional) = 1 when some shard's LAST gathered latent ranks inside the merged
+//                 top-k (that shard may own more members than it sent; the host redoes those tokens with k_loc = k).
+//   second round: the tokens with mask[t] != 0 only, nothing of the others is written (the redone tokens' full local top-k
+//                 lists replace the truncated merge; everybody else keeps round 1's result); idx, idx64: either may be null.
+// (One kernel with every argument optional was measured first: 37.3 us against 36.2 on the second round's call and 40.6
+// against 39.7 on the first's at T = 8192, G = 8, kl = 32 -- outside the parent's spread, so the rounds keep a kernel each.)
+template <bool SECOND> struct MergeOut;
+template <> struct MergeOut<false> { float *vals; int32_t *idx; int32_t *flagged; };
+template <> struct MergeOut<true> { const int32_t *mask; float *vals; int32_t *idx; int64_t *idx64; };
+
+template <bool SECOND>
+__global__ __launch_bounds__(64) void merge_topk_kernel(const int32_t *__restrict__ gathered, int T, int G, int kl, int k,
+                                                        MergeOut<SECOND> o) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long mkeys[];
   const int lane = threadIdx.x, t = blockIdx.x;
+  if constexpr (SECOND) { if (o.mask[t] == 0) return; }   // wave-uniform
   const int M = G * kl, np = next_pow2(M);
   unsigned long long worst_last = 0ull;  // best (largest) key among the shards' last entries
   for (int i = lane; i < np; i += 64) {
@@ -331,100 +313,43 @@ __global__ __launch_bounds__(64) void merge_topk_kernel(const int32_t *__restric
       const float v = __int_as_float(gathered[(((size_t)g * 2 + 0) * T + t) * kl + j]);
       const int f = gathered[(((size_t)g * 2 + 1) * T + t) * kl + j];
       key = rank_key(v, f);
-      if (j == kl - 1) worst_last = key > worst_last ? key : worst_last;
+      if constexpr (!SECOND) { if (j == kl - 1) worst_last = key > worst_last ? key : worst_last; }
     }
     mkeys[i] = key;
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const unsigned long long o = __shfl_xor(worst_last, off, 64);
-    worst_last = o > worst_last ? o : worst_last;
-  }
-  for (int size = 2; size <= np; size <<= 1)
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      __syncthreads();
-      for (int i = lane; i < (np >> 1); i += 64) {
-        const int lo = (i / stride) * (stride << 1) + (i % stride), hi = lo + stride;
-        const bool desc = ((lo & size) == 0);
-        const unsigned long long x = mkeys[lo], y = mkeys[hi];
-        if ((x < y) == desc) { mkeys[lo] = y; mkeys[hi] = x; }
-      }
-    }
-  __syncthreads();
+  if constexpr (!SECOND) worst_last = wave_max(worst_last);
+  bitonic_sort_desc_u64<64>(mkeys, np, lane);
   for (int j = lane; j < k; j += 64) {
     const unsigned long long key = mkeys[j];
-    idx[(size_t)t * k + j] = rank_key_index(key);
-    vals[(size_t)t * k + j] = f32_from_order_key((unsigned)(key >> 32));
+    if constexpr (SECOND) {
+      if (o.idx) o.idx[(size_t)t * k + j] = rank_key_index(key);
+      if (o.idx64) o.idx64[(size_t)t * k + j] = rank_key_index(key);
+    } else {
+      o.idx[(size_t)t * k + j] = rank_key_index(key);
+    }
+    o.vals[(size_t)t * k + j] = rank_key_value(key);
   }
-  if (lane == 0 && flagged) flagged[t] = (kl < k && worst_last >= mkeys[k - 1]) ? 1 : 0;
+  if constexpr (!SECOND) { if (lane == 0 && o.flagged) o.flagged[t] = (kl < k && worst_last >= mkeys[k - 1]) ? 1 : 0; }
 }
 
 // rows[0 .. n) = the t with flags[t] != 0, ascending; *n_rows = n.  ONE workgroup walks the flags 1024 at a time (ballot
-// prefix counts): the device-side redo list of the feature-sharded engine's second round -- every rank derives the same
-// list from the same gathered data, nothing is read back to the host.
+// prefix counts inside a wave, block_wave_offset across them): the device-side redo list of the feature-sharded engine's
+// second round -- every rank derives the same list from the same gathered data, nothing is read back to the host.
 __global__ __launch_bounds__(1024) void compact_flags_kernel(const int32_t *__restrict__ flags, int T,
                                                              int32_t *__restrict__ rows, int32_t *__restrict__ n_rows) {
-  __shared__ int wsum[16];
-  __shared__ int s_base;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  if (tid == 0) s_base = 0;
-  __syncthreads();
+  __shared__ int wave_tot[16];
+  const int lane = threadIdx.x & 63;
+  int carry = 0;                                    // flags set before this tile (the same in every thread)
   for (int base = 0; base < T; base += 1024) {
-    const int t = base + tid;
+    const int t = base + threadIdx.x;
     const bool f = t < T && flags[t] != 0;
     const unsigned long long m = __builtin_amdgcn_ballot_w64(f);
-    if (lane == 0) wsum[wv] = __builtin_popcountll(m);
-    __syncthreads();
-    int off = s_base;
-    for (int w = 0; w < wv; ++w) off += wsum[w];
+    int total;
+    const int off = carry + block_wave_offset<16>((int)__builtin_popcountll(m), wave_tot, &total);
     if (f) rows[off + __builtin_popcountll(m & ((1ull << lane) - 1ull))] = t;
-    __syncthreads();
-    if (tid == 0) {
-      int tot = 0;
-      for (int w = 0; w < 16; ++w) tot += wsum[w];
-      s_base += tot;
-    }
-    __syncthreads();
+    carry += total;
   }
-  if (tid == 0) *n_rows = s_base;
-}
-
-// merge_topk_kernel for the tokens of a mask only (second round: the redone tokens' full local top-k lists replace the
-// truncated merge; everybody else keeps round 1's result).  One wave per token, same key order.
-__global__ __launch_bounds__(64) void merge_topk_masked_kernel(const int32_t *__restrict__ gathered, int T, int G, int kl,
-                                                               int k, const int32_t *__restrict__ mask,
-                                                               float *__restrict__ vals, int32_t *__restrict__ idx,
-                                                               int64_t *__restrict__ idx64) {
-  extern __shared__ __attribute__((aligned(16))) unsigned long long mkeys[];
-  const int lane = threadIdx.x, t = blockIdx.x;
-  if (mask[t] == 0) return;                         // wave-uniform
-  const int M = G * kl, np = next_pow2(M);
-  for (int i = lane; i < np; i += 64) {
-    unsigned long long key = 0ull;
-    if (i < M) {
-      const int g = i / kl, j = i % kl;
-      const float v = __int_as_float(gathered[(((size_t)g * 2 + 0) * T + t) * kl + j]);
-      key = rank_key(v, gathered[(((size_t)g * 2 + 1) * T + t) * kl + j]);
-    }
-    mkeys[i] = key;
-  }
-  for (int size = 2; size <= np; size <<= 1)
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      __syncthreads();
-      for (int i = lane; i < (np >> 1); i += 64) {
-        const int lo = (i / stride) * (stride << 1) + (i % stride), hi = lo + stride;
-        const bool desc = ((lo & size) == 0);
-        const unsigned long long x = mkeys[lo], y = mkeys[hi];
-        if ((x < y) == desc) { mkeys[lo] = y; mkeys[hi] = x; }
-      }
-    }
-  __syncthreads();
-  for (int j = lane; j < k; j += 64) {
-    const unsigned long long key = mkeys[j];
-    if (idx) idx[(size_t)t * k + j] = rank_key_index(key);
-    if (idx64) idx64[(size_t)t * k + j] = rank_key_index(key);
-    vals[(size_t)t * k + j] = f32_from_order_key((unsigned)(key >> 32));
-  }
+  if (threadIdx.x == 0) *n_rows = carry;
 }
 
 }  // namespace
@@ -478,16 +403,20 @@ extern "C" int msae_topk_f32(const float *latents, int T, int N, int k, float *v
   return msae_topk_launch(latents, T, N, k, N, nullptr, vals, idx, (hipStream_t)stream, TopkExtra());
 }
 
-extern "C" int msae_merge_topk(const int32_t *gathered, int T, int G, int kl, int k, float *vals,
-                               int32_t *idx, int32_t *flagged, void *stream) {
+// argument check, LDS size and launch of merge_topk_kernel for both entry points
+template <bool SECOND>
+static int merge_topk_launch(const int32_t *gathered, int T, int G, int kl, int k, MergeOut<SECOND> o, void *stream) {
   if (T < 0 || G <= 0 || kl <= 0 || k <= 0 || (long)G * kl < k || (long)G * kl > 8192) return MSAE_EINVAL;
   if (T == 0) return 0;
   const size_t smem = (size_t)next_pow2(G * kl) * sizeof(unsigned long long);
-  MSAE_HIP_TRY(hipFuncSetAttribute((const void *)merge_topk_kernel,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-  hipLaunchKernelGGL(merge_topk_kernel, dim3(T), dim3(64), smem, (hipStream_t)stream, gathered, T, G,
-                     kl, k, vals, idx, flagged);
+  MSAE_HIP_TRY(hipFuncSetAttribute((const void *)merge_topk_kernel<SECOND>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+  hipLaunchKernelGGL(merge_topk_kernel<SECOND>, dim3(T), dim3(64), smem, (hipStream_t)stream, gathered, T, G, kl, k, o);
   return msae_launch_status();
+}
+
+extern "C" int msae_merge_topk(const int32_t *gathered, int T, int G, int kl, int k, float *vals,
+                               int32_t *idx, int32_t *flagged, void *stream) {
+  return merge_topk_launch<false>(gathered, T, G, kl, k, {vals, idx, flagged}, stream);
 }
 
 extern "C" int msae_compact_flags(const int32_t *flags, int T, int32_t *rows, int32_t *n_rows, void *stream) {
@@ -498,13 +427,6 @@ extern "C" int msae_compact_flags(const int32_t *flags, int T, int32_t *rows, in
 
 extern "C" int msae_merge_topk_masked(const int32_t *gathered, int T, int G, int kl, int k, const int32_t *mask,
                                       float *vals, int32_t *idx, int64_t *idx64, void *stream) {
-  if (T < 0 || G <= 0 || kl <= 0 || k <= 0 || (long)G * kl < k || (long)G * kl > 8192 || !mask || !vals || (!idx && !idx64))
-    return MSAE_EINVAL;
-  if (T == 0) return 0;
-  const size_t smem = (size_t)next_pow2(G * kl) * sizeof(unsigned long long);
-  MSAE_HIP_TRY(hipFuncSetAttribute((const void *)merge_topk_masked_kernel,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-  hipLaunchKernelGGL(merge_topk_masked_kernel, dim3(T), dim3(64), smem, (hipStream_t)stream, gathered, T, G, kl, k, mask,
-                     vals, idx, idx64);
-  return msae_launch_status();
+  if (!mask || !vals || (!idx && !idx64)) return MSAE_EINVAL;
+  return merge_topk_launch<true>(gathered, T, G, kl, k, {mask, vals, idx, idx64}, stream);
 }
