@@ -541,6 +541,42 @@ int msae_adam_rows_f32(float *W, const float *G, float *M, float *V, int rows, i
                        const float *total_sumsq, float max_norm, int project, float lr, float beta1,
                        float beta2, float eps, int step, void *stream);
 
+/* ---- blockwise 8-bit Adam moments ("adam8"; the role of bitsandbytes' Adam8bit in train/sae/sae/trainer.py:139-147,
+ * a format of this project's own: checkpoints are NOT interchangeable with bitsandbytes') ----
+ * A parameter is the [rows][d] view msae_adam_rows_f32 takes.  A BLOCK is 256 consecutive elements of one row, the last
+ * block of a row may be partial: nb = rows * ceil(d / 256) blocks, block b of row r is number r * ceil(d / 256) + b.
+ *   M8 uint8 [rows*d]   codes of the first moment m
+ *   R8 uint8 [rows*d]   codes of r = sqrt(v), the SQUARE ROOT of the second moment (v spans twice the binades of r)
+ *   SM, SR float32 [nb] one scale per block
+ * A code is OCP e4m3fn (gfx950's conversion instructions); stored value = decode(code) * scale, scale = absmax_block / 448.f
+ * (an all-zero block: scale 0, codes 0).
+ *   encode   q = x * (448.f / absmax), clamped to +-448 in float32, rounded to nearest, ties to even, subnormals included.
+ *            The NaN codes 0x7F / 0xFF are never written; 0x80 (-0) and 0x00 are the same value, either is valid.
+ *            R8 never loses a positive value: r > 0 that would round to 0 is stored as code 1 (the smallest subnormal) --
+ *            else an element whose v underflows inside a block with a large absmax would divide its still-nonzero m by eps.
+ *   decode   m = dec(M8) * SM[b];  r = dec(R8) * SR[b];  v = r * r -- three separate float32 multiplications, none of them
+ *            contracted into an fma.
+ * Shapes: d % 4 == 0, d <= 8192, and not one row of a length that is no multiple of 1024 (the view of a vector whose
+ * length 1024 does not divide: one workgroup would own the whole parameter); others return MSAE_ENOTIMPL and keep
+ * float32 moments.  msae_adam8_blocks adds the caller's policy floor rows * d >= 4096 (bitsandbytes' min_8bit_size): it
+ * returns nb, or 0 for a parameter that stays float32 (pure host code).  W, G, M, V, M8, R8 16-byte aligned.
+ *
+ * msae_adam8_rows_f32:       msae_adam_rows_fused_f32 (same clip, projection, Adam arithmetic, renorm_eps and prepared /
+ *                            T_next / opts tails, same bits of those tails given the same updated W) with the moments read
+ *                            from and written to the format above.  The update of W uses the float32 m', v' of this step;
+ *                            only the carried state is quantised.  No atomics: two runs give the same bits.
+ * msae_adam8_quantize_f32:   M, V (float32, V >= 0) -> M8, R8, SM, SR.
+ * msae_adam8_dequantize_f32: the inverse: exactly the m and v msae_adam8_rows_f32 computes with. */
+size_t msae_adam8_blocks(int rows, int d);
+int msae_adam8_rows_f32(float *W, const float *G, uint8_t *M8, uint8_t *R8, float *SM, float *SR, int rows, int d,
+                        const float *total_sumsq, float max_norm, int project, float lr, float beta1, float beta2,
+                        float eps, int step, float renorm_eps, void *prepared, int T_next, const msae_options *opts,
+                        void *stream);
+int msae_adam8_quantize_f32(const float *M, const float *V, uint8_t *M8, uint8_t *R8, float *SM, float *SR, int rows,
+                            int d, void *stream);
+int msae_adam8_dequantize_f32(const uint8_t *M8, const uint8_t *R8, const float *SM, const float *SR, float *M, float *V,
+                              int rows, int d, void *stream);
+
 /* ---- stage timing of msae_encode_topk's fused path (measurement aid for bench.py) --------------
  * A profile handle passed in msae_options::profile makes every fused msae_encode_topk call made with it
  * record HIP events, on the stream it launches on, at the boundaries of its 6 stages:

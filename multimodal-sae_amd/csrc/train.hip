@@ -15,6 +15,7 @@
 #include "common.h"
 #include "encode_defs.h"
 #include "encode_prep.h"
+#include "wave_ops.h"
 
 namespace {
 
@@ -220,6 +221,68 @@ struct FusedTail {
   RowQuantOut rq;
   unsigned short *wb, *ws;      // REFRESH 2: bf16 copy + bf16 sample rows
 };
+
+// ---- the steps of the fused pass as functions: adam8_rows_kernel (8-bit moments) is built from them.  adam_rows_fused_kernel
+// (float32 moments) uses clip_coef and refresh_row and keeps its projection / KEEP loops written out as they were: it is the
+// benchmarked kernel, and written this way the compiler emits the instructions it emitted before the 8-bit kernel existed.
+// c = min(1, max_norm / (sqrt(*total_sumsq) + 1e-6)), 1 without a total
+__device__ __forceinline__ float clip_coef(const float *__restrict__ total_sumsq, float max_norm) {
+  float clip = 1.f;
+  if (total_sumsq) {
+    const float c = max_norm / (sqrtf(*total_sumsq) + 1e-6f);
+    clip = c < 1.f ? c : 1.f;
+  }
+  return clip;
+}
+// <clip * G[r], W[r]> of the workgroup's row (d % 4 == 0)
+__device__ __forceinline__ float row_along(const float *__restrict__ G, const float *__restrict__ W, size_t base, int d,
+                                           float clip, float *red) {
+  float dot = 0.f;
+  for (int c = threadIdx.x * 4; c < d; c += 1024) {
+    const f32x4 g = *reinterpret_cast<const f32x4 *>(G + base + c);
+    const f32x4 w = *reinterpret_cast<const f32x4 *>(W + base + c);
+    dot += (g[0] * clip) * w[0] + (g[1] * clip) * w[1] + (g[2] * clip) * w[2] + (g[3] * clip) * w[3];
+  }
+  return block_sum(dot, red);
+}
+// the updated row waits in registers for its norm: trip `it` of a thread is keep[it] (d <= 8192, checked by the host)
+constexpr int KEEP = 8;
+__device__ __forceinline__ void keep_put(f32x4 (&keep)[KEEP], int it, const f32x4 w) {
+#pragma unroll
+  for (int q = 0; q < KEEP; ++q) if (q == it) keep[q] = w;
+}
+__device__ __forceinline__ void renorm_store(float *__restrict__ W, size_t base, int d, const f32x4 (&keep)[KEEP], float inv) {
+  int it = 0;
+  for (int c = threadIdx.x * 4; c < d; c += 1024, ++it) {
+    f32x4 v = keep[0];
+#pragma unroll
+    for (int q = 1; q < KEEP; ++q) if (q == it) v = keep[q];
+    v[0] *= inv; v[1] *= inv; v[2] *= inv; v[3] *= inv;
+    *reinterpret_cast<f32x4 *>(W + base + c) = v;
+  }
+}
+// REFRESH 1 / 2: the coarse-pass operands of the row the workgroup has just written
+template <int REFRESH>
+__device__ __forceinline__ void refresh_row(float *__restrict__ W, size_t base, int d, const FusedTail &ft,
+                                            float (&red3)[3][4]) {
+  __threadfence_block();
+  __syncthreads();                              // the whole updated row is visible to the workgroup (same CU, same L1)
+  const int n = blockIdx.x;
+  if constexpr (REFRESH == 1) {
+    row_stats_quant_row<true>(W, n, d, ft.rq, red3);
+  } else {
+    row_stats_quant_row<false>(W, n, d, ft.rq, red3);
+    const bool samp = (n % SAMPLE_STRIDE) == SAMPLE_OFF;
+    for (int c = threadIdx.x * 4; c < d; c += 1024) {
+      const f32x4 v = *reinterpret_cast<const f32x4 *>(W + base + c);
+      u16x4 o;
+      o[0] = f32_to_bf16_bits(v[0]); o[1] = f32_to_bf16_bits(v[1]); o[2] = f32_to_bf16_bits(v[2]); o[3] = f32_to_bf16_bits(v[3]);
+      *reinterpret_cast<u16x4 *>(ft.wb + base + c) = o;
+      if (samp) *reinterpret_cast<u16x4 *>(ft.ws + (size_t)(n / SAMPLE_STRIDE) * d + c) = o;
+    }
+  }
+}
+
 template <int REFRESH>
 __global__ __launch_bounds__(256) void adam_rows_fused_kernel(float *__restrict__ W, const float *__restrict__ G,
                                                               float *__restrict__ M, float *__restrict__ V,
@@ -228,11 +291,7 @@ __global__ __launch_bounds__(256) void adam_rows_fused_kernel(float *__restrict_
   __shared__ float red[4];
   __shared__ float red3[3][4];
   const size_t base = (size_t)blockIdx.x * d;
-  float clip = 1.f;
-  if (total_sumsq) {
-    const float c = a.max_norm / (sqrtf(*total_sumsq) + 1e-6f);
-    clip = c < 1.f ? c : 1.f;
-  }
+  const float clip = clip_coef(total_sumsq, a.max_norm);
   float along = 0.f;
   if (a.project) {
     float dot = 0.f;
@@ -244,7 +303,6 @@ __global__ __launch_bounds__(256) void adam_rows_fused_kernel(float *__restrict_
     along = block_sum(dot, red);
   }
   const bool renorm = ft.renorm_eps >= 0.f;
-  constexpr int KEEP = 8;                         // d <= 8192 (checked by the host)
   f32x4 keep[KEEP];
   float ss = 0.f;
   {
@@ -286,23 +344,134 @@ __global__ __launch_bounds__(256) void adam_rows_fused_kernel(float *__restrict_
       *reinterpret_cast<f32x4 *>(W + base + c) = v;
     }
   }
-  if constexpr (REFRESH != 0) {
-    __threadfence_block();
-    __syncthreads();                              // the whole updated row is visible to the workgroup (same CU, same L1)
-    const int n = blockIdx.x;
-    if constexpr (REFRESH == 1) {
-      row_stats_quant_row<true>(W, n, d, ft.rq, red3);
-    } else {
-      row_stats_quant_row<false>(W, n, d, ft.rq, red3);
-      const bool samp = (n % SAMPLE_STRIDE) == SAMPLE_OFF;
-      for (int c = threadIdx.x * 4; c < d; c += 1024) {
-        const f32x4 v = *reinterpret_cast<const f32x4 *>(W + base + c);
-        u16x4 o;
-        o[0] = f32_to_bf16_bits(v[0]); o[1] = f32_to_bf16_bits(v[1]); o[2] = f32_to_bf16_bits(v[2]); o[3] = f32_to_bf16_bits(v[3]);
-        *reinterpret_cast<u16x4 *>(ft.wb + base + c) = o;
-        if (samp) *reinterpret_cast<u16x4 *>(ft.ws + (size_t)(n / SAMPLE_STRIDE) * d + c) = o;
+  if constexpr (REFRESH != 0) refresh_row<REFRESH>(W, base, d, ft, red3);
+}
+
+// ---- 8-bit moments ("adam8", include/msae.h) -------------------------------------------------------------------
+// M8 = e4m3 codes of m, R8 = e4m3 codes of sqrt(v), one float32 scale (absmax / 448) per block of ADAM8_BLOCK consecutive
+// elements of a row.  With one workgroup per row and one f32x4 per thread per trip, a block is what ONE WAVE holds in ONE TRIP:
+// its absmax is a wave_max, its codes are one 32-bit word per lane, lane 0 writes the scales.
+constexpr int ADAM8_BLOCK = 256;
+constexpr float E4M3_MAX = 448.f;
+struct Adam8Ptrs {
+  unsigned *M8, *R8;            // the code arrays, addressed as words of four codes
+  float *SM, *SR;
+};
+typedef __attribute__((ext_vector_type(2))) float f32x2;
+__device__ __forceinline__ f32x4 unpack4_fp8(unsigned w) {
+  const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
+  return f32x4{lo[0], lo[1], hi[0], hi[1]};
+}
+// codes of x * (448 / absmax), clamped to +-448 in float32, rounded to nearest even by the conversion instruction
+__device__ __forceinline__ unsigned adam8_codes(const f32x4 x, float absmax) {
+  const float inv = absmax > 0.f ? E4M3_MAX / absmax : 0.f;
+  f32x4 q;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) q[e] = fminf(fmaxf(x[e] * inv, -E4M3_MAX), E4M3_MAX);
+  return (unsigned)pack4_fp8(q);
+}
+// One wave, one block: word `word` of the code arrays is this lane's (live lanes only; the others pass m = r = 0), block `blk`
+// the wave's.  A positive r never becomes code 0 (it would turn a still-nonzero m / sqrt(v) into m / eps): code 1 instead.
+__device__ __forceinline__ void adam8_store_block(const Adam8Ptrs &st, size_t word, size_t blk, bool live, const f32x4 m,
+                                                  const f32x4 r) {
+  const float am = wave_max(fmaxf(fmaxf(fabsf(m[0]), fabsf(m[1])), fmaxf(fabsf(m[2]), fabsf(m[3]))));
+  const float ar = wave_max(fmaxf(fmaxf(r[0], r[1]), fmaxf(r[2], r[3])));
+  if (live) {
+    const unsigned cm = adam8_codes(m, am);
+    unsigned cr = adam8_codes(r, ar);
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (r[e] > 0.f && ((cr >> (8 * e)) & 0xFFu) == 0u) cr |= 1u << (8 * e);
+    MSAE_ADAM_STORE(cm, st.M8 + word);
+    MSAE_ADAM_STORE(cr, st.R8 + word);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    st.SM[blk] = am / E4M3_MAX;
+    st.SR[blk] = ar / E4M3_MAX;
+  }
+}
+// m = dec(M8) * SM, r = dec(R8) * SR, v = r * r: three separate float32 multiplications (the build has -ffp-contract=off)
+__device__ __forceinline__ void adam8_load(const Adam8Ptrs &st, size_t word, size_t blk, f32x4 &m, f32x4 &v) {
+  const float sm = st.SM[blk], sr = st.SR[blk];
+  m = unpack4_fp8(MSAE_ADAM_LOAD(st.M8 + word)) * sm;
+  const f32x4 r = unpack4_fp8(MSAE_ADAM_LOAD(st.R8 + word)) * sr;
+  v = r * r;
+}
+
+// adam_rows_fused_kernel with the moments carried in the adam8 format: decoded on the way in, the update computed from the
+// float32 m', v' of this step, m' and sqrt(v') encoded on the way out.  The trip loop runs a whole wave at a time (the
+// wave_max needs all 64 lanes): a wave whose block lies past d skips the trip, lanes past d inside a block contribute 0.
+template <int REFRESH>
+__global__ __launch_bounds__(256) void adam8_rows_kernel(float *__restrict__ W, const float *__restrict__ G, Adam8Ptrs st,
+                                                         int d, const float *__restrict__ total_sumsq, AdamArgs a,
+                                                         FusedTail ft) {
+  __shared__ float red[4];
+  __shared__ float red3[3][4];
+  const size_t base = (size_t)blockIdx.x * d;
+  const float clip = clip_coef(total_sumsq, a.max_norm);
+  const float along = a.project ? row_along(G, W, base, d, clip, red) : 0.f;
+  const bool renorm = ft.renorm_eps >= 0.f;
+  const int bpr = (d + ADAM8_BLOCK - 1) / ADAM8_BLOCK;
+  f32x4 keep[KEEP];
+  float ss = 0.f;
+  int it = 0;
+  for (int c = threadIdx.x * 4; (c & ~(ADAM8_BLOCK - 1)) < d; c += 1024, ++it) {
+    const bool live = c < d;
+    const size_t word = (base + c) >> 2, blk = (size_t)blockIdx.x * bpr + (c >> 8);
+    f32x4 w = {0.f, 0.f, 0.f, 0.f}, m = w, r = w;
+    if (live) {
+      const f32x4 g = a.project ? *reinterpret_cast<const f32x4 *>(G + base + c)     // L2 hit when projecting
+                                : MSAE_ADAM_LOAD(reinterpret_cast<const f32x4 *>(G + base + c));
+      w = *reinterpret_cast<const f32x4 *>(W + base + c);
+      f32x4 v;
+      adam8_load(st, word, blk, m, v);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float ge = g[e] * clip, we = w[e], me = m[e], ve = v[e];
+        if (a.project) ge -= along * we;
+        adam_update(we, ge, me, ve, a);
+        w[e] = we; m[e] = me; r[e] = sqrtf(ve);
       }
     }
+    adam8_store_block(st, word, blk, live, m, r);
+    if (live) {
+      if (renorm) {
+        keep_put(keep, it, w);
+        ss += w[0] * w[0] + w[1] * w[1] + w[2] * w[2] + w[3] * w[3];
+      } else {
+        *reinterpret_cast<f32x4 *>(W + base + c) = w;
+      }
+    }
+  }
+  if (renorm) renorm_store(W, base, d, keep, 1.f / (sqrtf(block_sum(ss, red)) + ft.renorm_eps));
+  if constexpr (REFRESH != 0) refresh_row<REFRESH>(W, base, d, ft, red3);
+}
+
+// float32 moments -> the adam8 format (checkpoints, switching precision on resume): one workgroup per row, as above
+__global__ __launch_bounds__(256) void adam8_quantize_kernel(const float *__restrict__ M, const float *__restrict__ V,
+                                                             Adam8Ptrs st, int d) {
+  const size_t base = (size_t)blockIdx.x * d;
+  const int bpr = (d + ADAM8_BLOCK - 1) / ADAM8_BLOCK;
+  for (int c = threadIdx.x * 4; (c & ~(ADAM8_BLOCK - 1)) < d; c += 1024) {
+    const bool live = c < d;
+    f32x4 m = {0.f, 0.f, 0.f, 0.f}, r = m;
+    if (live) {
+      m = *reinterpret_cast<const f32x4 *>(M + base + c);
+      const f32x4 v = *reinterpret_cast<const f32x4 *>(V + base + c);
+      r = f32x4{sqrtf(v[0]), sqrtf(v[1]), sqrtf(v[2]), sqrtf(v[3])};
+    }
+    adam8_store_block(st, (base + c) >> 2, (size_t)blockIdx.x * bpr + (c >> 8), live, m, r);
+  }
+}
+// ... and back: the values adam8_rows_kernel computes with
+__global__ __launch_bounds__(256) void adam8_dequantize_kernel(Adam8Ptrs st, float *__restrict__ M, float *__restrict__ V, int d) {
+  const size_t base = (size_t)blockIdx.x * d;
+  const int bpr = (d + ADAM8_BLOCK - 1) / ADAM8_BLOCK;
+  for (int c = threadIdx.x * 4; c < d; c += 1024) {
+    f32x4 m, v;
+    adam8_load(st, (base + c) >> 2, (size_t)blockIdx.x * bpr + (c >> 8), m, v);
+    *reinterpret_cast<f32x4 *>(M + base + c) = m;
+    *reinterpret_cast<f32x4 *>(V + base + c) = v;
   }
 }
 
@@ -371,6 +540,48 @@ extern "C" int msae_adam_rows_f32(float *W, const float *G, float *M, float *V, 
   return msae_launch_status();
 }
 
+// the host half the fused entry points share: Adam's constants ...
+static AdamArgs adam_args(float max_norm, int project, float lr, float beta1, float beta2, float eps, int step) {
+  AdamArgs a{};
+  a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.max_norm = max_norm;
+  a.bc1 = (float)(1.0 - pow((double)beta1, (double)step));
+  a.bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
+  a.project = project ? 1 : 0;
+  return a;
+}
+// ... and the tail: the renorm switch, and for an encoder weight the header of its prepared buffer, the dither table and the
+// kernel's output pointers.  *refresh = the kernel's REFRESH (0: no operands to build).
+static int fused_tail(int rows, int d, float renorm_eps, void *prepared, int T_next, const msae_options *opts, hipStream_t s,
+                      FusedTail *ft, int *refresh) {
+  *ft = FusedTail{};
+  ft->renorm_eps = renorm_eps >= 0.f ? renorm_eps : -1.f;
+  *refresh = 0;
+  if (!prepared) return 0;
+  CallOpts co;
+  if (!resolve_opts(opts, co)) return MSAE_EINVAL;
+  if (!msae_aligned(prepared, 256)) return MSAE_EALIGN;
+  const int N = rows;
+  Prepared p = make_prepared(N, d);
+  if (!p.S) {
+    MSAE_HIP_TRY(hipMemcpyAsync(prepared, &p, sizeof(p), hipMemcpyHostToDevice, s));   // no fused path for this shape: header only
+    return 0;
+  }
+  const bool i8 = co.mode == 1 && i8_shape_ok(N, d);
+  const int modes = (i8 ? 2 : 1) | (T_next > 256 ? 4 : 0);     // as msae_encoder_refresh[_for]
+  p.valid = prep_valid_bits(modes, N, d);
+  p.dseed = i8 ? co.seed : 0ull;                                // (the shared dither of the int8 operands, encode_defs.h)
+  MSAE_HIP_TRY(hipMemcpyAsync(prepared, &p, sizeof(p), hipMemcpyHostToDevice, s));
+  unsigned char *base = static_cast<unsigned char *>(prepared);
+  ft->rq = row_quant_out(base, p, modes, i8);
+  ft->rq.seed = co.seed;                                        // msae_options::dither: this refresh's own seed
+  if (p.dseed != 0ull)
+    hipLaunchKernelGGL(sd_table_kernel, dim3(1), dim3(1024), 0, s, co.seed, d, reinterpret_cast<int *>(base + p.off_sdtab));
+  ft->wb = reinterpret_cast<unsigned short *>(base + p.off_wb);
+  ft->ws = reinterpret_cast<unsigned short *>(base + p.off_ws);
+  *refresh = i8 ? 1 : 2;
+  return 0;
+}
+
 extern "C" int msae_adam_rows_fused_f32(float *W, const float *G, float *M, float *V, int rows, int d,
                                         const float *total_sumsq, float max_norm, int project, float lr,
                                         float beta1, float beta2, float eps, int step, float renorm_eps,
@@ -387,43 +598,79 @@ extern "C" int msae_adam_rows_fused_f32(float *W, const float *G, float *M, floa
     return 0;
   }
   if (!(msae_aligned(W, 16) && msae_aligned(G, 16) && msae_aligned(M, 16) && msae_aligned(V, 16))) return MSAE_EALIGN;
-  AdamArgs a{};
-  a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.max_norm = max_norm;
-  a.bc1 = (float)(1.0 - pow((double)beta1, (double)step));
-  a.bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
-  a.project = project ? 1 : 0;
-  FusedTail ft{};
-  ft.renorm_eps = renorm ? renorm_eps : -1.f;
-  int refresh = 0;
-  if (prepared) {
-    CallOpts co;
-    if (!resolve_opts(opts, co)) return MSAE_EINVAL;
-    if (!msae_aligned(prepared, 256)) return MSAE_EALIGN;
-    const int N = rows;
-    Prepared p = make_prepared(N, d);
-    if (p.S) {
-      const bool i8 = co.mode == 1 && i8_shape_ok(N, d);
-      const int modes = (i8 ? 2 : 1) | (T_next > 256 ? 4 : 0);     // as msae_encoder_refresh[_for]
-      p.valid = prep_valid_bits(modes, N, d);
-      p.dseed = i8 ? co.seed : 0ull;                                // (the shared dither of the int8 operands, encode_defs.h)
-      MSAE_HIP_TRY(hipMemcpyAsync(prepared, &p, sizeof(p), hipMemcpyHostToDevice, s));
-      unsigned char *base = static_cast<unsigned char *>(prepared);
-      ft.rq = row_quant_out(base, p, modes, i8);
-      ft.rq.seed = co.seed;                                        // msae_options::dither: this refresh's own seed
-      if (p.dseed != 0ull)
-        hipLaunchKernelGGL(sd_table_kernel, dim3(1), dim3(1024), 0, s, co.seed, d, reinterpret_cast<int *>(base + p.off_sdtab));
-      ft.wb = reinterpret_cast<unsigned short *>(base + p.off_wb);
-      ft.ws = reinterpret_cast<unsigned short *>(base + p.off_ws);
-      refresh = i8 ? 1 : 2;
-    } else {
-      MSAE_HIP_TRY(hipMemcpyAsync(prepared, &p, sizeof(p), hipMemcpyHostToDevice, s));   // no fused path for this shape: header only
-    }
-  }
+  const AdamArgs a = adam_args(max_norm, project, lr, beta1, beta2, eps, step);
+  FusedTail ft;
+  int refresh;
+  if (int rc = fused_tail(rows, d, renorm_eps, prepared, T_next, opts, s, &ft, &refresh)) return rc;
   if (refresh == 1)
     hipLaunchKernelGGL(adam_rows_fused_kernel<1>, dim3(rows), dim3(256), 0, s, W, G, M, V, d, total_sumsq, a, ft);
   else if (refresh == 2)
     hipLaunchKernelGGL(adam_rows_fused_kernel<2>, dim3(rows), dim3(256), 0, s, W, G, M, V, d, total_sumsq, a, ft);
   else
     hipLaunchKernelGGL(adam_rows_fused_kernel<0>, dim3(rows), dim3(256), 0, s, W, G, M, V, d, total_sumsq, a, ft);
+  return msae_launch_status();
+}
+
+// ---- 8-bit moments -------------------------------------------------------------------------------------------------------------
+// what the kernels take: f32x4 rows inside the KEEP window.  A one-row view that is no multiple of 1024 long is what a vector gets
+// whose length does not divide (ops.adam_rows_): the whole parameter would be ONE workgroup's -- such a parameter keeps float32
+// moments.
+static bool adam8_kernel_shape(int rows, int d) {
+  return rows > 0 && d > 0 && (d & 3) == 0 && d <= 8192 && !(rows == 1 && (d & 1023) != 0);
+}
+static size_t adam8_nb(int rows, int d) { return (size_t)rows * ((d + ADAM8_BLOCK - 1) / ADAM8_BLOCK); }
+
+extern "C" size_t msae_adam8_blocks(int rows, int d) {
+  if (!adam8_kernel_shape(rows, d) || (size_t)rows * d < 4096) return 0;      // (the floor is policy: small parameters stay float32)
+  return adam8_nb(rows, d);
+}
+
+static int adam8_check(const void *M8, const void *R8, const void *SM, const void *SR, int rows, int d) {
+  if (!M8 || !R8 || !SM || !SR || rows <= 0 || d <= 0) return MSAE_EINVAL;
+  if (!adam8_kernel_shape(rows, d)) return MSAE_ENOTIMPL;
+  if (!(msae_aligned(M8, 16) && msae_aligned(R8, 16) && msae_aligned(SM, 4) && msae_aligned(SR, 4))) return MSAE_EALIGN;
+  return 0;
+}
+
+extern "C" int msae_adam8_rows_f32(float *W, const float *G, uint8_t *M8, uint8_t *R8, float *SM, float *SR, int rows, int d,
+                                   const float *total_sumsq, float max_norm, int project, float lr, float beta1,
+                                   float beta2, float eps, int step, float renorm_eps, void *prepared, int T_next,
+                                   const msae_options *opts, void *stream) {
+  if (!W || !G || step < 1) return MSAE_EINVAL;
+  if (int rc = adam8_check(M8, R8, SM, SR, rows, d)) return rc;
+  if (!(msae_aligned(W, 16) && msae_aligned(G, 16))) return MSAE_EALIGN;
+  hipStream_t s = (hipStream_t)stream;
+  const AdamArgs a = adam_args(max_norm, project, lr, beta1, beta2, eps, step);
+  const Adam8Ptrs st{reinterpret_cast<unsigned *>(M8), reinterpret_cast<unsigned *>(R8), SM, SR};
+  FusedTail ft;
+  int refresh;
+  if (int rc = fused_tail(rows, d, renorm_eps, prepared, T_next, opts, s, &ft, &refresh)) return rc;
+  if (refresh == 1)
+    hipLaunchKernelGGL(adam8_rows_kernel<1>, dim3(rows), dim3(256), 0, s, W, G, st, d, total_sumsq, a, ft);
+  else if (refresh == 2)
+    hipLaunchKernelGGL(adam8_rows_kernel<2>, dim3(rows), dim3(256), 0, s, W, G, st, d, total_sumsq, a, ft);
+  else
+    hipLaunchKernelGGL(adam8_rows_kernel<0>, dim3(rows), dim3(256), 0, s, W, G, st, d, total_sumsq, a, ft);
+  return msae_launch_status();
+}
+
+extern "C" int msae_adam8_quantize_f32(const float *M, const float *V, uint8_t *M8, uint8_t *R8, float *SM, float *SR, int rows,
+                                       int d, void *stream) {
+  if (!M || !V) return MSAE_EINVAL;
+  if (int rc = adam8_check(M8, R8, SM, SR, rows, d)) return rc;
+  if (!(msae_aligned(M, 16) && msae_aligned(V, 16))) return MSAE_EALIGN;
+  const Adam8Ptrs st{reinterpret_cast<unsigned *>(M8), reinterpret_cast<unsigned *>(R8), SM, SR};
+  hipLaunchKernelGGL(adam8_quantize_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, M, V, st, d);
+  return msae_launch_status();
+}
+
+extern "C" int msae_adam8_dequantize_f32(const uint8_t *M8, const uint8_t *R8, const float *SM, const float *SR, float *M,
+                                         float *V, int rows, int d, void *stream) {
+  if (!M || !V) return MSAE_EINVAL;
+  if (int rc = adam8_check(M8, R8, SM, SR, rows, d)) return rc;
+  if (!(msae_aligned(M, 16) && msae_aligned(V, 16))) return MSAE_EALIGN;
+  const Adam8Ptrs st{reinterpret_cast<unsigned *>(const_cast<uint8_t *>(M8)), reinterpret_cast<unsigned *>(const_cast<uint8_t *>(R8)),
+                     const_cast<float *>(SM), const_cast<float *>(SR)};
+  hipLaunchKernelGGL(adam8_dequantize_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, st, M, V, d);
   return msae_launch_status();
 }

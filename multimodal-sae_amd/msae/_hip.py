@@ -114,6 +114,13 @@ PROTOTYPES = {
                                          c_opts_p, c_void_p]),
     "msae_adam_rows_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_float,
                                    c_int, c_float, c_float, c_float, c_float, c_int, c_void_p]),
+    "msae_adam8_blocks": (c_size_t, [c_int, c_int]),
+    "msae_adam8_rows_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                    c_float, c_int, c_float, c_float, c_float, c_float, c_int, c_float, c_void_p, c_int,
+                                    c_opts_p, c_void_p]),
+    "msae_adam8_quantize_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "msae_adam8_dequantize_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                          c_void_p]),
     "msae_profile_create": (c_int, [c_int, ctypes.POINTER(c_void_p)]),
     "msae_profile_read": (c_int, [c_void_p, c_void_p, c_void_p]),
     "msae_profile_destroy": (c_int, [c_void_p]),

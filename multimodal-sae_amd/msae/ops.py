@@ -21,6 +21,7 @@ from __future__ import annotations
 import collections
 import contextlib
 import ctypes
+import dataclasses
 import os
 import weakref
 from typing import Optional, Tuple
@@ -1274,6 +1275,15 @@ def sum_into_(accum: Tensor, v: Tensor) -> Tensor:
     return accum
 
 
+def _kernel_rows(p: Tensor) -> Tuple[int, int]:
+    """[rows, d] as the Adam passes see a parameter: a matrix as it is, a vector as [numel / 1024, 1024] when that
+    divides and as one row otherwise (any row length works without the projection)."""
+    if p.dim() == 2:
+        return p.shape[0], p.shape[1]
+    d = 1024 if p.numel() % 1024 == 0 else p.numel()
+    return p.numel() // d, d
+
+
 def adam_rows_(p: Tensor, g: Tensor, m: Tensor, v: Tensor, step: int, lr: float, *,
                total_sumsq: Optional[Tensor] = None, max_norm: float = 1.0, project: bool = False,
                betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, renorm_eps: Optional[float] = None,
@@ -1287,12 +1297,8 @@ def adam_rows_(p: Tensor, g: Tensor, m: Tensor, v: Tensor, step: int, lr: float,
     dev = _hip.require_device(p, g, m, v, refresh)
     for t in (p, g, m, v):
         assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == p.shape
-    if p.dim() == 2:
-        rows, d = p.shape
-    else:   # vectors: any row length works without the projection
-        assert not project
-        d = 1024 if p.numel() % 1024 == 0 else p.numel()
-        rows = p.numel() // d
+    assert p.dim() == 2 or not project
+    rows, d = _kernel_rows(p)
     with torch.cuda.device(dev):
         if renorm_eps is not None or refresh is not None:
             assert p.dim() == 2, "renorm / refresh are row operations on a [rows, d] matrix"
@@ -1308,3 +1314,93 @@ def adam_rows_(p: Tensor, g: Tensor, m: Tensor, v: Tensor, step: int, lr: float,
             _hip.ptr(total_sumsq) if total_sumsq is not None else None, float(max_norm), int(project),
             float(lr), float(betas[0]), float(betas[1]), float(eps), int(step), _hip.stream_of(p)),
             "msae_adam_rows_f32")
+
+
+# ---- blockwise 8-bit Adam moments (the "adam8" format of include/msae.h) ---------------------------------
+@dataclasses.dataclass
+class Adam8State:
+    """The Adam moments of one parameter in 8 bits: e4m3 codes of m (`m8`) and of sqrt(v) (`r8`), shaped like the
+    parameter, and one float32 scale per block of 256 consecutive elements of a kernel row (`sm`, `sr`)."""
+    m8: Tensor
+    r8: Tensor
+    sm: Tensor
+    sr: Tensor
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in self.tensors())
+
+    def tensors(self) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+        return self.m8, self.r8, self.sm, self.sr
+
+
+def adam8_state(p: Tensor, *, _any_size: bool = False) -> Optional[Adam8State]:
+    """A zeroed Adam8State for `p`, or None when its shape keeps float32 moments (msae_adam8_blocks: d % 4, d > 8192,
+    fewer than 4096 elements, a vector 1024 does not divide).  `_any_size` is for the tests: it skips the 4096-element
+    floor, which is policy and no limit of the kernel."""
+    rows, d = _kernel_rows(p)
+    nb = _hip.load().msae_adam8_blocks(rows, d)
+    if nb == 0 and _any_size and d % 4 == 0:
+        nb = rows * -(-d // 256)
+    if nb == 0:
+        return None
+    return Adam8State(torch.zeros(p.shape, dtype=torch.uint8, device=p.device), torch.zeros(p.shape, dtype=torch.uint8, device=p.device),
+                      torch.zeros(nb, dtype=torch.float32, device=p.device), torch.zeros(nb, dtype=torch.float32, device=p.device))
+
+
+def _adam8_args(state: Adam8State, like: Tensor):
+    rows, d = _kernel_rows(like)
+    for t in (state.m8, state.r8):
+        assert t.dtype == torch.uint8 and t.is_contiguous() and t.shape == like.shape
+    for t in (state.sm, state.sr):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == rows * -(-d // 256)
+    return [_hip.ptr(t) for t in state.tensors()], rows, d
+
+
+def adam8_rows_(p: Tensor, g: Tensor, state: Adam8State, step: int, lr: float, *,
+                total_sumsq: Optional[Tensor] = None, max_norm: float = 1.0, project: bool = False,
+                betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, renorm_eps: Optional[float] = None,
+                refresh: Optional[Tensor] = None, tokens_next: int = 0) -> None:
+    """adam_rows_ with the moments carried in an Adam8State (msae_adam8_rows_f32): same clip, projection, update, renorm
+    and operand refresh; the update uses this step's float32 moments, the state keeps their 8-bit codes.  Raises
+    _hip.MsaeNotImplemented for a shape the kernel does not take."""
+    dev = _hip.require_device(p, g, *state.tensors(), refresh)
+    for t in (p, g):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == p.shape
+    assert p.dim() == 2 or (not project and renorm_eps is None and refresh is None)
+    ptrs, rows, d = _adam8_args(state, p)
+    with torch.cuda.device(dev):
+        _hip.check(_hip.load().msae_adam8_rows_f32(
+            _hip.ptr(p), _hip.ptr(g), *ptrs, rows, d,
+            _hip.ptr(total_sumsq) if total_sumsq is not None else None, float(max_norm), int(project),
+            float(lr), float(betas[0]), float(betas[1]), float(eps), int(step),
+            float(renorm_eps) if renorm_eps is not None else -1.0, _hip.ptr(refresh), int(tokens_next),
+            _opts().ref(), _hip.stream_of(p)), "msae_adam8_rows_f32")
+
+
+def adam8_quantize(m: Tensor, v: Tensor) -> Adam8State:
+    """float32 moments -> an Adam8State (msae_adam8_quantize_f32); raises _hip.MsaeNotImplemented for a shape the
+    format does not take."""
+    dev = _hip.require_device(m, v)
+    for t in (m, v):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == m.shape
+    state = adam8_state(m, _any_size=True)
+    if state is None:
+        _hip.check(-4, "adam8_quantize")
+    ptrs, rows, d = _adam8_args(state, m)
+    with torch.cuda.device(dev):
+        _hip.check(_hip.load().msae_adam8_quantize_f32(_hip.ptr(m), _hip.ptr(v), *ptrs, rows, d, _hip.stream_of(m)),
+                   "msae_adam8_quantize_f32")
+    return state
+
+
+def adam8_dequantize(state: Adam8State) -> Tuple[Tensor, Tensor]:
+    """-> (m, v) float32, shaped like the parameter: the values adam8_rows_ computes with (msae_adam8_dequantize_f32)."""
+    dev = _hip.require_device(*state.tensors())
+    m = torch.empty(state.m8.shape, dtype=torch.float32, device=dev)
+    v = torch.empty_like(m)
+    ptrs, rows, d = _adam8_args(state, m)
+    with torch.cuda.device(dev):
+        _hip.check(_hip.load().msae_adam8_dequantize_f32(*ptrs, _hip.ptr(m), _hip.ptr(v), rows, d, _hip.stream_of(m)),
+                   "msae_adam8_dequantize_f32")
+    return m, v

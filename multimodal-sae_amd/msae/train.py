@@ -21,6 +21,9 @@ MI355X-side design:
     step).  Between steps `W_dec` therefore holds unit-norm rows (the reference renormalises at the top of the
     next step, trainer.py:352 -- the same values one kernel later; a checkpoint written between steps differs from
     the reference's by that normalisation, ~1e-5 relative);
+  * `optim_bits=8` (the reference takes bitsandbytes' Adam8bit when it can import it, trainer.py:139-147): the Adam
+    moments of every parameter the format takes are carried as blockwise 8-bit codes (ops.Adam8State) --
+    2 bytes per element instead of 8, and 16 instead of 28 bytes moved per element by the Adam pass;
   * data parallel: each parameter's gradient all-reduce (RCCL, ReduceOp.AVG -- no division pass) is
     launched ASYNCHRONOUSLY from a post-accumulate-grad hook the moment autograd has finished that
     parameter, so the 2 GiB W_dec exchange over xGMI overlaps the encoder backward, and the W_enc
@@ -70,7 +73,7 @@ class SaeTrainStep:
     def __init__(self, sae: Sae, lr: Optional[float] = None, auxk_alpha: float = 0.0,
                  dead_feature_threshold: int = 10_000_000, group=None, grad_acc_steps: int = 1,
                  micro_acc_steps: int = 1, lr_warmup_steps: int = 0, total_steps: Optional[int] = None,
-                 init_b_dec: bool = False, fuse_next_step: bool = True):
+                 init_b_dec: bool = False, fuse_next_step: bool = True, optim_bits: int = 32):
         from .parallel import _unpinned
 
         group = _unpinned(group)          # (the default group is addressed as None: nothing here keeps it alive past its destroy)
@@ -83,8 +86,15 @@ class SaeTrainStep:
         self.lr_warmup_steps, self.total_steps, self.init_b_dec = lr_warmup_steps, total_steps, init_b_dec
         self.params = [p for p in sae.parameters()]
         assert all(p.dtype == torch.float32 for p in self.params), "the SAE trains in fp32 (trainer.py:190)"
-        self.exp_avg = [torch.zeros_like(p) for p in self.params]       # torch.optim.Adam state
-        self.exp_avg_sq = [torch.zeros_like(p) for p in self.params]
+        if optim_bits not in (8, 32):
+            raise ValueError(f"optim_bits is 32 or 8, not {optim_bits}")
+        if optim_bits == 8 and not sae.W_dec.is_cuda:
+            raise ValueError("optim_bits=8 needs the Sae on a HIP device: the 8-bit moments exist in the HIP kernels only")
+        self.optim_bits = optim_bits
+        # per parameter: an ops.Adam8State where the 8-bit format takes the shape, else None and float32 moments
+        self.state8 = [ops.adam8_state(p) if optim_bits == 8 else None for p in self.params]
+        self.exp_avg = [torch.zeros_like(p) if s8 is None else None for p, s8 in zip(self.params, self.state8)]   # torch.optim.Adam state
+        self.exp_avg_sq = [torch.zeros_like(p) if s8 is None else None for p, s8 in zip(self.params, self.state8)]
         self.t = 0                     # optimizer steps taken (= lr scheduler steps)
         self.global_step = 0           # batches seen (trainer.py:394)
         self._sumsq = torch.zeros(1, dtype=torch.float32, device=sae.device)
@@ -109,15 +119,39 @@ class SaeTrainStep:
     def current_lr(self) -> float:
         return self.lr * linear_schedule_with_warmup(self.t, self.lr_warmup_steps, self.total_steps)
 
+    @property
+    def optimizer_state_bytes(self) -> int:
+        """Bytes of Adam moments held (float32 tensors and 8-bit states together)."""
+        f32 = sum(t.numel() * t.element_size() for t in self.exp_avg + self.exp_avg_sq if t is not None)
+        return f32 + sum(s8.nbytes for s8 in self.state8 if s8 is not None)
+
     def state_dict(self) -> dict:
-        return {"step": self.t, "global_step": self.global_step, "exp_avg": self.exp_avg,
-                "exp_avg_sq": self.exp_avg_sq, "num_tokens_since_fired": self.num_tokens_since_fired}
+        sd = {"step": self.t, "global_step": self.global_step, "exp_avg": self.exp_avg,
+              "exp_avg_sq": self.exp_avg_sq, "num_tokens_since_fired": self.num_tokens_since_fired}
+        if self.optim_bits == 8:        # (a float32 state dict is what it always was)
+            sd["optim_bits"] = 8
+            sd["adam8"] = [None if s8 is None else {"m8": s8.m8, "r8": s8.r8, "sm": s8.sm, "sr": s8.sr} for s8 in self.state8]
+        return sd
 
     def load_state_dict(self, sd: dict) -> None:
+        """Takes a checkpoint of either precision: float32 moments are quantised into an 8-bit state, an 8-bit state is
+        dequantised into float32 moments, per parameter."""
         self.t = int(sd["step"])
         self.global_step = int(sd.get("global_step", self.t * self.grad_acc_steps))
-        for dst, src in zip(self.exp_avg + self.exp_avg_sq, list(sd["exp_avg"]) + list(sd["exp_avg_sq"])):
-            dst.copy_(src)
+        saved8 = sd.get("adam8") or [None] * len(self.params)
+        for i, (m, v) in enumerate(zip(sd["exp_avg"], sd["exp_avg_sq"])):
+            src8 = None if saved8[i] is None else ops.Adam8State(**saved8[i])
+            if self.state8[i] is None:
+                if src8 is not None:
+                    m, v = ops.adam8_dequantize(ops.Adam8State(*(t.to(self.params[i].device) for t in src8.tensors())))
+                self.exp_avg[i].copy_(m)
+                self.exp_avg_sq[i].copy_(v)
+            else:
+                if src8 is None:
+                    dev = self.params[i].device
+                    src8 = ops.adam8_quantize(m.to(dev, torch.float32).contiguous(), v.to(dev, torch.float32).contiguous())
+                for dst, src in zip(self.state8[i].tensors(), src8.tensors()):
+                    dst.copy_(src)
         self.num_tokens_since_fired.copy_(sd["num_tokens_since_fired"])
 
     # ---- data-parallel plumbing -------------------------------------------------------------------------
@@ -171,7 +205,7 @@ class SaeTrainStep:
                 ops.grad_sumsq_(self._sumsq, p.grad)
         self._wgrad_sumsq = {}
         fuse = self.fuse_next_step and sae.W_dec.is_cuda
-        for p, m, v in zip(self.params, self.exp_avg, self.exp_avg_sq):
+        for p, m, v, s8 in zip(self.params, self.exp_avg, self.exp_avg_sq, self.state8):
             if p.grad is None:
                 continue
             kw = {}
@@ -181,9 +215,12 @@ class SaeTrainStep:
                 kw["renorm_eps"] = torch.finfo(p.dtype).eps          # sae.py:252
             if fuse and is_enc and self._chunk_tokens > 0 and ops.coarse_in_force() != "fp8":   # (the fused pass builds int8 / bf16 operands; MSAE_COARSE=fp8 in the environment counts: ADVICE r5)
                 kw["refresh"], kw["tokens_next"] = ops.train_operand_buffer(p), self._chunk_tokens
-            ops.adam_rows_(p.data, p.grad, m, v, self.t, lr, total_sumsq=self._sumsq,
-                           max_norm=self.max_grad_norm, betas=self.betas, eps=self.eps,
-                           project=sae.cfg.normalize_decoder and is_dec, **kw)
+            kw.update(total_sumsq=self._sumsq, max_norm=self.max_grad_norm, betas=self.betas, eps=self.eps,
+                      project=sae.cfg.normalize_decoder and is_dec)
+            if s8 is None:
+                ops.adam_rows_(p.data, p.grad, m, v, self.t, lr, **kw)
+            else:
+                ops.adam8_rows_(p.data, p.grad, s8, self.t, lr, **kw)
             p.grad = None
             torch.autograd.graph.increment_version(p)    # p changed behind autograd's back: caches keyed on it go stale
             if "renorm_eps" in kw:
