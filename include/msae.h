@@ -452,6 +452,29 @@ int msae_rows_topk_i64_f32(const float *Q, int Qn, const int32_t *q_rows, int M,
                            const float *q_scale, const float *k_scale, const int32_t *exclude, int k, int chunks,
                            float *vals, int64_t *idx, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- exact encode over a feature subset (AuxK without the dense latents; Sae.pre_acts(x, features=...)) ----------------
+ * Replaces the AuxK selection of sae_auto_interp/sae/sae.py:207-225, where(dead_mask, pre_acts, -inf).topk(k_aux), without
+ * the two dense [T][N] tensors: pre-activations of the M listed features only, then the canonical top-k of rows of width M.
+ * Both calls are asynchronous on `stream`; neither allocates, needs scratch, nor reads anything back to the host.
+ * msae_pre_acts_features_f32: features int32 [M] (device), out[T][ld_out] with ld_out >= M; columns [M, ld_out) are not
+ *   written.  Numerics contract: out[t][m] is bit for bit the value msae_pre_acts_f32 writes at [t][features[m]] -- the same
+ *   ascending-k single-accumulator f32 fma chain of (x[t][c] - b_dec[c]) * W_enc[f][c] from +0, then + b_enc[f], then the
+ *   same ReLU rule (relu != 0: a value that is not > 0 becomes +0).  It does not depend on M, on the order of the list or
+ *   on its other entries.  The list may be unsorted and may repeat entries; an entry outside [0, N) is clamped into it,
+ *   never faults (as q_rows in msae_rows_topk_f32).
+ *   Envelope: any d (d % 4 != 0 and unaligned pointers take the tile's generic staging path), any M >= 0 (M == 0 returns 0
+ *   without a launch), T as msae_pre_acts_f32 (T <= 65535 * 128, else MSAE_ENOTIMPL), x in f32, bf16 or f16.
+ * msae_topk_map_i64_f32: msae_topk_f32 on latents[T][ld] rows of width M (ld >= M), with idx[t][j] = col_map[p] (int64) for
+ *   the winner at position p.  Selection, values and tie order are msae_topk_f32's: value descending, then ascending
+ *   POSITION -- with an ascending col_map that is ascending feature index, i.e. exactly the dense where(...).topk()
+ *   result restricted to the listed features.  1 <= k <= min(M, 16384).  Rows with M % 4 == 0, ld % 4 == 0 and a 16-byte
+ *   aligned base take the vector loads. */
+int msae_pre_acts_features_f32(const void *x, int x_dtype, const float *W_enc, const float *b_enc, const float *b_dec,
+                               const int32_t *features, int M, int T, int d, int N, int relu,
+                               float *out, int ld_out, void *stream);
+int msae_topk_map_i64_f32(const float *latents, int T, int M, int k, int ld, const int32_t *col_map,
+                          float *vals, int64_t *idx, void *stream);
+
 /* ---- set-valued hook edits on a top-k list (Sae.encode(edits=...)) -------------------------------
  * The reference's hooks edit the dense latents with torch indexing, so the edited feature may be a LIST or tensor:
  * latents[:, :, f] = clamp (features/steering.py:113-114), mask[:, off_features] = 0 (features/patching/utils.py:43-48).

@@ -97,10 +97,12 @@ __device__ __forceinline__ unsigned long long rank_key_with_index(unsigned long 
 
 // optional outputs of the row top-k launch (exact fallback of the fused encoder): 64-bit indices beside or
 // instead of the 32-bit ones, output rows through a map (row i of the input -> token row_map[i]), and the
-// status word of a token recomputed this way (1, or 1 | reason << 8 with `detail`)
+// status word of a token recomputed this way (1, or 1 | reason << 8 with `detail`); col_map: the index written for position
+// ix of a row is col_map[ix] (rows over a feature list) -- selection, values and tie order stay by POSITION
 struct TopkExtra {
   int64_t *idx64 = nullptr;
   const int *row_map = nullptr;
+  const int *col_map = nullptr;
   int32_t *status = nullptr;
   int detail = 0;
 };

@@ -1,4 +1,5 @@
-// f32_tile.h -- the exact f32 MFMA tile shared by msae_pre_acts_f32 (encode_f32.hip) and the pooled probe (probe.hip).
+// f32_tile.h -- the exact f32 MFMA tile shared by msae_pre_acts_f32 / msae_pre_acts_features_f32 (encode_f32.hip), the pooled
+// probe (probe.hip) and the neighbours (neighbors.hip).
 //
 // Roofline: f32 MFMA (157 TFLOP/s dense on gfx950; there is no TF32/xf32).  2*d*N FLOP per token.
 //
@@ -46,8 +47,12 @@ struct StageRows {
   size_t xo[4], wo[4];
   unsigned live_a, live_b;      // bit `it`: the row exists
 };
-template <int DT>
-__device__ __forceinline__ StageRows stage_rows(const int *rows, int T, int d, int N, int m0, int n0) {
+// COLS: feature row n of the B operand is W[cols[n]] (a FEATURE list; N counts the list, n_src the rows of W).  The entry is
+// read here, once per tile for the four rows a staging thread owns, never per k-tile; one outside [0, n_src) is clamped.
+__device__ __forceinline__ int clamp_col(int c, int n_src) { return c < 0 ? 0 : (c < n_src ? c : n_src - 1); }
+template <int DT, bool COLS = false>
+__device__ __forceinline__ StageRows stage_rows(const int *rows, int T, int d, int N, int m0, int n0,
+                                                const int *cols = nullptr, int n_src = 0) {
   const int rr = threadIdx.x >> 3;
   StageRows r;
   r.live_a = r.live_b = 0u;
@@ -57,7 +62,8 @@ __device__ __forceinline__ StageRows stage_rows(const int *rows, int T, int d, i
     const int t = m0 + row, n = n0 + row;
     const int tc = t < T ? t : T - 1, nc = n < N ? n : N - 1;
     r.xo[it] = (rows ? (size_t)rows[tc] : (size_t)tc) * d;
-    r.wo[it] = (size_t)nc * d;
+    if constexpr (COLS) r.wo[it] = (size_t)clamp_col(cols[nc], n_src) * d;
+    else r.wo[it] = (size_t)nc * d;
     r.live_a |= (t < T ? 1u : 0u) << it;
     r.live_b |= (n < N ? 1u : 0u) << it;
   }
@@ -111,10 +117,22 @@ struct StageRegsG {
   f32x4 a[4];
   f32x4 b[4];
 };
-template <int DT>
+// (COLS: the four feature rows of this thread, gathered and clamped once per tile -- stage_cols_gen -- not per k-tile)
+struct StageColsG { int c[4]; };
+__device__ __forceinline__ StageColsG stage_cols_gen(const int *cols, int n_src, int N, int n0) {
+  const int rr = threadIdx.x >> 3;
+  StageColsG g;
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int n = n0 + rr + it * 32;
+    g.c[it] = n < N ? clamp_col(cols[n], n_src) : 0;
+  }
+  return g;
+}
+template <int DT, bool COLS = false>
 __device__ __forceinline__ void stage_load_gen(StageRegsG &r, const void *x, const float *W,
                                                const float *b_dec, const int *rows, int T, int d, int N,
-                                               int m0, int n0, int k0) {
+                                               int m0, int n0, int k0, const StageColsG *gc = nullptr) {
   const int q = threadIdx.x & 7, rr = threadIdx.x >> 3;
   const int kq = k0 + q * 4;
   f32x4 bd = {0.f, 0.f, 0.f, 0.f};
@@ -135,9 +153,11 @@ __device__ __forceinline__ void stage_load_gen(StageRegsG &r, const void *x, con
     }
     const int n = n0 + row;
     if (n < N) {
+      size_t wr = (size_t)n;
+      if constexpr (COLS) wr = (size_t)gc->c[it];
 #pragma unroll
       for (int e = 0; e < 4; ++e)
-        if (kq + e < d) bv[e] = W[(size_t)n * d + kq + e];
+        if (kq + e < d) bv[e] = W[wr * d + kq + e];
     }
     r.a[it] = av;
     r.b[it] = bv;
@@ -162,10 +182,13 @@ __device__ __forceinline__ void stage_store_gen(const StageRegsG &r, float *sA, 
 // beyond T and features at or beyond N read as zeros.  Every thread of the 256-thread block calls; `smem` is the F_LDS_FLOATS
 // staging area, free again when the call returns (its last k-tile ends with a barrier).  Accumulator layout: wave w = 2 wr + wc
 // holds C[wr*64 + i*32 + row][wc*64 + j*32 + col] in acc[i][j][e], col = lane&31, row = (e&3) + 8*(e>>2) + 4*(lane>>5).
-template <int DT, bool VEC>
+// COLS (a compile-time flag: the dense instantiations carry nothing of it): column n of the tile is W[cols[n]], N = the
+// list's length, n_src = the rows of W (entries are clamped into [0, n_src)).
+template <int DT, bool VEC, bool COLS = false>
 __device__ __forceinline__ void f32_tile_mma(f32x16 (&acc)[2][2], const void *__restrict__ x, const float *__restrict__ W,
                                              const float *__restrict__ b_dec, const int *__restrict__ rows, int T, int d,
-                                             int N, int m0, int n0, float *smem) {
+                                             int N, int m0, int n0, float *smem, const int *__restrict__ cols = nullptr,
+                                             int n_src = 0) {
   constexpr int STAGE = (F_BM + F_BN) * F_PITCH;  // floats per stage: A tile then B tile
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wr = wave >> 1, wc = wave & 1;
@@ -180,9 +203,12 @@ __device__ __forceinline__ void f32_tile_mma(f32x16 (&acc)[2][2], const void *__
   const int nk = (d + F_BK - 1) / F_BK;
   typename std::conditional<VEC, StageRegs<DT>, StageRegsG>::type regs;
   [[maybe_unused]] StageRows srows;
-  if constexpr (VEC) srows = stage_rows<DT>(rows, T, d, N, m0, n0);
+  if constexpr (VEC) srows = stage_rows<DT, COLS>(rows, T, d, N, m0, n0, cols, n_src);
+  [[maybe_unused]] StageColsG gcols;
+  if constexpr (COLS && !VEC) gcols = stage_cols_gen(cols, n_src, N, n0);
   auto load = [&](int k0) {
     if constexpr (VEC) stage_load_vec<DT>(regs, x, W, b_dec, srows, d, k0);
+    else if constexpr (COLS) stage_load_gen<DT, true>(regs, x, W, b_dec, rows, T, d, N, m0, n0, k0, &gcols);
     else stage_load_gen<DT>(regs, x, W, b_dec, rows, T, d, N, m0, n0, k0);
   };
   auto store = [&](int k0, float *sA, float *sB) {

@@ -186,8 +186,9 @@ __global__ __launch_bounds__(TK_THREADS) void topk_rows_kernel(const float *__re
   for (int j = threadIdx.x; j < k; j += TK_THREADS) {
     const unsigned long long kk = keys[j];
     const int ix = rank_key_index(kk);
-    if (idx) idx[(size_t)orow * k + j] = ix;
-    if (ex.idx64) ex.idx64[(size_t)orow * k + j] = ix;
+    const int ox = ex.col_map ? ex.col_map[ix] : ix;
+    if (idx) idx[(size_t)orow * k + j] = ox;
+    if (ex.idx64) ex.idx64[(size_t)orow * k + j] = ox;
     vals[(size_t)orow * k + j] = row[ix];  // the stored value (keeps -0.0 as stored)
   }
   // a token the fused encoder could not verify, recomputed here: status 1 (msae_options::status_detail keeps why)
@@ -401,6 +402,15 @@ extern "C" int msae_topk_f32(const float *latents, int T, int N, int k, float *v
                              void *ws, size_t ws_bytes, void *stream) {
   (void)ws; (void)ws_bytes;
   return msae_topk_launch(latents, T, N, k, N, nullptr, vals, idx, (hipStream_t)stream, TopkExtra());
+}
+
+// rows over a feature list (msae_pre_acts_features_f32's output): idx[t][j] = col_map[position], int64, written directly
+extern "C" int msae_topk_map_i64_f32(const float *latents, int T, int M, int k, int ld, const int32_t *col_map,
+                                     float *vals, int64_t *idx, void *stream) {
+  if (!latents || !col_map || !vals || !idx) return MSAE_EINVAL;
+  TopkExtra ex;
+  ex.idx64 = idx; ex.col_map = col_map;
+  return msae_topk_launch(latents, T, M, k, ld, nullptr, vals, nullptr, (hipStream_t)stream, ex);
 }
 
 // argument check, LDS size and launch of merge_topk_kernel for both entry points

@@ -12,6 +12,7 @@ These are the operators the drop-in ``Sae`` module (msae/sae/sae.py) and the fea
     msae::probe_maps    latents[:, :, idx]                   tools/probe_activations.py:126
     msae::row_inv_norms F.normalize's 1 / max(norm, eps)     features/stats.py:80-81
     msae::rows_topk     torch.mm + torch.topk, fused         features/stats.py:35-37,83,107
+    msae::pre_acts_features  pre_acts(x)[..., features]      sae/sae.py:207-225 (AuxK: the dead latents only)
 
 All ops run on the tensor's device on the current stream, never synchronise (``sparsify`` reads one
 int64 back, as ``torch.nonzero`` does), and raise on CPU tensors.
@@ -385,6 +386,94 @@ def _topk_backward(ctx, g_vals, _g_idx):
 
 
 topk.register_autograd(_topk_backward, setup_context=_topk_setup)
+
+
+# ---- exact encode over a feature subset (csrc/encode_f32.hip) -----------------------------------------
+TOPK_MAX_K = 16384           # msae_topk_f32's limit: the k winners live in LDS
+
+
+def _pre_acts_features_into(xa: Tensor, W: Tensor, be: Optional[Tensor], bd: Optional[Tensor], feats: Tensor,
+                            out: Tensor, ld: int, relu: int = 1) -> None:
+    """msae_pre_acts_features_f32 on prepared operands: xa [T, d] (f32 / bf16 / f16, contiguous), feats int32 [M], out a
+    buffer of at least T * ld floats."""
+    (N, d), T, M = W.shape, xa.shape[0], feats.numel()
+    with torch.cuda.device(xa.device):
+        _hip.check(_hip.load().msae_pre_acts_features_f32(_hip.ptr(xa), _hip.DTYPE_CODE[xa.dtype], _hip.ptr(W), _hip.ptr(be),
+                                                          _hip.ptr(bd), _hip.ptr(feats), M, T, d, N, relu, _hip.ptr(out),
+                                                          ld, _hip.stream_of(xa)), "msae_pre_acts_features_f32")
+
+
+@torch.library.custom_op("msae::pre_acts_features", mutates_args=())
+def pre_acts_features(x: Tensor, W_enc: Tensor, b_enc: Optional[Tensor], b_dec: Optional[Tensor],
+                      features: Tensor) -> Tensor:
+    """relu((x - b_dec) @ W_enc[features].T + b_enc[features]) -> [..., M] f32 without the dense [..., N] latents: column m
+    is bit for bit column features[m] of `pre_acts` (include/msae.h, "exact encode over a feature subset").  features: int32
+    device tensor [M], any order, repeats allowed, entries outside [0, N) clamped.  The result is a view of a buffer whose
+    rows are M rounded up to 4 floats apart (so that a top-k over it takes its vector loads).  No autograd."""
+    dev = _hip.require_device(x, W_enc, b_enc, b_dec, features)
+    assert features.dtype == torch.int32 and features.dim() == 1, \
+        f"features must be a 1-d int32 tensor, got {features.dtype} {tuple(features.shape)}"
+    xa, W, be, bd = _act(x), _f32c(W_enc), _f32c(b_enc), _f32c(b_dec)
+    N, d = W.shape
+    assert xa.shape[-1] == d, f"x last dim {xa.shape[-1]} != d_in {d}"
+    feats = features.detach().contiguous()
+    M = feats.numel()
+    ld = (M + 3) & ~3
+    out = torch.empty(*xa.shape[:-1], ld, dtype=torch.float32, device=dev)
+    if M and out.numel():
+        _pre_acts_features_into(xa.reshape(-1, d), W, be, bd, feats, out, ld)
+    return out[..., :M]
+
+
+@pre_acts_features.register_fake
+def _(x, W_enc, b_enc, b_dec, features):
+    M = features.shape[0]
+    return x.new_empty(*x.shape[:-1], (M + 3) & ~3, dtype=torch.float32)[..., :M]
+
+
+def rows_per_chunk(T: int, M: int, max_ws_bytes: int = 256 << 20) -> int:
+    """Token rows per chunk of `topk_within`: the largest multiple of 128 (the GEMM's row tile) whose [rows, ld] f32
+    buffer, ld = M rounded up to 4, stays within max_ws_bytes -- at least 128, at most T."""
+    ld = max((M + 3) & ~3, 4)
+    rows = max(max_ws_bytes // (ld * 4) // 128 * 128, 128)
+    return min(rows, T)
+
+
+def topk_within(x: Tensor, W_enc: Tensor, b_enc: Optional[Tensor], b_dec: Optional[Tensor], features: Tensor, k: int, *,
+                max_ws_bytes: int = 256 << 20) -> Tuple[Tensor, Tensor]:
+    """The canonical top-k of every token's latents WITHIN a feature list -> (vals [T, k] f32, idx [T, k] int64, global
+    feature ids): what `where(mask, pre_acts(x), -inf).topk(k)` returns for the mask of an ascending `features` (int32
+    device tensor [M]), bit for bit, without the dense latents.  Ties: value descending, then ascending position in the
+    list.  x [T, d].  T is walked in chunks of `rows_per_chunk(T, M, max_ws_bytes)` rows: each chunk's [rows, M] latents go
+    into one reused buffer (the default cap is the Infinity Cache's 256 MiB), its top-k straight into the output rows.
+    Nothing is read back to the host.  1 <= k <= min(M, 16384), else ValueError.  No autograd."""
+    assert features.dtype == torch.int32 and features.dim() == 1, \
+        f"features must be a 1-d int32 tensor, got {features.dtype} {tuple(features.shape)}"
+    M = features.numel()
+    if not 1 <= k <= min(M, TOPK_MAX_K):
+        raise ValueError(f"topk_within: k must be in [1, min(len(features), {TOPK_MAX_K})], got k = {k} with "
+                         f"{M} features")
+    dev = _hip.require_device(x, W_enc, b_enc, b_dec, features)
+    xa, W, be, bd = _act(x), _f32c(W_enc), _f32c(b_enc), _f32c(b_dec)
+    N, d = W.shape
+    assert xa.dim() == 2 and xa.shape[1] == d, f"x must be [T, {d}], got {tuple(xa.shape)}"
+    feats = features.detach().contiguous()
+    T = xa.shape[0]
+    vals = torch.empty(T, k, dtype=torch.float32, device=dev)
+    idx = torch.empty(T, k, dtype=torch.int64, device=dev)
+    if T == 0:
+        return vals, idx
+    ld = (M + 3) & ~3
+    rows = rows_per_chunk(T, M, max_ws_bytes)
+    buf = torch.empty(rows * ld, dtype=torch.float32, device=dev)
+    lib = _hip.load()
+    for t0 in range(0, T, rows):
+        n = min(rows, T - t0)
+        _pre_acts_features_into(xa[t0:t0 + n], W, be, bd, feats, buf, ld)
+        with torch.cuda.device(dev):
+            _hip.check(lib.msae_topk_map_i64_f32(_hip.ptr(buf), n, M, k, ld, _hip.ptr(feats), _hip.ptr(vals[t0:t0 + n]),
+                                                 _hip.ptr(idx[t0:t0 + n]), _hip.stream_of(xa)), "msae_topk_map_i64_f32")
+    return vals, idx
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1113,6 +1202,9 @@ def encode_topk_rows_(x: Tensor, W_enc: Tensor, b_enc: Optional[Tensor], b_dec: 
 
 
 # ---- trainable encoder (training forward, sae.py:193-247) -------------------------------------------
+AUXK_PATHS = ("dense", "subset")
+
+
 class _SparseEncode(torch.autograd.Function):
     """pre_acts + the three TopK selections of Sae.forward as ONE autograd node with a SPARSE
     backward.  The reference back-propagates a dense [T, N] gradient through topk -> relu ->
@@ -1125,7 +1217,7 @@ class _SparseEncode(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, W_enc, b_enc, b_dec, k, dead_mask, k_aux, k_multi, prepared=None, set_feature=-1,
-                set_value=0.0, zero_feature=-1, edit_set=None):
+                set_value=0.0, zero_feature=-1, edit_set=None, auxk_path="dense", dead_list=None):
         vals, idxs = [], []
         edits = set_feature >= 0 or zero_feature >= 0 or edit_set is not None
         assert not (edits and (k_aux > 0 or k_multi > 0)), "hook edits apply to the plain top-k only"
@@ -1147,6 +1239,19 @@ class _SparseEncode(torch.autograd.Function):
                                   prepared if prepared is not None else _refresh_train_operands(W_enc, x.shape[0]), kk,
                                   set_feature, set_value, zero_feature)
             vals.append(v[..., :k].contiguous()); idxs.append(i[..., :k].contiguous())
+            if k_multi > 0:
+                vals.append(v); idxs.append(i)
+        elif auxk_path == "subset" and k_aux > 0 and max(k, k_multi) <= 256:
+            # AuxK without the dense latents: the main and Multi-TopK selections from the fused encoder
+            # as above, the AuxK selection from the exact GEMM over the dead features only -- the same bits as the branch below
+            kk = max(k, k_multi)
+            v, i, _ = encode_topk(x, W_enc, b_enc, b_dec,
+                                  prepared if prepared is not None else _refresh_train_operands(W_enc, x.shape[0]), kk)
+            vals.append(v[..., :k].contiguous()); idxs.append(i[..., :k].contiguous())
+            if dead_list is None:      # ascending, built on the device (the one host read: the list's length)
+                dead_list = torch.nonzero(dead_mask).flatten().to(torch.int32)
+            va, ia = topk_within(x, W_enc, b_enc, b_dec, dead_list, k_aux)
+            vals.append(va); idxs.append(ia)
             if k_multi > 0:
                 vals.append(v); idxs.append(i)
         else:
@@ -1209,20 +1314,26 @@ class _SparseEncode(torch.autograd.Function):
             da = decode(idx_cat, g_cat, W_enc, None)
             g_x = da.to(x.dtype) if need_x else None
             g_bd = -da.sum(0) if need_bd else None
-        return g_x, g_W, g_be, g_bd, None, None, None, None, None, None, None, None, None
+        return g_x, g_W, g_be, g_bd, None, None, None, None, None, None, None, None, None, None, None
 
 
 def sparse_encode(x: Tensor, W_enc: Tensor, b_enc: Tensor, b_dec: Tensor, k: int,
                   dead_mask: Optional[Tensor] = None, k_aux: int = 0, k_multi: int = 0, *,
                   prepared: Optional[Tensor] = None, set_feature: int = -1, set_value: float = 0.0,
-                  zero_feature: int = -1, edits=None):
+                  zero_feature: int = -1, edits=None, auxk_path: str = "dense", dead_list: Optional[Tensor] = None):
     """-> [(acts, idx)] for the top-k, (optional) AuxK and (optional) Multi-TopK selections.
     Differentiable w.r.t. x, W_enc, b_enc, b_dec through the selected latents (the graph of the
     reference's pre_acts -> [mask] -> topk, sae.py:172-185, patching/utils.py:43-49).  `edits`: a
-    msae.features.FeatureEdits instead of the scalar edit arguments; an edited latent carries no gradient."""
+    msae.features.FeatureEdits instead of the scalar edit arguments; an edited latent carries no gradient.
+    auxk_path: "dense" (pre_acts + three top-k over [T, N]) or "subset": with k_aux > 0 and max(k, k_multi) <= 256 the AuxK
+    selection comes from `topk_within` over the dead features (dead_list: their ascending int32 device list, built from
+    dead_mask when None) and the other two from the fused encoder -- the same selections bit for bit; in every other case
+    the value changes nothing."""
+    if auxk_path not in AUXK_PATHS:
+        raise ValueError(f"auxk_path must be one of {AUXK_PATHS}, got {auxk_path!r}")
     lead = x.shape[:-1]
     out = _SparseEncode.apply(x.reshape(-1, x.shape[-1]), W_enc, b_enc, b_dec, k, dead_mask, k_aux, k_multi, prepared,
-                              set_feature, float(set_value), zero_feature, edits)  # the node works on [T, d]
+                              set_feature, float(set_value), zero_feature, edits, auxk_path, dead_list)  # the node works on [T, d]
     if len(lead) != 1:
         out = tuple(o.reshape(*lead, o.shape[-1]) for o in out)
     return [(out[2 * j], out[2 * j + 1]) for j in range(len(out) // 2)]

@@ -12,6 +12,8 @@ unchanged.  What differs is underneath:
 * `decode`        -> torch.ops.msae.decode     (coalesced gather-matmul over W_dec rows, autograd)
 * `probe`         -> torch.ops.msae.pooled_acts + topk + probe_maps (tools/probe_activations.py:109-126 without the
                      dense latents: new)
+* `pre_acts(x, features=[...])` -> torch.ops.msae.pre_acts_features (the listed columns of `pre_acts` without the dense
+                     latents); `forward(..., auxk_path="subset")` builds the AuxK selection on it
 * `neighbors`, `top_logits` -> torch.ops.msae.row_inv_norms + rows_topk (features/stats.py:12-47,76-120 as one fused
                      f32 GEMM + per-row top-k: DESIGN.md section 7c)
 
@@ -82,6 +84,7 @@ def _natural_key(s: str):
 
 class Sae(nn.Module):
     _warned_detached = False     # the one-time notice of Sae.encode (see its docstring)
+    auxk_path = "dense"          # how `forward` builds the AuxK selection when it is not told: "dense" or "subset"
 
     def __init__(self, d_in: int, cfg: SaeConfig, device: Union[str, torch.device] = "cpu",
                  dtype: Union[torch.dtype, None] = None, *, decoder: bool = True):
@@ -166,11 +169,22 @@ class Sae(nn.Module):
         return self.encoder.weight.dtype
 
     # ---- hot path -----------------------------------------------------------------------------------
-    def pre_acts(self, x: Tensor) -> Tensor:
+    def pre_acts(self, x: Tensor, features=None) -> Tensor:
         """relu((x - b_dec) W_enc^T + b_enc) as a dense [..., N] f32 tensor (sae.py:172-177).
         Kept for callers that edit or reduce the dense latents (steering.py:111-114,
-        tools/probe_activations.py:116); the caching / encode paths use the fused op instead."""
-        return ops.pre_acts(x, self.encoder.weight, self.encoder.bias, self.b_dec)
+        tools/probe_activations.py:116); the caching / encode paths use the fused op instead.
+
+        `features` (a list or 1-d int tensor of M feature indices, any order, repeats allowed): only those columns,
+        [..., M] f32 -- bit for bit `pre_acts(x)[..., features]`, sub-threshold values included, without building the
+        [..., N] latents (activation histograms and dashboards of a filter list).  A host list with an index outside
+        [0, N) raises ValueError; a tensor's entries are clamped.  Inference only: differentiate the dense `pre_acts`."""
+        if features is None:
+            return ops.pre_acts(x, self.encoder.weight, self.encoder.bias, self.b_dec)
+        feats = self._feature_rows(features, "pre_acts")          # validates before any device work
+        if torch.is_grad_enabled() and any(t.requires_grad for t in (x, self.encoder.weight, self.encoder.bias, self.b_dec)):
+            raise NotImplementedError("Sae.pre_acts(x, features=...) has no autograd: call it under torch.no_grad(), or "
+                                      "differentiate the dense pre_acts(x) and index its result")
+        return ops.pre_acts_features(x, self.encoder.weight, self.encoder.bias, self.b_dec, feats)
 
     def select_topk(self, latents: Tensor) -> EncoderOutput:
         """Top-k latents (sae.py:179-181).  Order is canonical (value desc, index asc), a valid
@@ -378,19 +392,45 @@ class Sae(nn.Module):
         with torch.no_grad():
             return ops.rows_topk(self.W_dec.detach(), W_U.detach(), k, q_rows=rows)
 
-    def forward(self, x: Tensor, dead_mask: Union[Tensor, None] = None) -> ForwardOutput:
+    @staticmethod
+    def _dead_list(dead_mask: Tensor) -> Tensor:
+        """The dead features as an ascending int32 device list.  Its length is the forward's ONE host read (torch.nonzero
+        sizes its result on the host): it takes the place of `int(dead_mask.sum())`."""
+        return torch.nonzero(dead_mask).flatten().to(torch.int32)
+
+    def forward(self, x: Tensor, dead_mask: Union[Tensor, None] = None, *, auxk_path: Optional[str] = None) -> ForwardOutput:
         """Training forward (sae.py:193-247): reconstruction, FVU, AuxK and Multi-TopK terms, fully
         differentiable.  The encoder is one autograd node with a sparse backward (ops._SparseEncode):
         gradients reach encoder.weight / encoder.bias / b_dec / x only through the selected latents,
-        exactly as in the reference's dense graph, without its second [T,N]x[T,d] GEMM."""
-        k_aux, scale = 0, 0.0
-        if dead_mask is not None and (num_dead := int(dead_mask.sum())) > 0:
-            k_aux = x.shape[-1] // 2                      # heuristic from the paper (sae.py:209)
-            scale = min(num_dead / k_aux, 1.0)
-            k_aux = min(k_aux, num_dead)
+        exactly as in the reference's dense graph, without its second [T,N]x[T,d] GEMM.
+
+        auxk_path ("dense" / "subset"; None: the attribute `self.auxk_path`, "dense" unless set): how the AuxK selection
+        of a non-empty dead_mask is built.  "dense" materialises the [T, N] latents (pre_acts, where(dead_mask, ., -inf),
+        top-k three times).  "subset" (with max(k, 4k) <= 256; otherwise the dense branch runs) keeps the main and
+        Multi-TopK selections on the fused encoder and takes the AuxK one from an exact GEMM over the dead features only
+        (ops.topk_within) -- the same selections bit for bit, no [T, N] tensor."""
+        if auxk_path is None:
+            auxk_path = self.auxk_path
+        if auxk_path not in ops.AUXK_PATHS:
+            raise ValueError(f"auxk_path must be one of {ops.AUXK_PATHS}, got {auxk_path!r}")
+        k_aux, scale, dead_list = 0, 0.0, None
+        if dead_mask is not None:
+            if auxk_path == "subset":
+                dead_list = self._dead_list(dead_mask)
+                num_dead = dead_list.numel()
+            else:
+                num_dead = int(dead_mask.sum())
+            if num_dead > 0:
+                k_aux = x.shape[-1] // 2                      # heuristic from the paper (sae.py:209)
+                scale = min(num_dead / k_aux, 1.0)
+                k_aux = min(k_aux, num_dead)
         k_multi = 4 * self.cfg.k if self.cfg.multi_topk else 0
-        sel = ops.sparse_encode(x, self.encoder.weight, self.encoder.bias, self.b_dec, self.cfg.k,
-                                dead_mask, k_aux, k_multi)
+        if auxk_path == "subset":
+            sel = ops.sparse_encode(x, self.encoder.weight, self.encoder.bias, self.b_dec, self.cfg.k,
+                                    dead_mask, k_aux, k_multi, auxk_path="subset", dead_list=dead_list)
+        else:
+            sel = ops.sparse_encode(x, self.encoder.weight, self.encoder.bias, self.b_dec, self.cfg.k,
+                                    dead_mask, k_aux, k_multi)
         top_acts, top_indices = sel[0]
         sae_out = self.decode(top_acts, top_indices)
         # the loss terms in as few T x d sweeps as autograd allows (each elementwise torch op on [T, d] is a 45-us kernel at

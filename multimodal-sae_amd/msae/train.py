@@ -73,7 +73,7 @@ class SaeTrainStep:
     def __init__(self, sae: Sae, lr: Optional[float] = None, auxk_alpha: float = 0.0,
                  dead_feature_threshold: int = 10_000_000, group=None, grad_acc_steps: int = 1,
                  micro_acc_steps: int = 1, lr_warmup_steps: int = 0, total_steps: Optional[int] = None,
-                 init_b_dec: bool = False, fuse_next_step: bool = True, optim_bits: int = 32):
+                 init_b_dec: bool = False, fuse_next_step: bool = True, optim_bits: int = 32, auxk_path: str = "dense"):
         from .parallel import _unpinned
 
         group = _unpinned(group)          # (the default group is addressed as None: nothing here keeps it alive past its destroy)
@@ -91,6 +91,9 @@ class SaeTrainStep:
         if optim_bits == 8 and not sae.W_dec.is_cuda:
             raise ValueError("optim_bits=8 needs the Sae on a HIP device: the 8-bit moments exist in the HIP kernels only")
         self.optim_bits = optim_bits
+        if auxk_path not in ops.AUXK_PATHS:
+            raise ValueError(f"auxk_path must be one of {ops.AUXK_PATHS}, got {auxk_path!r}")
+        self.auxk_path = auxk_path        # how Sae.forward builds the AuxK selection ("subset": no dense [T, N] latents)
         # per parameter: an ops.Adam8State where the 8-bit format takes the shape, else None and float32 moments
         self.state8 = [ops.adam8_state(p) if optim_bits == 8 else None for p in self.params]
         self.exp_avg = [torch.zeros_like(p) if s8 is None else None for p, s8 in zip(self.params, self.state8)]   # torch.optim.Adam state
@@ -176,7 +179,7 @@ class SaeTrainStep:
 
     # ---- compute (overridden with torch-CPU restatements by the gloo tests) ----------------------------------
     def _forward(self, hiddens: Tensor, dead_mask: Optional[Tensor]):
-        return self.sae(hiddens, dead_mask)
+        return self.sae(hiddens, dead_mask, auxk_path=self.auxk_path)
 
     def _renorm_decoder(self) -> None:
         W = self.sae.W_dec
