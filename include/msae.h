@@ -392,6 +392,53 @@ int msae_feature_stats_merge(int N, int n_top, uint64_t *count, float *act_max, 
                              int64_t *top_id, const uint64_t *src_count, const float *src_max,
                              const double *src_sum, const float *src_val, const int64_t *src_id, void *stream);
 
+/* ---- per-feature uniform example sample (opt-in part of the statistics update) ----------------------------------
+ * The top tables answer the reference's train_type "top" (sae_auto_interp/features/samplers.py); "random" and
+ * "quantile" (and detection-style scoring) need examples from a feature's whole activation range.  A CANDIDATE is what
+ * it is for the top tables: one pooling segment of one feature with a nonzero pooled value c and its id.  Per
+ * feature f, updated in place by the same call that updates the top tables:
+ *   seg_count[f]          u64  candidates of f seen so far (the population the sample is drawn from)         exact
+ *   smp_val[f][n_sample]  f32, smp_id[f][n_sample] i64: the n_sample candidates of f with the SMALLEST priority
+ *                         prio(seed, f, id) = mix64( mix64(seed + 0x9E3779B97F4A7C15 * (f + 1)) ^ (uint64)id )
+ *                         (arithmetic mod 2^64; mix64 = the splitmix64 finaliser: z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9,
+ *                         z = (z ^ z >> 27) * 0x94D049BB133111EB, z ^ z >> 31), sorted by priority ascending, then id
+ *                         ascending; free slots (0, -1) at the tail (initialise so, and seg_count to 0).
+ *                         1 <= n_sample <= 256.  Only val and id are stored: priorities are recomputed from (f, id).
+ * For fixed (seed, f) the priority is a bijection of id, so distinct ids never tie; f is mixed in so that two features'
+ * samples do not prefer the same rows.  Pinned:
+ *   prio(22, 0, 0) = 0xbe5264ad2aa020f4          prio(1, 5, 7) = 0xb2e6c178b81a5c56
+ *   prio(22, 7, 2^33) = 0x27044a0765e2616f       prio(22, 131071, 12345) = 0x45984866898b23bf
+ *   prio(2^64 - 1, 262143, 2^40 + 3) = 0xaf8ee0a530541d25
+ * Consequences:
+ *   - the table is a uniform sample without replacement of the feature's candidates (bottom-n of a hash of the id);
+ *   - it is independent of the candidates' values;
+ *   - it is bit-identical however the rows are cut into calls, in whatever order the calls arrive, and however the rows
+ *     are split over ranks (msae_feature_sample_merge);
+ *   - the first m entries of a table are the table one would get with n_sample = m and the same seed.
+ * Ids are unique per feature over a table's life because a row never spans two calls.  A caller that breaks that may
+ * see the id twice in a table, as in the top table; nothing else is promised, and nothing faults.
+ * msae_feature_stats_update_sampled: msae_feature_stats_update with `sample` (NULL: exactly that call); the workspace
+ * is the same msae_feature_stats_ws_bytes.  `sample->size` is sizeof(msae_feature_sample) of the caller.  n_sample
+ * outside 1..256, a short struct or a null table pointer: MSAE_EINVAL before any launch.
+ * msae_feature_sample_merge: dst += src for two samples of the same N, n_sample and seed: counts add, tables merge in
+ * the same (priority, id) order.  Neither call allocates or synchronises with the host. */
+typedef struct msae_feature_sample {
+  uint32_t size;        /* sizeof(msae_feature_sample) */
+  int32_t n_sample;     /* 1..256 */
+  uint64_t seed;
+  uint64_t *seg_count;  /* [N] */
+  float *smp_val;       /* [N][n_sample] */
+  int64_t *smp_id;      /* [N][n_sample] */
+} msae_feature_sample;
+int msae_feature_stats_update_sampled(const float *vals, const int32_t *idx, int B, int S, int k, float thresh, int N,
+                                      int mode, int pool_len, int window, int64_t row_base, int n_top,
+                                      uint64_t *count, float *act_max, double *act_sum, float *top_val,
+                                      int64_t *top_id, const msae_feature_sample *sample, void *ws, size_t ws_bytes,
+                                      void *stream);
+int msae_feature_sample_merge(int N, int n_sample, uint64_t seed, uint64_t *seg_count, float *smp_val,
+                              int64_t *smp_id, const uint64_t *src_seg_count, const float *src_val,
+                              const int64_t *src_id, void *stream);
+
 /* ---- probe: segment-pooled feature ranking and activation maps (Sae.probe) ---------------------------------------
  * Replaces the dense probe of tools/probe_activations.py:109-126 (latents = pre_acts(h); latents.mean(0).topk(k);
  * latents[:, :, idx]) without materialising the [T][N] latents.  x[T][d] (element type x_dtype) as msae_pre_acts_f32;

@@ -30,6 +30,14 @@ __host__ __device__ static inline size_t msae_align_up(size_t v, size_t a) {
   return (v + a - 1) / a * a;
 }
 
+// 64-bit finaliser of splitmix64: the hash of the encoder's dither (encode_defs.h, encode_prep.h) and of the feature
+// statistics' sample priorities (feature_stats.hip)
+__host__ __device__ inline unsigned long long mix64(unsigned long long z) {
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
 // ---- element conversion ---------------------------------------------------------------------
 __device__ __forceinline__ float bf16_bits_to_f32(unsigned short b) {
   return __uint_as_float(((unsigned)b) << 16);

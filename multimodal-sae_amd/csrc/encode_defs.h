@@ -120,12 +120,6 @@ struct CallOpts {
   int cert;              // msae_options::certified: two-plane operands, deterministic band (encode_cert.h)
   const void *cert_ops;  // ... and msae_encoder_prepare_certified's buffer
 };
-// 64-bit finaliser of splitmix64 (also the device-side hash of the dither, encode_prep.h)
-__host__ __device__ inline unsigned long long mix64(unsigned long long z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 // A fresh non-zero seed: process-random base (std::random_device at first use) + an atomic counter, mixed.  The only
 // mutable process state of the library -- it is a random number generator.
 inline unsigned long long draw_seed() {

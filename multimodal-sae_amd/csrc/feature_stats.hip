@@ -18,6 +18,10 @@
 //   4. table merge    one wave per feature with records in this batch: the candidates of its run are ranked
 //                     against its sorted top-n table (value descending, id ascending: a total order) and merged.
 //                     The table after a batch is the top-n of every candidate seen, whatever the cut into calls.
+//                     With a sample (msae_feature_stats_update_sampled) the same wave, while the chunk of candidates is
+//                     in LDS, also merges it into the feature's uniform sample table: the same rank-and-scatter body
+//                     under another order (FsSampleOrder: a hash of (seed, feature, id) ascending), and counts the
+//                     feature's candidates.
 // No host synchronisation, no allocation (workspace: msae_feature_stats_ws_bytes).
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -40,17 +44,146 @@ __device__ __forceinline__ long long fs_id(const FsGeom &g, int b, int grp) {
   return g.mode == MSAE_POOL_WINDOW ? (g.row_base + b) * (long long)g.nw + grp : g.row_base + b;
 }
 
-// strict "a ranks before b": value descending, then id ascending
-__device__ __forceinline__ bool fs_before(float av, long long ai, float bv, long long bi) {
-  return av > bv || (av == bv && ai < bi);
-}
-
 __device__ __forceinline__ void atomic_max_f32(float *p, float v) {
   if (v >= 0.f)
     atomicMax((int *)p, __float_as_int(v));
   else
     atomicMin((unsigned *)p, __float_as_uint(v));
 }
+
+// ---- table orders --------------------------------------------------------------------------------------------------
+// A table is one feature's list of (value, id) entries, sorted under a strict total order of (key, id).  The key is derived
+// from the entry (and the feature), never stored in HBM: `feature(f)` is the per-feature part of it, `key(h, v, id)` the rest.
+struct FsTopOrder {      // top examples: value descending, then id ascending; the key is the value itself
+  using Key = float;
+  static constexpr bool kKeyIsValue = true;
+  __device__ __forceinline__ unsigned long long feature(int) const { return 0ull; }
+  __device__ __forceinline__ Key key(unsigned long long, float v, long long) const { return v; }
+  static __device__ __forceinline__ bool before(Key ak, long long ai, Key bk, long long bi) {
+    return ak > bk || (ak == bk && ai < bi);
+  }
+};
+// uniform sample: prio(seed, f, id) = mix64(mix64(seed + 0x9E3779B97F4A7C15 * (f + 1)) ^ (uint64)id) ascending, then id
+// ascending.  For fixed (seed, f) a bijection of id: distinct ids never tie.  Pinned (include/msae.h, tests):
+//   prio(22, 0, 0) = 0xbe5264ad2aa020f4   prio(1, 5, 7) = 0xb2e6c178b81a5c56   prio(22, 7, 2^33) = 0x27044a0765e2616f
+//   prio(22, 131071, 12345) = 0x45984866898b23bf   prio(2^64 - 1, 262143, 2^40 + 3) = 0xaf8ee0a530541d25
+struct FsSampleOrder {
+  using Key = unsigned long long;
+  static constexpr bool kKeyIsValue = false;
+  unsigned long long seed;
+  __device__ __forceinline__ unsigned long long feature(int f) const {
+    return mix64(seed + 0x9E3779B97F4A7C15ull * ((unsigned long long)f + 1ull));
+  }
+  __device__ __forceinline__ Key key(unsigned long long h, float, long long id) const {
+    return mix64(h ^ (unsigned long long)id);
+  }
+  static __device__ __forceinline__ bool before(Key ak, long long ai, Key bk, long long bi) {
+    return ak < bk || (ak == bk && ai < bi);
+  }
+};
+
+// Two sorted lists of one feature, of up to CAP entries each, in LDS (the merge kernel's double buffer; dst and src of the
+// table-to-table merge).  An order whose key is the value keeps no value array.
+template <class O, int CAP, bool = O::kKeyIsValue>
+struct FsTableVal {
+  float val[2][CAP];
+};
+template <class O, int CAP>
+struct FsTableVal<O, CAP, true> {};
+template <class O, int CAP = FS_MAX_TOP>
+struct FsTable : FsTableVal<O, CAP> {
+  typename O::Key key[2][CAP];
+  long long id[2][CAP];
+  __device__ __forceinline__ float value(int b, int j) const {
+    if constexpr (O::kKeyIsValue) return key[b][j]; else return this->val[b][j];
+  }
+  __device__ __forceinline__ void put(int b, int j, typename O::Key k, float v, long long i) {
+    key[b][j] = k;
+    id[b][j] = i;
+    if constexpr (!O::kKeyIsValue) this->val[b][j] = v;
+  }
+};
+
+// HBM table of n slots -> list b, keys derived on the way; returns the number of valid entries (they sit at the front)
+template <class O, int CAP>
+__device__ __forceinline__ int fs_table_load(FsTable<O, CAP> &T, int b, const O &o, unsigned long long h,
+                                             const float *__restrict__ tv, const long long *__restrict__ ti, int n,
+                                             int lane) {
+  int tn = 0;
+  for (int j = lane; j < n; j += 64) {
+    const float v = tv[j];
+    const long long i = ti[j];
+    T.put(b, j, o.key(h, v, i), v, i);
+    tn += i >= 0;
+  }
+  return wave_sum(tn);
+}
+
+// One chunk of up to 64 candidates (key ck / value cv / id ci per lane of `mask`, in LDS; this lane's own in k, v, id) into
+// list `cur` of tn entries -> list cur ^ 1 of min(n, tn + candidates) entries: every candidate and every entry computes its
+// rank in the merged list and scatters itself there.  Equal (key, id) pairs (a caller that repeats an id) rank by lane.
+template <class O, int CAP>
+__device__ __forceinline__ void fs_table_merge_chunk(FsTable<O, CAP> &T, int cur, int &tn, int n, unsigned long long mask,
+                                                     bool is_c, int lane, const typename O::Key *ck,
+                                                     const long long *ci, typename O::Key k, float v, long long id) {
+  using Key = typename O::Key;
+  const Key *A = T.key[cur];
+  const long long *AI = T.id[cur];
+  if (is_c) {
+    int r = 0;                                      // candidates of this chunk ranked before this one
+    for (unsigned long long m = mask; m; m &= m - 1) {
+      const int o = __builtin_ctzll(m);
+      r += O::before(ck[o], ci[o], k, id) || (ck[o] == k && ci[o] == id && o < lane);
+    }
+    int lo = 0, hi = tn;                            // table entries ranked before or equal: upper bound
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (O::before(k, id, A[mid], AI[mid])) hi = mid; else lo = mid + 1;
+    }
+    r += lo;
+    if (r < n) T.put(cur ^ 1, r, k, v, id);
+  }
+  for (int j = lane; j < tn; j += 64) {
+    const Key ak = A[j];
+    const long long aid = AI[j];
+    int r = j;
+    for (unsigned long long m = mask; m; m &= m - 1) {
+      const int o = __builtin_ctzll(m);
+      r += O::before(ck[o], ci[o], ak, aid);
+    }
+    if (r < n) T.put(cur ^ 1, r, ak, T.value(cur, j), aid);
+  }
+  tn = min(n, tn + __popcll(mask));
+}
+
+template <class O, int CAP>
+__device__ __forceinline__ void fs_table_store(const FsTable<O, CAP> &T, int b, int tn, float *__restrict__ tv,
+                                               long long *__restrict__ ti, int n, int lane) {
+  for (int j = lane; j < n; j += 64) {
+    tv[j] = j < tn ? T.value(b, j) : 0.f;
+    ti[j] = j < tn ? T.id[b][j] : -1ll;
+  }
+}
+
+struct FsSampleArgs {    // msae_feature_sample on the device side
+  int n;
+  unsigned long long seed;
+  unsigned long long *seg_count;
+  float *val;
+  long long *id;
+};
+
+template <bool SAMPLE, int CAP>
+struct FsMergeLds {
+  FsTable<FsTopOrder, CAP> top;
+  float cv[64];
+  long long ci[64];
+};
+template <int CAP>
+struct FsMergeLds<true, CAP> : FsMergeLds<false, CAP> {
+  FsTable<FsSampleOrder, CAP> smp;
+  unsigned long long cp[64];
+};
 
 __global__ __launch_bounds__(256) void fs_keys_kernel(const float *__restrict__ vals, const int32_t *__restrict__ idx,
                                                       long M, int k, float thresh, int N, int tb,
@@ -123,30 +256,36 @@ __global__ __launch_bounds__(256) void fs_group_kernel(const unsigned long long 
   cand[i] = (c == c) ? c : 0.f;                     // NaN never enters a table
 }
 
-// one single-wave workgroup per feature (grid-stride): rank this batch's candidates against the table, merge
+// one single-wave workgroup per feature (grid-stride): rank this batch's candidates against the feature's table(s), merge.
+// SAMPLE: the same chunk of candidates, while it is in LDS, also goes into the feature's sample table under FsSampleOrder, and
+// the feature's candidates are counted (the popcount of the ballots: this wave owns the feature, no atomics).
+// CAP >= n (and >= sa.n) sizes the tables in LDS.  The kernel waits on HBM, one wave per workgroup, so the workgroups a CU
+// holds -- LDS-bound -- set its speed: tables of <= 64 entries on both sides take the CAP = 64 instantiation (5.4 KB against
+// 17.3 KB).
+template <bool SAMPLE, int CAP>
 __global__ __launch_bounds__(64) void fs_merge_kernel(const unsigned long long *__restrict__ keys,
                                                       const float *__restrict__ cand, int N, int n, FsGeom g,
                                                       const int *__restrict__ run_start, const int *__restrict__ run_end,
-                                                      float *__restrict__ top_val, long long *__restrict__ top_id) {
-  __shared__ float av[2][FS_MAX_TOP];
-  __shared__ long long ai[2][FS_MAX_TOP];
-  __shared__ float cv[64];
-  __shared__ long long ci[64];
+                                                      float *__restrict__ top_val, long long *__restrict__ top_id,
+                                                      FsSampleArgs sa) {
+  __shared__ FsMergeLds<SAMPLE, CAP> L;
   const int lane = threadIdx.x;
   const unsigned long long tmask = (1ull << g.tb) - 1ull;
+  const FsTopOrder top_order{};
+  const FsSampleOrder smp_order{sa.seed};
   for (int f = blockIdx.x; f < N; f += gridDim.x) {
     const int e = run_end[f];
     if (e == 0) continue;                           // no record of f in this batch
     const int s0 = run_start[f];
     float *tv = top_val + (size_t)f * n;
     long long *ti = top_id + (size_t)f * n;
-    int tn = 0;
-    for (int j = lane; j < n; j += 64) {
-      av[0][j] = tv[j];
-      ai[0][j] = ti[j];
-      tn += ti[j] >= 0;                             // valid entries sit at the front
+    int tn = fs_table_load(L.top, 0, top_order, 0ull, tv, ti, n, lane);
+    unsigned long long h = 0ull;
+    int sn = 0, nseg = 0;
+    if constexpr (SAMPLE) {
+      h = smp_order.feature(f);
+      sn = fs_table_load(L.smp, 0, smp_order, h, sa.val + (size_t)f * sa.n, sa.id + (size_t)f * sa.n, sa.n, lane);
     }
-    tn = wave_sum(tn);
     int cur = 0;
     bool changed = false;
     __syncthreads();
@@ -162,110 +301,77 @@ __global__ __launch_bounds__(64) void fs_merge_kernel(const unsigned long long *
         const int t = (int)(keys[i] & tmask), b = t / g.S;
         id = fs_id(g, b, fs_group(g, t - b * g.S));
       }
-      cv[lane] = c;
-      ci[lane] = id;
+      L.cv[lane] = c;
+      L.ci[lane] = id;
+      unsigned long long p = 0ull;
+      if constexpr (SAMPLE) {
+        p = smp_order.key(h, c, id);
+        L.cp[lane] = p;
+        nseg += __popcll(mask);
+      }
       __syncthreads();
-      const float *A = av[cur];
-      const long long *AI = ai[cur];
-      float *Bv = av[cur ^ 1];
-      long long *Bi = ai[cur ^ 1];
-      if (is_c) {
-        int r = 0;                                  // candidates of this chunk ranked before this one
-        for (unsigned long long m = mask; m; m &= m - 1) {
-          const int o = __builtin_ctzll(m);
-          r += fs_before(cv[o], ci[o], c, id) || (cv[o] == c && ci[o] == id && o < lane);
-        }
-        int lo = 0, hi = tn;                        // table entries ranked before or equal: upper bound
-        while (lo < hi) {
-          const int mid = (lo + hi) >> 1;
-          if (fs_before(c, id, A[mid], AI[mid])) hi = mid; else lo = mid + 1;
-        }
-        r += lo;
-        if (r < n) {
-          Bv[r] = c;
-          Bi[r] = id;
-        }
-      }
-      for (int j = lane; j < tn; j += 64) {
-        int r = j;
-        for (unsigned long long m = mask; m; m &= m - 1) {
-          const int o = __builtin_ctzll(m);
-          r += fs_before(cv[o], ci[o], A[j], AI[j]);
-        }
-        if (r < n) {
-          Bv[r] = A[j];
-          Bi[r] = AI[j];
-        }
-      }
-      tn = min(n, tn + __popcll(mask));
+      fs_table_merge_chunk(L.top, cur, tn, n, mask, is_c, lane, L.cv, L.ci, c, c, id);
+      if constexpr (SAMPLE)
+        fs_table_merge_chunk(L.smp, cur, sn, sa.n, mask, is_c, lane, L.cp, L.ci, p, c, id);
       cur ^= 1;
       __syncthreads();
     }
     if (changed) {
-      for (int j = lane; j < n; j += 64) {
-        tv[j] = j < tn ? av[cur][j] : 0.f;
-        ti[j] = j < tn ? ai[cur][j] : -1ll;
+      fs_table_store(L.top, cur, tn, tv, ti, n, lane);
+      if constexpr (SAMPLE) {
+        fs_table_store(L.smp, cur, sn, sa.val + (size_t)f * sa.n, sa.id + (size_t)f * sa.n, sa.n, lane);
+        if (lane == 0) sa.seg_count[f] += (unsigned long long)nseg;
       }
     }
     __syncthreads();
   }
 }
 
-// dst += src, feature by feature: counts add, maxima max, sums add, tables merge in the same total order
+// dst += src, feature by feature, for the tables of order O: counts add (and, with the top table's statistics, maxima max and
+// sums add: act_max != null), tables merge in O's total order
+template <class O>
 __global__ __launch_bounds__(64) void fs_merge_tables_kernel(
-    int N, int n, unsigned long long *__restrict__ count, float *__restrict__ act_max, double *__restrict__ act_sum,
-    float *__restrict__ top_val, long long *__restrict__ top_id, const unsigned long long *__restrict__ s_count,
-    const float *__restrict__ s_max, const double *__restrict__ s_sum, const float *__restrict__ s_val,
-    const long long *__restrict__ s_id) {
-  __shared__ float av[FS_MAX_TOP], bv[FS_MAX_TOP];
-  __shared__ long long ai[FS_MAX_TOP], bi[FS_MAX_TOP];
+    int N, int n, O order, unsigned long long *__restrict__ count, float *__restrict__ act_max,
+    double *__restrict__ act_sum, float *__restrict__ dst_val, long long *__restrict__ dst_id,
+    const unsigned long long *__restrict__ s_count, const float *__restrict__ s_max, const double *__restrict__ s_sum,
+    const float *__restrict__ s_val, const long long *__restrict__ s_id) {
+  __shared__ FsTable<O> T;                          // list 0: dst, list 1: src
   const int lane = threadIdx.x;
   for (int f = blockIdx.x; f < N; f += gridDim.x) {
     if (lane == 0) {
       count[f] += s_count[f];
-      act_max[f] = fmaxf(act_max[f], s_max[f]);
-      act_sum[f] += s_sum[f];
+      if (act_max) {
+        act_max[f] = fmaxf(act_max[f], s_max[f]);
+        act_sum[f] += s_sum[f];
+      }
     }
-    float *tv = top_val + (size_t)f * n;
-    long long *ti = top_id + (size_t)f * n;
-    const float *sv = s_val + (size_t)f * n;
-    const long long *si = s_id + (size_t)f * n;
-    int na = 0, nb = 0;
-    for (int j = lane; j < n; j += 64) {
-      av[j] = tv[j];
-      ai[j] = ti[j];
-      bv[j] = sv[j];
-      bi[j] = si[j];
-      na += ai[j] >= 0;
-      nb += bi[j] >= 0;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      na += __shfl_xor(na, off, 64);
-      nb += __shfl_xor(nb, off, 64);
-    }
+    float *tv = dst_val + (size_t)f * n;
+    long long *ti = dst_id + (size_t)f * n;
+    const unsigned long long h = order.feature(f);
+    const int na = fs_table_load(T, 0, order, h, tv, ti, n, lane);
+    const int nb = fs_table_load(T, 1, order, h, s_val + (size_t)f * n, s_id + (size_t)f * n, n, lane);
     __syncthreads();
     if (nb) {
       for (int j = lane; j < na; j += 64) {         // dst entries: after the src entries strictly before them
         int lo = 0, hi = nb;
         while (lo < hi) {
           const int mid = (lo + hi) >> 1;
-          if (fs_before(bv[mid], bi[mid], av[j], ai[j])) lo = mid + 1; else hi = mid;
+          if (O::before(T.key[1][mid], T.id[1][mid], T.key[0][j], T.id[0][j])) lo = mid + 1; else hi = mid;
         }
         if (j + lo < n) {
-          tv[j + lo] = av[j];
-          ti[j + lo] = ai[j];
+          tv[j + lo] = T.value(0, j);
+          ti[j + lo] = T.id[0][j];
         }
       }
       for (int j = lane; j < nb; j += 64) {         // src entries: after the dst entries before or equal
         int lo = 0, hi = na;
         while (lo < hi) {
           const int mid = (lo + hi) >> 1;
-          if (fs_before(bv[j], bi[j], av[mid], ai[mid])) hi = mid; else lo = mid + 1;
+          if (O::before(T.key[1][j], T.id[1][j], T.key[0][mid], T.id[0][mid])) hi = mid; else lo = mid + 1;
         }
         if (j + lo < n) {
-          tv[j + lo] = bv[j];
-          ti[j + lo] = bi[j];
+          tv[j + lo] = T.value(1, j);
+          ti[j + lo] = T.id[1][j];
         }
       }
     }
@@ -311,13 +417,21 @@ extern "C" size_t msae_feature_stats_ws_bytes(int T, int k, int N) {
   return fs_layout((long)T * k, N).total;
 }
 
-extern "C" int msae_feature_stats_update(const float *vals, const int32_t *idx, int B, int S, int k, float thresh,
-                                         int N, int mode, int pool_len, int window, int64_t row_base, int n_top,
-                                         uint64_t *count, float *act_max, double *act_sum, float *top_val,
-                                         int64_t *top_id, void *ws, size_t ws_bytes, void *stream) {
+namespace {
+
+bool fs_sample_ok(const msae_feature_sample *sm) {
+  if (sm->size < sizeof(msae_feature_sample)) return false;
+  if (sm->n_sample <= 0 || sm->n_sample > FS_MAX_TOP) return false;
+  return sm->seg_count && sm->smp_val && sm->smp_id;
+}
+
+int fs_update(const float *vals, const int32_t *idx, int B, int S, int k, float thresh, int N, int mode, int pool_len,
+              int window, int64_t row_base, int n_top, uint64_t *count, float *act_max, double *act_sum, float *top_val,
+              int64_t *top_id, const msae_feature_sample *sample, void *ws, size_t ws_bytes, void *stream) {
   if (B < 0 || S < 0 || (B > 0 && S > MSAE_STATS_MAX_T / B)) return MSAE_EINVAL;
   const int T = B * S;
   if (!fs_args_ok(T, k, N, n_top, mode, pool_len, window) || row_base < 0) return MSAE_EINVAL;
+  if (sample && !fs_sample_ok(sample)) return MSAE_EINVAL;
   if (T == 0) return 0;
   const long M = (long)T * k;
   const FsLayout L = fs_layout(M, N);
@@ -350,9 +464,38 @@ extern "C" int msae_feature_stats_update(const float *vals, const int32_t *idx, 
   hipLaunchKernelGGL(fs_group_kernel, dim3(blocks), dim3(256), 0, st, kb.current(), vb.current(), M, N, g, starts,
                      ends, cand, (unsigned long long *)count, act_max, act_sum);
   const unsigned mblocks = (unsigned)(N < 8192 ? N : 8192);
-  hipLaunchKernelGGL(fs_merge_kernel, dim3(mblocks), dim3(64), 0, st, kb.current(), cand, N, n_top, g, starts, ends,
-                     top_val, (long long *)top_id);
+  FsSampleArgs sa{};
+  if (sample) {
+    sa = FsSampleArgs{sample->n_sample, (unsigned long long)sample->seed, (unsigned long long *)sample->seg_count,
+                      sample->smp_val, (long long *)sample->smp_id};
+    auto kern = n_top <= 64 && sa.n <= 64 ? fs_merge_kernel<true, 64> : fs_merge_kernel<true, FS_MAX_TOP>;
+    hipLaunchKernelGGL(kern, dim3(mblocks), dim3(64), 0, st, kb.current(), cand, N, n_top, g, starts, ends, top_val,
+                       (long long *)top_id, sa);
+  } else {
+    hipLaunchKernelGGL((fs_merge_kernel<false, FS_MAX_TOP>), dim3(mblocks), dim3(64), 0, st, kb.current(), cand, N, n_top, g, starts,
+                       ends, top_val, (long long *)top_id, sa);
+  }
   return msae_launch_status();
+}
+
+}  // namespace
+
+extern "C" int msae_feature_stats_update(const float *vals, const int32_t *idx, int B, int S, int k, float thresh,
+                                         int N, int mode, int pool_len, int window, int64_t row_base, int n_top,
+                                         uint64_t *count, float *act_max, double *act_sum, float *top_val,
+                                         int64_t *top_id, void *ws, size_t ws_bytes, void *stream) {
+  return fs_update(vals, idx, B, S, k, thresh, N, mode, pool_len, window, row_base, n_top, count, act_max, act_sum,
+                   top_val, top_id, nullptr, ws, ws_bytes, stream);
+}
+
+extern "C" int msae_feature_stats_update_sampled(const float *vals, const int32_t *idx, int B, int S, int k,
+                                                 float thresh, int N, int mode, int pool_len, int window,
+                                                 int64_t row_base, int n_top, uint64_t *count, float *act_max,
+                                                 double *act_sum, float *top_val, int64_t *top_id,
+                                                 const msae_feature_sample *sample, void *ws, size_t ws_bytes,
+                                                 void *stream) {
+  return fs_update(vals, idx, B, S, k, thresh, N, mode, pool_len, window, row_base, n_top, count, act_max, act_sum,
+                   top_val, top_id, sample, ws, ws_bytes, stream);
 }
 
 extern "C" int msae_feature_stats_merge(int N, int n_top, uint64_t *count, float *act_max, double *act_sum,
@@ -361,8 +504,22 @@ extern "C" int msae_feature_stats_merge(int N, int n_top, uint64_t *count, float
                                         const int64_t *src_id, void *stream) {
   if (N <= 0 || N > 262144 || n_top <= 0 || n_top > FS_MAX_TOP) return MSAE_EINVAL;
   const unsigned blocks = (unsigned)(N < 8192 ? N : 8192);
-  hipLaunchKernelGGL(fs_merge_tables_kernel, dim3(blocks), dim3(64), 0, (hipStream_t)stream, N, n_top,
-                     (unsigned long long *)count, act_max, act_sum, top_val, (long long *)top_id,
+  hipLaunchKernelGGL(fs_merge_tables_kernel<FsTopOrder>, dim3(blocks), dim3(64), 0, (hipStream_t)stream, N, n_top,
+                     FsTopOrder{}, (unsigned long long *)count, act_max, act_sum, top_val, (long long *)top_id,
                      (const unsigned long long *)src_count, src_max, src_sum, src_val, (const long long *)src_id);
+  return msae_launch_status();
+}
+
+extern "C" int msae_feature_sample_merge(int N, int n_sample, uint64_t seed, uint64_t *seg_count, float *smp_val,
+                                         int64_t *smp_id, const uint64_t *src_seg_count, const float *src_val,
+                                         const int64_t *src_id, void *stream) {
+  if (N <= 0 || N > 262144 || n_sample <= 0 || n_sample > FS_MAX_TOP) return MSAE_EINVAL;
+  if (!seg_count || !smp_val || !smp_id || !src_seg_count || !src_val || !src_id) return MSAE_EINVAL;
+  const unsigned blocks = (unsigned)(N < 8192 ? N : 8192);
+  hipLaunchKernelGGL(fs_merge_tables_kernel<FsSampleOrder>, dim3(blocks), dim3(64), 0, (hipStream_t)stream, N,
+                     n_sample, FsSampleOrder{(unsigned long long)seed}, (unsigned long long *)seg_count,
+                     (float *)nullptr, (double *)nullptr, smp_val, (long long *)smp_id,
+                     (const unsigned long long *)src_seg_count, (const float *)nullptr, (const double *)nullptr, src_val,
+                     (const long long *)src_id);
   return msae_launch_status();
 }

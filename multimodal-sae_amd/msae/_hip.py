@@ -31,6 +31,15 @@ class MsaeOptions(ctypes.Structure):
 
 c_opts_p = ctypes.POINTER(MsaeOptions)
 
+
+class MsaeFeatureSample(ctypes.Structure):
+    """struct msae_feature_sample of include/msae.h: the per-feature uniform sample tables of a statistics update."""
+    _fields_ = [("size", ctypes.c_uint32), ("n_sample", ctypes.c_int32), ("seed", ctypes.c_uint64),
+                ("seg_count", ctypes.c_void_p), ("smp_val", ctypes.c_void_p), ("smp_id", ctypes.c_void_p)]
+
+
+c_sample_p = ctypes.POINTER(MsaeFeatureSample)
+
 # name -> (restype, argtypes); mirrors include/msae.h one to one
 PROTOTYPES = {
     "msae_options_init": (None, [c_opts_p]),
@@ -86,6 +95,11 @@ PROTOTYPES = {
                                           c_size_t, c_void_p]),
     "msae_feature_stats_merge": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "msae_feature_stats_update_sampled": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_int, c_int,
+                                                  c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                  c_sample_p, c_void_p, c_size_t, c_void_p]),
+    "msae_feature_sample_merge": (c_int, [c_int, c_int, ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p]),
     "msae_pooled_acts_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int,
                                      c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "msae_probe_maps_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int,

@@ -41,6 +41,10 @@ class CacheConfig:
     """Top examples kept per feature in the statistics (55..256)"""
     example_ctx_len: int = 64
     """Window length of the text statistics' max-pooled examples"""
+    stats_sample: int = 0
+    """Uniformly sampled examples kept per feature in the statistics (0: none, up to 256)"""
+    stats_seed: int = 22
+    """Seed of the statistics' example sample"""
 
     def to_dict(self):
         return dataclasses.asdict(self)

@@ -12,6 +12,7 @@ tables (msae/features/stats.py) next to them:
 
     <save_dir>/<module>/Rank{r}_feature_stats.safetensors      per rank
     <save_dir>/<module>/feature_stats.safetensors              the ranks merged in rank order by the concat
+                                                               (with `n_sample`: the uniform example sample too)
 
 with keys `locations [nnz,3] int64 = (row, pos, feature)` and `activations [nnz] f32`, which is what
 `features/loader.py:143-196` (FeatureDataset) reads.
@@ -60,8 +61,8 @@ class Cache:
         `save()` reads them back in batch order, so the final tensors are identical.
         `device_budget_bytes`: records of the fused path wait on the device (worst-case sized buffers, 7 MB
         per 8192-token batch at k = 32) and cross to the host in one transfer once this much is pending.
-        `stats`: keyword arguments of `FeatureStats` (pool, n_top, pool_len, window, thresh) -- one `FeatureStats` per
-        module is then updated in `add_topk` on the compute stream, over every feature (the filter is not applied);
+        `stats`: keyword arguments of `FeatureStats` (pool, n_top, pool_len, window, thresh, n_sample, sample_seed) -- one
+        `FeatureStats` per module is then updated in `add_topk` on the compute stream, over every feature (the filter is not applied);
         None (default): nothing of it runs."""
         self.feature_locations = defaultdict(list)
         self.feature_activations = defaultdict(list)

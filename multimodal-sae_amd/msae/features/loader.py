@@ -12,7 +12,8 @@ stats.py), two questions are answered from them instead of the records: the `min
 their count before any split file is read (the count covers every record of the feature, so a feature it drops has
 fewer records than `min_examples` too: the selection is the same), and `top_example_records` returns one feature's
 top examples -- what `pool_max_activation_windows` / `pool_max_activations_windows_image` select
-(features/constructors.py:28-141) -- from the one split file that holds it.
+(features/constructors.py:28-141) -- from the one split file that holds it.  `sample_example_records` does the same for the
+examples the reference's samplers pick (features/samplers.py: "top", "random", "quantile"), from the statistics' uniform sample.
 """
 from __future__ import annotations
 
@@ -150,6 +151,36 @@ def dedup_image_rows(rows: Sequence[int], image_ids: Sequence, max_examples: int
     return out[:max_examples]
 
 
+def _feature_records(raw_dir: str, st: FeatureStats, module: str, feature: int, n_splits: int) -> FeatureRecords:
+    return SplitBuffer(split_path(raw_dir, module, st.num_latents, n_splits, feature), module).get(feature)
+
+
+def _rebuild_examples(st: FeatureStats, rec: FeatureRecords, ids: Tensor, vals: Tensor, tokens: Optional[Tensor],
+                      seq_len: int) -> TopExamples:
+    """The examples `ids` (window ids in window mode, rows in image mode) of one feature rebuilt from its records:
+    activation windows [m, W] (and token windows from `tokens` [rows, S] if given), or dense rows [m, seq_len] and the image
+    constructor's zero tokens."""
+    rows_of, pos_of, acts = rec.locations[:, 0], rec.locations[:, 1], rec.activations
+    if st.pool == "window":
+        W = st.window
+        nw = st.windows_per_row if tokens is None else tokens.shape[1] // W
+        rows, wins = ids // nw, ids % nw
+        act_w = torch.zeros(len(ids), W, dtype=torch.float32)
+        for m, (r, w) in enumerate(zip(rows.tolist(), wins.tolist())):
+            sel = (rows_of == r) & (pos_of >= w * W) & (pos_of < (w + 1) * W)
+            act_w[m, pos_of[sel] - w * W] = acts[sel]
+        tok_w = None
+        if tokens is not None:
+            tok_w = torch.stack([tokens[r, w * W:(w + 1) * W] for r, w in zip(rows.tolist(), wins.tolist())]) \
+                if len(ids) else tokens.new_zeros(0, W)
+        return TopExamples(ids, vals, tok_w, act_w)
+    dense = torch.zeros(len(ids), seq_len, dtype=torch.float32)
+    for m, r in enumerate(ids.tolist()):
+        sel = rows_of == r
+        dense[m, pos_of[sel]] = acts[sel]
+    return TopExamples(ids, vals, torch.zeros(len(ids), seq_len), dense)
+
+
 def top_example_records(raw_dir: str, stats, module: str, feature: int, max_examples: int, n_splits: int,
                         tokens: Optional[Tensor] = None, image_ids: Optional[Sequence] = None,
                         seq_len: int = 8000) -> TopExamples:
@@ -163,22 +194,9 @@ def top_example_records(raw_dir: str, stats, module: str, feature: int, max_exam
                  (constructors.py:88-141): dense activation rows [m, seq_len] and the constructor's zero tokens."""
     st = stats if isinstance(stats, FeatureStats) else FeatureStats.load(stats)
     ids, vals = st.top_examples(feature)
-    rec = SplitBuffer(split_path(raw_dir, module, st.num_latents, n_splits, feature), module).get(feature)
-    rows_of, pos_of, acts = rec.locations[:, 0], rec.locations[:, 1], rec.activations
+    rec = _feature_records(raw_dir, st, module, feature, n_splits)
     if st.pool == "window":
-        W = st.window
-        ids, vals = ids[:max_examples], vals[:max_examples]
-        nw = st.windows_per_row if tokens is None else tokens.shape[1] // W
-        rows, wins = ids // nw, ids % nw
-        act_w = torch.zeros(len(ids), W, dtype=torch.float32)
-        for m, (r, w) in enumerate(zip(rows.tolist(), wins.tolist())):
-            sel = (rows_of == r) & (pos_of >= w * W) & (pos_of < (w + 1) * W)
-            act_w[m, pos_of[sel] - w * W] = acts[sel]
-        tok_w = None
-        if tokens is not None:
-            tok_w = torch.stack([tokens[r, w * W:(w + 1) * W] for r, w in zip(rows.tolist(), wins.tolist())]) \
-                if len(ids) else tokens.new_zeros(0, W)
-        return TopExamples(ids, vals, tok_w, act_w)
+        return _rebuild_examples(st, rec, ids[:max_examples], vals[:max_examples], tokens, seq_len)
     ids, vals = ids[:max_examples + 50], vals[:max_examples + 50]
     if image_ids is not None:
         keep = dedup_image_rows(ids.tolist(), image_ids, max_examples)
@@ -189,8 +207,26 @@ def top_example_records(raw_dir: str, stats, module: str, feature: int, max_exam
         ids = torch.tensor(keep, dtype=torch.int64)
     else:
         ids, vals = ids[:max_examples], vals[:max_examples]
-    dense = torch.zeros(len(ids), seq_len, dtype=torch.float32)
-    for m, r in enumerate(ids.tolist()):
-        sel = rows_of == r
-        dense[m, pos_of[sel]] = acts[sel]
-    return TopExamples(ids, vals, torch.zeros(len(ids), seq_len), dense)
+    return _rebuild_examples(st, rec, ids, vals, tokens, seq_len)
+
+
+def sample_example_records(raw_dir: str, stats, module: str, feature: int, train_type: str, n_train: int,
+                           n_splits: int, tokens: Optional[Tensor] = None, image_ids: Optional[Sequence] = None,
+                           seq_len: int = 8000, n_quantiles: int = 10, seed: int = 22) -> TopExamples:
+    """The examples the reference's sampler would train on (features/samplers.py: `train_type` "top", "random" or
+    "quantile"), picked from the statistics by `samplers.stats_examples` and rebuilt, like `top_example_records`, from the
+    ONE split file that holds the feature's records.  "random" and "quantile" need statistics with a sample
+    (`n_sample > 0`).  Image mode with `image_ids`: the first row of every image id is kept, in list order, and the list is
+    not padded."""
+    from .samplers import stats_examples
+
+    st = stats if isinstance(stats, FeatureStats) else FeatureStats.load(stats)
+    ids, vals = stats_examples(st, feature, train_type, n_train, n_quantiles=n_quantiles, seed=seed)
+    if st.pool == "image" and image_ids is not None:
+        seen, keep = set(), []
+        for j, r in enumerate(ids.tolist()):
+            if image_ids[r] not in seen:
+                seen.add(image_ids[r])
+                keep.append(j)
+        ids, vals = ids[keep], vals[keep]
+    return _rebuild_examples(st, _feature_records(raw_dir, st, module, feature, n_splits), ids, vals, tokens, seq_len)

@@ -12,9 +12,15 @@ with their ids.
     pool="window"  windows of `window` positions: max; id = global row * (S // window) + w
 
 The keep rule is the cache's (|v| > thresh, default 1e-5), without the cache's feature filter.
+
+With `n_sample > 0` the same update also keeps, per feature, a uniform random sample of `n_sample` of ALL its nonzero pooled
+segments (not only the largest) and their number `seg_count`: the `n_sample` segments whose hash of (sample_seed, feature,
+id) is smallest.  That is what the reference's "random" and "quantile" example samplers need (msae/features/samplers.py).
+The sample does not depend on the values, on how rows are cut into calls or ranks, or on the order of the calls.
 """
 from __future__ import annotations
 
+import ctypes
 import json
 from typing import Optional, Tuple
 
@@ -27,6 +33,7 @@ from .. import _hip, ops
 
 POOL_MODES = {"image": 0, "window": 1}
 MIN_TOP, MAX_TOP = 55, 256      # 55 = the README's --max_examples 5 + the image constructor's 50 spare ids
+MAX_SAMPLE = 256
 
 
 @torch.library.custom_op("msae::feature_stats_update", mutates_args=("count", "act_max", "act_sum", "top_val",
@@ -54,13 +61,45 @@ def _(top_acts, top_indices, row_base, thresh, mode, pool_len, window, count, ac
     return None
 
 
+@torch.library.custom_op("msae::feature_stats_update_sampled",
+                         mutates_args=("count", "act_max", "act_sum", "top_val", "top_id", "seg_count", "smp_val", "smp_id"))
+def feature_stats_update_sampled(top_acts: Tensor, top_indices: Tensor, row_base: int, thresh: float, mode: int,
+                                 pool_len: int, window: int, count: Tensor, act_max: Tensor, act_sum: Tensor,
+                                 top_val: Tensor, top_id: Tensor, seed: int, seg_count: Tensor, smp_val: Tensor,
+                                 smp_id: Tensor) -> None:
+    """`feature_stats_update` that also merges the batch into the uniform sample tables (`seed`: the 64-bit sample seed,
+    taken mod 2^64) -- one more table merge in the same launch."""
+    dev = _hip.require_device(top_acts, top_indices, count, act_max, act_sum, top_val, top_id, seg_count, smp_val, smp_id)
+    lib = _hip.load()
+    assert top_acts.dim() == 3 and top_acts.shape == top_indices.shape
+    B, S, k = top_acts.shape
+    N, n = top_val.shape
+    assert smp_val.shape == smp_id.shape and smp_val.shape[0] == N and seg_count.shape == (N,)
+    vals, idx = ops._f32c(top_acts), ops._idx32(top_indices)
+    sample = _hip.MsaeFeatureSample(ctypes.sizeof(_hip.MsaeFeatureSample), smp_val.shape[1], seed % (1 << 64),
+                                    seg_count.data_ptr(), smp_val.data_ptr(), smp_id.data_ptr())
+    with torch.cuda.device(dev):
+        ws = ops._workspace(dev, lib.msae_feature_stats_ws_bytes(B * S, k, N))
+        _hip.check(lib.msae_feature_stats_update_sampled(
+            _hip.ptr(vals), _hip.ptr(idx), B, S, k, thresh, N, mode, pool_len, window, row_base, n,
+            _hip.ptr(count), _hip.ptr(act_max), _hip.ptr(act_sum), _hip.ptr(top_val), _hip.ptr(top_id),
+            ctypes.byref(sample), _hip.ptr(ws), ws.numel(), _hip.stream_of(vals)), "msae_feature_stats_update_sampled")
+
+
+@feature_stats_update_sampled.register_fake
+def _(top_acts, top_indices, row_base, thresh, mode, pool_len, window, count, act_max, act_sum, top_val, top_id, seed,
+      seg_count, smp_val, smp_id):
+    return None
+
+
 class FeatureStats:
     """Statistics of `num_latents` features: count (int64), act_max (f32), act_sum (f64), and the sorted top-n tables
-    top_val [N, n] (f32) / top_id [N, n] (int64; -1 = free slot).  The tables live on `device`; `update` and `merge`
-    need a HIP device, reading a loaded file does not."""
+    top_val [N, n] (f32) / top_id [N, n] (int64; -1 = free slot).  With `n_sample > 0` also seg_count (int64: nonzero pooled
+    segments seen) and the uniform sample tables smp_val / smp_id [N, n_sample], sorted by hash priority.  The tables live
+    on `device`; `update` and `merge` need a HIP device, reading a loaded file does not."""
 
     def __init__(self, num_latents: int, n_top: int = 64, pool: str = "image", pool_len: int = 576, window: int = 64,
-                 thresh: float = 1e-5, device=None):
+                 thresh: float = 1e-5, device=None, n_sample: int = 0, sample_seed: int = 22):
         if pool not in POOL_MODES:
             raise ValueError(f"pool must be one of {sorted(POOL_MODES)}, got {pool!r}")
         if not MIN_TOP <= n_top <= MAX_TOP:
@@ -71,6 +110,10 @@ class FeatureStats:
             raise ValueError(f"pool_len must lie in [1, 2880], got {pool_len}")
         if pool == "window" and not 0 < window <= 4096:
             raise ValueError(f"window must lie in [1, 4096], got {window}")
+        if not 0 <= n_sample <= MAX_SAMPLE:
+            raise ValueError(f"n_sample must lie in [0, {MAX_SAMPLE}] (0: no sample), got {n_sample}")
+        if not 0 <= sample_seed < 1 << 64:
+            raise ValueError(f"sample_seed must lie in [0, 2^64), got {sample_seed}")
         self.num_latents, self.n_top, self.pool = num_latents, n_top, pool
         self.pool_len, self.window, self.thresh = pool_len, window, float(thresh)
         self.tokens_seen = 0
@@ -82,6 +125,11 @@ class FeatureStats:
         self.act_sum = torch.zeros(N, dtype=torch.float64, device=dev)
         self.top_val = torch.zeros(N, n_top, dtype=torch.float32, device=dev)
         self.top_id = torch.full((N, n_top), -1, dtype=torch.int64, device=dev)
+        self.n_sample, self.sample_seed = int(n_sample), int(sample_seed)
+        if self.n_sample:
+            self.seg_count = torch.zeros(N, dtype=torch.int64, device=dev)
+            self.smp_val = torch.zeros(N, n_sample, dtype=torch.float32, device=dev)
+            self.smp_id = torch.full((N, n_sample), -1, dtype=torch.int64, device=dev)
 
     @property
     def device(self) -> torch.device:
@@ -89,9 +137,9 @@ class FeatureStats:
 
     def _same_kind(self, other: "FeatureStats") -> None:
         mine = (self.num_latents, self.n_top, self.pool, self.pool_len if self.pool == "image" else self.window,
-                self.thresh)
+                self.thresh, self.n_sample, self.sample_seed)
         theirs = (other.num_latents, other.n_top, other.pool, other.pool_len if other.pool == "image" else other.window,
-                  other.thresh)
+                  other.thresh, other.n_sample, other.sample_seed)
         if mine != theirs:
             raise ValueError(f"cannot merge feature statistics of different kinds: {mine} vs {theirs}")
 
@@ -103,9 +151,13 @@ class FeatureStats:
             if self.windows_per_row is not None and self.windows_per_row != nw:
                 raise ValueError(f"rows of {S} positions give {nw} windows, earlier rows gave {self.windows_per_row}")
             self.windows_per_row = nw
-        torch.ops.msae.feature_stats_update(top_acts, top_indices, int(row_base), self.thresh, POOL_MODES[self.pool],
-                                            self.pool_len, self.window, self.count, self.act_max, self.act_sum,
-                                            self.top_val, self.top_id)
+        args = (top_acts, top_indices, int(row_base), self.thresh, POOL_MODES[self.pool], self.pool_len, self.window,
+                self.count, self.act_max, self.act_sum, self.top_val, self.top_id)
+        if self.n_sample:       # the custom op's int is 64-bit signed: the seed travels as its two's complement
+            seed = self.sample_seed - (1 << 64) if self.sample_seed >= 1 << 63 else self.sample_seed
+            torch.ops.msae.feature_stats_update_sampled(*args, seed, self.seg_count, self.smp_val, self.smp_id)
+        else:
+            torch.ops.msae.feature_stats_update(*args)
         self.tokens_seen += B * S
 
     def merge(self, other: "FeatureStats") -> "FeatureStats":
@@ -121,6 +173,12 @@ class FeatureStats:
                 self.num_latents, self.n_top, _hip.ptr(self.count), _hip.ptr(self.act_max), _hip.ptr(self.act_sum),
                 _hip.ptr(self.top_val), _hip.ptr(self.top_id), *[_hip.ptr(t) for t in o],
                 _hip.stream_of(self.count)), "msae_feature_stats_merge")
+            if self.n_sample:
+                so = [t.to(dev).contiguous() for t in (other.seg_count, other.smp_val, other.smp_id)]
+                _hip.check(_hip.load().msae_feature_sample_merge(
+                    self.num_latents, self.n_sample, self.sample_seed, _hip.ptr(self.seg_count), _hip.ptr(self.smp_val),
+                    _hip.ptr(self.smp_id), *[_hip.ptr(t) for t in so], _hip.stream_of(self.count)),
+                    "msae_feature_sample_merge")
         self.tokens_seen += other.tokens_seen
         if self.windows_per_row is None:
             self.windows_per_row = other.windows_per_row
@@ -136,15 +194,36 @@ class FeatureStats:
         keep = ids >= 0
         return ids[keep], vals[keep]
 
+    def sample_examples(self, feature: int) -> Tuple[Tensor, Tensor]:
+        """(ids int64, pooled values f32) of the feature's uniform sample, in priority order (host tensors): a uniform
+        draw without replacement from all `seg_count[feature]` nonzero pooled segments; any prefix is one too."""
+        if not self.n_sample:
+            raise ValueError("these statistics keep no sample (n_sample = 0)")
+        ids, vals = self.smp_id[feature].cpu(), self.smp_val[feature].cpu()
+        keep = ids >= 0
+        return ids[keep], vals[keep]
+
+    def sample_fraction(self) -> Tensor:
+        """min(1, n_sample / seg_count) per feature (f64): the share of a feature's nonzero pooled segments its sample
+        holds (1 where the sample is the whole population)."""
+        if not self.n_sample:
+            raise ValueError("these statistics keep no sample (n_sample = 0)")
+        return (self.n_sample / self.seg_count.double().clamp(min=1.0)).clamp(max=1.0)
+
     def metadata(self) -> dict:
-        return {"format": "msae.feature_stats.v1", "pool": self.pool, "pool_len": str(self.pool_len),
+        meta = {"format": "msae.feature_stats.v1", "pool": self.pool, "pool_len": str(self.pool_len),
                 "window": str(self.window), "n_top": str(self.n_top), "thresh": repr(self.thresh),
                 "num_latents": str(self.num_latents), "tokens_seen": str(self.tokens_seen),
                 "windows_per_row": json.dumps(self.windows_per_row)}
+        if self.n_sample:
+            meta.update(n_sample=str(self.n_sample), sample_seed=str(self.sample_seed))
+        return meta
 
     def save(self, path: str) -> None:
         tensors = {"count": self.count, "act_max": self.act_max, "act_sum": self.act_sum, "top_val": self.top_val,
                    "top_id": self.top_id}
+        if self.n_sample:
+            tensors.update(seg_count=self.seg_count, smp_val=self.smp_val, smp_id=self.smp_id)
         save_file({k: v.detach().contiguous().cpu() for k, v in tensors.items()}, path, metadata=self.metadata())
 
     @classmethod
@@ -156,7 +235,7 @@ class FeatureStats:
             tensors = {k: fh.get_tensor(k) for k in fh.keys()}
         st = cls(int(meta["num_latents"]), n_top=int(meta["n_top"]), pool=meta["pool"],
                  pool_len=int(meta["pool_len"]), window=int(meta["window"]), thresh=float(meta["thresh"]),
-                 device="cpu")
+                 device="cpu", n_sample=int(meta.get("n_sample", 0)), sample_seed=int(meta.get("sample_seed", 22)))
         for k, v in tensors.items():
             setattr(st, k, v if device is None else v.to(device))
         st.tokens_seen = int(meta["tokens_seen"])

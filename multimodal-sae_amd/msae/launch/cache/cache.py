@@ -101,7 +101,10 @@ def main(cfg: CacheConfig):
         dataset = dataset.shard(world, rank, contiguous=True)       # contiguous chunks (cache.py:66)
         shard_size = sum(shard_offsets(len(dataset), model.device)[:rank])   # all_gather_into_tensor (cache.py:67-75)
     saes = load_saes(cfg.sae_path, filters=filters, device=model.device)
-    stats = dict(pool="window", window=cfg.example_ctx_len, n_top=cfg.stats_top) if cfg.feature_stats else None
+    stats = None
+    if cfg.feature_stats:
+        stats = dict(pool="window", window=cfg.example_ctx_len, n_top=cfg.stats_top, n_sample=cfg.stats_sample,
+                     sample_seed=cfg.stats_seed)
     cache = FeatureCache(model, tokenizer, saes, batch_size=cfg.batch_size, shard_size=shard_size,
                          filters=filters, stats=stats)
     if ddp:

@@ -28,7 +28,8 @@ def main(cfg: CacheConfig):
     saes = load_saes(cfg.sae_path, filters=filters, device=model.device)
     stats = None
     if cfg.feature_stats:   # the image constructor pools the processor's first num_image_tokens positions
-        stats = dict(pool="image", pool_len=getattr(processor, "num_image_tokens", None) or 576, n_top=cfg.stats_top)
+        stats = dict(pool="image", pool_len=getattr(processor, "num_image_tokens", None) or 576, n_top=cfg.stats_top,
+                     n_sample=cfg.stats_sample, sample_seed=cfg.stats_seed)
     cache = FeatureImageCache(model, tokenizer, saes, batch_size=cfg.batch_size, shard_size=shard_size,
                               processor=processor, filters=filters, stats=stats)
     if ddp:
