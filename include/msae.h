@@ -29,6 +29,7 @@
  *   msae_rows_topk_f32       cos + get_neighbors; logits   features/stats.py:76-120; stats.py:12-47
  *   msae_row_inv_norms_f32   F.normalize's norms in cos    features/stats.py:80-81
  *   msae_edit_topk_f32       hook edits with a feature LIST features/steering.py:113-114, patching/utils.py:43-48
+ *   msae_edit_topk_rows_f32  the same with one table per token (a feature per batch row of one generate)
  *
  * Numerics contract: all dot products are ascending-k f32 fused
  * multiply-add chains (v_mfma_f32_32x32x2_f32 / v_fma_f32), bit-identical to oracle/sae_oracle.c.
@@ -557,6 +558,40 @@ int msae_edit_topk_f32(const float *vals_in, const int32_t *idx_in, int T, int k
 int msae_edit_topk_i64_f32(const float *vals_in, const int64_t *idx_in, int T, int kk, const int32_t *edit_feat,
                            const float *edit_val, const int32_t *edit_kind, int E, int N, int k, float *vals,
                            int64_t *idx, void *stream);
+
+/* ---- per-token edit tables (Sae.encode(edits=RowEdits, edit_group=...)) ---------------------------
+ * The same edit with a table that is a function of the token: B features steered in the B rows of one generate, G
+ * ablations in the G copies of one attribution batch.  The tables of G groups are concatenated:
+ *   group_of int32 [T]        the group of token t; any value outside [0, G) (-1 by convention): the token is unedited
+ *   group_off int32 [G + 1]   ascending offsets into the edit arrays: group g owns [group_off[g], group_off[g + 1])
+ *   edit_feat / edit_val / edit_kind [E_total]   as above; edit_feat STRICTLY ASCENDING inside each group
+ *   E_max                     >= every group's length; it sizes the sort (and the kernel layout) of the whole call
+ *   edited uint8 [T][k] or NULL   1 where the output slot came from an edit entry (the differentiable encode masks those)
+ * Asynchronous on `stream`; allocates nothing, never synchronises, needs no workspace.
+ * MSAE_EINVAL: T < 0, G < 1, k < 1, E_max < 1, E_total < 0, k + E_max > min(N, 4096), kk < k + E_max, a null pointer
+ * (`edited` may be null).  T == 0 does nothing and returns 0.
+ * Contract:
+ *   1. Edited tokens.  For g = group_of[t] in [0, G) with E_g > 0 entries the output row is the canonical top-k (value
+ *      descending, index ascending) of the latents edited with group g's table -- bit-identical to what msae_edit_topk_f32
+ *      returns for that token with that table alone (so points 1-4 and 6 above hold per token).
+ *   2. Entries read.  Only the first k + E_g entries of the row are read: the result does not depend on kk beyond
+ *      kk >= k + E_max, nor on the other tokens or groups of the call.
+ *   3. Unedited tokens.  A token whose group id lies outside [0, G), and a token of an empty group (E_g = 0), gets the
+ *      first k input entries copied bit for bit, `edited` all 0: a batch carries its unedited baseline row this way.
+ *   4. Device data.  group_of and group_off are never trusted: a slice is clamped into [0, E_total], its length into
+ *      [0, E_max].  Like msae_edit_topk_f32 the kernels never index memory by a list entry's feature.  A hostile id or
+ *      offset can give a wrong row for that token; it cannot give an out-of-bounds access.
+ *   5. Layout.  next_pow2(k + 2 E_max) <= 256: one wave per token, keys in registers, no LDS, no barriers; above: one
+ *      workgroup per token with the token's slice and keys in LDS (8 next_pow2(k + 2 E_max) + 4 E_max bytes <= 80 KiB). */
+int msae_edit_topk_rows_f32(const float *vals_in, const int32_t *idx_in, int T, int kk, const int32_t *group_of,
+                            const int32_t *group_off, int G, const int32_t *edit_feat, const float *edit_val,
+                            const int32_t *edit_kind, int E_total, int E_max, int N, int k, float *vals, int32_t *idx,
+                            uint8_t *edited, void *stream);
+/* the same reading and writing 64-bit indices */
+int msae_edit_topk_rows_i64_f32(const float *vals_in, const int64_t *idx_in, int T, int kk, const int32_t *group_of,
+                                const int32_t *group_off, int G, const int32_t *edit_feat, const float *edit_val,
+                                const int32_t *edit_kind, int E_total, int E_max, int N, int k, float *vals, int64_t *idx,
+                                uint8_t *edited, void *stream);
 
 /* ---- merge of per-shard results (feature-sharded encode; no reference counterpart) ----
  * gathered: int32 [G][2][T][kl], the all-gather of each rank's packed block [2][T][kl]

@@ -20,6 +20,19 @@
 //   5. the first k are decoded: value from the order key (a value of -0 comes back as +0, as msae_merge_topk's does), index
 // LDS per workgroup: 8 n_sort + 4 E bytes (2.2 KiB at k = 32, E = 50; 80 KiB at the envelope k + E = 4096, E = 4095).
 // The kernel never indexes memory by a list entry's feature, so a hostile index cannot fault it.
+//
+// PER-TOKEN TABLES (msae_edit_topk_rows_f32): token t applies the slice
+// [group_off[g], group_off[g + 1]) of the concatenated edit arrays, g = group_of[t]; a g outside [0, G) or an empty slice
+// copies the first k entries.  The argument above is a statement about ONE token and its table, so it holds unchanged.  Both
+// device arrays are clamped (slice into [0, E_total], length into [0, E_max]) before anything is indexed by them.
+//   edit_topk_rows_wave_kernel<R>: next_pow2(k + 2 E_max) <= 64 R <= 256.  ONE WAVE PER TOKEN, ET_ROWS_WAVES waves per
+//     workgroup, the 64 R keys in R registers per lane (sortsel.h wave_sort_desc_u64_regs), the slice read from global memory
+//     (the same few lines for every token of a group: L2 hits; a linear scan up to ET_SCAN_MAX entries, else edit_find).
+//     No LDS, no barriers; a wave whose token is unedited copies its row and leaves.
+//   edit_topk_rows_wg_kernel: above 256 keys, edit_topk_kernel's layout with the token's slice in LDS and the token's own
+//     n_sort = next_pow2(k + 2 E_g) <= the launch's; LDS 8 n_sort + 4 E_max bytes, 80 KiB at the envelope as above.
+// `edited` (optional) marks the output slots whose feature is in the token's table: every surviving list entry's is not, so
+// those are exactly the slots that came from an edit entry.
 #include <algorithm>
 
 #include "common.h"
@@ -90,7 +103,178 @@ int edit_topk_impl(const float *vals_in, const IDX *idx_in, int T, int kk, const
   return msae_launch_status();
 }
 
+// ---- per-token tables -----------------------------------------------------------------------------------------------------
+constexpr int ET_ROWS_WAVES = 4;            // tokens per workgroup of the wave layout
+constexpr int ET_SCAN_MAX = 8;              // slices up to this length are scanned, longer ones searched
+
+// the token's slice of the edit arrays -> (first entry, length), both clamped: nothing read from the device is trusted
+__device__ __forceinline__ int edit_slice(const int32_t *__restrict__ group_of, const int32_t *__restrict__ group_off, size_t t,
+                                          int G, int E_total, int E_max, int &first) {
+  const int g = group_of[t];
+  first = 0;
+  if (g < 0 || g >= G) return 0;
+  const int a = min(max(group_off[g], 0), E_total), b = min(max(group_off[g + 1], 0), E_total);
+  first = a;
+  return min(max(b - a, 0), E_max);
+}
+
+// is f one of feat[0 .. E) (strictly ascending)?
+__device__ __forceinline__ bool edit_has(const int32_t *feat, int E, int f) {
+  if (E <= ET_SCAN_MAX) {
+    bool hit = false;
+    for (int e = 0; e < E; ++e) hit |= (feat[e] == f);
+    return hit;
+  }
+  return edit_find(feat, E, f) >= 0;
+}
+
+template <typename IDX>
+__device__ __forceinline__ void edit_copy_row(const float *__restrict__ vals_in, const IDX *__restrict__ idx_in, size_t t, int kk,
+                                              int k, float *__restrict__ vals, IDX *__restrict__ idx,
+                                              uint8_t *__restrict__ edited, int tid, int nt) {
+  for (int j = tid; j < k; j += nt) {
+    vals[t * k + j] = vals_in[t * kk + j];
+    idx[t * k + j] = idx_in[t * kk + j];
+    if (edited) edited[t * k + j] = 0;
+  }
+}
+
+template <typename IDX, int R>
+__global__ __launch_bounds__(ET_ROWS_WAVES * MSAE_WAVE) void edit_topk_rows_wave_kernel(
+    const float *__restrict__ vals_in, const IDX *__restrict__ idx_in, int T, int kk, const int32_t *__restrict__ group_of,
+    const int32_t *__restrict__ group_off, int G, const int32_t *__restrict__ edit_feat, const float *__restrict__ edit_val,
+    const int32_t *__restrict__ edit_kind, int E_total, int E_max, int k, float *__restrict__ vals, IDX *__restrict__ idx,
+    uint8_t *__restrict__ edited) {
+  const int lane = threadIdx.x & (MSAE_WAVE - 1);
+  const size_t t = (size_t)blockIdx.x * ET_ROWS_WAVES + (size_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / MSAE_WAVE));
+  if (t >= (size_t)T) return;                                       // (no barrier anywhere in this kernel)
+  int first;
+  const int E = __builtin_amdgcn_readfirstlane(edit_slice(group_of, group_off, t, G, E_total, E_max, first));
+  if (E == 0) {
+    edit_copy_row(vals_in, idx_in, t, kk, k, vals, idx, edited, lane, MSAE_WAVE);
+    return;
+  }
+  first = __builtin_amdgcn_readfirstlane(first);
+  const int32_t *feat = edit_feat + first;
+  const int L = k + E;                                              // k + 2 E <= 64 R: the host chose R for E_max
+  unsigned long long v[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int j = r * MSAE_WAVE + lane;
+    unsigned long long key = 0ull;
+    if (j < L) {
+      const int f = (int)idx_in[t * kk + j];
+      if (!edit_has(feat, E, f)) key = rank_key(vals_in[t * kk + j], f);
+    } else if (j < L + E) {
+      const int e = first + (j - L);
+      key = rank_key(edit_kind[e] == MSAE_EDIT_ZERO ? 0.f : edit_val[e], edit_feat[e]);
+    }
+    v[r] = key;
+  }
+  wave_sort_desc_u64_regs<R>(v, lane);
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int j = r * MSAE_WAVE + lane;
+    if (j < k) {
+      const int f = rank_key_index(v[r]);
+      vals[t * k + j] = rank_key_value(v[r]);
+      idx[t * k + j] = (IDX)f;
+      if (edited) edited[t * k + j] = edit_has(feat, E, f) ? 1 : 0;
+    }
+  }
+}
+
+template <typename IDX>
+__global__ __launch_bounds__(ET_MAX_THREADS) void edit_topk_rows_wg_kernel(
+    const float *__restrict__ vals_in, const IDX *__restrict__ idx_in, int kk, const int32_t *__restrict__ group_of,
+    const int32_t *__restrict__ group_off, int G, const int32_t *__restrict__ edit_feat, const float *__restrict__ edit_val,
+    const int32_t *__restrict__ edit_kind, int E_total, int E_max, int k, int n_sort, float *__restrict__ vals,
+    IDX *__restrict__ idx, uint8_t *__restrict__ edited) {
+  extern __shared__ __attribute__((aligned(16))) unsigned long long et_smem[];
+  unsigned long long *keys = et_smem;                               // [n_sort]
+  int32_t *feat = reinterpret_cast<int32_t *>(keys + n_sort);       // [E_max]
+  const size_t t = blockIdx.x;
+  int first;
+  const int E = edit_slice(group_of, group_off, t, G, E_total, E_max, first);   // uniform over the workgroup
+  if (E == 0) {
+    edit_copy_row(vals_in, idx_in, t, kk, k, vals, idx, edited, threadIdx.x, blockDim.x);
+    return;
+  }
+  const int L = k + E;
+  const int n = min(next_pow2(k + 2 * E), n_sort);                  // the token's own key count (E <= E_max: n <= n_sort)
+  for (int e = threadIdx.x; e < E; e += blockDim.x) feat[e] = edit_feat[first + e];
+  __syncthreads();
+  for (int j = threadIdx.x; j < n; j += blockDim.x) {
+    unsigned long long key = 0ull;
+    if (j < L) {
+      const int f = (int)idx_in[t * kk + j];
+      if (edit_find(feat, E, f) < 0) key = rank_key(vals_in[t * kk + j], f);
+    } else if (j < L + E) {
+      const int e = j - L;
+      key = rank_key(edit_kind[first + e] == MSAE_EDIT_ZERO ? 0.f : edit_val[first + e], feat[e]);
+    }
+    keys[j] = key;
+  }
+  bitonic_sort_desc_u64<0>(keys, n, threadIdx.x);
+  for (int j = threadIdx.x; j < k; j += blockDim.x) {
+    const unsigned long long key = keys[j];
+    const int f = rank_key_index(key);
+    vals[t * k + j] = rank_key_value(key);
+    idx[t * k + j] = (IDX)f;
+    if (edited) edited[t * k + j] = edit_find(feat, E, f) >= 0 ? 1 : 0;
+  }
+}
+
+template <typename IDX>
+int edit_topk_rows_impl(const float *vals_in, const IDX *idx_in, int T, int kk, const int32_t *group_of,
+                        const int32_t *group_off, int G, const int32_t *edit_feat, const float *edit_val,
+                        const int32_t *edit_kind, int E_total, int E_max, int N, int k, float *vals, IDX *idx, uint8_t *edited,
+                        void *stream) {
+  if (T < 0 || G < 1 || k < 1 || E_max < 1 || E_total < 0) return MSAE_EINVAL;
+  if ((long long)k + E_max > ET_MAX_SEL || (long long)k + E_max > N || kk < k + E_max) return MSAE_EINVAL;
+  if (!vals_in || !idx_in || !group_of || !group_off || !edit_feat || !edit_val || !edit_kind || !vals || !idx)
+    return MSAE_EINVAL;
+  if (T == 0) return 0;
+  const int n_sort = next_pow2(k + 2 * E_max);                      // <= 8192
+  hipStream_t st = (hipStream_t)stream;
+  if (n_sort <= 256) {
+    const dim3 grid((unsigned)(((long long)T + ET_ROWS_WAVES - 1) / ET_ROWS_WAVES)), block(ET_ROWS_WAVES * MSAE_WAVE);
+#define ET_ROWS_LAUNCH(R)                                                                                                 \
+  hipLaunchKernelGGL((edit_topk_rows_wave_kernel<IDX, R>), grid, block, 0, st, vals_in, idx_in, T, kk, group_of, group_off, G, \
+                     edit_feat, edit_val, edit_kind, E_total, E_max, k, vals, idx, edited)
+    if (n_sort <= 64) ET_ROWS_LAUNCH(1);
+    else if (n_sort <= 128) ET_ROWS_LAUNCH(2);
+    else ET_ROWS_LAUNCH(4);
+#undef ET_ROWS_LAUNCH
+    return msae_launch_status();
+  }
+  const int threads = std::min(ET_MAX_THREADS, std::max(MSAE_WAVE, n_sort / 2));
+  const size_t smem = (size_t)n_sort * sizeof(unsigned long long) + (size_t)E_max * sizeof(int32_t);
+  auto kern = edit_topk_rows_wg_kernel<IDX>;
+  if (smem > 64 * 1024)
+    MSAE_HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+  hipLaunchKernelGGL(kern, dim3(T), dim3(threads), smem, st, vals_in, idx_in, kk, group_of, group_off, G, edit_feat, edit_val,
+                     edit_kind, E_total, E_max, k, n_sort, vals, idx, edited);
+  return msae_launch_status();
+}
+
 }  // namespace
+
+extern "C" int msae_edit_topk_rows_f32(const float *vals_in, const int32_t *idx_in, int T, int kk, const int32_t *group_of,
+                                       const int32_t *group_off, int G, const int32_t *edit_feat, const float *edit_val,
+                                       const int32_t *edit_kind, int E_total, int E_max, int N, int k, float *vals,
+                                       int32_t *idx, uint8_t *edited, void *stream) {
+  return edit_topk_rows_impl<int32_t>(vals_in, idx_in, T, kk, group_of, group_off, G, edit_feat, edit_val, edit_kind, E_total,
+                                      E_max, N, k, vals, idx, edited, stream);
+}
+
+extern "C" int msae_edit_topk_rows_i64_f32(const float *vals_in, const int64_t *idx_in, int T, int kk, const int32_t *group_of,
+                                           const int32_t *group_off, int G, const int32_t *edit_feat, const float *edit_val,
+                                           const int32_t *edit_kind, int E_total, int E_max, int N, int k, float *vals,
+                                           int64_t *idx, uint8_t *edited, void *stream) {
+  return edit_topk_rows_impl<int64_t>(vals_in, idx_in, T, kk, group_of, group_off, G, edit_feat, edit_val, edit_kind, E_total,
+                                      E_max, N, k, vals, idx, edited, stream);
+}
 
 extern "C" int msae_edit_topk_f32(const float *vals_in, const int32_t *idx_in, int T, int kk, const int32_t *edit_feat,
                                   const float *edit_val, const int32_t *edit_kind, int E, int N, int k, float *vals,

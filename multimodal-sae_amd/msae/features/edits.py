@@ -141,13 +141,93 @@ class FeatureEdits:
         return f"FeatureEdits(num_latents={self.num_latents}, E={self.E}: {self.E - n_zero} set, {n_zero} zero)"
 
 
+class RowEdits:
+    """RowEdits(num_latents, groups, device="cuda") -- one edit table PER GROUP of tokens for one encode: B features steered
+    in the B rows of one `generate`, G ablations in the G copies of one attribution batch.
+
+    groups  a sequence; element g is a FeatureEdits, a dict(set=..., zero=...) spec (FeatureEdits' arguments and rules), or
+            None: an empty group, whose tokens stay unedited -- it keeps its index, so "row b uses group b" holds.
+    `Sae.encode(x, edits=RowEdits, edit_group=...)` names every token's group; an id outside [0, G) is unedited as well.
+
+    Everything host-side happens ONCE, here: each group's validation (FeatureEdits), the concatenation, the offsets and ONE
+    pinned upload of one int32 buffer.  Errors (ValueError): whatever FeatureEdits raises for a group, a group built for
+    another num_latents, an element of another type, no group at all, every group empty.
+
+    Attributes: G, E_max (the longest group), E_total, num_latents, device, tables (host copy: per group a
+    (features, values, kinds) triple of tuples, features ascending); the device arrays offsets int32 [G + 1], feat int32 / val f32 / kind int32 [E_total] that
+    ops.edit_topk_rows takes."""
+
+    def __init__(self, num_latents: int, groups, device: Union[str, torch.device] = "cuda"):
+        self.num_latents = int(num_latents)
+        if isinstance(groups, (FeatureEdits, Mapping)) or not hasattr(groups, "__len__"):
+            raise ValueError("RowEdits: groups must be a sequence of FeatureEdits, dict(set=..., zero=...) specs or None")
+        feats, vals, kinds, offsets = [], [], [], [0]
+        for g, spec in enumerate(groups):
+            if spec is None:
+                fe = None
+            elif isinstance(spec, FeatureEdits):
+                if spec.num_latents != self.num_latents:
+                    raise ValueError(f"RowEdits: group {g} was built for num_latents = {spec.num_latents}, not {self.num_latents}")
+                fe = spec
+            elif isinstance(spec, Mapping):
+                if not set(spec) <= {"set", "zero"}:
+                    raise ValueError(f"RowEdits: group {g}: a spec has the keys 'set' and 'zero', got {sorted(map(str, spec))}")
+                fe = FeatureEdits(self.num_latents, set=spec.get("set"), zero=spec.get("zero"), device="cpu")
+            else:
+                raise ValueError(f"RowEdits: group {g} must be a FeatureEdits, a dict(set=..., zero=...) or None, got "
+                                 f"{type(spec).__name__}")
+            if fe is not None:                      # host copies only: a FeatureEdits on the device is not read back
+                feats += fe.features
+                vals += fe.values
+                kinds += fe.kinds
+            offsets.append(len(feats))
+        self.G = len(offsets) - 1
+        if self.G < 1 or not feats:
+            raise ValueError("RowEdits: nothing to edit (no group, or every group is empty)")
+        self.E_total = len(feats)
+        self.E_max = max(b - a for a, b in zip(offsets[:-1], offsets[1:]))
+        self.tables = tuple((tuple(feats[a:b]), tuple(vals[a:b]), tuple(kinds[a:b])) for a, b in zip(offsets[:-1], offsets[1:]))
+        # one buffer, one copy: int32 [G + 1 + 3 E_total] = offsets, features, value bits, kinds
+        G1, E = self.G + 1, self.E_total
+        host = np.empty(G1 + 3 * E, dtype=np.int32)
+        host[:G1] = offsets
+        host[G1:G1 + E] = feats
+        host[G1 + E:G1 + 2 * E] = np.asarray(vals, dtype=np.float32).view(np.int32)
+        host[G1 + 2 * E:] = kinds
+        self.device = torch.device(device)
+        buf = torch.from_numpy(host)
+        if self.device.type == "cuda":
+            buf = buf.pin_memory().to(self.device, non_blocking=True)
+        self._buf = buf
+        self.offsets, self.feat, self.kind = buf[:G1], buf[G1:G1 + E], buf[G1 + 2 * E:]
+        self.val = buf[G1 + E:G1 + 2 * E].view(torch.float32)
+
+    def check(self, num_latents: int, k: int, device=None) -> None:
+        """Raise ValueError unless this object fits an encode of `num_latents` features selecting k."""
+        if self.num_latents != num_latents:
+            raise ValueError(f"RowEdits was built for num_latents = {self.num_latents}, the Sae has {num_latents}")
+        if k + self.E_max > min(num_latents, MAX_SELECTED):
+            raise ValueError(f"k + E_max = {k} + {self.E_max} exceeds min(num_latents, {MAX_SELECTED}) = "
+                             f"{min(num_latents, MAX_SELECTED)}")
+        if device is not None:
+            want, have = torch.device(device), self.feat.device
+            if want.type != have.type or (want.index is not None and have.index is not None and want.index != have.index):
+                raise ValueError(f"RowEdits lives on {have}, the encode runs on {want}")
+
+    def __len__(self) -> int:
+        return self.G
+
+    def __repr__(self) -> str:
+        return f"RowEdits(num_latents={self.num_latents}, G={self.G}, E_max={self.E_max}, E_total={self.E_total})"
+
+
 def as_off_features(off_features, sae) -> Tuple[int, Optional[FeatureEdits]]:
     """The attribution hooks' `off_features` (None, an int, a sequence or a tensor: what `mask[:, off_features] = 0`
     takes) -> (zero_feature for the in-kernel scalar route, or -1; FeatureEdits on `sae`'s device for the list route, or
     None).  `sae` is only looked at for a list: a feature-sharded engine takes the scalar route alone."""
     if off_features is None:
         return -1, None
-    if isinstance(off_features, FeatureEdits):
+    if isinstance(off_features, (FeatureEdits, RowEdits)):
         return -1, off_features
     if isinstance(off_features, (int, np.integer)) and not isinstance(off_features, bool):
         return int(off_features), None

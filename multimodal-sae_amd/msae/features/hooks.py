@@ -11,24 +11,34 @@ reference's indexing takes one -- goes through `FeatureEdits`: an over-fetching 
 """
 from __future__ import annotations
 
-from typing import Callable, Dict, Mapping, Optional
+from typing import Callable, Dict, Mapping, Optional, Sequence
 
 import torch
 from torch import Tensor
 
 from ..sae import Sae
-from .edits import FeatureEdits, as_off_features
+from .edits import FeatureEdits, RowEdits, as_off_features
 
 
 def sae_reconstruct(sae, hidden: Tensor, *, set_feature: int = -1, set_value: float = 0.0,
                     zero_feature: int = -1, out_dtype: Optional[torch.dtype] = None,
-                    differentiable: Optional[bool] = None, edits: Optional[FeatureEdits] = None) -> Tensor:
+                    differentiable: Optional[bool] = None, edits: Optional[FeatureEdits] = None,
+                    edit_group: Optional[Tensor] = None) -> Tensor:
     """[..., d] hidden states -> SAE reconstruction of the same shape.  `sae` is an `Sae` module or a
     feature-sharded engine (msae.parallel.ShardedSae over an N/G slice of the encoder per rank, SURVEY 8f rank 4:
     "N-sharded across 8 GPUs"; every rank must hold the same hidden states): same edits, by GLOBAL feature id, same
-    bits out.  `edits`: a set of edits instead of the scalar arguments (single-GPU `Sae` only)."""
+    bits out.  `edits`: a set of edits instead of the scalar arguments (single-GPU `Sae` only); with a `RowEdits`,
+    `edit_group` as in `Sae.encode` (None: row b of a [G, S, d] input uses group b)."""
     flat = hidden.reshape(-1, hidden.shape[-1])
-    if isinstance(sae, Sae):
+    if isinstance(edits, RowEdits) or edit_group is not None:
+        if not isinstance(sae, Sae):
+            raise NotImplementedError("per-row edits run on the single-GPU msae.Sae only: a feature-sharded engine takes "
+                                      "one feature")
+        # (the groups are resolved against the UNFLATTENED input: "row b uses group b" is a statement about [G, S, d])
+        top = sae.encode(hidden, differentiable=differentiable, edits=edits, edit_group=edit_group)
+        k = top.top_acts.shape[-1]
+        out = sae.decode(top.top_acts.reshape(-1, k), top.top_indices.reshape(-1, k))
+    elif isinstance(sae, Sae):
         top = sae.encode(flat, set_feature=set_feature, set_value=set_value, zero_feature=zero_feature,
                          differentiable=differentiable, edits=edits)
         out = sae.decode(top.top_acts, top.top_indices)
@@ -77,7 +87,8 @@ class _DecodeStepGraph:
                 ops._defaults.coarse, ops._defaults.guard_z, ops._defaults.exact, getattr(ops._defaults, "certified", False))
 
     def __call__(self, sae, h: Tensor) -> Optional[Tensor]:
-        """h [1, d] -> fp16 reconstruction [1, d] (a fresh tensor), or None: take the eager path."""
+        """h [B, d] (B = 1: clamp_features_max; one step of B rows: clamp_features_rows) -> fp16 reconstruction [B, d] (a
+        fresh tensor), or None: take the eager path.  The key holds the shape: another B is another capture."""
         if self.failed or torch.cuda.is_current_stream_capturing():
             return None
         key = self._key(sae, h)
@@ -163,10 +174,63 @@ def clamp_features_max(sae, feature, hooked_module: torch.nn.Module, k: float = 
     return [handle]
 
 
+def _row_spec(element, k: float):
+    """One element of clamp_features_rows' `features` -> a RowEdits group (None, a FeatureEdits or a dict spec)."""
+    if element is None or isinstance(element, FeatureEdits):
+        return element
+    if isinstance(element, Mapping):
+        return {"set": element}
+    if isinstance(element, Tensor):
+        element = element.reshape(-1).tolist()
+    if isinstance(element, (list, tuple, range)):
+        return {"set": {int(f): float(k) for f in element}} if len(element) else None
+    return {"set": {int(element): float(k)}}
+
+
+def clamp_features_rows(sae, features: Sequence, hooked_module: torch.nn.Module, k: float = 10,
+                        graph_step: Optional[bool] = None):
+    """The steering hook for a BATCH whose rows steer different features: `features` has one element
+    per batch row -- an int, a list of ints (all clamped to `k`), a mapping feature -> value, or None for an unedited row
+    (the batch's baseline).  On prefill (S != 1) row b's latents are clamped per element b before TopK; every call replaces
+    the whole [B, S, d] layer output by the fp16 reconstruction.  The tables are validated and uploaded once, here, as a
+    RowEdits.  The S = 1 step of the batch ([B, 1, d], no edit) replays from a captured HIP graph like clamp_features_max's
+    (`graph_step`: default on under no_grad unless MSAE_HOOK_GRAPH=0).  Single-GPU `Sae` only.  The prefill's batch size
+    must equal len(features) (ValueError)."""
+    import os
+
+    if not isinstance(sae, Sae):
+        raise NotImplementedError("clamp_features_rows runs on the single-GPU msae.Sae only: a feature-sharded engine takes "
+                                  "one feature (clamp_features_max)")
+    if isinstance(features, (Mapping, Tensor, str)) or not hasattr(features, "__len__"):
+        raise ValueError("clamp_features_rows: features must be a sequence with one element per batch row")
+    if graph_step is None:
+        graph_step = os.environ.get("MSAE_HOOK_GRAPH", "1") not in ("0", "")
+    step_graph = _DecodeStepGraph() if graph_step else None
+    edits = RowEdits(sae.num_latents, [_row_spec(f, k) for f in features], device=sae.device)
+
+    def hook(module, _, outputs):
+        h = outputs[0] if isinstance(outputs, tuple) else outputs
+        if h.shape[1] != 1:
+            if h.shape[0] != edits.G:
+                raise ValueError(f"clamp_features_rows: {edits.G} rows of features, a batch of {h.shape[0]}")
+            return _replace_first(outputs, sae_reconstruct(sae, h, out_dtype=torch.float16, edits=edits))
+        if step_graph is not None and h.is_cuda and not torch.is_grad_enabled() and not sae.training:
+            out = step_graph(sae, h[:, 0])
+            if out is not None:
+                return _replace_first(outputs, out.unsqueeze(1))
+        return _replace_first(outputs, sae_reconstruct(sae, h, out_dtype=torch.float16))
+
+    handle = hooked_module.register_forward_hook(hook)
+    handle.step_graph = step_graph          # (diagnostics / tests: the captured S = 1 step, or None)
+    handle.edits = edits
+    return [handle]
+
+
 def attribution_sae_hook(sae_dict: Dict[str, Sae], module_to_name: Dict[torch.nn.Module, str],
-                         cache: Dict[str, Tensor], off_features=None) -> Callable:
+                         cache: Dict[str, Tensor], off_features=None, edit_group: Optional[Tensor] = None) -> Callable:
     """Hook body of get_model_forward_cache_with_sae (patching/utils.py:33-58).  `off_features`: None, an int, or a
-    sequence / tensor of ints (`mask[:, off_features] = 0` takes any of them)."""
+    sequence / tensor of ints (`mask[:, off_features] = 0` takes any of them); or a RowEdits with `edit_group` as in
+    `Sae.encode`: another ablation per batch row."""
     per_module: dict = {}         # a list of features becomes one FeatureEdits per hooked Sae, built at its first call
 
     def hook(module, inputs, outputs):
@@ -176,7 +240,7 @@ def attribution_sae_hook(sae_dict: Dict[str, Sae], module_to_name: Dict[torch.nn
         if name not in per_module:
             per_module[name] = as_off_features(off_features, sae)
         zero, edits = per_module[name]
-        out = sae_reconstruct(sae, h, zero_feature=zero, edits=edits,
+        out = sae_reconstruct(sae, h, zero_feature=zero, edits=edits, edit_group=edit_group,
                               out_dtype=torch.float16, differentiable=torch.is_grad_enabled())
         cache[name] = out
         return _replace_first(outputs, out)

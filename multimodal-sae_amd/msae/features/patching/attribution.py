@@ -96,11 +96,16 @@ class Attribution:
         sae = next(iter(self.sae_dict.values()))
         return torch.arange(sae.num_latents)      # (the reference reads a misspelt cfg field here, attribution.py:121)
 
-    def get_attribution(self, indices: Union[List[int], Tensor, None] = None, method: str = "exact"):
+    def get_attribution(self, indices: Union[List[int], Tensor, None] = None, method: str = "exact",
+                        features_per_pass: int = 1):
         """-> {module name: [fp16 CPU tensor [B, S] per requested feature]} (attribution.py:116-189).  With
         method="exact" an element of `indices` may itself be a list of features: the group is ablated together
         (`mask[:, off_features] = 0` with a list) and yields one result; "batched" linearises per feature and takes
-        plain indices only."""
+        plain indices only.  `features_per_pass` = G > 1 (method="exact"): the batch is repeated G times and copy g
+        ablates entry g of a chunk of G entries through one RowEdits -- ONE forward + backward of the LLM per G entries
+        instead of one per entry; same structure of results."""
+        if int(features_per_pass) < 1:
+            raise ValueError(f"features_per_pass must be >= 1, got {features_per_pass}")
         if indices is None:
             indices = self._default_indices()
         indices = [[int(j) for j in i] if isinstance(i, (list, tuple)) else int(i)
@@ -110,6 +115,8 @@ class Attribution:
                              "ablate a group of features with method='exact'")
         if method == "batched":
             out = self._batched(indices)
+        elif method == "exact" and int(features_per_pass) > 1:
+            out = self._per_feature_rows(indices, int(features_per_pass))
         elif method == "exact":
             out = self._per_feature(indices)
         else:
@@ -132,6 +139,49 @@ class Attribution:
             for name in self.sae_dict.keys():
                 attribution = (clean_cache[name] - corrupted_cache[name]) * corrupted_cache[name].grad
                 attribution_dict[name].append(attribution.detach().sum(dim=-1).cpu())
+            self._zero_param_grads()
+        return attribution_dict
+
+    def _repeated_inputs(self, G: int) -> dict:
+        """The model's inputs with the batch repeated G times: copy g holds the rows [g B, (g + 1) B)."""
+        out = {}
+        for key, v in self.inputs.items():
+            if isinstance(v, Tensor):
+                out[key] = v.repeat(G, *([1] * (v.dim() - 1)))
+            elif isinstance(v, (list, tuple)):
+                out[key] = type(v)(list(v) * G)
+            else:
+                out[key] = v
+        return out
+
+    def _per_feature_rows(self, indices: list, G: int):
+        """The exact loop with G entries per pass: the batch repeated G times, copy g ablating entry g (a RowEdits of ZERO
+        groups, one per copy), one forward + backward per chunk.  The metric is a mean over the G B rows, so it is multiplied
+        by G: each copy's gradient then equals its own unbatched run's.  A short last chunk leaves its spare copies unedited."""
+        from ..edits import RowEdits
+
+        attribution_dict = collections.defaultdict(list)
+        sae0 = next(iter(self.sae_dict.values()))
+        dev = sae0.device
+        B = self.answer_ids.shape[0]
+        inputs = self._repeated_inputs(G)
+        answers = self.answer_ids.repeat(G, 1)
+        row_group = torch.arange(G, device=dev, dtype=torch.int32).repeat_interleave(B)      # batch row -> its copy
+        with torch.no_grad():    # the clean run, once, on the same repeated batch
+            _, clean_cache = get_model_forward_cache_with_sae(self.model, inputs, self.sae_dict, self.module_to_name)
+        for lo in range(0, len(indices), G):
+            chunk = indices[lo:lo + G]
+            groups = [dict(zero=e if isinstance(e, list) else [e]) for e in chunk] + [None] * (G - len(chunk))
+            edits = RowEdits(sae0.num_latents, groups, device=dev)
+            logits, cache = get_model_forward_cache_with_sae(self.model, inputs, self.sae_dict, self.module_to_name,
+                                                             off_features=edits, edit_group=row_group)
+            for tensor in cache.values():
+                tensor.retain_grad()
+            (G * get_logit_diff(logits, answers)).backward()
+            for name in self.sae_dict.keys():
+                attribution = ((clean_cache[name] - cache[name]) * cache[name].grad).detach().sum(dim=-1)
+                for g in range(len(chunk)):
+                    attribution_dict[name].append(attribution[g * B:(g + 1) * B].cpu())
             self._zero_param_grads()
         return attribution_dict
 

@@ -20,7 +20,7 @@ import torch
 from torch import Tensor
 
 from ...sae import Sae
-from ..edits import as_off_features
+from ..edits import RowEdits, as_off_features
 
 
 def get_logit_diff(logits: Tensor, answer_token_indices: Tensor) -> Tensor:
@@ -34,10 +34,13 @@ def get_logit_diff(logits: Tensor, answer_token_indices: Tensor) -> Tensor:
 
 def sae_splice_hook(sae_dict: Dict[str, Sae], module_to_name: Dict[torch.nn.Module, str],
                     cache: Dict[str, Tensor], off_features=None,
-                    keep_latents: Optional[Dict[str, Tuple[Tensor, Tensor]]] = None, extra_k: int = 0) -> Callable:
+                    keep_latents: Optional[Dict[str, Tuple[Tensor, Tensor]]] = None, extra_k: int = 0,
+                    edit_group: Optional[Tensor] = None) -> Callable:
     """Forward-hook body of get_model_forward_cache_with_sae (utils.py:33-58).  `off_features`: None, an int (the edit
     inside the fused kernel), or a sequence / tensor of ints as `mask[:, off_features] = 0` takes (one FeatureEdits per
-    hooked Sae, built at its first call: over-fetching encode + list edit).  `keep_latents`
+    hooked Sae, built at its first call: over-fetching encode + list edit); or a
+    msae.features.RowEdits with `edit_group` as in `Sae.encode` (None: batch row b uses group b) -- another ablation per
+    batch row in one forward (section 7g; not with `extra_k`).  `keep_latents`
     (optional) receives the (top_acts, top_indices) of every hooked module -- the batched
     attribution needs them; `extra_k` asks the encoder for that many latents beyond k (the
     reconstruction still uses the first k)."""
@@ -53,6 +56,13 @@ def sae_splice_hook(sae_dict: Dict[str, Sae], module_to_name: Dict[torch.nn.Modu
         if name not in per_module:
             per_module[name] = as_off_features(off_features, sae)
         zero, edits = per_module[name]
+        rows = isinstance(edits, RowEdits)
+        if edit_group is not None and not rows:
+            raise ValueError("sae_splice_hook: edit_group goes with a msae.features.RowEdits in off_features")
+        if rows and extra_k:
+            raise ValueError("sae_splice_hook: extra_k is not available with a RowEdits")
+        # the groups are resolved against [B, S, d] ("row b uses group b"), then flattened with the tokens
+        groups = sae._token_groups(unpacked[0], edits, edit_group).reshape(-1) if rows else None
         if extra_k:
             from ... import ops
 
@@ -69,7 +79,7 @@ def sae_splice_hook(sae_dict: Dict[str, Sae], module_to_name: Dict[torch.nn.Modu
                 keep_latents[name] = (va, ia)
         # the reference's graph is differentiable wherever autograd is on (the SAE's parameters require grad even under
         # a frozen LLM): keep that, rather than Sae.encode's default of following x.requires_grad
-        top = sae.encode(flat, zero_feature=zero, edits=edits, differentiable=torch.is_grad_enabled())
+        top = sae.encode(flat, zero_feature=zero, edits=edits, edit_group=groups, differentiable=torch.is_grad_enabled())
         if keep_latents is not None and not extra_k:
             keep_latents[name] = (top.top_acts.detach(), top.top_indices)
         sae_out = sae.decode(top.top_acts, top.top_indices).to(torch.float16).view(bs, seq_len, dim)
@@ -83,12 +93,13 @@ def sae_splice_hook(sae_dict: Dict[str, Sae], module_to_name: Dict[torch.nn.Modu
 
 def get_model_forward_cache_with_sae(model: torch.nn.Module, inputs: Dict[str, Any], sae_dict: Dict[str, Sae],
                                      module_to_name: Dict[torch.nn.Module, str], off_features=None,
-                                     keep_latents: Optional[dict] = None, extra_k: int = 0):
+                                     keep_latents: Optional[dict] = None, extra_k: int = 0,
+                                     edit_group: Optional[Tensor] = None):
     """Run the model with every hooked module's output replaced by its SAE reconstruction.
-    `off_features`: None, an int, or a sequence / tensor of features zeroed together.
+    `off_features`: None, an int, or a sequence / tensor of features zeroed together; or a RowEdits (+ `edit_group`).
     -> (logits, {module name: fp16 reconstruction [B, S, d]})   (utils.py:21-71)."""
     cache: Dict[str, Tensor] = {}
-    hook = sae_splice_hook(sae_dict, module_to_name, cache, off_features, keep_latents, extra_k)
+    hook = sae_splice_hook(sae_dict, module_to_name, cache, off_features, keep_latents, extra_k, edit_group)
     handles = [mod.register_forward_hook(hook) for mod in module_to_name.keys()]
     try:
         outputs = model(**inputs)

@@ -30,7 +30,15 @@ def parse_argument(argv=None):
                         "(the latency mode for wide SAEs); results are identical")
     p.add_argument("--shard-mode", default="topk", choices=["topk", "candidates"],
                    help="exchange scheme of --shard-sae (msae.parallel.ShardedSae)")
-    return p.parse_args(argv)
+    p.add_argument("--batch-features", "--batch_features", type=int, default=1,
+                   help="(new) steer this many features in the rows of ONE generate (another clamp per batch row); "
+                        "1 = the reference's loop.  Same output file.  Not with --shard-sae")
+    args = p.parse_args(argv)
+    if args.batch_features < 1:
+        p.error("--batch-features must be >= 1")
+    if args.batch_features > 1 and args.shard_sae:
+        p.error("--batch-features > 1 runs on the single-GPU Sae: it cannot be combined with --shard-sae")
+    return args
 
 
 def main(argv=None):
@@ -56,7 +64,8 @@ def main(argv=None):
             feature_idx = (feats.tensor_split(world)[rank] if ddp else feats).cpu().tolist()
         result = SteeringController(sae=engine, module_name=module_name, feature_idx=feature_idx,
                                     prompt=args.text, model=model, processor=processor,
-                                    image_path=args.image_path, k=args.clamp_value).run()
+                                    image_path=args.image_path, k=args.clamp_value,
+                                    batch_features=args.batch_features).run()
         if ddp and not shard:
             gathered = [None] * world
             dist.gather_object(result, gathered if rank == 0 else None, dst=0)

@@ -925,6 +925,78 @@ def edit_topk(vals_in: Tensor, idx_in: Tensor, edit_feat: Tensor, edit_val: Tens
     return _edit_topk(vals_in, idx_in, edit_feat, edit_val, edit_kind, num_latents, k)
 
 
+# ---- the same with one edit table per token (msae_edit_topk_rows_*) ------------------------------------
+@torch.library.custom_op("msae::edit_topk_rows", mutates_args=())
+def _edit_topk_rows(vals_in: Tensor, idx_in: Tensor, group_of: Tensor, group_off: Tensor, edit_feat: Tensor,
+                    edit_val: Tensor, edit_kind: Tensor, e_max: int, num_latents: int, k: int,
+                    want_mask: bool) -> Tuple[Tensor, Tensor, Tensor]:
+    dev = _hip.require_device(vals_in, idx_in, group_of, group_off, edit_feat, edit_val, edit_kind)
+    lib = _hip.load()
+    assert vals_in.shape == idx_in.shape and vals_in.dim() >= 1, \
+        f"vals_in and idx_in must share a shape [..., kk], got {tuple(vals_in.shape)} and {tuple(idx_in.shape)}"
+    assert idx_in.dtype in (torch.int32, torch.int64), f"idx_in must be int32 or int64, got {idx_in.dtype}"
+    E_total, kk, G = edit_feat.numel(), vals_in.shape[-1], group_off.numel() - 1
+    assert edit_val.numel() == E_total and edit_kind.numel() == E_total, "the edit table's three arrays must have one length"
+    v_in = _f32c(vals_in)
+    i_in = idx_in.detach().contiguous()
+    T = v_in.numel() // max(kk, 1)
+    assert group_of.numel() == T, f"group_of must hold one id per token ({T}), got {tuple(group_of.shape)}"
+    go = group_of.detach()
+    if go.dtype != torch.int32:         # an id beyond int32 must stay outside [0, G): clamp on the device, then narrow
+        go = go.clamp(-1, G).to(torch.int32)
+    go = go.contiguous()
+    gf = group_off.detach().to(torch.int32).contiguous()
+    ef = edit_feat.detach().to(torch.int32).contiguous()
+    ev = _f32c(edit_val)
+    ek = edit_kind.detach().to(torch.int32).contiguous()
+    vals = torch.empty(*v_in.shape[:-1], k, dtype=torch.float32, device=dev)
+    idx = torch.empty(*v_in.shape[:-1], k, dtype=i_in.dtype, device=dev)
+    edited = torch.empty(*v_in.shape[:-1], k if want_mask else 0, dtype=torch.uint8, device=dev)
+    wide = i_in.dtype == torch.int64
+    fn, name = (lib.msae_edit_topk_rows_i64_f32, "msae_edit_topk_rows_i64_f32") if wide else \
+        (lib.msae_edit_topk_rows_f32, "msae_edit_topk_rows_f32")
+    with torch.cuda.device(dev):
+        _hip.check(fn(_hip.ptr(v_in), _hip.ptr(i_in), T, kk, _hip.ptr(go), _hip.ptr(gf), G, _hip.ptr(ef), _hip.ptr(ev),
+                      _hip.ptr(ek), E_total, e_max, num_latents, k, _hip.ptr(vals), _hip.ptr(idx),
+                      _hip.ptr(edited) if want_mask else None, _hip.stream_of(v_in)), name)
+    return vals, idx, edited
+
+
+@_edit_topk_rows.register_fake
+def _(vals_in, idx_in, group_of, group_off, edit_feat, edit_val, edit_kind, e_max, num_latents, k, want_mask):
+    return (vals_in.new_empty(*vals_in.shape[:-1], k, dtype=torch.float32),
+            idx_in.new_empty(*idx_in.shape[:-1], k),
+            vals_in.new_empty(*vals_in.shape[:-1], k if want_mask else 0, dtype=torch.uint8))
+
+
+def edit_topk_rows(vals_in: Tensor, idx_in: Tensor, group_of: Tensor, row_edits, num_latents: int, k: int,
+                   want_mask: bool = False):
+    """`edit_topk` with one edit table PER TOKEN -> (vals f32 [..., k], idx [..., k] in idx_in's dtype[, edited uint8
+    [..., k]]).  vals_in / idx_in [..., kk]: encode_topk's output for kk >= k + E_max without edits; group_of int32 / int64
+    [...]: the group of every token, any id outside [0, G) = unedited (the first k entries are copied); row_edits: a
+    msae.features.RowEdits (offsets [G + 1], feat / val / kind [E_total], E_max).  `edited` (want_mask=True): 1 where the slot
+    came from an edit entry.  Exact per token: include/msae.h, "per-token edit tables".  Nothing is read back; the arguments
+    the library would refuse raise ValueError here."""
+    kk, e_max, G = vals_in.shape[-1], int(row_edits.E_max), int(row_edits.G)
+    if G < 1 or e_max < 1 or k < 1 or kk < k + e_max or k + e_max > min(num_latents, EDIT_TOPK_MAX_SELECTED):
+        raise ValueError(f"edit_topk_rows: need G >= 1, E_max >= 1, k >= 1, kk >= k + E_max and k + E_max <= min(num_latents, "
+                         f"{EDIT_TOPK_MAX_SELECTED}); got kk = {kk}, k = {k}, E_max = {e_max}, G = {G}, "
+                         f"num_latents = {num_latents}")
+    if vals_in.shape != idx_in.shape:
+        raise ValueError(f"edit_topk_rows: vals_in {tuple(vals_in.shape)} and idx_in {tuple(idx_in.shape)} must share a shape")
+    if idx_in.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"edit_topk_rows: idx_in must be int32 or int64, got {idx_in.dtype}")
+    if not isinstance(group_of, Tensor) or group_of.dtype not in (torch.int32, torch.int64):
+        raise ValueError("edit_topk_rows: group_of must be an int32 or int64 tensor")
+    if tuple(group_of.shape) != tuple(vals_in.shape[:-1]):
+        raise ValueError(f"edit_topk_rows: group_of must have one id per token, shape {tuple(vals_in.shape[:-1])}, got "
+                         f"{tuple(group_of.shape)}")
+    _no_grad_inputs("ops.edit_topk_rows", vals_in, row_edits.val)
+    vals, idx, edited = _edit_topk_rows(vals_in, idx_in, group_of, row_edits.offsets, row_edits.feat, row_edits.val,
+                                        row_edits.kind, e_max, num_latents, k, want_mask)
+    return (vals, idx, edited) if want_mask else (vals, idx)
+
+
 def shard_candidates(x: Tensor, b_enc_shard: Optional[Tensor], b_dec: Optional[Tensor], prepared_shard: Tensor,
                      N_shard: int, k: int, row_offset: int, C: int, set_feature: int = -1,
                      zero_feature: int = -1) -> Tensor:
@@ -1217,11 +1289,21 @@ class _SparseEncode(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, W_enc, b_enc, b_dec, k, dead_mask, k_aux, k_multi, prepared=None, set_feature=-1,
-                set_value=0.0, zero_feature=-1, edit_set=None, auxk_path="dense", dead_list=None):
+                set_value=0.0, zero_feature=-1, edit_set=None, auxk_path="dense", dead_list=None, edit_group=None):
         vals, idxs = [], []
         edits = set_feature >= 0 or zero_feature >= 0 or edit_set is not None
         assert not (edits and (k_aux > 0 or k_multi > 0)), "hook edits apply to the plain top-k only"
-        if edit_set is not None:
+        row_mask = None
+        if edit_set is not None and edit_group is not None:
+            # one table per token (msae.features.RowEdits + the tokens' group ids): the same two steps, and the kernel says
+            # which output slots hold an edit's own value -- a feature-wide mask is wrong once the tables differ per token
+            assert set_feature < 0 and zero_feature < 0, "edits= and the scalar edit arguments are mutually exclusive"
+            v, i, _ = encode_topk(x, W_enc, b_enc, b_dec,
+                                  prepared if prepared is not None else _refresh_train_operands(W_enc, x.shape[0]),
+                                  k + edit_set.E_max)
+            v, i, row_mask = edit_topk_rows(v, i, edit_group, edit_set, W_enc.shape[0], k, want_mask=True)
+            vals.append(v); idxs.append(i)
+        elif edit_set is not None:
             # a SET of edits (msae.features.FeatureEdits): the unedited encode over-fetches k + E entries, edit_topk re-ranks
             # each list with the edits applied (exact: DESIGN.md section 7d) -- the same two steps as the inference path
             assert set_feature < 0 and zero_feature < 0, "edits= and the scalar edit arguments are mutually exclusive"
@@ -1272,7 +1354,8 @@ class _SparseEncode(torch.autograd.Function):
         ctx.save_for_backward(x, W_enc, b_dec, torch.cat(idxs, -1), torch.cat(vals, -1))
         ctx.splits = [t.shape[-1] for t in vals]
         ctx.set_feature = set_feature
-        ctx.edit_mask = None if edit_set is None else edit_set.mask
+        ctx.edit_mask = None if edit_set is None or row_mask is not None else edit_set.mask
+        ctx.row_mask = row_mask
         ctx.has_b_enc = b_enc is not None
         out = []
         for v, i in zip(vals, idxs):
@@ -1291,6 +1374,8 @@ class _SparseEncode(torch.autograd.Function):
             g_cat = g_cat * (idx_cat != ctx.set_feature)
         if ctx.edit_mask is not None:                              # ... and neither does one of a set of edited latents
             g_cat = g_cat * ~ctx.edit_mask[idx_cat]
+        if ctx.row_mask is not None:                               # ... per token: the slots that came from an edit entry
+            g_cat = g_cat * ~ctx.row_mask.bool()
         a = x.float() - b_dec
         need_x, need_W, need_be, need_bd = ctx.needs_input_grad[:4]
         g_x = g_W = g_be = g_bd = None
@@ -1314,17 +1399,19 @@ class _SparseEncode(torch.autograd.Function):
             da = decode(idx_cat, g_cat, W_enc, None)
             g_x = da.to(x.dtype) if need_x else None
             g_bd = -da.sum(0) if need_bd else None
-        return g_x, g_W, g_be, g_bd, None, None, None, None, None, None, None, None, None, None, None
+        return g_x, g_W, g_be, g_bd, None, None, None, None, None, None, None, None, None, None, None, None
 
 
 def sparse_encode(x: Tensor, W_enc: Tensor, b_enc: Tensor, b_dec: Tensor, k: int,
                   dead_mask: Optional[Tensor] = None, k_aux: int = 0, k_multi: int = 0, *,
                   prepared: Optional[Tensor] = None, set_feature: int = -1, set_value: float = 0.0,
-                  zero_feature: int = -1, edits=None, auxk_path: str = "dense", dead_list: Optional[Tensor] = None):
+                  zero_feature: int = -1, edits=None, auxk_path: str = "dense", dead_list: Optional[Tensor] = None,
+                  edit_group: Optional[Tensor] = None):
     """-> [(acts, idx)] for the top-k, (optional) AuxK and (optional) Multi-TopK selections.
     Differentiable w.r.t. x, W_enc, b_enc, b_dec through the selected latents (the graph of the
     reference's pre_acts -> [mask] -> topk, sae.py:172-185, patching/utils.py:43-49).  `edits`: a
-    msae.features.FeatureEdits instead of the scalar edit arguments; an edited latent carries no gradient.
+    msae.features.FeatureEdits instead of the scalar edit arguments; an edited latent carries no gradient.  A
+    msae.features.RowEdits comes with `edit_group` (int tensor x.shape[:-1]: every token's group): the same per token.
     auxk_path: "dense" (pre_acts + three top-k over [T, N]) or "subset": with k_aux > 0 and max(k, k_multi) <= 256 the AuxK
     selection comes from `topk_within` over the dead features (dead_list: their ascending int32 device list, built from
     dead_mask when None) and the other two from the fused encoder -- the same selections bit for bit; in every other case
@@ -1332,8 +1419,15 @@ def sparse_encode(x: Tensor, W_enc: Tensor, b_enc: Tensor, b_dec: Tensor, k: int
     if auxk_path not in AUXK_PATHS:
         raise ValueError(f"auxk_path must be one of {AUXK_PATHS}, got {auxk_path!r}")
     lead = x.shape[:-1]
+    if (edit_group is not None) != hasattr(edits, "offsets"):
+        raise ValueError("sparse_encode: edit_group goes with a msae.features.RowEdits, and a RowEdits needs it")
+    if edit_group is not None:
+        if tuple(edit_group.shape) != tuple(lead):
+            raise ValueError(f"sparse_encode: edit_group must have shape {tuple(lead)}, got {tuple(edit_group.shape)}")
+        edit_group = edit_group.reshape(-1)
     out = _SparseEncode.apply(x.reshape(-1, x.shape[-1]), W_enc, b_enc, b_dec, k, dead_mask, k_aux, k_multi, prepared,
-                              set_feature, float(set_value), zero_feature, edits, auxk_path, dead_list)  # the node works on [T, d]
+                              set_feature, float(set_value), zero_feature, edits, auxk_path, dead_list,
+                              edit_group)                              # the node works on [T, d]
     if len(lead) != 1:
         out = tuple(o.reshape(*lead, o.shape[-1]) for o in out)
     return [(out[2 * j], out[2 * j + 1]) for j in range(len(out) // 2)]

@@ -358,11 +358,12 @@ class ShardedSae:
 
         return join, (vals[: hi - lo], idx[: hi - lo]), pack
 
-    def encode(self, x: Tensor, set_feature: int = -1, set_value: float = 0.0, zero_feature: int = -1, edits=None):
+    def encode(self, x: Tensor, set_feature: int = -1, set_value: float = 0.0, zero_feature: int = -1, edits=None,
+               edit_group=None):
         """-> (top_acts [T,k] f32, top_indices [T,k] int64 GLOBAL feature ids, status [T]).  The optional edits are
         the hooks' (`latents[:, set_feature] = set_value`, `latents[:, zero_feature] = 0` before the TopK), by global
         feature id.  A SET of edits (`edits=`, msae.features.FeatureEdits) is not implemented on sharded engines."""
-        if edits is not None:
+        if edits is not None or edit_group is not None:   # FeatureEdits, or RowEdits with its per-token groups
             raise NotImplementedError("edits= (a set of edited features) runs on the single-GPU msae.Sae only: a feature-sharded "
                                       "engine takes the scalar set_feature / zero_feature arguments")
         ed = {}
@@ -599,8 +600,9 @@ class EmulatedShardGroup:
         self.mode, self.world = mode, world
         self._second_round = None
 
-    def encode(self, x: Tensor, set_feature: int = -1, set_value: float = 0.0, zero_feature: int = -1, edits=None):
-        if edits is not None:
+    def encode(self, x: Tensor, set_feature: int = -1, set_value: float = 0.0, zero_feature: int = -1, edits=None,
+               edit_group=None):
+        if edits is not None or edit_group is not None:   # FeatureEdits, or RowEdits with its per-token groups
             raise NotImplementedError("edits= (a set of edited features) runs on the single-GPU msae.Sae only: a feature-sharded "
                                       "engine takes the scalar set_feature / zero_feature arguments")
         ed = {}

@@ -217,13 +217,19 @@ class Sae(nn.Module):
 
     def encode(self, x: Tensor, *, set_feature: int = -1, set_value: float = 0.0,
                zero_feature: int = -1, return_status: bool = False, resolve: bool = True,
-               differentiable: Optional[bool] = None, exact: bool = False, certified: bool = False, edits=None):
+               differentiable: Optional[bool] = None, exact: bool = False, certified: bool = False, edits=None,
+               edit_group: Optional[Tensor] = None):
         """Fused encode + TopK (sae.py:183-185).  `set_feature/set_value` and `zero_feature` apply
         the steering / attribution hooks' edits of the dense latents (steering.py:113-114,
         patching/utils.py:43-48) inside the kernel, before TopK.  `edits` (a msae.features.FeatureEdits) applies a SET of
         such edits -- the reference's indexing takes a list or tensor of features: the unedited encode over-fetches
         k + E entries per token and ops.edit_topk re-ranks each list with the edits applied; exact, bit-identical to the
         scalar arguments for E = 1.  It is mutually exclusive with the scalar arguments (ValueError).
+        A msae.features.RowEdits holds one table per GROUP and `edit_group` names every token's group: an
+        int32 / int64 device tensor of shape x.shape[:-1], or for a 3-d x of shape x.shape[:1] (per batch row, expanded on the
+        device), or None: row b of a 3-d x with x.shape[0] == G uses group b.  A token whose id lies outside [0, G) (-1 by
+        convention) or whose group is empty comes out as the plain encode's.  `edit_group` with anything but a RowEdits is a
+        ValueError.
 
         The kernel verifies every token and recomputes the ones it cannot verify (degenerate
         activations: all-zero rows, fewer than k positive latents, tokens the error model of the
@@ -244,6 +250,12 @@ class Sae(nn.Module):
             if set_feature >= 0 or zero_feature >= 0:
                 raise ValueError("Sae.encode: pass either edits= or the scalar set_feature / zero_feature arguments, not both")
             edits.check(self.num_latents, self.cfg.k, self.encoder.weight.device)
+        rows = edits is not None and hasattr(edits, "offsets")        # a RowEdits: one table per token
+        if edit_group is not None and not rows:
+            raise ValueError("Sae.encode: edit_group names the groups of a msae.features.RowEdits; it does not go with a "
+                             "FeatureEdits or with the scalar set_feature / zero_feature arguments")
+        if rows:
+            edit_group = self._token_groups(x, edits, edit_group)
         if differentiable is None:
             params = self.encoder.weight.requires_grad or self.encoder.bias.requires_grad or self.b_dec.requires_grad
             differentiable = x.requires_grad or (self.training and params and not (exact or certified or return_status))
@@ -259,10 +271,16 @@ class Sae(nn.Module):
             # same kernel, as one autograd node with the sparse backward
             (acts, idx), = ops.sparse_encode(x, self.encoder.weight, self.encoder.bias, self.b_dec, self.cfg.k,
                                              prepared=self._prepared_weights(), set_feature=set_feature,
-                                             set_value=set_value, zero_feature=zero_feature, edits=edits)
+                                             set_value=set_value, zero_feature=zero_feature, edits=edits,
+                                             edit_group=edit_group)
             return EncoderOutput(acts, idx)
         with torch.no_grad():      # (a custom op without an autograd formula would hang a raising node on the outputs)
-            if edits is not None:  # over-fetch, then edit: `exact` / `certified` only change the first call
+            if rows:               # the same two steps with the table of every token's own group
+                acts, idx, status = ops.encode_topk(x, self.encoder.weight, self.encoder.bias, self.b_dec,
+                                                    self._prepared_weights(), self.cfg.k + edits.E_max, exact=exact,
+                                                    certified=certified)
+                acts, idx = ops.edit_topk_rows(acts, idx, edit_group, edits, self.num_latents, self.cfg.k)
+            elif edits is not None:  # over-fetch, then edit: `exact` / `certified` only change the first call
                 acts, idx, status = ops.encode_topk(x, self.encoder.weight, self.encoder.bias, self.b_dec,
                                                     self._prepared_weights(), self.cfg.k + edits.E, exact=exact,
                                                     certified=certified)
@@ -273,6 +291,24 @@ class Sae(nn.Module):
                                                     float(set_value), zero_feature, exact=exact, certified=certified)
         out = EncoderOutput(acts, idx)
         return (out, status) if return_status else out
+
+    @staticmethod
+    def _token_groups(x: Tensor, edits, edit_group: Optional[Tensor]) -> Tensor:
+        """`edit_group` of encode -> one group id per token, shape x.shape[:-1] (device work only: nothing is read back)."""
+        lead = tuple(x.shape[:-1])
+        if edit_group is None:
+            if x.dim() != 3 or x.shape[0] != edits.G:
+                raise ValueError(f"Sae.encode: edit_group=None means row b uses group b: x must be [G, S, d] with G = "
+                                 f"{edits.G}, got {tuple(x.shape)}")
+            return torch.arange(edits.G, dtype=torch.int32, device=x.device)[:, None].expand(*lead)
+        if not isinstance(edit_group, Tensor) or edit_group.dtype not in (torch.int32, torch.int64):
+            raise ValueError("Sae.encode: edit_group must be an int32 or int64 tensor")
+        if tuple(edit_group.shape) == lead:
+            return edit_group
+        if x.dim() == 3 and tuple(edit_group.shape) == lead[:1]:
+            return edit_group[:, None].expand(*lead)
+        raise ValueError(f"Sae.encode: edit_group must have shape {lead} (per token)" +
+                         (f" or {lead[:1]} (per batch row)" if x.dim() == 3 else "") + f", got {tuple(edit_group.shape)}")
 
     def decode(self, top_acts: Tensor, top_indices: Tensor) -> Tensor:
         assert self.W_dec is not None, "Decoder weight was not initialized."
