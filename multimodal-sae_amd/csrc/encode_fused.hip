@@ -86,11 +86,14 @@ using GemmI8Cert = GemmCfg<256, 256, 2, 2, 4, true, 32 | kGemmI8Shape>;   // msa
 using GemmF8 = GemmCfg<256, 256, 2, 2, 4, false, 64>;      // MSAE_COARSE_FP8: e4m3 operands (BASELINE configs[4])
 constexpr int G_BM = GemmBf16::BM;
 
-// three scratch ranges in one launch (candidate counters, flag list, column maxima)
-__global__ void zero3_i32_kernel(int *p0, size_t n0, int *p1, size_t n1, int *p2, size_t n2) {
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n0; i += (size_t)gridDim.x * 256) p0[i] = 0;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n1; i += (size_t)gridDim.x * 256) p1[i] = 0;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n2; i += (size_t)gridDim.x * 256) p2[i] = 0;
+// the scratch ranges of a call in one launch (candidate counters, flag list, column maxima; with the feature-major re-score its
+// pair counters and defer flags): (pointer, count) pairs by value, unused ones empty
+constexpr int ZERO_RANGES = 5;
+struct ZeroRanges { int *p[ZERO_RANGES]; size_t n[ZERO_RANGES]; };
+__global__ void zero_ranges_i32_kernel(ZeroRanges z) {
+#pragma unroll
+  for (int r = 0; r < ZERO_RANGES; ++r)
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < z.n[r]; i += (size_t)gridDim.x * 256) z.p[r][i] = 0;
 }
 
 __global__ void zero_i32_kernel(int *p, size_t n) {
@@ -433,9 +436,7 @@ int rescore_stage(RescoreArgs &ra, const float *a32, const EncodeCall &c, unsign
   fm.count = fcount; fm.target = at<int>(ws, pl.off_fmtarget);
   fm.keys = at<u64>(ws, pl.off_fmkeys); fm.pre = fpre; fm.rcap = pl.r_max; fm.cand = at<u64>(ws, pl.off_cand);
   fm.rank = reinterpret_cast<int *>(fpre);
-  fm.defer = at<int>(ws, pl.off_fmdefer);
-  MSAE_HIP_TRY(hipMemsetAsync(fm.defer, 0, (size_t)T * 2 * 4, s));
-  MSAE_HIP_TRY(hipMemsetAsync(fcount, 0, ((size_t)N + 1) * 4, s));
+  fm.defer = at<int>(ws, pl.off_fmdefer);             // (defer and fcount[0 .. N]: zeroed at the start of the call, zero_call_scratch)
   const int lrc = launch_select_rescore<false, 1>(ra, a32, c.W_enc, s);
   if (lrc) return lrc;
   const int scan_blocks = (N + FM_SCAN_BLOCK - 1) / FM_SCAN_BLOCK, G = fm_group_lanes(T, k, N);
@@ -467,13 +468,20 @@ struct CandidatePass {
   int i8;                      // the three-term band (int8, fp8, certified)
 };
 
-// zeroes the call's scratch: candidate counters (+ segment counters), flag list and, for the passes that pick outlier dims, the
-// column maxima
+// zeroes the call's scratch: candidate counters (+ segment counters), flag list, for the passes that pick outlier dims the
+// column maxima, and where the plan has the feature-major re-score its pair counters [N + 1] and defer flags [2 T] -- nothing
+// in front of rescore_stage touches those two (their only user), so they need no launches of their own there
 void zero_call_scratch(const EncodeCall &c, unsigned char *ws, const FusedPlan &pl, bool colmax) {
   const size_t n_cnt = pl.segs > 1 ? (pl.off_segcnt - pl.off_cnt) / 4 + (size_t)c.T * pl.segs : (size_t)c.T;
-  hipLaunchKernelGGL(zero3_i32_kernel, dim3(64), dim3(256), 0, c.s, at<int>(ws, pl.off_cnt), n_cnt, pl.fb.flagged(ws),
-                     pl.fb.flag_words(c.T), colmax ? at<int>(ws, pl.off_colmax) : (int *)nullptr,
-                     colmax ? (size_t)c.d * COLMAX_PARTS : (size_t)0);
+  ZeroRanges z{};
+  z.p[0] = at<int>(ws, pl.off_cnt); z.n[0] = n_cnt;
+  z.p[1] = pl.fb.flagged(ws); z.n[1] = pl.fb.flag_words(c.T);
+  if (colmax) { z.p[2] = at<int>(ws, pl.off_colmax); z.n[2] = (size_t)c.d * COLMAX_PARTS; }
+  if (pl.fm) {
+    z.p[3] = at<int>(ws, pl.off_fmcount); z.n[3] = (size_t)c.N + 1;
+    z.p[4] = at<int>(ws, pl.off_fmdefer); z.n[4] = (size_t)c.T * 2;
+  }
+  hipLaunchKernelGGL(zero_ranges_i32_kernel, dim3(pl.fm ? 256 : 64), dim3(256), 0, c.s, z);
 }
 
 // the sample (DENSE) or main pass of `cp` over n_cols columns
