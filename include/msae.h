@@ -26,6 +26,7 @@
  *   msae_decode_bwd_wdec_f32 TritonDecoder.backward (W)    sae/kernels.py:417-419,10-175
  *   msae_sparsify_*          scatter_ + Cache.add/get_nonzeros  features/cache.py:214-217,42-92
  *   msae_feature_stats_*     per-feature counts + top examples  features/loader.py:103-106, constructors.py:28-141
+ *   msae_coact_*             co-activation counters + neighbours (no reference counterpart)
  *   msae_rows_topk_f32       cos + get_neighbors; logits   features/stats.py:76-120; stats.py:12-47
  *   msae_row_inv_norms_f32   F.normalize's norms in cos    features/stats.py:80-81
  *   msae_edit_topk_f32       hook edits with a feature LIST features/steering.py:113-114, patching/utils.py:43-48
@@ -439,6 +440,42 @@ int msae_feature_stats_update_sampled(const float *vals, const int32_t *idx, int
 int msae_feature_sample_merge(int N, int n_sample, uint64_t seed, uint64_t *seg_count, float *smp_val,
                               int64_t *smp_id, const uint64_t *src_seg_count, const float *src_val,
                               const int64_t *src_id, void *stream);
+
+/* ---- co-activation counters of a query list, and neighbour lists from them (msae.features.CoactStats) ---------------
+ * Which features fire together, counted while the cache runs, for F query features (no reference counterpart; the
+ * decoder-geometry neighbours are msae_rows_topk_f32).  Input: one batch's top-k vals/idx[B*S][k], as the feature
+ * statistics take it; an entry is kept when |v| > thresh and 0 <= idx < N (no filter bitmap on the member side).
+ * Segments (a row never spans two calls, so each segment is complete in one call):
+ *   MSAE_POOL_TOKEN   every position its own segment: B*S per call
+ *   MSAE_POOL_WINDOW  positions s < (S / W) * W belong to b * (S / W) + s / W (the ragged tail is not pooled): B * (S / W)
+ *   MSAE_POOL_IMAGE   positions s < pool_len belong to segment b, later ones to none: B
+ * A feature is ACTIVE in a segment that holds at least one kept entry of it; a repeat inside a segment counts once.
+ * State, updated in place (initialise to 0):
+ *   counts[F][N]  i32  counts[i][g] = segments in which the query of slot i and g are both active; the entry at the
+ *                      query's own column is the query's count
+ *   seg_count[N]  u64  segments in which g is active
+ * slot_of[N] i32: the slot of a query feature, -1 for every other feature (a value outside [0, F) counts as -1).
+ * Every update is an integer atomic add: the state is bit-identical however the rows are cut into calls, in whatever
+ * order the calls arrive, and adds over ranks.  A counter wraps at 2^31 segments: the caller keeps the total below.
+ * Envelope: B*S <= 65536, k <= 256, N <= 262144, 1 <= F <= 16384, pool_len <= 2880, window <= 4096 (else MSAE_EINVAL).
+ * No host synchronisation, no allocation: the workspace is msae_coact_ws_bytes(B*S, k, N) (token mode uses none of it),
+ * whatever F and however many entries are queries.
+ * msae_coact_topk: for slot i with query q = queries[i] and every g with c = counts[i][g] > 0 (g != q with exclude_self)
+ *   MSAE_COACT_JACCARD  score = (float)((double)c / (double)(seg_count[q] + seg_count[g] - c))   integers, one f64
+ *                       quotient (IEEE, correctly rounded), one rounding to f32
+ *   MSAE_COACT_COUNT    score = (float)c
+ *   out_val[F][m] / out_idx[F][m]: the best m in (score descending, g ascending) order -- the library's rank key --,
+ *   free slots (0.0, -1) at the tail.  1 <= m <= 64.  A pure function of the state; no scratch. */
+enum { MSAE_POOL_TOKEN = 2 };
+enum { MSAE_COACT_JACCARD = 0, MSAE_COACT_COUNT = 1 };
+size_t msae_coact_ws_bytes(int T, int k, int N);
+int msae_coact_update(const float *vals, const int32_t *idx, int B, int S, int k, float thresh, int N, int mode,
+                      int pool_len, int window, const int32_t *slot_of, int F, int32_t *counts, uint64_t *seg_count,
+                      void *ws, size_t ws_bytes, void *stream);
+int msae_coact_topk(const int32_t *counts, const int64_t *seg_count, const int32_t *queries, int F, int N, int m,
+                    int metric, int exclude_self, float *out_val, int32_t *out_idx, void *stream);
+int msae_coact_topk_i64(const int32_t *counts, const int64_t *seg_count, const int32_t *queries, int F, int N, int m,
+                        int metric, int exclude_self, float *out_val, int64_t *out_idx, void *stream);
 
 /* ---- probe: segment-pooled feature ranking and activation maps (Sae.probe) ---------------------------------------
  * Replaces the dense probe of tools/probe_activations.py:109-126 (latents = pre_acts(h); latents.mean(0).topk(k);

@@ -100,6 +100,13 @@ PROTOTYPES = {
                                                   c_sample_p, c_void_p, c_size_t, c_void_p]),
     "msae_feature_sample_merge": (c_int, [c_int, c_int, ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p]),
+    "msae_coact_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "msae_coact_update": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_int, c_int, c_int, c_void_p,
+                                  c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "msae_coact_topk": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                c_void_p]),
+    "msae_coact_topk_i64": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                    c_void_p]),
     "msae_pooled_acts_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int,
                                      c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "msae_probe_maps_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int,

@@ -45,6 +45,12 @@ class CacheConfig:
     """Uniformly sampled examples kept per feature in the statistics (0: none, up to 256)"""
     stats_seed: int = 22
     """Seed of the statistics' example sample"""
+    coact: bool = False
+    """Also count which features fire together with the filtered features (coact.safetensors per module)"""
+    coact_pool: Optional[str] = None
+    """Segments of the co-activation counters: token, window or image (default: image on cache_image, token on cache)"""
+    coact_features: Optional[str] = None
+    """Filter-format json {module: [ids]} of the co-activation query features (default: --filters_path)"""
 
     def to_dict(self):
         return dataclasses.asdict(self)
@@ -93,4 +99,26 @@ def parse_cache_config(argv: Optional[Sequence[str]] = None) -> CacheConfig:
         else:
             typ = int if f.type in (int, "int") else str
             p.add_argument(f"--{f.name}", type=typ, default=f.default)
-    return CacheConfig(**vars(p.parse_args(argv)))
+    cfg = CacheConfig(**vars(p.parse_args(argv)))
+    if cfg.coact_pool is not None and cfg.coact_pool not in COACT_POOLS:
+        p.error(f"--coact_pool must be one of {', '.join(COACT_POOLS)}, got {cfg.coact_pool!r}")
+    if cfg.coact and not (cfg.coact_features or cfg.filters_path):
+        p.error("--coact needs query features: give --coact_features or --filters_path")
+    return cfg
+
+
+COACT_POOLS = ("token", "window", "image")
+
+
+def coact_kwargs(cfg: CacheConfig, default_pool: str, pool_len: int = 576, device="cpu") -> Optional[dict]:
+    """The `coact=` argument of the feature caches for a parsed command line (None without --coact): the pool (the
+    launcher's default unless --coact_pool), the window of the text statistics, `pool_len` of the image ones, and the
+    query lists of --coact_features (without it the caches take the filter lists)."""
+    if not cfg.coact:
+        return None
+    kw = dict(pool=cfg.coact_pool or default_pool, window=cfg.example_ctx_len, pool_len=pool_len)
+    if cfg.coact_features:
+        from .utils import load_filter
+
+        kw["queries"] = load_filter(cfg.coact_features, device=device)
+    return kw

@@ -14,6 +14,11 @@ tables (msae/features/stats.py) next to them:
     <save_dir>/<module>/feature_stats.safetensors              the ranks merged in rank order by the concat
                                                                (with `n_sample`: the uniform example sample too)
 
+and, with `coact=` (opt-in; no reference counterpart), the co-activation counters of a query list (msae/features/coact.py):
+
+    <save_dir>/<module>/Rank{r}_coact.safetensors              per rank
+    <save_dir>/<module>/coact.safetensors                      the ranks added in rank order by the concat
+
 with keys `locations [nnz,3] int64 = (row, pos, feature)` and `activations [nnz] f32`, which is what
 `features/loader.py:143-196` (FeatureDataset) reads.
 
@@ -40,6 +45,7 @@ from torch import Tensor
 
 from .. import ops
 from ..sae import Sae
+from .coact import CoactStats
 from .stats import FeatureStats
 
 
@@ -55,7 +61,7 @@ class Cache:
 
     def __init__(self, shard_size: int, filters: Optional[Dict[str, Tensor]] = None,
                  batch_size: int = 64, spill_dir: Optional[str] = None, device_budget_bytes: int = 256 << 20,
-                 stats: Optional[dict] = None):
+                 stats: Optional[dict] = None, coact: Optional[dict] = None):
         """`spill_dir`: stream every batch's records to disk instead of holding the whole run in host
         RAM (the reference keeps everything in Python lists until save_splits, cache.py:56-57);
         `save()` reads them back in batch order, so the final tensors are identical.
@@ -63,7 +69,11 @@ class Cache:
         per 8192-token batch at k = 32) and cross to the host in one transfer once this much is pending.
         `stats`: keyword arguments of `FeatureStats` (pool, n_top, pool_len, window, thresh, n_sample, sample_seed) -- one
         `FeatureStats` per module is then updated in `add_topk` on the compute stream, over every feature (the filter is not applied);
-        None (default): nothing of it runs."""
+        None (default): nothing of it runs.
+        `coact`: keyword arguments of `CoactStats` (pool, pool_len, window, thresh, max_bytes, queries) -- one `CoactStats`
+        per module is then updated in `add_topk` next to the feature statistics.  `queries` (a list of features, or
+        {module: list}) defaults to the module's filter list; without either it is a ValueError.  None (default): nothing
+        of it is allocated, launched or written."""
         self.feature_locations = defaultdict(list)
         self.feature_activations = defaultdict(list)
         self.spill_dir = spill_dir
@@ -80,6 +90,10 @@ class Cache:
         self._copy_stream = None
         self.stats = None if stats is None else dict(stats)
         self.feature_stats: Dict[str, FeatureStats] = {}
+        self.coact = None if coact is None else dict(coact)
+        if self.coact is not None and self.coact.get("queries") is None and filters is None:
+            raise ValueError("coact needs query features: pass coact['queries'] or a feature filter")
+        self.coact_stats: Dict[str, CoactStats] = {}
 
     def _bitmap(self, module_path: str, num_latents: int, device) -> Optional[Tensor]:
         if self.filters is None:
@@ -101,6 +115,11 @@ class Cache:
             if st is None:
                 st = self.feature_stats[module_path] = FeatureStats(num_latents, device=top_acts.device, **self.stats)
             st.update(top_acts, top_indices, row_base)
+        if self.coact is not None:
+            co = self.coact_stats.get(module_path)
+            if co is None:
+                co = self.coact_stats[module_path] = self._new_coact(module_path, num_latents, top_acts.device)
+            co.update(top_acts, top_indices)
         loc, act, nnz = ops.sparsify(top_acts, top_indices, num_latents, row_base=row_base, thresh=1e-5,
                                      filter_bitmap=self._bitmap(module_path, num_latents, top_acts.device), sync=False)
         # stays on the device, stream-ordered (the reference does a nonzero() + two .cpu() per batch inside the
@@ -111,6 +130,17 @@ class Cache:
             # this group starts its way to the host; the one before it (a whole budget's worth of batches ago) is finished
             self._start_transfer()
             self._drain(keep=1)
+
+    def _new_coact(self, module_path: str, num_latents: int, device) -> CoactStats:
+        kw = dict(self.coact)
+        queries = kw.pop("queries", None)
+        if isinstance(queries, dict):
+            queries = queries.get(module_path)
+        if queries is None and self.filters is not None:
+            queries = self.filters.get(module_path)
+        if queries is None:
+            raise ValueError(f"coact: no query features for module {module_path!r}")
+        return CoactStats(num_latents, queries, device=device, **kw)
 
     # free pinned byte buffers, reused from group to group and from Cache to Cache (pinning a few hundred MB takes tens of
     # milliseconds: a pool per instance paid it again for every run)
@@ -212,7 +242,8 @@ class Cache:
 
 class FeatureCache:
     def __init__(self, model, tokenizer, submodule_dict: Dict[str, Sae], batch_size: int,
-                 shard_size: int, filters: Optional[Dict[str, Tensor]] = None, stats: Optional[dict] = None):
+                 shard_size: int, filters: Optional[Dict[str, Tensor]] = None, stats: Optional[dict] = None,
+                 coact: Optional[dict] = None):
         # LlavaNextForConditionalGeneration wraps the language model (cache.py:104-109)
         if hasattr(model, "language_model") and hasattr(model, "vision_tower"):
             self.llava_model, self.model = model, model.language_model
@@ -225,7 +256,7 @@ class FeatureCache:
         self.batch_size = batch_size
         first = next(iter(submodule_dict.values()))
         self.width = first.cfg.num_latents or first.d_in * first.cfg.expansion_factor
-        self.cache = Cache(shard_size, filters, batch_size=batch_size, stats=stats)
+        self.cache = Cache(shard_size, filters, batch_size=batch_size, stats=stats, coact=coact)
         if filters is not None:
             self.filter_submodules(filters)
 
@@ -307,6 +338,10 @@ class FeatureCache:
             module_dir = f"{save_dir}/{module_path}"
             os.makedirs(module_dir, exist_ok=True)
             st.save(f"{module_dir}/Rank{rank}_feature_stats.safetensors")
+        for module_path, co in self.cache.coact_stats.items():
+            module_dir = f"{save_dir}/{module_path}"
+            os.makedirs(module_dir, exist_ok=True)
+            co.save(f"{module_dir}/Rank{rank}_coact.safetensors")
 
     def concate_safetensors(self, n_splits: int, save_dir):
         for module_path in self.cache.feature_locations.keys():
@@ -325,6 +360,8 @@ class FeatureCache:
                           f"{module_dir}/{start}_{end}.safetensors")
         for module_path, st in self.cache.feature_stats.items():
             merge_rank_stats(f"{save_dir}/{module_path}", st.device)
+        for module_path, co in self.cache.coact_stats.items():
+            merge_rank_coact(f"{save_dir}/{module_path}", co.device)
 
 
 def merge_rank_stats(module_dir: str, device) -> Optional[str]:
@@ -345,13 +382,31 @@ def merge_rank_stats(module_dir: str, device) -> Optional[str]:
     return out
 
 
+def merge_rank_coact(module_dir: str, device=None) -> Optional[str]:
+    """Add `Rank{r}_coact.safetensors` of `module_dir` in rank order (on `device`; any device, the CPU included) into
+    `coact.safetensors` and remove the rank files.  Returns the written path (None: no rank file)."""
+    pat = re.compile(r"^Rank(\d+)_coact\.safetensors$")
+    parts = sorted((int(m.group(1)), f) for f in os.listdir(module_dir) if (m := pat.match(f)))
+    if not parts:
+        return None
+    total = None
+    for _, fname in parts:
+        co = CoactStats.load(os.path.join(module_dir, fname), device=device)
+        total = co if total is None else total.merge(co)
+    out = os.path.join(module_dir, "coact.safetensors")
+    total.save(out)
+    for _, fname in parts:
+        os.remove(os.path.join(module_dir, fname))
+    return out
+
+
 class FeatureImageCache(FeatureCache):
     """Image variant (cache.py:312-429): `<image>` prompt per image through the LLaVA processor,
     BOS position dropped before the SAE."""
 
     def __init__(self, model, tokenizer, submodule_dict, batch_size: int, shard_size: int,
-                 filters=None, processor=None, stats: Optional[dict] = None):
-        super().__init__(model, tokenizer, submodule_dict, batch_size, shard_size, filters, stats=stats)
+                 filters=None, processor=None, stats: Optional[dict] = None, coact: Optional[dict] = None):
+        super().__init__(model, tokenizer, submodule_dict, batch_size, shard_size, filters, stats=stats, coact=coact)
         if processor is None:  # resolved lazily, not at import time as cache.py:321 does
             from transformers import LlavaNextProcessor
 

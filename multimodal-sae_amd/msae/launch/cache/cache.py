@@ -10,9 +10,12 @@ import os
 import torch
 import torch.distributed as dist
 
-from ...config import CacheConfig, parse_cache_config
+from ...config import CacheConfig, coact_kwargs, parse_cache_config
 from ...features import FeatureCache
 from ...utils import ddp_setup, load_filter, load_saes, maybe_load_llava_model, shard_offsets
+
+
+COACT_DEFAULT_POOL = "token"
 
 
 def chunk_and_tokenize(dataset, tokenizer, max_seq_len: int, text_key: str = "text", batch_docs: int = 2048,
@@ -106,7 +109,7 @@ def main(cfg: CacheConfig):
         stats = dict(pool="window", window=cfg.example_ctx_len, n_top=cfg.stats_top, n_sample=cfg.stats_sample,
                      sample_seed=cfg.stats_seed)
     cache = FeatureCache(model, tokenizer, saes, batch_size=cfg.batch_size, shard_size=shard_size,
-                         filters=filters, stats=stats)
+                         filters=filters, stats=stats, coact=coact_kwargs(cfg, COACT_DEFAULT_POOL, device=model.device))
     if ddp:
         dist.barrier()
     cache.run(cfg.ctx_len, dataset)

@@ -5,9 +5,12 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
-from ...config import CacheConfig, parse_cache_config
+from ...config import CacheConfig, coact_kwargs, parse_cache_config
 from ...features import FeatureImageCache
 from ...utils import ddp_setup, load_filter, load_saes, maybe_load_llava_model, shard_offsets
+
+
+COACT_DEFAULT_POOL = "image"
 
 
 def main(cfg: CacheConfig):
@@ -27,11 +30,13 @@ def main(cfg: CacheConfig):
         shard_size = sum(shard_offsets(len(dataset), model.device)[:rank])
     saes = load_saes(cfg.sae_path, filters=filters, device=model.device)
     stats = None
+    pool_len = getattr(processor, "num_image_tokens", None) or 576
     if cfg.feature_stats:   # the image constructor pools the processor's first num_image_tokens positions
-        stats = dict(pool="image", pool_len=getattr(processor, "num_image_tokens", None) or 576, n_top=cfg.stats_top,
+        stats = dict(pool="image", pool_len=pool_len, n_top=cfg.stats_top,
                      n_sample=cfg.stats_sample, sample_seed=cfg.stats_seed)
     cache = FeatureImageCache(model, tokenizer, saes, batch_size=cfg.batch_size, shard_size=shard_size,
-                              processor=processor, filters=filters, stats=stats)
+                              processor=processor, filters=filters, stats=stats,
+                              coact=coact_kwargs(cfg, COACT_DEFAULT_POOL, pool_len=pool_len, device=model.device))
     if ddp:
         dist.barrier()
     cache.run(cfg.ctx_len, dataset)
