@@ -645,6 +645,17 @@ int msae_compact_flags(const int32_t *flags, int T, int32_t *rows, int32_t *n_ro
 int msae_merge_topk_masked(const int32_t *gathered, int T, int G, int kl, int k, const int32_t *mask,
                            float *vals, int32_t *idx, int64_t *idx64, void *stream);
 
+/* ---- debug entry: the threshold select of the fused encoder on its own (csrc/topk.hip) ----
+ * out[t] = the float whose order key is the r-th largest order key of rows[t][0 .. S) with its low 14 bits cleared (the
+ * r-th largest rounded down by < 0.2 %: at least r values of the row are at or above it).  With cnt != NULL and out[t] > 0
+ * every value of the row ABOVE out[t] is appended to the row's list: cnt[t] advances by their number in one atomic add
+ * and cand[t * cap + slot] = (order key << 32) | (0x7FFFFFFF - (j * stride + off)) for column j, slots at or past cap
+ * dropped; the order inside a list is unspecified.  rows 16-byte aligned, ld % 4 == 0, ld >= S, S % 256 == 0 and
+ * S <= 8192 or S % 1024 == 0; other shapes return MSAE_ENOTIMPL.  MSAE_KTH_STREAM=0 in the environment (read at every
+ * call) keeps the register-resident kernel where the streaming one would run; both return the same values. */
+int msae_kth_value_f32(const float *rows, int T, int S, int ld, int r, float *out, int32_t *cnt,
+                       unsigned long long *cand, int cap, int stride, int off, void *stream);
+
 /* ---- parameter-sized passes of one optimisation step (training) ----
  * msae_unit_norm_rows_f32: W[r][:] /= ||W[r][:]||_2 + eps, in place
  *                          (Sae.set_decoder_norm_to_unit_norm, sae_auto_interp/sae/sae.py:249-255).

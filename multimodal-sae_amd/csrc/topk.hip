@@ -11,6 +11,8 @@
 // the k winners -- every element above the pivot plus the r lowest-index elements equal to it --
 // and an LDS bitonic sort puts them in canonical order.  HBM-bound: the row is streamed once from
 // HBM and re-read from L2 by the later passes (N*4 B = 512 KiB at N = 131072).
+#include <stdlib.h>
+
 #include "common.h"
 #include "sortsel.h"
 #include "wave_ops.h"
@@ -284,6 +286,165 @@ __global__ __launch_bounds__(256) void kth_value_kernel(const float *__restrict_
   }
 }
 
+// ---- the same select, streaming (S % 1024 == 0, S >= 2048, small r) ----------------------------------
+// kth_value_kernel keeps the whole row in registers (VPL = 64 at S = 4096: 102 VGPRs, 4 waves per SIMD) and compares every key
+// at every bisection step, though after the first step only a few dozen keys can still matter.  Here a wave walks its row in
+// chunks of 1024 values (16 keys per lane, the next chunk's loads in flight), takes a lower bound lo0 of the answer from chunk
+// 0 alone -- the same rounded-down bisection over the chunk: >= r of ITS keys are >= lo0, so the row's threshold is >= lo0 --
+// and keeps only the keys >= lo0 ("survivors", with their columns) in a per-wave LDS buffer.  The survivors hold every key the
+// full bisection can tell apart from "below the answer": count(key >= mid) over them equals the row's for mid > lo0, and for
+// mid <= lo0 the step succeeds whatever the count.  So the bisection over the survivors (8 per lane) returns kth_value_kernel's
+// threshold bit for bit, and the keys above it are all among them.  About r S / 1024 keys survive on rows without structure.
+// A row whose survivors do not fit (equal values, an ascending row, a chunk 0 of small values) is finished by the same wave
+// with a bisection that re-reads the row at every step: slow, rare, and light on registers.
+constexpr int KS_CHUNK = 1024, KS_CAP = 512;   // 4 waves x 512 x (key + column) = 16 KB per workgroup: 8 workgroups per CU
+
+__device__ __forceinline__ int wave_count(bool p) { return (int)__builtin_popcountll(__builtin_amdgcn_ballot_w64(p)); }
+__device__ __forceinline__ int lanes_below(unsigned long long m) {
+  return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+}
+// one reservation of `total` entries in row t's candidate list; the first slot, wave-uniform
+__device__ __forceinline__ int kth_push_reserve(const KthPush &push, int t, int lane, int total) {
+  int base = 0;
+  if (lane == 0) base = atomicAdd(push.cnt + (size_t)t * push.cnt_stride, total);
+  return __builtin_amdgcn_readfirstlane(base);
+}
+
+__global__ __launch_bounds__(256, 8) void kth_stream_kernel(const float *__restrict__ rows, int T, int S, int ld, int r,
+                                                            float *__restrict__ out, int out_ld, int out_col, KthPush push) {
+  __shared__ unsigned s_key[4][KS_CAP];
+  __shared__ int s_col[4][KS_CAP];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int t = blockIdx.x * 4 + w;
+  if (t >= T) return;                                  // (no workgroup barrier below: a wave owns its row and its buffer)
+  const float *row = rows + (size_t)t * ld;
+  unsigned *sk = s_key[w];
+  int *sc = s_col[w];
+  const int nchunk = S / KS_CHUNK;
+  f32x4 nxt[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) nxt[q] = *reinterpret_cast<const f32x4 *>(row + (q * 64 + lane) * 4);
+  unsigned lo0 = 0u;                                   // from chunk 0: count(key >= lo0) >= r, a multiple of 2^KTH_LOW_BIT
+  int n = 0;                                           // survivors so far (wave-uniform)
+#pragma unroll 1
+  for (int c = 0; c < nchunk && n <= KS_CAP; ++c) {
+    unsigned key[16];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      key[4 * q + 0] = f32_order_key(nxt[q][0]); key[4 * q + 1] = f32_order_key(nxt[q][1]);
+      key[4 * q + 2] = f32_order_key(nxt[q][2]); key[4 * q + 3] = f32_order_key(nxt[q][3]);
+    }
+    if (c + 1 < nchunk) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) nxt[q] = *reinterpret_cast<const f32x4 *>(row + (c + 1) * KS_CHUNK + (q * 64 + lane) * 4);
+    }
+    if (c == 0) {
+#pragma unroll 1
+      for (int bit = 31; bit >= KTH_LOW_BIT; --bit) {
+        const unsigned mid = lo0 | (1u << bit);
+        int cnt = 0;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) cnt += wave_count(key[i] >= mid);
+        if (cnt >= r) lo0 = mid;
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const bool hit = key[i] >= lo0;
+      const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
+      if (m == 0ull) continue;                         // wave-uniform
+      const int slot = n + lanes_below(m);
+      if (hit && slot < KS_CAP) {
+        sk[slot] = key[i];
+        sc[slot] = c * KS_CHUNK + ((i >> 2) * 64 + lane) * 4 + (i & 3);
+      }
+      n += (int)__builtin_popcountll(m);
+    }
+  }
+  const bool pushing = push.cnt != nullptr;
+  unsigned long long *list = pushing ? push.cand + (size_t)t * (push.row_stride ? push.row_stride : push.cap) : nullptr;
+  unsigned lo = 0u;                                    // invariant: count(key >= lo) >= r over the row
+  if (n <= KS_CAP) {
+    // the wave's own LDS writes, read back by other lanes: wave-scope release / acquire, no workgroup barrier
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    unsigned k8[KS_CAP / 64];
+#pragma unroll
+    for (int i = 0; i < KS_CAP / 64; ++i) k8[i] = (i * 64 + lane < n) ? sk[i * 64 + lane] : 0u;   // 0: below every mid
+#pragma unroll 1
+    for (int bit = 31; bit >= KTH_LOW_BIT; --bit) {
+      const unsigned mid = lo | (1u << bit);
+      bool take = mid <= lo0;                          // wave-uniform; chunk 0 alone has r keys there
+      if (!take) {
+        int cnt = 0;
+#pragma unroll
+        for (int i = 0; i < KS_CAP / 64; ++i) cnt += wave_count(k8[i] >= mid);
+        take = cnt >= r;
+      }
+      if (take) lo = mid;
+    }
+    if (lane == 0) out[(size_t)t * out_ld + out_col] = f32_from_order_key(lo);
+    if (!pushing || !(f32_from_order_key(lo) > 0.f)) return;
+    int total = 0;
+#pragma unroll
+    for (int i = 0; i < KS_CAP / 64; ++i) total += wave_count(k8[i] > lo);
+    if (total == 0) return;
+    int base = kth_push_reserve(push, t, lane, total);
+#pragma unroll
+    for (int i = 0; i < KS_CAP / 64; ++i) {
+      const bool hit = k8[i] > lo;                     // (an empty slot holds 0: never above a positive threshold's key)
+      const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
+      if (m == 0ull) continue;
+      const int slot = base + lanes_below(m);
+      if (hit && slot < push.cap) list[slot] = rank_key_from_order(k8[i], sc[i * 64 + lane] * push.stride + push.off);
+      base += (int)__builtin_popcountll(m);
+    }
+    return;
+  }
+  // ---- the survivors overflowed: bisection over the row itself (L2 holds it: S * 4 B per step) ----
+#pragma unroll 1
+  for (int bit = 31; bit >= KTH_LOW_BIT; --bit) {
+    const unsigned mid = lo | (1u << bit);
+    bool take = mid <= lo0;
+    if (!take) {
+      int cnt = 0;
+#pragma unroll 1
+      for (int j = lane * 4; j < S; j += 256) {
+        const f32x4 v = *reinterpret_cast<const f32x4 *>(row + j);
+        cnt += (f32_order_key(v[0]) >= mid) + (f32_order_key(v[1]) >= mid) + (f32_order_key(v[2]) >= mid) + (f32_order_key(v[3]) >= mid);
+      }
+      take = wave_sum(cnt) >= r;
+    }
+    if (take) lo = mid;
+  }
+  if (lane == 0) out[(size_t)t * out_ld + out_col] = f32_from_order_key(lo);
+  if (!pushing || !(f32_from_order_key(lo) > 0.f)) return;
+  int total = 0;
+#pragma unroll 1
+  for (int j = lane * 4; j < S; j += 256) {
+    const f32x4 v = *reinterpret_cast<const f32x4 *>(row + j);
+    total += (f32_order_key(v[0]) > lo) + (f32_order_key(v[1]) > lo) + (f32_order_key(v[2]) > lo) + (f32_order_key(v[3]) > lo);
+  }
+  total = wave_sum(total);
+  if (total == 0) return;
+  int base = kth_push_reserve(push, t, lane, total);
+#pragma unroll 1
+  for (int j = lane * 4; j < S; j += 256) {            // S % 256 == 0: every lane runs every trip
+    const f32x4 v = *reinterpret_cast<const f32x4 *>(row + j);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const unsigned key = f32_order_key(v[e]);
+      const bool hit = key > lo;
+      const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
+      if (m == 0ull) continue;
+      const int slot = base + lanes_below(m);
+      if (hit && slot < push.cap) list[slot] = rank_key_from_order(key, (j + e) * push.stride + push.off);
+      base += (int)__builtin_popcountll(m);
+    }
+  }
+}
+
 // ---- merge of per-shard top-k_loc lists (feature-sharded encode, msae/parallel.py) ---------------
 // gathered: int32 [G][2][T][kl] exactly as all_gather_into_tensor lays out each rank's packed
 // [2][T][kl] block (plane 0 = f32 activation bits, plane 1 = GLOBAL feature index).
@@ -390,6 +551,13 @@ bool msae_kth_value_launch(const float *rows, int T, int S, int ld, int r, float
                            int out_col, hipStream_t s, const KthPush &push) {
   if (S % 256 || ld % 4 || !msae_aligned(rows, 16) || r < 1 || r > S) return false;
   const dim3 grid((T + 3) / 4), block(256);
+  // the streaming kernel where about r S / 1024 survivors fill at most half its buffer; MSAE_KTH_STREAM=0 keeps the
+  // register-resident kernel (read at every call, like MSAE_FM: a test compares the two in one process)
+  const char *e = getenv("MSAE_KTH_STREAM");
+  if (S % KS_CHUNK == 0 && S >= 2 * KS_CHUNK && (long)r * (S / KS_CHUNK) <= KS_CAP / 2 && !(e && e[0] == '0')) {
+    hipLaunchKernelGGL(kth_stream_kernel, grid, block, 0, s, rows, T, S, ld, r, out, out_ld, out_col, push);
+    return true;
+  }
   switch (S / 64) {
 #define KTH_CASE(V) case V: hipLaunchKernelGGL(kth_value_kernel<V>, grid, block, 0, s, rows, T, S, ld, r, out, out_ld, out_col, push); return true;
     KTH_CASE(4) KTH_CASE(8) KTH_CASE(16) KTH_CASE(32) KTH_CASE(64) KTH_CASE(128)
