@@ -31,6 +31,7 @@
  *   msae_row_inv_norms_f32   F.normalize's norms in cos    features/stats.py:80-81
  *   msae_edit_topk_f32       hook edits with a feature LIST features/steering.py:113-114, patching/utils.py:43-48
  *   msae_edit_topk_rows_f32  the same with one table per token (a feature per batch row of one generate)
+ *   msae_delta_decode_f32    x + decode(edited) - decode(plain): error-preserving hooks (no reference counterpart)
  *
  * Numerics contract: all dot products are ascending-k f32 fused
  * multiply-add chains (v_mfma_f32_32x32x2_f32 / v_fma_f32), bit-identical to oracle/sae_oracle.c.
@@ -629,6 +630,45 @@ int msae_edit_topk_rows_i64_f32(const float *vals_in, const int64_t *idx_in, int
                                 const int32_t *group_off, int G, const int32_t *edit_feat, const float *edit_val,
                                 const int32_t *edit_kind, int E_total, int E_max, int N, int k, float *vals, int64_t *idx,
                                 uint8_t *edited, void *stream);
+
+/* ---- error-preserving interventions (Sae.intervene) ------------------------------------------------
+ * out = x + (decode(edited list) - decode(plain list)): the hidden state keeps the SAE's reconstruction error and moves by
+ * the decoded EDIT alone.  Entries the two lists share cancel, so only the entries that differ are gathered.
+ *   x [T][d]                          the hidden states, x_dtype MSAE_F32 / MSAE_BF16 / MSAE_F16
+ *   plain_vals / plain_idx [T][ld_plain]   P: the canonical top-k of the UNEDITED latents in the first k columns of each row
+ *                                     (the over-fetched encode's output is passed as it is, ld_plain = kk)
+ *   edit_vals / edit_idx [T][ld_edit]      Q: the edited list (msae_edit_topk_f32 / msae_edit_topk_rows_f32), first k columns
+ *   W_dec f32 [N][d]
+ *   out [T][d]                        x's dtype; may be x itself (no other overlap)
+ *   status int32 [1] or NULL          bit 0 is ORed in when an entry's feature lies outside [0, N), as msae_decode_f32 does
+ * Asynchronous on `stream`; allocates nothing, needs no workspace, never synchronises.  MSAE_EINVAL: a null pointer
+ * (`status` may be null), k < 1, k > 4096, ld_plain < k, ld_edit < k, T < 0, N < 1, d < 1, a bad dtype code.  T == 0 returns 0.
+ * Contract, per token t (nothing depends on T or on the other tokens):
+ *   1. Surviving entries.  An entry (value, feature) of one list SURVIVES when its value is not +-0 and the other list
+ *      holds no entry with the same feature and the bit-identical value (values compared as 32-bit patterns).  A feature in
+ *      both lists with different values survives twice, once from each list.
+ *   2. Difference sequence D_t: the surviving entries of Q in slot order, each with coefficient +value, then the surviving
+ *      entries of P in slot order, each with coefficient -value.
+ *   3. delta[t][c] is the f32 chain acc = fmaf(coef_j, W_dec[f_j][c], acc) over D_t in that order, from acc = +0.
+ *   4. out[t][c] = convert(f32(x[t][c]) + delta[t][c]): one f32 add, one round-to-nearest-even conversion to x's dtype
+ *      (a NaN sum stays a NaN).  b_dec is in both reconstructions and cancels: it is not an argument.
+ *   5. Empty D_t: out[t][:] holds x[t][:]'s own bits -- nothing is added, so -0 and NaN payloads pass through; with
+ *      out == x the row is not touched at all.
+ *   6. A surviving entry whose feature lies outside [0, N) is skipped (and flagged in `status`, like every out-of-range
+ *      entry of either list).  No memory is indexed by a feature that was not range-checked: a hostile list -- repeated
+ *      features, any order -- follows the same survival rule; it can give a wrong row, not an out-of-bounds access.
+ *   7. f32(x) + (msae_decode_f32(Q) - msae_decode_f32(P)) is the MEANING of this definition, not its bits: the two differ by
+ *      the rounding of the cancelled entries.
+ * Layout: one workgroup per (token, slab of 1024 columns), both lists and D_t in LDS (32 k bytes; the two lists alone are
+ * 16 k <= 64 KiB); 16-byte loads per lane when d % 4 == 0 and W_dec, x, out are aligned to 4 elements, one column per lane
+ * otherwise. */
+int msae_delta_decode_f32(const void *x, int x_dtype, const float *plain_vals, const int32_t *plain_idx, int ld_plain,
+                          const float *edit_vals, const int32_t *edit_idx, int ld_edit, const float *W_dec, int T, int k,
+                          int N, int d, void *out, int32_t *status, void *stream);
+/* the same reading 64-bit indices (msae_encode_topk_i64's and msae_edit_topk_i64_f32's output type) */
+int msae_delta_decode_i64_f32(const void *x, int x_dtype, const float *plain_vals, const int64_t *plain_idx, int ld_plain,
+                              const float *edit_vals, const int64_t *edit_idx, int ld_edit, const float *W_dec, int T,
+                              int k, int N, int d, void *out, int32_t *status, void *stream);
 
 /* ---- merge of per-shard results (feature-sharded encode; no reference counterpart) ----
  * gathered: int32 [G][2][T][kl], the all-gather of each rank's packed block [2][T][kl]

@@ -71,6 +71,8 @@ class AttributionConfig:
     """Save dir for your feature attribution result"""
     method: str = "exact"
     """"exact": the reference's per-feature loop; "batched": all features from one forward + backward"""
+    preserve_error: bool = False
+    """(new) ablate in the model itself: the hooked layer keeps the SAE's reconstruction error (method "exact" only)"""
 
     def to_dict(self):
         return dataclasses.asdict(self)
@@ -81,6 +83,8 @@ def parse_attribution_config(argv: Optional[Sequence[str]] = None) -> Attributio
     for f in dataclasses.fields(AttributionConfig):
         if f.name == "model":
             p.add_argument("model", nargs="?", default=f.default, type=str)
+        elif f.type in (bool, "bool"):
+            p.add_argument(f"--{f.name}", f"--{f.name.replace('_', '-')}", dest=f.name, action="store_true", default=f.default)
         else:
             p.add_argument(f"--{f.name}", type=str, default=f.default)
     return AttributionConfig(**vars(p.parse_args(argv)))

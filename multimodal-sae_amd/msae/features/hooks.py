@@ -23,12 +23,25 @@ from .edits import FeatureEdits, RowEdits, as_off_features
 def sae_reconstruct(sae, hidden: Tensor, *, set_feature: int = -1, set_value: float = 0.0,
                     zero_feature: int = -1, out_dtype: Optional[torch.dtype] = None,
                     differentiable: Optional[bool] = None, edits: Optional[FeatureEdits] = None,
-                    edit_group: Optional[Tensor] = None) -> Tensor:
+                    edit_group: Optional[Tensor] = None, preserve_error: bool = False) -> Tensor:
     """[..., d] hidden states -> SAE reconstruction of the same shape.  `sae` is an `Sae` module or a
     feature-sharded engine (msae.parallel.ShardedSae over an N/G slice of the encoder per rank, SURVEY 8f rank 4:
     "N-sharded across 8 GPUs"; every rank must hold the same hidden states): same edits, by GLOBAL feature id, same
     bits out.  `edits`: a set of edits instead of the scalar arguments (single-GPU `Sae` only); with a `RowEdits`,
-    `edit_group` as in `Sae.encode` (None: row b of a [G, S, d] input uses group b)."""
+    `edit_group` as in `Sae.encode` (None: row b of a [G, S, d] input uses group b).
+
+    `preserve_error=True` (single-GPU `Sae` only) returns hidden + (decode(encode(hidden, edits)) -
+    decode(encode(hidden))) in the hidden state's OWN dtype instead: the reconstruction error is carried along, so a
+    position no edit touches comes out bit-identical to the input (`out_dtype` with it is a ValueError).  Under no_grad it
+    is `Sae.intervene` with an edit (a scalar set_feature / zero_feature becomes a one-entry FeatureEdits: the hooks build it
+    once, at registration) and the hidden state itself -- no SAE call -- without one.  Under autograd it is
+    out = y_Q + (hidden - y_P).detach() from the differentiable encode and decode, y_P from a no_grad plain encode (y_Q.detach()
+    when nothing is edited): the error term is a constant of the forward, so the gradients with respect to the latents and
+    the SAE's parameters are exactly the reconstruct path's.  Its values agree with the fused path's within the derived
+    bound of tests/intervene_ref.py (the cancelled entries round differently), not bitwise."""
+    if preserve_error:
+        return _reconstruct_preserving(sae, hidden, set_feature, set_value, zero_feature, out_dtype, differentiable, edits,
+                                       edit_group)
     flat = hidden.reshape(-1, hidden.shape[-1])
     if isinstance(edits, RowEdits) or edit_group is not None:
         if not isinstance(sae, Sae):
@@ -48,6 +61,51 @@ def sae_reconstruct(sae, hidden: Tensor, *, set_feature: int = -1, set_value: fl
                                   zero_feature=zero_feature, **ed)
         out = sae.decode(acts, idx)
     return out.to(out_dtype or hidden.dtype).view(hidden.shape)
+
+
+def _scalar_edits(sae, set_feature: int, set_value: float, zero_feature: int) -> Optional[FeatureEdits]:
+    """The scalar hook arguments as a FeatureEdits (ZERO over SET, as the kernel applies them), or None without an edit."""
+    if set_feature < 0 and zero_feature < 0:
+        return None
+    return FeatureEdits(sae.num_latents, set={int(set_feature): float(set_value)} if set_feature >= 0 else None,
+                        zero=[int(zero_feature)] if zero_feature >= 0 else None, device=sae.device)
+
+
+def _reconstruct_preserving(sae, hidden: Tensor, set_feature: int, set_value: float, zero_feature: int, out_dtype,
+                            differentiable, edits, edit_group) -> Tensor:
+    """sae_reconstruct(preserve_error=True): see there."""
+    if out_dtype is not None:
+        raise ValueError("sae_reconstruct: preserve_error=True returns the hidden state's own dtype (unedited positions come "
+                         "out identical to the input); it does not take out_dtype")
+    if not isinstance(sae, Sae):
+        raise NotImplementedError("preserve_error runs on the single-GPU msae.Sae only: a feature-sharded engine "
+                                  "reconstructs (preserve_error=False)")
+    if edits is not None and (set_feature >= 0 or zero_feature >= 0):
+        raise ValueError("sae_reconstruct: pass either edits= or the scalar set_feature / zero_feature arguments, not both")
+    if edit_group is not None and not isinstance(edits, RowEdits):
+        raise ValueError("sae_reconstruct: edit_group names the groups of a RowEdits")
+    if differentiable is None:
+        differentiable = hidden.requires_grad
+    if not (torch.is_grad_enabled() and differentiable):
+        if edits is None:
+            edits = _scalar_edits(sae, set_feature, set_value, zero_feature)
+        if edits is None:
+            return hidden                       # nothing edited: the model is left untouched, exactly
+        with torch.no_grad():
+            return sae.intervene(hidden, edits, edit_group)
+    # autograd: today's differentiable reconstruction of the edited latents plus a CONSTANT error term
+    k = sae.cfg.k
+    shaped = hidden if isinstance(edits, RowEdits) else hidden.reshape(-1, hidden.shape[-1])
+    top = sae.encode(shaped, set_feature=set_feature, set_value=set_value, zero_feature=zero_feature, differentiable=True,
+                     edits=edits, edit_group=edit_group)
+    y_q = sae.decode(top.top_acts.reshape(-1, k), top.top_indices.reshape(-1, k)).view(hidden.shape)
+    if edits is None and set_feature < 0 and zero_feature < 0:
+        y_p = y_q.detach()
+    else:
+        with torch.no_grad():
+            plain = sae.encode(hidden.detach().reshape(-1, hidden.shape[-1]))
+            y_p = sae.decode(plain.top_acts, plain.top_indices).view(hidden.shape)
+    return (y_q + (hidden.detach().to(y_q.dtype) - y_p)).to(hidden.dtype)
 
 
 def _replace_first(outputs, new0):
@@ -141,7 +199,8 @@ def _steering_edits(sae, feature, k: float):
     return -1, FeatureEdits(sae.num_latents, set=table, device=sae.device)
 
 
-def clamp_features_max(sae, feature, hooked_module: torch.nn.Module, k: float = 10, graph_step: Optional[bool] = None):
+def clamp_features_max(sae, feature, hooked_module: torch.nn.Module, k: float = 10, graph_step: Optional[bool] = None,
+                       preserve_error: bool = False):
     """Register the steering hook (steering.py:102-128): on prefill (S != 1) the feature's latent
     is set to `k` before TopK; every call replaces the layer output by the fp16 reconstruction.
     `feature`: an int (the in-kernel edit), a sequence or tensor of ints (`latents[:, :, f] = k` with a list: all
@@ -149,9 +208,13 @@ def clamp_features_max(sae, feature, hooked_module: torch.nn.Module, k: float = 
     `sae`: an `Sae`, or a `ShardedSae` engine (the S = 1 decode steps then stream N/G rows of the encoder per rank
     and exchange 8 k_loc bytes; the decode of so few tokens is local on every rank).
     `graph_step`: replay the S = 1 step from a captured HIP graph (_DecodeStepGraph); default: on for a single-GPU `Sae`
-    under no_grad unless MSAE_HOOK_GRAPH=0."""
+    under no_grad unless MSAE_HOOK_GRAPH=0.
+    `preserve_error` (single-GPU `Sae` only): the prefill output is h + the decoded EDIT in h's own
+    dtype (`Sae.intervene`), the S = 1 steps return the layer output unchanged -- no SAE call, no captured graph."""
     import os
 
+    if preserve_error:
+        return _clamp_preserving(sae, hooked_module, _preserving_edits(sae, feature, k))
     if graph_step is None:
         graph_step = os.environ.get("MSAE_HOOK_GRAPH", "1") not in ("0", "")
     step_graph = _DecodeStepGraph() if (graph_step and isinstance(sae, Sae)) else None
@@ -174,6 +237,33 @@ def clamp_features_max(sae, feature, hooked_module: torch.nn.Module, k: float = 
     return [handle]
 
 
+def _preserving_edits(sae, feature, k: float) -> FeatureEdits:
+    """`feature` of clamp_features_max(preserve_error=True) -> the FeatureEdits of the prefill, built once."""
+    if not isinstance(sae, Sae):
+        raise NotImplementedError("preserve_error runs on the single-GPU msae.Sae only: a feature-sharded engine "
+                                  "reconstructs (preserve_error=False)")
+    set_feature, edits = _steering_edits(sae, feature, k)
+    return edits if edits is not None else _scalar_edits(sae, set_feature, float(k), -1)
+
+
+def _clamp_preserving(sae, hooked_module: torch.nn.Module, edits):
+    """The error-preserving steering hook of both clamps: prefill through Sae.intervene, S = 1 steps untouched."""
+    rows = isinstance(edits, RowEdits)
+
+    def hook(module, _, outputs):
+        h = outputs[0] if isinstance(outputs, tuple) else outputs
+        if h.shape[1] == 1:                     # a decode step: no clamp there, so nothing to add
+            return outputs
+        if rows and h.shape[0] != edits.G:
+            raise ValueError(f"clamp_features_rows: {edits.G} rows of features, a batch of {h.shape[0]}")
+        return _replace_first(outputs, sae_reconstruct(sae, h, edits=edits, preserve_error=True))
+
+    handle = hooked_module.register_forward_hook(hook)
+    handle.step_graph = None                    # (no _DecodeStepGraph: the S = 1 step makes no SAE call)
+    handle.edits = edits
+    return [handle]
+
+
 def _row_spec(element, k: float):
     """One element of clamp_features_rows' `features` -> a RowEdits group (None, a FeatureEdits or a dict spec)."""
     if element is None or isinstance(element, FeatureEdits):
@@ -188,14 +278,15 @@ def _row_spec(element, k: float):
 
 
 def clamp_features_rows(sae, features: Sequence, hooked_module: torch.nn.Module, k: float = 10,
-                        graph_step: Optional[bool] = None):
+                        graph_step: Optional[bool] = None, preserve_error: bool = False):
     """The steering hook for a BATCH whose rows steer different features: `features` has one element
     per batch row -- an int, a list of ints (all clamped to `k`), a mapping feature -> value, or None for an unedited row
     (the batch's baseline).  On prefill (S != 1) row b's latents are clamped per element b before TopK; every call replaces
     the whole [B, S, d] layer output by the fp16 reconstruction.  The tables are validated and uploaded once, here, as a
     RowEdits.  The S = 1 step of the batch ([B, 1, d], no edit) replays from a captured HIP graph like clamp_features_max's
     (`graph_step`: default on under no_grad unless MSAE_HOOK_GRAPH=0).  Single-GPU `Sae` only.  The prefill's batch size
-    must equal len(features) (ValueError)."""
+    must equal len(features) (ValueError).  `preserve_error`: as in clamp_features_max -- row b's prefill output is
+    h[b] + its decoded edit, a row of None and every S = 1 step keep the layer's output bit for bit."""
     import os
 
     if not isinstance(sae, Sae):
@@ -205,8 +296,10 @@ def clamp_features_rows(sae, features: Sequence, hooked_module: torch.nn.Module,
         raise ValueError("clamp_features_rows: features must be a sequence with one element per batch row")
     if graph_step is None:
         graph_step = os.environ.get("MSAE_HOOK_GRAPH", "1") not in ("0", "")
-    step_graph = _DecodeStepGraph() if graph_step else None
     edits = RowEdits(sae.num_latents, [_row_spec(f, k) for f in features], device=sae.device)
+    if preserve_error:
+        return _clamp_preserving(sae, hooked_module, edits)
+    step_graph = _DecodeStepGraph() if graph_step else None
 
     def hook(module, _, outputs):
         h = outputs[0] if isinstance(outputs, tuple) else outputs
@@ -227,10 +320,13 @@ def clamp_features_rows(sae, features: Sequence, hooked_module: torch.nn.Module,
 
 
 def attribution_sae_hook(sae_dict: Dict[str, Sae], module_to_name: Dict[torch.nn.Module, str],
-                         cache: Dict[str, Tensor], off_features=None, edit_group: Optional[Tensor] = None) -> Callable:
+                         cache: Dict[str, Tensor], off_features=None, edit_group: Optional[Tensor] = None,
+                         preserve_error: bool = False) -> Callable:
     """Hook body of get_model_forward_cache_with_sae (patching/utils.py:33-58).  `off_features`: None, an int, or a
     sequence / tensor of ints (`mask[:, off_features] = 0` takes any of them); or a RowEdits with `edit_group` as in
-    `Sae.encode`: another ablation per batch row."""
+    `Sae.encode`: another ablation per batch row.  `preserve_error`: the layer output is
+    h + (decode(ablated) - decode(plain)) in h's own dtype -- the ablation's effect in the model itself, not in a model that
+    runs on reconstructions; sae_reconstruct states the autograd rule."""
     per_module: dict = {}         # a list of features becomes one FeatureEdits per hooked Sae, built at its first call
 
     def hook(module, inputs, outputs):
@@ -238,10 +334,19 @@ def attribution_sae_hook(sae_dict: Dict[str, Sae], module_to_name: Dict[torch.nn
         name = module_to_name[module]
         sae = sae_dict[name]
         if name not in per_module:
-            per_module[name] = as_off_features(off_features, sae)
+            zero, edits = as_off_features(off_features, sae)
+            if preserve_error and zero >= 0:    # the scalar route as a one-entry table, built once per hooked Sae
+                if not isinstance(sae, Sae):
+                    raise NotImplementedError("preserve_error runs on the single-GPU msae.Sae only")
+                zero, edits = -1, _scalar_edits(sae, -1, 0.0, zero)
+            per_module[name] = (zero, edits)
         zero, edits = per_module[name]
-        out = sae_reconstruct(sae, h, zero_feature=zero, edits=edits, edit_group=edit_group,
-                              out_dtype=torch.float16, differentiable=torch.is_grad_enabled())
+        if preserve_error:
+            out = sae_reconstruct(sae, h, edits=edits, edit_group=edit_group, differentiable=torch.is_grad_enabled(),
+                                  preserve_error=True)
+        else:
+            out = sae_reconstruct(sae, h, zero_feature=zero, edits=edits, edit_group=edit_group,
+                                  out_dtype=torch.float16, differentiable=torch.is_grad_enabled())
         cache[name] = out
         return _replace_first(outputs, out)
 

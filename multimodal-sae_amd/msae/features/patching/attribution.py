@@ -38,11 +38,12 @@ os.environ.setdefault("TOKENIZERS_PARALLELISM", "false")
 
 class Attribution:
     def __init__(self, model, tokenizer, sae_path: str, data_path: str, selected_sae: str = None,
-                 image_processor=None) -> None:
+                 image_processor=None, preserve_error: bool = False) -> None:
         from PIL import Image
 
         self.model = model
         self.image_processor = image_processor
+        self.preserve_error = bool(preserve_error)
         if selected_sae is not None:
             if not os.path.exists(sae_path):
                 sae = Sae.load_from_hub(sae_path, hookpoint=selected_sae, device=model.device)
@@ -70,10 +71,14 @@ class Attribution:
                                "attention_mask": prompt_ids.ne(tokenizer.pad_token_id)}, answer_ids)
 
     @classmethod
-    def from_parts(cls, model, sae_dict: Dict[str, Sae], inputs: dict, answer_ids: Tensor) -> "Attribution":
+    def from_parts(cls, model, sae_dict: Dict[str, Sae], inputs: dict, answer_ids: Tensor,
+                   preserve_error: bool = False) -> "Attribution":
         """Build from already-tokenised inputs (tests, programmatic use): `inputs` is what the model's
-        forward takes, `answer_ids` [B, 2] = (correct token id, baseline token id)."""
+        forward takes, `answer_ids` [B, 2] = (correct token id, baseline token id).  `preserve_error` (DESIGN.md section
+        7i; method "exact"): the hooked layers keep the SAE's reconstruction error, so the clean run is the model itself and
+        `clean - corrupted` is the decoded ablation alone."""
         self = cls.__new__(cls)
+        self.preserve_error = bool(preserve_error)
         self.model, self.image_processor, self.data_path, self.data = model, None, None, None
         self._setup(sae_dict, inputs, answer_ids)
         return self
@@ -113,6 +118,8 @@ class Attribution:
         if method == "batched" and any(isinstance(i, list) for i in indices):
             raise ValueError("method='batched' scores one feature at a time (its linearisation is per feature): "
                              "ablate a group of features with method='exact'")
+        if method == "batched" and getattr(self, "preserve_error", False):
+            raise ValueError("method='batched' linearises the reconstruction path: preserve_error goes with method='exact'")
         if method == "batched":
             out = self._batched(indices)
         elif method == "exact" and int(features_per_pass) > 1:
@@ -125,14 +132,17 @@ class Attribution:
             dist.barrier()
         return out
 
+    def _pe(self) -> dict:
+        return {"preserve_error": True} if getattr(self, "preserve_error", False) else {}
+
     def _per_feature(self, indices: list):
         attribution_dict = collections.defaultdict(list)
         with torch.no_grad():    # the clean run does not depend on the feature and is never differentiated
             _, clean_cache = get_model_forward_cache_with_sae(self.model, self.inputs, self.sae_dict,
-                                                              self.module_to_name)
+                                                              self.module_to_name, **self._pe())
         for idx in indices:
             corrupted_logits, corrupted_cache = get_model_forward_cache_with_sae(
-                self.model, self.inputs, self.sae_dict, self.module_to_name, off_features=idx)
+                self.model, self.inputs, self.sae_dict, self.module_to_name, off_features=idx, **self._pe())
             for tensor in corrupted_cache.values():
                 tensor.retain_grad()
             get_model_backward_cache_with_sae(logits=corrupted_logits, metrics=self.metric)
@@ -168,13 +178,14 @@ class Attribution:
         answers = self.answer_ids.repeat(G, 1)
         row_group = torch.arange(G, device=dev, dtype=torch.int32).repeat_interleave(B)      # batch row -> its copy
         with torch.no_grad():    # the clean run, once, on the same repeated batch
-            _, clean_cache = get_model_forward_cache_with_sae(self.model, inputs, self.sae_dict, self.module_to_name)
+            _, clean_cache = get_model_forward_cache_with_sae(self.model, inputs, self.sae_dict, self.module_to_name,
+                                                              **self._pe())
         for lo in range(0, len(indices), G):
             chunk = indices[lo:lo + G]
             groups = [dict(zero=e if isinstance(e, list) else [e]) for e in chunk] + [None] * (G - len(chunk))
             edits = RowEdits(sae0.num_latents, groups, device=dev)
             logits, cache = get_model_forward_cache_with_sae(self.model, inputs, self.sae_dict, self.module_to_name,
-                                                             off_features=edits, edit_group=row_group)
+                                                             off_features=edits, edit_group=row_group, **self._pe())
             for tensor in cache.values():
                 tensor.retain_grad()
             (G * get_logit_diff(logits, answers)).backward()

@@ -35,7 +35,7 @@ def get_logit_diff(logits: Tensor, answer_token_indices: Tensor) -> Tensor:
 def sae_splice_hook(sae_dict: Dict[str, Sae], module_to_name: Dict[torch.nn.Module, str],
                     cache: Dict[str, Tensor], off_features=None,
                     keep_latents: Optional[Dict[str, Tuple[Tensor, Tensor]]] = None, extra_k: int = 0,
-                    edit_group: Optional[Tensor] = None) -> Callable:
+                    edit_group: Optional[Tensor] = None, preserve_error: bool = False) -> Callable:
     """Forward-hook body of get_model_forward_cache_with_sae (utils.py:33-58).  `off_features`: None, an int (the edit
     inside the fused kernel), or a sequence / tensor of ints as `mask[:, off_features] = 0` takes (one FeatureEdits per
     hooked Sae, built at its first call: over-fetching encode + list edit); or a
@@ -43,7 +43,15 @@ def sae_splice_hook(sae_dict: Dict[str, Sae], module_to_name: Dict[torch.nn.Modu
     batch row in one forward (section 7g; not with `extra_k`).  `keep_latents`
     (optional) receives the (top_acts, top_indices) of every hooked module -- the batched
     attribution needs them; `extra_k` asks the encoder for that many latents beyond k (the
-    reconstruction still uses the first k)."""
+    reconstruction still uses the first k).  `preserve_error` (not with `extra_k` / `keep_latents`):
+    the layer keeps the SAE's reconstruction error -- msae.features.hooks.attribution_sae_hook(preserve_error=True)."""
+    if preserve_error:
+        if extra_k or keep_latents is not None:
+            raise ValueError("sae_splice_hook: preserve_error is not available with extra_k / keep_latents (the batched "
+                             "linearisation is a statement about the reconstruction)")
+        from ..hooks import attribution_sae_hook
+
+        return attribution_sae_hook(sae_dict, module_to_name, cache, off_features, edit_group, preserve_error=True)
 
     per_module: dict = {}
 
@@ -94,12 +102,13 @@ def sae_splice_hook(sae_dict: Dict[str, Sae], module_to_name: Dict[torch.nn.Modu
 def get_model_forward_cache_with_sae(model: torch.nn.Module, inputs: Dict[str, Any], sae_dict: Dict[str, Sae],
                                      module_to_name: Dict[torch.nn.Module, str], off_features=None,
                                      keep_latents: Optional[dict] = None, extra_k: int = 0,
-                                     edit_group: Optional[Tensor] = None):
+                                     edit_group: Optional[Tensor] = None, preserve_error: bool = False):
     """Run the model with every hooked module's output replaced by its SAE reconstruction.
     `off_features`: None, an int, or a sequence / tensor of features zeroed together; or a RowEdits (+ `edit_group`).
     -> (logits, {module name: fp16 reconstruction [B, S, d]})   (utils.py:21-71)."""
     cache: Dict[str, Tensor] = {}
-    hook = sae_splice_hook(sae_dict, module_to_name, cache, off_features, keep_latents, extra_k, edit_group)
+    hook = sae_splice_hook(sae_dict, module_to_name, cache, off_features, keep_latents, extra_k, edit_group,
+                           **({"preserve_error": True} if preserve_error else {}))
     handles = [mod.register_forward_hook(hook) for mod in module_to_name.keys()]
     try:
         outputs = model(**inputs)

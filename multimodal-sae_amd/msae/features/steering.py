@@ -19,16 +19,24 @@ class SteeringController:
     at every hooked forward).
     `batch_features` = B > 1 (single-GPU `Sae` only): `run()` takes the feature list in chunks of B, repeats the
     processor's inputs along the batch, generates once per chunk and decodes each row; same result keys and values as
-    the default B = 1, which runs the reference's loop unchanged.  The rows share one prompt."""
+    the default B = 1, which runs the reference's loop unchanged.  The rows share one prompt.
+    `preserve_error` (single-GPU `Sae` only): the hooks add the decoded clamp to the layer's own output
+    instead of replacing it by the reconstruction, so `clamped_resps` differs from `original_resps` -- the un-hooked model --
+    by the edit alone."""
 
     def __init__(self, sae, module_name: str, feature_idx: List[int], model, processor,
-                 prompt: str, image_path: str = None, k: float = 50, batch_features: int = 1):
+                 prompt: str, image_path: str = None, k: float = 50, batch_features: int = 1,
+                 preserve_error: bool = False):
         if int(batch_features) < 1:
             raise ValueError(f"batch_features must be >= 1, got {batch_features}")
         if int(batch_features) > 1 and not isinstance(sae, Sae):
             raise NotImplementedError("batch_features > 1 runs on the single-GPU msae.Sae only: a feature-sharded engine "
                                       "takes one feature per generation")
+        if preserve_error and not isinstance(sae, Sae):
+            raise NotImplementedError("preserve_error runs on the single-GPU msae.Sae only: a feature-sharded engine "
+                                      "reconstructs")
         self.batch_features = int(batch_features)
+        self.preserve_error = bool(preserve_error)
         self.sae, self.feature_idx, self.model, self.k = sae, feature_idx, model, k
         self.module_name, self.processor = module_name, processor
         self.hooked_module = model.language_model.get_submodule(module_name)
@@ -47,6 +55,8 @@ class SteeringController:
         self.inputs = processor(images=self.image, text=self.prompt, return_tensors="pt").to(model.device)
 
     def clamp_features_max(self, sae, feature: int, hooked_module, k: float = 10):
+        if self.preserve_error:
+            return clamp_features_max(sae, feature, hooked_module, k=k, preserve_error=True)
         return clamp_features_max(sae, feature, hooked_module, k=k)
 
     def _generate(self) -> str:
@@ -92,7 +102,8 @@ class SteeringController:
         feats = list(self.feature_idx)
         for lo in range(0, len(feats), B):
             chunk = feats[lo:lo + B]                 # (a short last chunk generates a smaller batch)
-            handles = clamp_features_rows(self.sae, chunk, self.hooked_module, k=self.k)
+            handles = clamp_features_rows(self.sae, chunk, self.hooked_module, k=self.k,
+                                          **({"preserve_error": True} if self.preserve_error else {}))
             try:
                 texts = self._generate_rows(len(chunk))
             finally:

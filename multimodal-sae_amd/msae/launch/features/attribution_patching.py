@@ -4,7 +4,8 @@
 One process per GPU under torchrun; the feature axis is chunked over the ranks, rank 0 gathers and
 writes `<save_dir>/<model>_<selected_sae>.safetensors` with one [n_features * B, S] tensor per hooked
 module, as the reference does.  `--method batched` computes every feature from one forward + backward
-(msae/features/patching/attribution.py) instead of 2 forwards + 1 backward per feature.
+(msae/features/patching/attribution.py) instead of 2 forwards + 1 backward per feature.  `--preserve-error` (method exact)
+ablates in the model itself: the hooked layer's output keeps the SAE's reconstruction error.
 """
 from __future__ import annotations
 
@@ -27,7 +28,8 @@ def main(cfg: AttributionConfig):
     model, processor = maybe_load_llava_model(cfg.model, rank, torch.float16, None)
     attribution = Attribution(model, tokenizer, sae_path=cfg.sae_path, data_path=cfg.data_path,
                               selected_sae=cfg.selected_sae,
-                              image_processor=processor.image_processor if processor is not None else None)
+                              image_processor=processor.image_processor if processor is not None else None,
+                              preserve_error=cfg.preserve_error)
     if ddp:
         sae = next(iter(attribution.sae_dict.values()))
         indices = torch.arange(sae.num_latents).chunk(world)[rank]

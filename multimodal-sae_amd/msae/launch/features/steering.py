@@ -33,11 +33,17 @@ def parse_argument(argv=None):
     p.add_argument("--batch-features", "--batch_features", type=int, default=1,
                    help="(new) steer this many features in the rows of ONE generate (another clamp per batch row); "
                         "1 = the reference's loop.  Same output file.  Not with --shard-sae")
+    p.add_argument("--preserve-error", "--preserve_error", action="store_true",
+                   help="(new) add the decoded clamp to the layer's own output instead of replacing it by the SAE "
+                        "reconstruction: the steered generation differs from the original by the edit alone.  Not with "
+                        "--shard-sae")
     args = p.parse_args(argv)
     if args.batch_features < 1:
         p.error("--batch-features must be >= 1")
     if args.batch_features > 1 and args.shard_sae:
         p.error("--batch-features > 1 runs on the single-GPU Sae: it cannot be combined with --shard-sae")
+    if args.preserve_error and args.shard_sae:
+        p.error("--preserve-error runs on the single-GPU Sae: it cannot be combined with --shard-sae")
     return args
 
 
@@ -65,7 +71,7 @@ def main(argv=None):
         result = SteeringController(sae=engine, module_name=module_name, feature_idx=feature_idx,
                                     prompt=args.text, model=model, processor=processor,
                                     image_path=args.image_path, k=args.clamp_value,
-                                    batch_features=args.batch_features).run()
+                                    batch_features=args.batch_features, preserve_error=args.preserve_error).run()
         if ddp and not shard:
             gathered = [None] * world
             dist.gather_object(result, gathered if rank == 0 else None, dst=0)

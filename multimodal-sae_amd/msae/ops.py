@@ -997,6 +997,112 @@ def edit_topk_rows(vals_in: Tensor, idx_in: Tensor, group_of: Tensor, row_edits,
     return (vals, idx, edited) if want_mask else (vals, idx)
 
 
+# ---- error-preserving interventions (csrc/delta_decode.hip) -------------------------------------------
+DELTA_DECODE_MAX_K = 4096           # the encoder's own limit on k + E
+
+
+def _list_rows(vals: Tensor, idx: Tensor, k: int) -> Tuple[Tensor, Tensor, int]:
+    """A top-k list [..., k] -> (vals f32, idx, leading dimension) the kernel reads in place: a 2-d view with unit column
+    stride (the first k columns of an over-fetched [T, kk] output) is passed with its row stride, anything else contiguous."""
+    v, i = vals.detach(), idx.detach()
+    if v.dtype != torch.float32:
+        v = v.to(torch.float32)
+    T = v.numel() // k
+    if (v.dim() == 2 and i.dim() == 2 and v.stride(1) == 1 and i.stride(1) == 1 and v.stride(0) == i.stride(0) and
+            (T == 1 or v.stride(0) >= k)):
+        return v, i, max(int(v.stride(0)), k)
+    return v.contiguous(), i.contiguous(), k
+
+
+def _delta_decode_into(x: Tensor, plain_acts: Tensor, plain_idx: Tensor, edit_acts: Tensor, edit_idx: Tensor, W_dec: Tensor,
+                       out: Tensor) -> None:
+    dev = _hip.require_device(x, plain_acts, plain_idx, edit_acts, edit_idx, W_dec, out)
+    lib = _hip.load()
+    W = _f32c(W_dec)
+    N, d = W.shape
+    k = plain_acts.shape[-1]
+    T = x.numel() // d
+    if T == 0:
+        return
+    pv, pi, ld_p = _list_rows(plain_acts, plain_idx, k)
+    qv, qi, ld_q = _list_rows(edit_acts, edit_idx, k)
+    wide = pi.dtype == torch.int64
+    fn, name = (lib.msae_delta_decode_i64_f32, "msae_delta_decode_i64_f32") if wide else \
+        (lib.msae_delta_decode_f32, "msae_delta_decode_f32")
+    flag = _bounds_flag(dev)
+    with torch.cuda.device(dev):
+        _hip.check(fn(_hip.ptr(x), _hip.DTYPE_CODE[x.dtype], _hip.ptr(pv), _hip.ptr(pi), ld_p, _hip.ptr(qv), _hip.ptr(qi), ld_q,
+                      _hip.ptr(W), T, k, N, d, _hip.ptr(out), _hip.ptr(flag), _hip.stream_of(x)), name)
+    _check_bounds(flag, name)
+
+
+@torch.library.custom_op("msae::delta_decode", mutates_args=())
+def _delta_decode(x: Tensor, plain_acts: Tensor, plain_idx: Tensor, edit_acts: Tensor, edit_idx: Tensor,
+                  W_dec: Tensor) -> Tensor:
+    xa = x.detach().contiguous()
+    out = torch.empty_like(xa)
+    _delta_decode_into(xa, plain_acts, plain_idx, edit_acts, edit_idx, W_dec, out)
+    return out
+
+
+@_delta_decode.register_fake
+def _(x, plain_acts, plain_idx, edit_acts, edit_idx, W_dec):
+    return torch.empty_like(x, memory_format=torch.contiguous_format)
+
+
+@torch.library.custom_op("msae::delta_decode_out", mutates_args=("out",))
+def _delta_decode_out(x: Tensor, plain_acts: Tensor, plain_idx: Tensor, edit_acts: Tensor, edit_idx: Tensor,
+                      W_dec: Tensor, out: Tensor) -> None:
+    _delta_decode_into(x.detach(), plain_acts, plain_idx, edit_acts, edit_idx, W_dec, out)
+
+
+@_delta_decode_out.register_fake
+def _(x, plain_acts, plain_idx, edit_acts, edit_idx, W_dec, out):
+    return None
+
+
+def delta_decode(x: Tensor, plain_acts: Tensor, plain_idx: Tensor, edit_acts: Tensor, edit_idx: Tensor, W_dec: Tensor,
+                 out: Optional[Tensor] = None) -> Tensor:
+    """x + (decode(edited list) - decode(plain list)) in x's dtype, gathering only the entries in which the two lists
+    differ (include/msae.h, "error-preserving interventions"): a token whose lists agree keeps x's own bits.
+    x [..., d] f32 / bf16 / f16; plain_acts / plain_idx and edit_acts / edit_idx [..., k] with x's leading shape (or [T, k]),
+    idx int32 or int64 (one type for both lists); the plain list may be the non-contiguous `[:, :k]` view of an over-fetched
+    [T, kk] encode -- it is read in place.  W_dec [N, d].  `out`: a contiguous tensor of x's shape and dtype, or x itself
+    (in place: untouched tokens are not even written).  Nothing is read back; bad arguments raise ValueError before any
+    device work."""
+    if x.dim() < 1 or W_dec.dim() != 2 or x.shape[-1] != W_dec.shape[1]:
+        raise ValueError(f"delta_decode: x [..., d] and W_dec [N, d] must share d, got {tuple(x.shape)} and {tuple(W_dec.shape)}")
+    if x.dtype not in _hip.DTYPE_CODE:
+        raise ValueError(f"delta_decode: x must be float32, bfloat16 or float16, got {x.dtype}")
+    if plain_acts.shape != plain_idx.shape or edit_acts.shape != edit_idx.shape or plain_acts.shape != edit_acts.shape \
+            or plain_acts.dim() < 1:
+        raise ValueError("delta_decode: the four list tensors must share one shape [..., k], got "
+                         f"{tuple(plain_acts.shape)}, {tuple(plain_idx.shape)}, {tuple(edit_acts.shape)}, {tuple(edit_idx.shape)}")
+    k = plain_acts.shape[-1]
+    if not 1 <= k <= DELTA_DECODE_MAX_K:
+        raise ValueError(f"delta_decode: k must be in [1, {DELTA_DECODE_MAX_K}], got {k}")
+    T = x.numel() // max(x.shape[-1], 1)
+    if x.shape[-1] < 1 or plain_acts.numel() != T * k or \
+            (plain_acts.dim() != 2 and tuple(plain_acts.shape[:-1]) != tuple(x.shape[:-1])):
+        raise ValueError(f"delta_decode: the lists must hold one row per token of x {tuple(x.shape)}, got "
+                         f"{tuple(plain_acts.shape)}")
+    if plain_idx.dtype != edit_idx.dtype or plain_idx.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"delta_decode: plain_idx and edit_idx must both be int32 or both int64, got {plain_idx.dtype} and "
+                         f"{edit_idx.dtype}")
+    if plain_acts.dtype != torch.float32 or edit_acts.dtype != torch.float32:
+        raise ValueError(f"delta_decode: the lists' values must be float32, got {plain_acts.dtype} and {edit_acts.dtype}")
+    if out is not None:
+        if out.shape != x.shape or out.dtype != x.dtype or out.device != x.device or not out.is_contiguous():
+            raise ValueError(f"delta_decode: out must be a contiguous {x.dtype} tensor of shape {tuple(x.shape)} on {x.device}")
+        if not x.is_contiguous():       # (then out is not x: out is contiguous)
+            x = x.contiguous()
+    _no_grad_inputs("ops.delta_decode", x, plain_acts, edit_acts)
+    if out is None:
+        return _delta_decode(x, plain_acts, plain_idx, edit_acts, edit_idx, W_dec)
+    _delta_decode_out(x, plain_acts, plain_idx, edit_acts, edit_idx, W_dec, out)
+    return out
+
+
 def shard_candidates(x: Tensor, b_enc_shard: Optional[Tensor], b_dec: Optional[Tensor], prepared_shard: Tensor,
                      N_shard: int, k: int, row_offset: int, C: int, set_feature: int = -1,
                      zero_feature: int = -1) -> Tensor:

@@ -310,6 +310,46 @@ class Sae(nn.Module):
         raise ValueError(f"Sae.encode: edit_group must have shape {lead} (per token)" +
                          (f" or {lead[:1]} (per batch row)" if x.dim() == 3 else "") + f", got {tuple(edit_group.shape)}")
 
+    def intervene(self, x: Tensor, edits, edit_group: Optional[Tensor] = None, *, exact: bool = False,
+                  certified: bool = False) -> Tensor:
+        """Error-preserving intervention: x + (decode(encode(x, edits)) - decode(encode(x))) in x's
+        shape and dtype (f32 / bf16 / f16).  The hidden state keeps the SAE's reconstruction error and moves by the decoded
+        EDIT alone; a token no edit touches keeps its own bits.  `edits`: a msae.features.FeatureEdits or RowEdits,
+        `edit_group` as in `encode`.  One over-fetching encode (k + E, or k + E_max), the list edit, and ops.delta_decode, which
+        gathers only the entries the two lists differ in -- the over-fetch's first k columns ARE the plain list.  The bits:
+        include/msae.h, "error-preserving interventions".  Inference only: no host synchronisation, allocations through torch
+        alone (capturable in a HIP graph); with gradients enabled on x it raises RuntimeError -- the hooks' autograd path is
+        `msae.features.hooks.sae_reconstruct(preserve_error=True)`."""
+        if edits is None or not (hasattr(edits, "check") and (hasattr(edits, "offsets") or hasattr(edits, "E"))):
+            raise ValueError("Sae.intervene: edits must be a msae.features.FeatureEdits or RowEdits")
+        if self.W_dec is None:
+            raise ValueError("Sae.intervene: this Sae has no decoder")
+        if x.dim() < 1 or x.shape[-1] != self.d_in:
+            raise ValueError(f"Sae.intervene: x must be [..., {self.d_in}], got {tuple(x.shape)}")
+        if x.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+            raise ValueError(f"Sae.intervene: x must be float32, bfloat16 or float16, got {x.dtype}")
+        edits.check(self.num_latents, self.cfg.k, self.encoder.weight.device)
+        rows = hasattr(edits, "offsets")
+        if edit_group is not None and not rows:
+            raise ValueError("Sae.intervene: edit_group names the groups of a msae.features.RowEdits; it does not go with a "
+                             "FeatureEdits")
+        if rows:
+            edit_group = self._token_groups(x, edits, edit_group)
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise RuntimeError("Sae.intervene is an inference path: call it under torch.no_grad() or on a detached input "
+                               "(sae_reconstruct(preserve_error=True) is the differentiable form)")
+        k = self.cfg.k
+        with torch.no_grad():
+            flat = x.reshape(-1, self.d_in)
+            acts, idx, _ = ops.encode_topk(flat, self.encoder.weight, self.encoder.bias, self.b_dec, self._prepared_weights(),
+                                           k + (edits.E_max if rows else edits.E), exact=exact, certified=certified)
+            if rows:
+                q_acts, q_idx = ops.edit_topk_rows(acts, idx, edit_group.reshape(-1), edits, self.num_latents, k)
+            else:
+                q_acts, q_idx = ops.edit_topk(acts, idx, edits.feat, edits.val, edits.kind, self.num_latents, k)
+            out = ops.delta_decode(flat, acts[:, :k], idx[:, :k], q_acts, q_idx, self.W_dec)
+        return out.view(x.shape)
+
     def decode(self, top_acts: Tensor, top_indices: Tensor) -> Tensor:
         assert self.W_dec is not None, "Decoder weight was not initialized."
         # the module-level seam, as the reference (sae.py:190): `decoder_impl(top_indices, top_acts, W_dec.mT) + b_dec`.  The
