@@ -469,7 +469,8 @@ __device__ __forceinline__ void write_token(const RescoreArgs &p, const RescoreT
 // LEAN (PHASE 1 / 2): the PHASE kernels are chains of dependent steps of one lone workgroup per token, i.e. latency; how many
 // tokens a CU works on at a time is set by the LDS a workgroup claims, and that is sized for the worst token (the whole list:
 // 16-32 KB) although nearly every token is done with a sorted prefix of 128-512 keys.  A LEAN launch claims the prefix only
-// (6 KB at k = 32: 28 tokens per CU instead of 4-7) and LEAVES a token to the full-size launch behind it -- before any side
+// (6 KB at k = 32: 24 tokens per CU instead of 4-7 -- 6 waves per SIMD, the limit of the kernels' 106 SGPRs, not the 7 of their
+// 70-72 VGPRs: profiles/rescore_residency.txt) and LEAVES a token to the full-size launch behind it -- before any side
 // effect -- the moment it would need the whole list (a full sort, a candidate behind the prefix) or a follow-up round: every
 // `if constexpr (LEAN) { ... defer_token(); return; }` below stands in front of the steps with side effects (phase1_emit, write_token).
 template <int NW, bool EXT = false, bool LDSA = false, int PHASE = 0, bool LEAN = false>   // NW waves per token: 1 for k <= 64, 4 for larger k (longer lists)
