@@ -32,6 +32,7 @@
  *   msae_edit_topk_f32       hook edits with a feature LIST features/steering.py:113-114, patching/utils.py:43-48
  *   msae_edit_topk_rows_f32  the same with one table per token (a feature per batch row of one generate)
  *   msae_delta_decode_f32    x + decode(edited) - decode(plain): error-preserving hooks (no reference counterpart)
+ *   msae_recon_curve_f32     reconstruction error at several sparsities in one pass (sae.py:190-202 per checkpoint)
  *
  * Numerics contract: all dot products are ascending-k f32 fused
  * multiply-add chains (v_mfma_f32_32x32x2_f32 / v_fma_f32), bit-identical to oracle/sae_oracle.c.
@@ -669,6 +670,47 @@ int msae_delta_decode_f32(const void *x, int x_dtype, const float *plain_vals, c
 int msae_delta_decode_i64_f32(const void *x, int x_dtype, const float *plain_vals, const int64_t *plain_idx, int ld_plain,
                               const float *edit_vals, const int64_t *edit_idx, int ld_edit, const float *W_dec, int T,
                               int k, int N, int d, void *out, int32_t *status, void *stream);
+
+/* ---- reconstruction error against sparsity (Sae.recon_error, msae.features.ReconStats) ------------
+ * The canonical top-k list is value descending, index ascending, so its first kappa columns are the top-kappa list, and
+ * msae_decode_f32 is a slot-ordered fma chain from +0: ONE pass over the k decoder rows that stops at C checkpoints gives the
+ * error of the kappa-sparse reconstruction at every checkpoint.  x is read once and no [T][d] reconstruction is written.
+ *   x [T][d]                          the hidden states, x_dtype MSAE_F32 / MSAE_BF16 / MSAE_F16
+ *   vals / idx [T][ld]                the list in the first k columns of each row (an over-fetched list is passed as it
+ *                                     is, ld = kk)
+ *   W_dec f32 [N][d], b_dec f32 [d]   both required
+ *   ks int32 [C]                      the checkpoints, a HOST array: copied into the launch arguments during the call
+ *   mom f32 [T][C][3]                 (|e|^2, x . r, |r|^2) per token and checkpoint
+ *   xx f32 [T]                        |x|^2 per token
+ *   status int32 [1] or NULL          bit 0 is ORed in when an entry's feature lies outside [0, N), as msae_decode_f32 does
+ * Asynchronous on `stream`; allocates nothing, needs no workspace, never synchronises.  MSAE_EINVAL: a null pointer
+ * (`status` may be null), k < 1, k > 4096, ld < k, T < 0, N < 1, d < 1, C outside [1, MSAE_RECON_MAX_CHECKPOINTS], ks not
+ * strictly ascending or outside [0, k], a bad dtype code.  T == 0 returns 0.
+ * Contract, per token t (nothing depends on T or on the other tokens):
+ *   1. Checkpoints.  0 <= ks[0] < ks[1] < ... < ks[C-1] <= k.  kappa = 0 is the reconstruction by b_dec alone.
+ *   2. Reconstruction.  r_kappa[c] = (the f32 chain acc = fmaf(v_j, W_dec[f_j][c], acc) over the slots j < kappa in slot
+ *      order, from acc = +0) + b_dec[c], one f32 add behind the chain.  An entry with v_j == +-0 is skipped; an entry whose
+ *      f_j lies outside [0, N) is skipped and flagged in `status`.  This is msae_decode_f32's own rule, so r_kappa is
+ *      BIT-IDENTICAL to msae_decode_f32 over the first kappa columns.  No memory is indexed by a feature that was not
+ *      range-checked: a hostile list -- repeated features, any order -- follows the same rule.
+ *   3. Error.  e_kappa[c] = r_kappa[c] - f32(x[t][c]), one f32 subtract (the up-cast of bf16 / f16 is exact).
+ *   4. Moments.  mom[t][i] = (sum_c e^2, sum_c x r, sum_c r^2) at ks[i] and xx[t] = sum_c x^2, f32 sums over the d columns
+ *      of products formed by fmaf, in this order: a lane owns 4 consecutive columns (1 on the scalar path) of a slab of 1024
+ *      (256) columns and chains them in ascending order from +0; the 64 lanes of a wave are added by an xor butterfly,
+ *      partner distance 32, 16, ..., 1 (a lane past d holds +0); the four waves as ((w0 + w1) + w2) + w3; the slabs in
+ *      ascending order from +0.  The order depends on d and on which load path ran, never on T, the grid or timing: no
+ *      floating-point atomics.  Token t's outputs are the same bits alone or in any batch, in any call.
+ *   5. A non-finite x[t][c] makes token t's moments non-finite and touches no other token.
+ * Layout: one workgroup of 256 threads per token, the list in LDS (8 k bytes); 16-byte loads per lane when d % 4 == 0 and
+ * W_dec, b_dec, x are aligned to 4 elements, one column per lane otherwise. */
+#define MSAE_RECON_MAX_CHECKPOINTS 16
+int msae_recon_curve_f32(const void *x, int x_dtype, const float *vals, const int32_t *idx, int ld, const float *W_dec,
+                         const float *b_dec, int T, int k, int N, int d, const int32_t *ks, int C, float *mom, float *xx,
+                         int32_t *status, void *stream);
+/* the same reading 64-bit indices (msae_encode_topk_i64's output type) */
+int msae_recon_curve_i64_f32(const void *x, int x_dtype, const float *vals, const int64_t *idx, int ld, const float *W_dec,
+                             const float *b_dec, int T, int k, int N, int d, const int32_t *ks, int C, float *mom, float *xx,
+                             int32_t *status, void *stream);
 
 /* ---- merge of per-shard results (feature-sharded encode; no reference counterpart) ----
  * gathered: int32 [G][2][T][kl], the all-gather of each rank's packed block [2][T][kl]

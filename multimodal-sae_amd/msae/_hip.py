@@ -132,6 +132,10 @@ PROTOTYPES = {
                                       c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "msae_delta_decode_i64_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
                                           c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "msae_recon_curve_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                                     c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "msae_recon_curve_i64_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
+                                         c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "msae_merge_topk": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "msae_compact_flags": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "msae_merge_topk_masked": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,

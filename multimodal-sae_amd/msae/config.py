@@ -51,6 +51,10 @@ class CacheConfig:
     """Segments of the co-activation counters: token, window or image (default: image on cache_image, token on cache)"""
     coact_features: Optional[str] = None
     """Filter-format json {module: [ids]} of the co-activation query features (default: --filters_path)"""
+    recon_stats: bool = False
+    """Also measure every SAE's reconstruction error against sparsity and position (recon_stats.safetensors per module)"""
+    recon_ks: Optional[str] = None
+    """Comma-separated checkpoints of --recon_stats, e.g. 0,1,2,4,8,16,32 (default: powers of two up to k, and k)"""
 
     def to_dict(self):
         return dataclasses.asdict(self)
@@ -108,7 +112,31 @@ def parse_cache_config(argv: Optional[Sequence[str]] = None) -> CacheConfig:
         p.error(f"--coact_pool must be one of {', '.join(COACT_POOLS)}, got {cfg.coact_pool!r}")
     if cfg.coact and not (cfg.coact_features or cfg.filters_path):
         p.error("--coact needs query features: give --coact_features or --filters_path")
+    if cfg.recon_ks is not None:
+        try:
+            recon_ks_list(cfg.recon_ks)
+        except ValueError as e:
+            p.error(str(e))
     return cfg
+
+
+def recon_ks_list(text: str) -> list:
+    """'0,1,2,4' -> [0, 1, 2, 4]: non-negative, strictly ascending, at most 16."""
+    try:
+        ks = [int(t) for t in text.split(",")]
+    except ValueError:
+        raise ValueError(f"--recon_ks must be comma-separated integers, got {text!r}") from None
+    if not 1 <= len(ks) <= 16 or ks[0] < 0 or any(a >= b for a, b in zip(ks, ks[1:])):
+        raise ValueError(f"--recon_ks must be 1 to 16 strictly ascending non-negative integers, got {text!r}")
+    return ks
+
+
+def recon_kwargs(cfg: CacheConfig, position_edges=(0,)) -> Optional[dict]:
+    """The `recon=` argument of the feature caches for a parsed command line (None without --recon_stats): the checkpoints
+    of --recon_ks (None: every SAE's own default) and the launcher's position groups."""
+    if not cfg.recon_stats:
+        return None
+    return dict(ks=None if cfg.recon_ks is None else recon_ks_list(cfg.recon_ks), position_edges=tuple(position_edges))
 
 
 COACT_POOLS = ("token", "window", "image")

@@ -19,7 +19,13 @@ and, with `coact=` (opt-in; no reference counterpart), the co-activation counter
     <save_dir>/<module>/Rank{r}_coact.safetensors              per rank
     <save_dir>/<module>/coact.safetensors                      the ranks added in rank order by the concat
 
-with keys `locations [nnz,3] int64 = (row, pos, feature)` and `activations [nnz] f32`, which is what
+and, with `recon=` (opt-in; no reference counterpart), the reconstruction error of every SAE against sparsity and position
+(msae/features/recon.py), over exactly the positions the cache records, padding included:
+
+    <save_dir>/<module>/Rank{r}_recon_stats.safetensors        per rank
+    <save_dir>/<module>/recon_stats.safetensors                the ranks added in rank order by the concat
+
+The split files have keys `locations [nnz,3] int64 = (row, pos, feature)` and `activations [nnz] f32`, which is what
 `features/loader.py:143-196` (FeatureDataset) reads.
 
 What changed underneath: the reference computes dense `[B,S,N]` latents, `torch.topk`, a second
@@ -46,6 +52,7 @@ from torch import Tensor
 from .. import ops
 from ..sae import Sae
 from .coact import CoactStats
+from .recon import ReconStats
 from .stats import FeatureStats
 
 
@@ -61,7 +68,7 @@ class Cache:
 
     def __init__(self, shard_size: int, filters: Optional[Dict[str, Tensor]] = None,
                  batch_size: int = 64, spill_dir: Optional[str] = None, device_budget_bytes: int = 256 << 20,
-                 stats: Optional[dict] = None, coact: Optional[dict] = None):
+                 stats: Optional[dict] = None, coact: Optional[dict] = None, recon: Optional[dict] = None):
         """`spill_dir`: stream every batch's records to disk instead of holding the whole run in host
         RAM (the reference keeps everything in Python lists until save_splits, cache.py:56-57);
         `save()` reads them back in batch order, so the final tensors are identical.
@@ -73,7 +80,10 @@ class Cache:
         `coact`: keyword arguments of `CoactStats` (pool, pool_len, window, thresh, max_bytes, queries) -- one `CoactStats`
         per module is then updated in `add_topk` next to the feature statistics.  `queries` (a list of features, or
         {module: list}) defaults to the module's filter list; without either it is a ValueError.  None (default): nothing
-        of it is allocated, launched or written."""
+        of it is allocated, launched or written.
+        `recon`: {"ks": checkpoints, "position_edges": first position of every group} (both optional: the SAE's
+        `default_recon_ks()`, one group) -- one `ReconStats` per module is then updated by `add_recon` with the hidden state
+        the loop already holds.  None (default): nothing of it is allocated, launched or written."""
         self.feature_locations = defaultdict(list)
         self.feature_activations = defaultdict(list)
         self.spill_dir = spill_dir
@@ -94,6 +104,10 @@ class Cache:
         if self.coact is not None and self.coact.get("queries") is None and filters is None:
             raise ValueError("coact needs query features: pass coact['queries'] or a feature filter")
         self.coact_stats: Dict[str, CoactStats] = {}
+        self.recon = None if recon is None else dict(recon)
+        if self.recon is not None and set(self.recon) - {"ks", "position_edges"}:
+            raise ValueError(f"recon takes the keys 'ks' and 'position_edges', got {sorted(self.recon)}")
+        self.recon_stats: Dict[str, ReconStats] = {}
 
     def _bitmap(self, module_path: str, num_latents: int, device) -> Optional[Tensor]:
         if self.filters is None:
@@ -130,6 +144,18 @@ class Cache:
             # this group starts its way to the host; the one before it (a whole budget's worth of batches ago) is finished
             self._start_transfer()
             self._drain(keep=1)
+
+    def add_recon(self, hidden: Tensor, top_acts: Tensor, top_indices: Tensor, sae, module_path: str):
+        """The batch's hidden state [B, S, d] and its top-k list into the module's `ReconStats` (a no-op without `recon=`)."""
+        if self.recon is None:
+            return
+        st = self.recon_stats.get(module_path)
+        if st is None:
+            ks = self.recon.get("ks")
+            st = self.recon_stats[module_path] = ReconStats(
+                sae.d_in, sae.default_recon_ks() if ks is None else ks, self.recon.get("position_edges") or (0,),
+                b_dec=sae.b_dec, device=hidden.device)
+        st.update(hidden, top_acts, top_indices, sae)
 
     def _new_coact(self, module_path: str, num_latents: int, device) -> CoactStats:
         kw = dict(self.coact)
@@ -243,7 +269,7 @@ class Cache:
 class FeatureCache:
     def __init__(self, model, tokenizer, submodule_dict: Dict[str, Sae], batch_size: int,
                  shard_size: int, filters: Optional[Dict[str, Tensor]] = None, stats: Optional[dict] = None,
-                 coact: Optional[dict] = None):
+                 coact: Optional[dict] = None, recon: Optional[dict] = None):
         # LlavaNextForConditionalGeneration wraps the language model (cache.py:104-109)
         if hasattr(model, "language_model") and hasattr(model, "vision_tower"):
             self.llava_model, self.model = model, model.language_model
@@ -256,7 +282,7 @@ class FeatureCache:
         self.batch_size = batch_size
         first = next(iter(submodule_dict.values()))
         self.width = first.cfg.num_latents or first.d_in * first.cfg.expansion_factor
-        self.cache = Cache(shard_size, filters, batch_size=batch_size, stats=stats, coact=coact)
+        self.cache = Cache(shard_size, filters, batch_size=batch_size, stats=stats, coact=coact, recon=recon)
         if filters is not None:
             self.filter_submodules(filters)
 
@@ -294,6 +320,7 @@ class FeatureCache:
                 hidden = hidden[:, 1:, :]
             with torch.no_grad():
                 top = sae.encode(hidden)  # fused: replaces pre_acts + topk + zeros/scatter_
+            self.cache.add_recon(hidden, top.top_acts, top.top_indices, sae, module_path)
             self.cache.add_topk(top.top_acts, top.top_indices, sae.num_latents, batch_number, module_path)
 
     def run(self, n_tokens: int, tokens):
@@ -342,6 +369,10 @@ class FeatureCache:
             module_dir = f"{save_dir}/{module_path}"
             os.makedirs(module_dir, exist_ok=True)
             co.save(f"{module_dir}/Rank{rank}_coact.safetensors")
+        for module_path, rs in self.cache.recon_stats.items():
+            module_dir = f"{save_dir}/{module_path}"
+            os.makedirs(module_dir, exist_ok=True)
+            rs.save(f"{module_dir}/Rank{rank}_recon_stats.safetensors")
 
     def concate_safetensors(self, n_splits: int, save_dir):
         for module_path in self.cache.feature_locations.keys():
@@ -362,6 +393,8 @@ class FeatureCache:
             merge_rank_stats(f"{save_dir}/{module_path}", st.device)
         for module_path, co in self.cache.coact_stats.items():
             merge_rank_coact(f"{save_dir}/{module_path}", co.device)
+        for module_path, rs in self.cache.recon_stats.items():
+            merge_rank_recon(f"{save_dir}/{module_path}", rs.device)
 
 
 def merge_rank_stats(module_dir: str, device) -> Optional[str]:
@@ -400,13 +433,34 @@ def merge_rank_coact(module_dir: str, device=None) -> Optional[str]:
     return out
 
 
+def merge_rank_recon(module_dir: str, device=None) -> Optional[str]:
+    """Add `Rank{r}_recon_stats.safetensors` of `module_dir` in rank order (on `device`; any device, the CPU included) into
+    `recon_stats.safetensors` and remove the rank files.  Returns the written path (None: no rank file).  Float64 sums: the
+    result equals a one-rank run to float64 rounding, not bit for bit."""
+    pat = re.compile(r"^Rank(\d+)_recon_stats\.safetensors$")
+    parts = sorted((int(m.group(1)), f) for f in os.listdir(module_dir) if (m := pat.match(f)))
+    if not parts:
+        return None
+    total = None
+    for _, fname in parts:
+        rs = ReconStats.load(os.path.join(module_dir, fname), device=device)
+        total = rs if total is None else total.merge(rs)
+    out = os.path.join(module_dir, "recon_stats.safetensors")
+    total.save(out)
+    for _, fname in parts:
+        os.remove(os.path.join(module_dir, fname))
+    return out
+
+
 class FeatureImageCache(FeatureCache):
     """Image variant (cache.py:312-429): `<image>` prompt per image through the LLaVA processor,
     BOS position dropped before the SAE."""
 
     def __init__(self, model, tokenizer, submodule_dict, batch_size: int, shard_size: int,
-                 filters=None, processor=None, stats: Optional[dict] = None, coact: Optional[dict] = None):
-        super().__init__(model, tokenizer, submodule_dict, batch_size, shard_size, filters, stats=stats, coact=coact)
+                 filters=None, processor=None, stats: Optional[dict] = None, coact: Optional[dict] = None,
+                 recon: Optional[dict] = None):
+        super().__init__(model, tokenizer, submodule_dict, batch_size, shard_size, filters, stats=stats, coact=coact,
+                         recon=recon)
         if processor is None:  # resolved lazily, not at import time as cache.py:321 does
             from transformers import LlavaNextProcessor
 

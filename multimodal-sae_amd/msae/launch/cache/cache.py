@@ -10,7 +10,7 @@ import os
 import torch
 import torch.distributed as dist
 
-from ...config import CacheConfig, coact_kwargs, parse_cache_config
+from ...config import CacheConfig, coact_kwargs, parse_cache_config, recon_kwargs
 from ...features import FeatureCache
 from ...utils import ddp_setup, load_filter, load_saes, maybe_load_llava_model, shard_offsets
 
@@ -109,7 +109,8 @@ def main(cfg: CacheConfig):
         stats = dict(pool="window", window=cfg.example_ctx_len, n_top=cfg.stats_top, n_sample=cfg.stats_sample,
                      sample_seed=cfg.stats_seed)
     cache = FeatureCache(model, tokenizer, saes, batch_size=cfg.batch_size, shard_size=shard_size,
-                         filters=filters, stats=stats, coact=coact_kwargs(cfg, COACT_DEFAULT_POOL, device=model.device))
+                         filters=filters, stats=stats, coact=coact_kwargs(cfg, COACT_DEFAULT_POOL, device=model.device),
+                         recon=recon_kwargs(cfg))      # one position group
     if ddp:
         dist.barrier()
     cache.run(cfg.ctx_len, dataset)

@@ -5,7 +5,7 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
-from ...config import CacheConfig, coact_kwargs, parse_cache_config
+from ...config import CacheConfig, coact_kwargs, parse_cache_config, recon_kwargs
 from ...features import FeatureImageCache
 from ...utils import ddp_setup, load_filter, load_saes, maybe_load_llava_model, shard_offsets
 
@@ -36,7 +36,8 @@ def main(cfg: CacheConfig):
                      n_sample=cfg.stats_sample, sample_seed=cfg.stats_seed)
     cache = FeatureImageCache(model, tokenizer, saes, batch_size=cfg.batch_size, shard_size=shard_size,
                               processor=processor, filters=filters, stats=stats,
-                              coact=coact_kwargs(cfg, COACT_DEFAULT_POOL, pool_len=pool_len, device=model.device))
+                              coact=coact_kwargs(cfg, COACT_DEFAULT_POOL, pool_len=pool_len, device=model.device),
+                              recon=recon_kwargs(cfg, (0, pool_len)))    # the base image against the rest
     if ddp:
         dist.barrier()
     cache.run(cfg.ctx_len, dataset)

@@ -13,6 +13,7 @@ These are the operators the drop-in ``Sae`` module (msae/sae/sae.py) and the fea
     msae::row_inv_norms F.normalize's 1 / max(norm, eps)     features/stats.py:80-81
     msae::rows_topk     torch.mm + torch.topk, fused         features/stats.py:35-37,83,107
     msae::pre_acts_features  pre_acts(x)[..., features]      sae/sae.py:207-225 (AuxK: the dead latents only)
+    msae::recon_curve   decode + e.pow(2).sum() per checkpoint  sae/sae.py:190,201 (one pass for several sparsities)
 
 All ops run on the tensor's device on the current stream, never synchronise (``sparsify`` reads one
 int64 back, as ``torch.nonzero`` does), and raise on CPU tensors.
@@ -25,7 +26,7 @@ import ctypes
 import dataclasses
 import os
 import weakref
-from typing import Optional, Tuple
+from typing import Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor
@@ -1101,6 +1102,122 @@ def delta_decode(x: Tensor, plain_acts: Tensor, plain_idx: Tensor, edit_acts: Te
         return _delta_decode(x, plain_acts, plain_idx, edit_acts, edit_idx, W_dec)
     _delta_decode_out(x, plain_acts, plain_idx, edit_acts, edit_idx, W_dec, out)
     return out
+
+
+# ---- reconstruction error against sparsity (csrc/recon.hip) -------------------------------------------
+RECON_MAX_K = 4096
+RECON_MAX_CHECKPOINTS = 16
+
+
+def _recon_curve_host(x: Tensor, vals: Tensor, idx: Tensor, W_dec: Tensor, b_dec: Tensor, ks: Sequence[int]):
+    """The meaning of msae_recon_curve_f32 in plain torch (f32 terms, float64 sums rounded to f32): not its bits."""
+    W, b = W_dec.detach().to(torch.float32), b_dec.detach().to(torch.float32)
+    N, d = W.shape
+    k = vals.shape[-1]
+    xf = x.detach().reshape(-1, d).to(torch.float32)
+    v, i = vals.detach().reshape(-1, k).to(torch.float32), idx.detach().reshape(-1, k).to(torch.int64)
+    ok = (i >= 0) & (i < N) & (v != 0)
+    v, i = torch.where(ok, v, torch.zeros_like(v)), torch.where(ok, i, torch.zeros_like(i))
+    mom = torch.empty(xf.shape[0], len(ks), 3, dtype=torch.float32, device=xf.device)
+    for c, kc in enumerate(ks):
+        rows = torch.where(ok[:, :kc, None], v[:, :kc, None] * W[i[:, :kc]], torch.zeros((), dtype=torch.float32, device=W.device))
+        r = rows.sum(1) + b
+        e = r - xf
+        for m, term in enumerate((e * e, xf * r, r * r)):
+            mom[:, c, m] = term.sum(-1, dtype=torch.float64).to(torch.float32)
+    return mom, (xf * xf).sum(-1, dtype=torch.float64).to(torch.float32)
+
+
+@torch.library.custom_op("msae::recon_curve", mutates_args=())
+def _recon_curve(x: Tensor, top_acts: Tensor, top_indices: Tensor, W_dec: Tensor, b_dec: Tensor,
+                 ks: Sequence[int]) -> Tuple[Tensor, Tensor]:
+    d = W_dec.shape[1]
+    T = x.numel() // d
+    C = len(ks)
+    if not x.is_cuda:
+        return _recon_curve_host(x, top_acts, top_indices, W_dec, b_dec, ks)
+    dev = _hip.require_device(x, top_acts, top_indices, W_dec, b_dec)
+    lib = _hip.load()
+    xa, W, bd = x.detach().contiguous(), _f32c(W_dec), _f32c(b_dec)
+    N = W.shape[0]
+    k = top_acts.shape[-1]
+    mom = torch.empty(T, C, 3, dtype=torch.float32, device=dev)
+    xx = torch.empty(T, dtype=torch.float32, device=dev)
+    if T == 0:
+        return mom, xx
+    v, i, ld = _list_rows(top_acts, top_indices, k)
+    wide = i.dtype == torch.int64
+    fn, name = (lib.msae_recon_curve_i64_f32, "msae_recon_curve_i64_f32") if wide else \
+        (lib.msae_recon_curve_f32, "msae_recon_curve_f32")
+    ks_host = (ctypes.c_int32 * C)(*ks)             # read during the call: copied into the launch arguments
+    flag = _bounds_flag(dev)
+    with torch.cuda.device(dev):
+        _hip.check(fn(_hip.ptr(xa), _hip.DTYPE_CODE[xa.dtype], _hip.ptr(v), _hip.ptr(i), ld, _hip.ptr(W), _hip.ptr(bd), T, k, N,
+                      d, ks_host, C, _hip.ptr(mom), _hip.ptr(xx), _hip.ptr(flag), _hip.stream_of(xa)), name)
+    _check_bounds(flag, name)
+    return mom, xx
+
+
+@_recon_curve.register_fake
+def _(x, top_acts, top_indices, W_dec, b_dec, ks):
+    T = x.numel() // W_dec.shape[1]
+    return x.new_empty((T, len(ks), 3), dtype=torch.float32), x.new_empty((T,), dtype=torch.float32)
+
+
+def recon_ks(ks, k: int, what: str = "recon_curve") -> list:
+    """The checkpoint list as validated Python ints: strictly ascending, inside [0, k], 1 to 16 of them."""
+    if isinstance(ks, Tensor):
+        ks = ks.detach().cpu().reshape(-1).tolist()
+    try:
+        out = [int(c) for c in ks]
+        same = all(float(c) == float(o) for c, o in zip(ks, out))
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: ks must be a sequence of integers, got {ks!r}") from None
+    if not same:
+        raise ValueError(f"{what}: ks must be integers, got {list(ks)!r}")
+    if not 1 <= len(out) <= RECON_MAX_CHECKPOINTS:
+        raise ValueError(f"{what}: between 1 and {RECON_MAX_CHECKPOINTS} checkpoints, got {len(out)}")
+    if out[0] < 0 or out[-1] > k or any(a >= b for a, b in zip(out, out[1:])):
+        raise ValueError(f"{what}: ks must be strictly ascending inside [0, {k}], got {out}")
+    return out
+
+
+def recon_curve(x: Tensor, top_acts: Tensor, top_indices: Tensor, W_dec: Tensor, b_dec: Tensor, ks) -> Tuple[Tensor, Tensor]:
+    """Reconstruction error at several sparsities in one pass (include/msae.h, "reconstruction error against sparsity"):
+    -> (mom [..., C, 3] f32, xx [...] f32) with mom[..., c, :] = (|r - x|^2, x . r, |r|^2) of the reconstruction r from the
+    first ks[c] entries of each token's list (+ b_dec) and xx = |x|^2.  x [..., d] f32 / bf16 / f16; top_acts / top_indices
+    [..., k] with x's leading shape (or [T, k]), indices int32 or int64; the `[:, :k]` view of an over-fetched [T, kk] list
+    is read in place.  W_dec [N, d], b_dec [d].  ks: strictly ascending integers in [0, k], at most 16.  On a HIP device
+    the fused kernel (bit-defined per token); elsewhere a plain-torch composition with the same meaning, not the same
+    bits.  Nothing is read back; bad arguments raise ValueError before any device work."""
+    if x.dim() < 1 or W_dec.dim() != 2 or x.shape[-1] != W_dec.shape[1] or x.shape[-1] < 1:
+        raise ValueError(f"recon_curve: x [..., d] and W_dec [N, d] must share d, got {tuple(x.shape)} and {tuple(W_dec.shape)}")
+    if b_dec is None or b_dec.dim() != 1 or b_dec.shape[0] != W_dec.shape[1]:
+        raise ValueError(f"recon_curve: b_dec must be [d] = [{W_dec.shape[1]}], got "
+                         f"{None if b_dec is None else tuple(b_dec.shape)}")
+    if x.dtype not in _hip.DTYPE_CODE:
+        raise ValueError(f"recon_curve: x must be float32, bfloat16 or float16, got {x.dtype}")
+    if top_acts.shape != top_indices.shape or top_acts.dim() < 1:
+        raise ValueError(f"recon_curve: top_acts and top_indices must share one shape [..., k], got {tuple(top_acts.shape)} "
+                         f"and {tuple(top_indices.shape)}")
+    k = top_acts.shape[-1]
+    if not 1 <= k <= RECON_MAX_K:
+        raise ValueError(f"recon_curve: k must be in [1, {RECON_MAX_K}], got {k}")
+    T = x.numel() // x.shape[-1]
+    if top_acts.numel() != T * k or (top_acts.dim() != 2 and tuple(top_acts.shape[:-1]) != tuple(x.shape[:-1])):
+        raise ValueError(f"recon_curve: the list must hold one row per token of x {tuple(x.shape)}, got {tuple(top_acts.shape)}")
+    if top_indices.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"recon_curve: top_indices must be int32 or int64, got {top_indices.dtype}")
+    if top_acts.dtype != torch.float32:
+        raise ValueError(f"recon_curve: the list's values must be float32, got {top_acts.dtype}")
+    devs = {t.device for t in (x, top_acts, top_indices, W_dec, b_dec)}
+    if len(devs) != 1:
+        raise ValueError(f"recon_curve: all tensors must be on one device, got {sorted(str(d) for d in devs)}")
+    ks = recon_ks(ks, k)
+    _no_grad_inputs("ops.recon_curve", x, top_acts)
+    mom, xx = _recon_curve(x, top_acts, top_indices, W_dec.detach(), b_dec.detach(), ks)      # (weights are constants here)
+    lead = tuple(x.shape[:-1])
+    return mom.view(*lead, len(ks), 3), xx.view(lead)
 
 
 def shard_candidates(x: Tensor, b_enc_shard: Optional[Tensor], b_dec: Optional[Tensor], prepared_shard: Tensor,

@@ -450,6 +450,10 @@ class ShardedSae:
             outs.append(e._rescore(x[lo:hi].contiguous(), recv, hi - lo, **ed))
         return (torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs]), torch.cat([o[2] for o in outs]))
 
+    def recon_error(self, *args, **kwargs):
+        raise NotImplementedError("recon_error (reconstruction error against sparsity) runs on the single-GPU msae.Sae only: a "
+                                  "feature-sharded engine holds a slice of W_dec")
+
     def decode(self, vals: Tensor, idx: Tensor, gather: bool = True, async_gather: bool = False) -> Tensor:
         """Token-sharded decode.  With `async_gather` the all-gather of the reconstruction is issued
         asynchronously (RCCL's own stream) and overlaps whatever the caller enqueues next -- the
@@ -624,6 +628,10 @@ class EmulatedShardGroup:
     @property
     def second_round_tokens(self) -> int:
         return 0 if self._second_round is None else int(self._second_round)
+
+    def recon_error(self, *args, **kwargs):
+        raise NotImplementedError("recon_error (reconstruction error against sparsity) runs on the single-GPU msae.Sae only: a "
+                                  "feature-sharded engine holds a slice of W_dec")
 
     def decode(self, vals: Tensor, idx: Tensor, **_):
         return self.engines[0]._decode(idx, vals)

@@ -1,5 +1,5 @@
 from .config import SaeConfig, TrainConfig
 from .probe import ProbeOutput
-from .sae import EncoderOutput, ForwardOutput, Sae
+from .sae import EncoderOutput, ForwardOutput, ReconOutput, Sae
 
-__all__ = ["Sae", "SaeConfig", "TrainConfig", "EncoderOutput", "ForwardOutput", "ProbeOutput"]
+__all__ = ["Sae", "SaeConfig", "TrainConfig", "EncoderOutput", "ForwardOutput", "ProbeOutput", "ReconOutput"]

@@ -55,6 +55,40 @@ class ForwardOutput(NamedTuple):
     multi_topk_fvu: Tensor
 
 
+class ReconOutput(NamedTuple):
+    """Per-token moments of the reconstruction at several sparsities (Sae.recon_error; include/msae.h, "reconstruction
+    error against sparsity").  The tensor fields are the kernel's f32 outputs; the properties are float64."""
+    ks: tuple
+    """The checkpoints: entry c of the C axis reconstructs from the first ks[c] entries of the top-k list."""
+    err2: Tensor
+    """|r - x|^2, [..., C]."""
+    dot: Tensor
+    """x . r, [..., C]."""
+    rnorm2: Tensor
+    """|r|^2, [..., C]."""
+    xnorm2: Tensor
+    """|x|^2, [...]."""
+    total_variance: Tensor
+    """(x - x.mean(0)).pow(2).sum() over this call's tokens (sae.py:202), a float64 scalar."""
+    d_in: int
+
+    @property
+    def mse(self) -> Tensor:
+        """Mean squared error per element, [..., C]."""
+        return self.err2.to(torch.float64) / self.d_in
+
+    @property
+    def cosine(self) -> Tensor:
+        """x . r / (|x| |r|), [..., C] (nan where either norm is zero)."""
+        return self.dot.to(torch.float64) / (self.xnorm2.to(torch.float64)[..., None] * self.rnorm2.to(torch.float64)).sqrt()
+
+    @property
+    def fvu(self) -> Tensor:
+        """Fraction of variance unexplained of this call, [C]: e.pow(2).sum() / total_variance (sae.py:201-202, 228)."""
+        err = self.err2.to(torch.float64).reshape(-1, self.err2.shape[-1]).sum(0)
+        return err / self.total_variance
+
+
 class _SqErr(torch.autograd.Function):
     """sum((pred - target)^2) -> (scalar, pred - target) with ONE elementwise kernel and one reduction forward and one
     elementwise kernel backward, where the reference's `e = pred - x; e.pow(2).sum()` (sae.py:201,227) costs three
@@ -349,6 +383,60 @@ class Sae(nn.Module):
                 q_acts, q_idx = ops.edit_topk(acts, idx, edits.feat, edits.val, edits.kind, self.num_latents, k)
             out = ops.delta_decode(flat, acts[:, :k], idx[:, :k], q_acts, q_idx, self.W_dec)
         return out.view(x.shape)
+
+    def default_recon_ks(self) -> tuple:
+        """Powers of two up to cfg.k, plus cfg.k itself."""
+        k = self.cfg.k
+        return tuple(sorted({1 << i for i in range(k.bit_length()) if (1 << i) <= k} | {k}))
+
+    def recon_error(self, x: Tensor, ks=None, *, top=None, exact: bool = False, chunk: Optional[int] = None) -> ReconOutput:
+        """The SAE's reconstruction error on x [..., d_in] (f32 / bf16 / f16) at several sparsities, without materialising a
+        reconstruction: one pass over each token's k decoder rows that stops at the checkpoints `ks`
+        (default: `default_recon_ks()`; strictly ascending in [0, k], at most 16, 0 = b_dec alone).  The canonical top-k list
+        is value-descending, so its first kappa entries are the top-kappa list and checkpoint kappa is, bit for bit, the
+        error of `decode` over an Sae with cfg.k = kappa.  `top`: the list of x (an EncoderOutput or (top_acts, top_indices))
+        when the caller holds it already; None: `self.encode(x, exact=exact)`.  `chunk`: tokens per kernel call (None: one
+        call); the per-token outputs do not depend on it.  Inference only; nothing is read back."""
+        if self.W_dec is None:
+            raise ValueError("Sae.recon_error: this Sae has no decoder")
+        if x.dim() < 1 or x.shape[-1] != self.d_in:
+            raise ValueError(f"Sae.recon_error: x must be [..., {self.d_in}], got {tuple(x.shape)}")
+        if x.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+            raise ValueError(f"Sae.recon_error: x must be float32, bfloat16 or float16, got {x.dtype}")
+        if chunk is not None and chunk < 1:
+            raise ValueError(f"Sae.recon_error: chunk must be positive, got {chunk}")
+        if top is not None and len(top) != 2:
+            raise ValueError("Sae.recon_error: top must be an EncoderOutput or a (top_acts, top_indices) pair")
+        k = self.cfg.k if top is None else top[0].shape[-1]
+        ks = ops.recon_ks(self.default_recon_ks() if ks is None else ks, k, "Sae.recon_error")
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise RuntimeError("Sae.recon_error is an inference path: call it under torch.no_grad() or on a detached input")
+        with torch.no_grad():
+            flat = x.reshape(-1, self.d_in)
+            T = flat.shape[0]
+            if top is None:
+                top = self.encode(flat, exact=exact)
+            acts, idx = top[0].reshape(T, k), top[1].reshape(T, k)
+            step = T if chunk is None else chunk
+            parts = [ops.recon_curve(flat[a:a + step], acts[a:a + step], idx[a:a + step], self.W_dec, self.b_dec, ks)
+                     for a in range(0, T, max(step, 1))]
+            if len(parts) == 1:
+                mom, xx = parts[0]
+            elif parts:
+                mom, xx = torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+            else:
+                mom, xx = flat.new_empty((0, len(ks), 3), dtype=torch.float32), flat.new_empty((0,), dtype=torch.float32)
+            # this call's own total variance, two passes in float64, a block of rows at a time
+            tv = flat.new_zeros((), dtype=torch.float64)
+            if T:
+                rows = max(1, (32 << 20) // self.d_in)
+                mean = sum(flat[a:a + rows].sum(0, dtype=torch.float64) for a in range(0, T, rows)) / T
+                for a in range(0, T, rows):
+                    tv += (flat[a:a + rows].to(torch.float64) - mean).square().sum()
+        lead = tuple(x.shape[:-1])
+        C = len(ks)
+        return ReconOutput(tuple(ks), mom[..., 0].reshape(*lead, C), mom[..., 1].reshape(*lead, C),
+                           mom[..., 2].reshape(*lead, C), xx.reshape(lead), tv, self.d_in)
 
     def decode(self, top_acts: Tensor, top_indices: Tensor) -> Tensor:
         assert self.W_dec is not None, "Decoder weight was not initialized."
