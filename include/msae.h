@@ -27,6 +27,7 @@
  *   msae_sparsify_*          scatter_ + Cache.add/get_nonzeros  features/cache.py:214-217,42-92
  *   msae_feature_stats_*     per-feature counts + top examples  features/loader.py:103-106, constructors.py:28-141
  *   msae_coact_*             co-activation counters + neighbours (no reference counterpart)
+ *   msae_act_hist_*          per-feature activation histograms + quantiles (no reference counterpart)
  *   msae_rows_topk_f32       cos + get_neighbors; logits   features/stats.py:76-120; stats.py:12-47
  *   msae_row_inv_norms_f32   F.normalize's norms in cos    features/stats.py:80-81
  *   msae_edit_topk_f32       hook edits with a feature LIST features/steering.py:113-114, patching/utils.py:43-48
@@ -478,6 +479,47 @@ int msae_coact_topk(const int32_t *counts, const int64_t *seg_count, const int32
                     int metric, int exclude_self, float *out_val, int32_t *out_idx, void *stream);
 int msae_coact_topk_i64(const int32_t *counts, const int64_t *seg_count, const int32_t *queries, int F, int N, int m,
                         int metric, int exclude_self, float *out_val, int64_t *out_idx, void *stream);
+
+/* ---- per-feature activation histograms, and quantile bins from them (msae.features.ActHist) --------------------------
+ * HOW STRONGLY every feature fires, counted while the cache runs (no reference counterpart: the reference rebuilds dense
+ * per-feature tensors on the CPU for a handful of features).  Input: one batch's top-k vals/idx[B*S][k], as the feature
+ * statistics take it; an entry is kept when |v| > thresh and 0 <= idx < N (no filter bitmap).
+ * The bin rule is defined on the float32 bits, with no transcendental function and no tolerance.  Parameters: sub_bits s in
+ * [0, 4], e_lo (the exponent of the lowest octave, -126 <= e_lo, e_lo + octaves <= 128), octaves E >= 1,
+ * n_bins = E << s in [1, 512].  For a value c > 0 with bit pattern u:
+ *   raw     = (u >> (23 - s)) - ((127 + e_lo) << s)
+ *   bin     = clamp(raw, 0, n_bins - 1)
+ *   edge(b) = the float with bits ((b + ((127 + e_lo) << s)) << (23 - s)),  b = 0 .. n_bins
+ * so values below 2^e_lo (subnormals included) land in bin 0, values >= 2^(e_lo + E) and +inf in the last bin, and an
+ * unclamped value satisfies edge(bin) <= c < edge(bin + 1).  With s = 3, e_lo = -16, E = 32 (256 bins over [2^-16, 2^16),
+ * 8 per octave): 1e-5 -> 0, 1.0 -> 128, 1.125 -> 129, 65536 and +inf -> 255.
+ * A SEGMENT VALUE c of feature f (a row never spans two calls, so each segment is complete in one call):
+ *   MSAE_POOL_TOKEN   every kept entry is its own value, c = v; nothing is de-duplicated (a caller's repeat counts twice)
+ *   MSAE_POOL_WINDOW  exactly the candidate msae_feature_stats_update ranks, bit for bit: the maximum of f's kept values in
+ *                     the window, joined with 0 unless f has W kept entries there (positions >= (S / W) * W are not pooled)
+ *   MSAE_POOL_IMAGE   likewise: the f32 sum of f's kept values at s < pool_len, added in ascending s (list order inside a
+ *                     token) from +0, divided by (float)pool_len
+ * State, updated in place (initialise to 0):
+ *   hist[N][n_bins]  i32  hist[f][bin(c)] += 1 for every segment value c > 0 of f.  NaN, zero and negative values are
+ *                         counted nowhere.
+ * Every update is an integer atomic add: the state is bit-identical however the rows are cut into calls, in whatever
+ * order the calls arrive, and adds over ranks.  A counter wraps at 2^31: the caller keeps the number of segments below.
+ * Envelope: B*S <= 65536, k <= 256, N <= 262144, pool_len <= 2880, window <= 4096, the bin parameters as above (else
+ * MSAE_EINVAL).  No host synchronisation, no allocation: the workspace is msae_act_hist_ws_bytes(B*S, k, N) (token mode
+ * uses none of it).
+ * msae_act_hist_quantiles: bins[N][Q] i32 from hist, Q probabilities qs[Q] (f64, device; 1 <= Q <= 64; each in [0, 1]),
+ *   n_segments (segments seen, empty ones included) and the `zeros` flag.  Per feature, with n = the row total and
+ *   z = max(n_segments - n, 0) if zeros else 0 (the segments in which the feature's value was not > 0):
+ *     rank r = clamp(ceil(q * (double)(n + z)), 1, n + z)       one IEEE f64 multiply, then ceil
+ *     bin    = the first b with hist[f][0] + .. + hist[f][b] + z >= r;  -1 when r <= z (the quantile is a zero);
+ *              -2 when n + z = 0 (nothing to rank)
+ *   A pure function of its arguments; no scratch, no host synchronisation, no allocation. */
+size_t msae_act_hist_ws_bytes(int T, int k, int N);
+int msae_act_hist_update(const float *vals, const int32_t *idx, int B, int S, int k, float thresh, int N, int mode,
+                         int pool_len, int window, int sub_bits, int e_lo, int octaves, int32_t *hist, void *ws,
+                         size_t ws_bytes, void *stream);
+int msae_act_hist_quantiles(const int32_t *hist, int N, int n_bins, const double *qs, int Q, int64_t n_segments,
+                            int zeros, int32_t *bins, void *stream);
 
 /* ---- probe: segment-pooled feature ranking and activation maps (Sae.probe) ---------------------------------------
  * Replaces the dense probe of tools/probe_activations.py:109-126 (latents = pre_acts(h); latents.mean(0).topk(k);

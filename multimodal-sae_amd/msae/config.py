@@ -55,6 +55,12 @@ class CacheConfig:
     """Also measure every SAE's reconstruction error against sparsity and position (recon_stats.safetensors per module)"""
     recon_ks: Optional[str] = None
     """Comma-separated checkpoints of --recon_stats, e.g. 0,1,2,4,8,16,32 (default: powers of two up to k, and k)"""
+    act_hist: bool = False
+    """Also count how strongly every feature fires (act_hist.safetensors per module: a histogram per feature)"""
+    act_hist_pool: Optional[str] = None
+    """Segments of the activation histograms: token, window or image (default: image on cache_image, token on cache)"""
+    act_hist_bins: Optional[str] = None
+    """Bins of the activation histograms as s,e_lo,octaves: 2^s bins per octave from 2^e_lo up (default: 3,-16,32)"""
 
     def to_dict(self):
         return dataclasses.asdict(self)
@@ -117,6 +123,13 @@ def parse_cache_config(argv: Optional[Sequence[str]] = None) -> CacheConfig:
             recon_ks_list(cfg.recon_ks)
         except ValueError as e:
             p.error(str(e))
+    if cfg.act_hist_pool is not None and cfg.act_hist_pool not in COACT_POOLS:
+        p.error(f"--act_hist_pool must be one of {', '.join(COACT_POOLS)}, got {cfg.act_hist_pool!r}")
+    if cfg.act_hist_bins is not None:
+        try:
+            act_hist_bins(cfg.act_hist_bins)
+        except ValueError as e:
+            p.error(str(e))
     return cfg
 
 
@@ -153,4 +166,28 @@ def coact_kwargs(cfg: CacheConfig, default_pool: str, pool_len: int = 576, devic
         from .utils import load_filter
 
         kw["queries"] = load_filter(cfg.coact_features, device=device)
+    return kw
+
+
+def act_hist_bins(text: str) -> dict:
+    """'s,e_lo,octaves' -> dict(sub_bits=s, e_lo=e_lo, octaves=octaves), within what the histograms take (include/msae.h):
+    s in [0, 4], the octaves inside [-126, 128], at most 512 bins."""
+    try:
+        s, e_lo, octaves = (int(t) for t in text.split(","))
+    except ValueError:
+        raise ValueError(f"--act_hist_bins must be three comma-separated integers s,e_lo,octaves, got {text!r}") from None
+    if not (0 <= s <= 4 and octaves >= 1 and e_lo >= -126 and e_lo + octaves <= 128 and octaves << s <= 512):
+        raise ValueError(f"--act_hist_bins: s in [0, 4], octaves inside [-126, 128] and at most 512 bins, got {text!r}")
+    return dict(sub_bits=s, e_lo=e_lo, octaves=octaves)
+
+
+def act_hist_kwargs(cfg: CacheConfig, default_pool: str, pool_len: int = 576) -> Optional[dict]:
+    """The `hist=` argument of the feature caches for a parsed command line (None without --act_hist): the pool (the
+    launcher's default unless --act_hist_pool), the window of the text statistics, `pool_len` of the image ones, and the
+    bins of --act_hist_bins."""
+    if not cfg.act_hist:
+        return None
+    kw = dict(pool=cfg.act_hist_pool or default_pool, window=cfg.example_ctx_len, pool_len=pool_len)
+    if cfg.act_hist_bins is not None:
+        kw.update(act_hist_bins(cfg.act_hist_bins))
     return kw

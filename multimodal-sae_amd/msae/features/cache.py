@@ -25,6 +25,12 @@ and, with `recon=` (opt-in; no reference counterpart), the reconstruction error 
     <save_dir>/<module>/Rank{r}_recon_stats.safetensors        per rank
     <save_dir>/<module>/recon_stats.safetensors                the ranks added in rank order by the concat
 
+and, with `hist=` (opt-in; no reference counterpart), a histogram of every feature's activation strength
+(msae/features/hist.py):
+
+    <save_dir>/<module>/Rank{r}_act_hist.safetensors           per rank
+    <save_dir>/<module>/act_hist.safetensors                   the ranks added in rank order by the concat
+
 The split files have keys `locations [nnz,3] int64 = (row, pos, feature)` and `activations [nnz] f32`, which is what
 `features/loader.py:143-196` (FeatureDataset) reads.
 
@@ -52,6 +58,7 @@ from torch import Tensor
 from .. import ops
 from ..sae import Sae
 from .coact import CoactStats
+from .hist import ActHist
 from .recon import ReconStats
 from .stats import FeatureStats
 
@@ -68,7 +75,8 @@ class Cache:
 
     def __init__(self, shard_size: int, filters: Optional[Dict[str, Tensor]] = None,
                  batch_size: int = 64, spill_dir: Optional[str] = None, device_budget_bytes: int = 256 << 20,
-                 stats: Optional[dict] = None, coact: Optional[dict] = None, recon: Optional[dict] = None):
+                 stats: Optional[dict] = None, coact: Optional[dict] = None, recon: Optional[dict] = None,
+                 hist: Optional[dict] = None):
         """`spill_dir`: stream every batch's records to disk instead of holding the whole run in host
         RAM (the reference keeps everything in Python lists until save_splits, cache.py:56-57);
         `save()` reads them back in batch order, so the final tensors are identical.
@@ -83,7 +91,10 @@ class Cache:
         of it is allocated, launched or written.
         `recon`: {"ks": checkpoints, "position_edges": first position of every group} (both optional: the SAE's
         `default_recon_ks()`, one group) -- one `ReconStats` per module is then updated by `add_recon` with the hidden state
-        the loop already holds.  None (default): nothing of it is allocated, launched or written."""
+        the loop already holds.  None (default): nothing of it is allocated, launched or written.
+        `hist`: keyword arguments of `ActHist` (pool, pool_len, window, thresh, sub_bits, e_lo, octaves, max_bytes) -- one
+        `ActHist` per module is then updated in `add_topk` from the same top-k pairs, over every feature.  None (default):
+        nothing of it is allocated, launched or written."""
         self.feature_locations = defaultdict(list)
         self.feature_activations = defaultdict(list)
         self.spill_dir = spill_dir
@@ -108,6 +119,8 @@ class Cache:
         if self.recon is not None and set(self.recon) - {"ks", "position_edges"}:
             raise ValueError(f"recon takes the keys 'ks' and 'position_edges', got {sorted(self.recon)}")
         self.recon_stats: Dict[str, ReconStats] = {}
+        self.hist = None if hist is None else dict(hist)
+        self.act_hists: Dict[str, ActHist] = {}
 
     def _bitmap(self, module_path: str, num_latents: int, device) -> Optional[Tensor]:
         if self.filters is None:
@@ -134,6 +147,11 @@ class Cache:
             if co is None:
                 co = self.coact_stats[module_path] = self._new_coact(module_path, num_latents, top_acts.device)
             co.update(top_acts, top_indices)
+        if self.hist is not None:
+            ah = self.act_hists.get(module_path)
+            if ah is None:
+                ah = self.act_hists[module_path] = ActHist(num_latents, device=top_acts.device, **self.hist)
+            ah.update(top_acts, top_indices)
         loc, act, nnz = ops.sparsify(top_acts, top_indices, num_latents, row_base=row_base, thresh=1e-5,
                                      filter_bitmap=self._bitmap(module_path, num_latents, top_acts.device), sync=False)
         # stays on the device, stream-ordered (the reference does a nonzero() + two .cpu() per batch inside the
@@ -269,7 +287,7 @@ class Cache:
 class FeatureCache:
     def __init__(self, model, tokenizer, submodule_dict: Dict[str, Sae], batch_size: int,
                  shard_size: int, filters: Optional[Dict[str, Tensor]] = None, stats: Optional[dict] = None,
-                 coact: Optional[dict] = None, recon: Optional[dict] = None):
+                 coact: Optional[dict] = None, recon: Optional[dict] = None, hist: Optional[dict] = None):
         # LlavaNextForConditionalGeneration wraps the language model (cache.py:104-109)
         if hasattr(model, "language_model") and hasattr(model, "vision_tower"):
             self.llava_model, self.model = model, model.language_model
@@ -282,7 +300,7 @@ class FeatureCache:
         self.batch_size = batch_size
         first = next(iter(submodule_dict.values()))
         self.width = first.cfg.num_latents or first.d_in * first.cfg.expansion_factor
-        self.cache = Cache(shard_size, filters, batch_size=batch_size, stats=stats, coact=coact, recon=recon)
+        self.cache = Cache(shard_size, filters, batch_size=batch_size, stats=stats, coact=coact, recon=recon, hist=hist)
         if filters is not None:
             self.filter_submodules(filters)
 
@@ -373,6 +391,10 @@ class FeatureCache:
             module_dir = f"{save_dir}/{module_path}"
             os.makedirs(module_dir, exist_ok=True)
             rs.save(f"{module_dir}/Rank{rank}_recon_stats.safetensors")
+        for module_path, ah in self.cache.act_hists.items():
+            module_dir = f"{save_dir}/{module_path}"
+            os.makedirs(module_dir, exist_ok=True)
+            ah.save(f"{module_dir}/Rank{rank}_act_hist.safetensors")
 
     def concate_safetensors(self, n_splits: int, save_dir):
         for module_path in self.cache.feature_locations.keys():
@@ -395,6 +417,8 @@ class FeatureCache:
             merge_rank_coact(f"{save_dir}/{module_path}", co.device)
         for module_path, rs in self.cache.recon_stats.items():
             merge_rank_recon(f"{save_dir}/{module_path}", rs.device)
+        for module_path, ah in self.cache.act_hists.items():
+            merge_rank_act_hist(f"{save_dir}/{module_path}", ah.device)
 
 
 def merge_rank_stats(module_dir: str, device) -> Optional[str]:
@@ -433,6 +457,24 @@ def merge_rank_coact(module_dir: str, device=None) -> Optional[str]:
     return out
 
 
+def merge_rank_act_hist(module_dir: str, device=None) -> Optional[str]:
+    """Add `Rank{r}_act_hist.safetensors` of `module_dir` in rank order (on `device`; any device, the CPU included) into
+    `act_hist.safetensors` and remove the rank files.  Returns the written path (None: no rank file)."""
+    pat = re.compile(r"^Rank(\d+)_act_hist\.safetensors$")
+    parts = sorted((int(m.group(1)), f) for f in os.listdir(module_dir) if (m := pat.match(f)))
+    if not parts:
+        return None
+    total = None
+    for _, fname in parts:
+        ah = ActHist.load(os.path.join(module_dir, fname), device=device)
+        total = ah if total is None else total.merge(ah)
+    out = os.path.join(module_dir, "act_hist.safetensors")
+    total.save(out)
+    for _, fname in parts:
+        os.remove(os.path.join(module_dir, fname))
+    return out
+
+
 def merge_rank_recon(module_dir: str, device=None) -> Optional[str]:
     """Add `Rank{r}_recon_stats.safetensors` of `module_dir` in rank order (on `device`; any device, the CPU included) into
     `recon_stats.safetensors` and remove the rank files.  Returns the written path (None: no rank file).  Float64 sums: the
@@ -458,9 +500,9 @@ class FeatureImageCache(FeatureCache):
 
     def __init__(self, model, tokenizer, submodule_dict, batch_size: int, shard_size: int,
                  filters=None, processor=None, stats: Optional[dict] = None, coact: Optional[dict] = None,
-                 recon: Optional[dict] = None):
+                 recon: Optional[dict] = None, hist: Optional[dict] = None):
         super().__init__(model, tokenizer, submodule_dict, batch_size, shard_size, filters, stats=stats, coact=coact,
-                         recon=recon)
+                         recon=recon, hist=hist)
         if processor is None:  # resolved lazily, not at import time as cache.py:321 does
             from transformers import LlavaNextProcessor
 

@@ -10,12 +10,13 @@ import os
 import torch
 import torch.distributed as dist
 
-from ...config import CacheConfig, coact_kwargs, parse_cache_config, recon_kwargs
+from ...config import CacheConfig, act_hist_kwargs, coact_kwargs, parse_cache_config, recon_kwargs
 from ...features import FeatureCache
 from ...utils import ddp_setup, load_filter, load_saes, maybe_load_llava_model, shard_offsets
 
 
 COACT_DEFAULT_POOL = "token"
+ACT_HIST_DEFAULT_POOL = "token"
 
 
 def chunk_and_tokenize(dataset, tokenizer, max_seq_len: int, text_key: str = "text", batch_docs: int = 2048,
@@ -110,7 +111,8 @@ def main(cfg: CacheConfig):
                      sample_seed=cfg.stats_seed)
     cache = FeatureCache(model, tokenizer, saes, batch_size=cfg.batch_size, shard_size=shard_size,
                          filters=filters, stats=stats, coact=coact_kwargs(cfg, COACT_DEFAULT_POOL, device=model.device),
-                         recon=recon_kwargs(cfg))      # one position group
+                         recon=recon_kwargs(cfg),      # one position group
+                         hist=act_hist_kwargs(cfg, ACT_HIST_DEFAULT_POOL))
     if ddp:
         dist.barrier()
     cache.run(cfg.ctx_len, dataset)

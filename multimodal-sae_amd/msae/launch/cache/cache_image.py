@@ -5,12 +5,13 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
-from ...config import CacheConfig, coact_kwargs, parse_cache_config, recon_kwargs
+from ...config import CacheConfig, act_hist_kwargs, coact_kwargs, parse_cache_config, recon_kwargs
 from ...features import FeatureImageCache
 from ...utils import ddp_setup, load_filter, load_saes, maybe_load_llava_model, shard_offsets
 
 
 COACT_DEFAULT_POOL = "image"
+ACT_HIST_DEFAULT_POOL = "image"
 
 
 def main(cfg: CacheConfig):
@@ -37,7 +38,8 @@ def main(cfg: CacheConfig):
     cache = FeatureImageCache(model, tokenizer, saes, batch_size=cfg.batch_size, shard_size=shard_size,
                               processor=processor, filters=filters, stats=stats,
                               coact=coact_kwargs(cfg, COACT_DEFAULT_POOL, pool_len=pool_len, device=model.device),
-                              recon=recon_kwargs(cfg, (0, pool_len)))    # the base image against the rest
+                              recon=recon_kwargs(cfg, (0, pool_len)),    # the base image against the rest
+                              hist=act_hist_kwargs(cfg, ACT_HIST_DEFAULT_POOL, pool_len=pool_len))
     if ddp:
         dist.barrier()
     cache.run(cfg.ctx_len, dataset)
