@@ -8,6 +8,19 @@
  * caller (the reference calls this path inside an HF forward hook on the model's stream,
  * features/cache.py:187-204, so ops must be stream-ordered).
  *
+ * WORKSPACE CONTRACT (every entry that takes `void *ws, size_t ws_bytes`; tests/test_gpu_workspace_contract.py holds each of
+ * them to it with exact-size, guarded and dirty buffers):
+ *   - the contents of [ws, ws + ws_bytes) are UNSPECIFIED on entry and on return: a caller may hand over a fresh block, the
+ *     block a different entry has just used, or one it shares between all entries of a stream; nothing is kept in it
+ *     between calls;
+ *   - no entry reads a byte of the workspace that the same call has not written before;
+ *   - no entry reads or writes outside [ws, ws + ws_bytes), and ws_bytes equal to what the entry's *_ws_bytes() helper
+ *     returns for the same shape (and options) always suffices;
+ *   - a workspace the entry needs and that is missing (NULL) or smaller than that is refused with MSAE_EWS before anything
+ *     is launched or written: outputs and workspace are untouched;
+ *   - a *_ws_bytes() helper returns 0 for every shape its entry refuses with MSAE_EINVAL because of the sizes the helper
+ *     sees (zero or negative sizes, k or N beyond the entry's envelope).
+ *
  * Return value: 0 on success, a positive hipError_t from the HIP runtime, or a negative
  * MSAE_E* code for argument errors (the reference raises Python AssertionError on the same
  * conditions: sae/kernels.py:28-36,194-197,303-309; the Python host layer turns any non-zero
@@ -293,8 +306,11 @@ int msae_encode_topk_rows(const void *x, int x_dtype, const float *W_enc, const 
  *                            by upper value u as one record of msae_shard_record_bytes(C) bytes:
  *                            uint64 key[C] (order key of u << 32 | 0x7FFFFFFF - GLOBAL feature id, 0 = empty),
  *                            float z_sigma[C], float tau (largest u any OTHER feature of the shard can have; +inf when
- *                            the shard cannot bound it), float 0.  ws as for msae_encode_topk(T, d, N/G, k) with the
- *                            same options.  MSAE_ENOTIMPL for shapes without the fused pass and for MSAE_COARSE_FP8 (its
+ *                            the shard cannot bound it), float 0.  ws: msae_encode_topk_ws_bytes(T, d, N/G, k, opts) with the
+ *                            same options, for every C >= 1 (the shard plans the same regions as the encode with a
+ *                            threshold rank, list capacity and segment count that C can only lower, and without the
+ *                            feature-major re-score: no region grows; less than the helper's size is MSAE_EWS all the
+ *                            same).  MSAE_ENOTIMPL for shapes without the fused pass and for MSAE_COARSE_FP8 (its
  *                            band reads the f32 weights of the batch's massive-activation dims, which a shard call does
  *                            not receive): the caller runs msae_encode_topk per shard instead.
  *   (all-to-all / all-gather of the records: rank r needs the records of its tokens from every shard)
@@ -566,7 +582,8 @@ int msae_probe_maps_f32(const void *x, int x_dtype, const float *W_enc, const fl
  *   included), any M >= 0, 1 <= k <= 64.  q_rows may be unsorted and hold repeats; an entry outside [0, Qn) is clamped
  *   into it, never faults.  chunks: 0 = chosen by the library (the smallest count that gives two workgroups per CU over
  *   the 128-query tiles, at most the 128-key strips and 8192 / k), > 0 = forced (tests; capped at the strips,
- *   MSAE_EINVAL beyond 8192 / k).  ws: msae_rows_topk_ws_bytes(M, N, k, chunks) bytes (the clamped row list, the merge
+ *   MSAE_EINVAL beyond 8192 / k).  ws: msae_rows_topk_ws_bytes(M, N, k, chunks) bytes, read when q_rows is given or more than
+ *   one chunk runs -- then a missing or smaller one is MSAE_EWS -- (the clamped row list, the merge
  *   mask of the int64 variant, then the per-chunk lists [chunks][2][M][k] in msae_merge_topk's `gathered` layout, merged by one msae_merge_topk call).
  * msae_row_inv_norms_f32: inv[n] = the f32 nearest to 1 / max(||W_n||_2, 1e-12) (F.normalize's clamp) evaluated in f64
  *   (fixed summation order, no atomics: bit-reproducible; <= 1 f32 ulp from numpy f64).  The cosine is defined from the

@@ -950,7 +950,7 @@ extern "C" int msae_encoder_refresh_for(const float *W_enc, int N, int d, void *
 }
 
 extern "C" size_t msae_encode_topk_ws_bytes(int T, int d, int N, int k, const msae_options *opts) {
-  if (T <= 0 || d <= 0 || N <= 0 || k <= 0) return 0;
+  if (T <= 0 || d <= 0 || N <= 0 || k <= 0 || k > N || k > 4096) return 0;   // (what encode_topk_impl refuses)
   CallOpts co;
   if (!resolve_opts(opts, co)) return 0;
   const FusedPlan pl = make_plan(T, d, N, k, co.mode, 0, co.cert != 0);
@@ -1157,7 +1157,10 @@ extern "C" int msae_shard_candidates(const void *x, int x_dtype, const float *b_
   const int zf = (zero_feature >= row_offset && zero_feature < row_offset + N) ? zero_feature - row_offset : -1;
   const EncodeCall c{x, x_dtype, nullptr, b_enc, b_dec, T, d, N, k, sf, 0.f, zf, nullptr, IdxOut{nullptr, nullptr}, nullptr,
                      (hipStream_t)stream};
-  if (ws_bytes < pl.bytes || !ws) return MSAE_EWS;
+  // the contract is msae_encode_topk_ws_bytes (include/msae.h): the shard's own plan never exceeds it -- C only lowers r, cap and
+  // the segment count, and there is no feature-major re-score -- and a caller that brings less than the contract is told so
+  const size_t contract = make_plan(T, d, N, k, co.mode).bytes;
+  if (ws_bytes < (contract > pl.bytes ? contract : pl.bytes) || !ws) return MSAE_EWS;
   if (!msae_aligned(ws, 256) || !msae_aligned(records, 8)) return MSAE_EALIGN;
   if (!inputs_aligned(c)) return MSAE_EALIGN;
   const Prepared pp = make_prepared(N, d);
@@ -1168,6 +1171,7 @@ extern "C" int msae_shard_candidates(const void *x, int x_dtype, const float *b_
 
 extern "C" size_t msae_rescore_candidates_ws_bytes(int T, int d, int N, int k, int G, int C) {
   if (T <= 0 || d <= 0 || N <= 0 || k <= 0 || G <= 0 || C <= 0) return 0;
+  if (k > N || k > 256 || (long)G * C < k || (long)G * C > 8192 || d % 64 != 0) return 0;   // (what msae_rescore_candidates refuses)
   return make_plan_ext(T, d, N, k, G * C).bytes;
 }
 

@@ -413,7 +413,7 @@ bool fs_args_ok(int T, int k, int N, int n_top, int mode, int pool_len, int wind
 }  // namespace
 
 extern "C" size_t msae_feature_stats_ws_bytes(int T, int k, int N) {
-  if (T < 0 || k <= 0 || N <= 0) return 0;
+  if (T < 0 || T > MSAE_STATS_MAX_T || k <= 0 || k > 256 || N <= 0 || N > 262144) return 0;   // fs_args_ok's envelope
   return fs_layout((long)T * k, N).total;
 }
 

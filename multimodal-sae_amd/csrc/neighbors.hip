@@ -206,7 +206,7 @@ extern "C" int msae_row_inv_norms_f32(const float *W, int N, int d, float *inv, 
 }
 
 extern "C" size_t msae_rows_topk_ws_bytes(int M, int N, int k, int chunks) {
-  if (!shape_ok(M, N, k, chunks)) return 0;
+  if (!shape_ok(M, N, k, chunks) || k > N) return 0;
   const int C = plan_chunks(M, N, k, chunks);
   if (C == 0) return 0;
   return head_bytes(M) + (C > 1 ? (size_t)C * 2 * M * k * sizeof(int32_t) : 0);
@@ -222,7 +222,7 @@ static int rows_topk_impl(const float *Q, int Qn, const int32_t *q_rows, int M, 
   const int C = plan_chunks(M, N, k, chunks);
   if (C == 0) return MSAE_EINVAL;
   const size_t need = head_bytes(M) + (C > 1 ? (size_t)C * 2 * M * k * sizeof(int32_t) : 0);
-  if ((q_rows || C > 1) && (!ws || ws_bytes < need)) return MSAE_EINVAL;
+  if ((q_rows || C > 1) && (!ws || ws_bytes < need)) return MSAE_EWS;
   if (C > 65535) return MSAE_EINVAL;
   const hipStream_t s = (hipStream_t)stream;
   int32_t *rows = q_rows ? static_cast<int32_t *>(ws) : nullptr;

@@ -479,7 +479,7 @@ __global__ __launch_bounds__(256) void adam8_dequantize_kernel(Adam8Ptrs st, flo
 
 constexpr int WRS_MID = 64;        // partial rows after the first summation level
 extern "C" size_t msae_weighted_row_sum_ws_bytes(int N, int d) {
-  return (N > 0 && d > 0) ? (size_t)((N + WRS_ROWS - 1) / WRS_ROWS + WRS_MID) * d * 4 : 0;
+  return (N > 0 && d > 0 && (d & 3) == 0) ? (size_t)((N + WRS_ROWS - 1) / WRS_ROWS + WRS_MID) * d * 4 : 0;
 }
 
 extern "C" int msae_weighted_row_sum_f32(const float *W, const float *s, int N, int d, float scale, float *out, void *ws,
