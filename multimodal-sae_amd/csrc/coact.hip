@@ -2,7 +2,7 @@
 // neighbour lists read from them (include/msae.h: msae_coact_*).
 //
 // A SEGMENT is a token, a window of W positions or the first P positions of a row (pool mode); a feature is ACTIVE in a
-// segment that holds a kept entry of it (|v| > thresh, 0 <= index < N: fs_keys_kernel's rule).  Per update:
+// segment that holds a kept entry of it (|v| > thresh, 0 <= index < N: pool_segments.h's pool_keep).  Per update:
 //   counts[slot][g]  += 1 for every segment in which query `slot` and feature g are both active      int32 atomics
 //   seg_count[g]     += 1 for every segment in which g is active                                      u64 atomics
 // Integer adds commute: the state is the same bits whatever the order of the adds, the cut into calls or their order.
@@ -13,7 +13,7 @@
 // product.
 // Window / image mode: the distinct members of a segment come from a sort.
 //   1. coact_keys_kernel   kept entries of pooled positions -> key (segment << fb | feature); others -> segment = nseg.
-//   2. rocPRIM radix sort  over the used key bits (as feature_stats.hip).
+//   2. pool_sort           rocPRIM radix sort (keys) over the used key bits, in pool_segments.h's scratch layout.
 //   3. coact_heads_kernel  one thread per sorted key: the first key of a run is a distinct member (one add into
 //                          seg_count); the first / last key of a segment records its range.
 //   4. coact_pairs_kernel  one workgroup per (segment, slice of its range).  The segment's range is walked in chunks of
@@ -28,30 +28,25 @@
 // every nonzero one into a rank key (common.h: score descending, feature ascending) and appends the keys that beat the
 // current m-th best to an LDS buffer; a full buffer is sorted (sortsel.h) and cut back to its first m.  Rank keys are
 // distinct, so the list is a function of the set of candidates alone.
-#include <rocprim/device/device_radix_sort.hpp>
-
+#include "pool_segments.h"
 #include "sortsel.h"
 #include "wave_ops.h"
 
 namespace {
 
-constexpr int CO_MAX_K = 256, CO_MAX_F = 16384, CO_MAX_N = 262144, CO_MAX_M = 64;
+constexpr int CO_MAX_F = 16384, CO_MAX_M = 64;
 constexpr int CO_CHUNK = 1024;              // keys per round of the pairs kernel = capacity of its query list
 constexpr int CO_PAIR_THREADS = 256;
 constexpr int CO_TOPK_THREADS = 256, CO_TOPK_BUF = 2048, CO_TOPK_TILE = CO_TOPK_THREADS * 4;
 static_assert(CO_MAX_M + CO_TOPK_TILE <= CO_TOPK_BUF, "one tile of candidates fits behind a trimmed list");
-
-__device__ __forceinline__ bool co_keep(float v, int f, float thresh, int N) {
-  return fabsf(v) > thresh && (unsigned)f < (unsigned)N;
-}
 
 // ---- token mode ------------------------------------------------------------------------------------------------------
 // one single-wave workgroup per token: __syncthreads() orders the wave's LDS traffic
 __global__ __launch_bounds__(64) void coact_token_kernel(
     const float *__restrict__ vals, const int32_t *__restrict__ idx, int k, float thresh, int N,
     const int32_t *__restrict__ slot_of, int F, int *__restrict__ counts, unsigned long long *__restrict__ seg_count) {
-  __shared__ int feat[CO_MAX_K];
-  __shared__ int slot[CO_MAX_K];
+  __shared__ int feat[POOL_MAX_K];
+  __shared__ int slot[POOL_MAX_K];
   const int lane = threadIdx.x;
   const size_t base = (size_t)blockIdx.x * k;
   const unsigned long long below = (1ull << lane) - 1ull;
@@ -62,7 +57,7 @@ __global__ __launch_bounds__(64) void coact_token_kernel(
     bool keep = false;
     if (j < k) {
       f = idx[base + j];
-      keep = co_keep(vals[base + j], f, thresh, N);
+      keep = pool_keep(vals[base + j], f, thresh, N);
     }
     const unsigned long long m = __ballot(keep);
     if (keep) feat[n + __popcll(m & below)] = f;
@@ -100,8 +95,8 @@ __global__ __launch_bounds__(64) void coact_token_kernel(
 }
 
 // ---- window / image mode ---------------------------------------------------------------------------------------------
-struct CoGeom {
-  int S, k, mode, P, W, nw, fb, nseg;
+struct CoGeom : PoolGeom {      // ... and the segment-major key: (segment << fb | feature), nseg segments in the call
+  int k, fb, nseg;
 };
 
 // segment of token (b, s), or -1
@@ -117,7 +112,7 @@ __global__ __launch_bounds__(256) void coact_keys_kernel(const float *__restrict
   if (i >= M) return;
   const int f = idx[i];
   const int t = (int)(i / g.k), b = t / g.S, s = t - b * g.S;
-  const int seg = co_keep(vals[i], f, thresh, N) ? co_segment(g, b, s) : -1;
+  const int seg = pool_keep(vals[i], f, thresh, N) ? co_segment(g, b, s) : -1;
   keys[i] = seg >= 0 ? ((unsigned long long)seg << g.fb) | (unsigned)f : (unsigned long long)g.nseg << g.fb;
 }
 
@@ -237,51 +232,21 @@ __global__ __launch_bounds__(CO_TOPK_THREADS) void coact_topk_kernel(
   }
 }
 
-int co_bit_width(unsigned long long v) { return v ? 64 - __builtin_clzll(v) : 0; }
-
-struct CoLayout {
-  size_t keys0, keys1, starts, ends, sort, total;
-};
-
-size_t co_sort_bound(long M) { return (size_t)M * 8 + (1u << 20); }
-
-CoLayout co_layout(long T, long M) {
-  CoLayout L;
-  size_t o = 0;
-  auto take = [&](size_t b) { size_t r = o; o = msae_align_up(o + b, 256); return r; };
-  L.keys0 = take((size_t)M * 8);
-  L.keys1 = take((size_t)M * 8);
-  L.starts = take((size_t)(T > 0 ? T : 1) * 4);
-  L.ends = take((size_t)(T > 0 ? T : 1) * 4);
-  L.sort = take(co_sort_bound(M));
-  L.total = o;
-  return L;
-}
-
-bool co_shape_ok(int T, int k, int N) {
-  return T >= 0 && T <= MSAE_STATS_MAX_T && k > 0 && k <= CO_MAX_K && N > 0 && N <= CO_MAX_N;
-}
+PoolLayout co_layout(long T, long M) { return pool_layout(M, false, T > 0 ? T : 1); }
 
 }  // namespace
 
 extern "C" size_t msae_coact_ws_bytes(int T, int k, int N) {
-  if (!co_shape_ok(T, k, N)) return 0;
+  if (!pool_shape_ok(T, k, N)) return 0;
   return co_layout(T, (long)T * k).total;
 }
 
 extern "C" int msae_coact_update(const float *vals, const int32_t *idx, int B, int S, int k, float thresh, int N, int mode,
                                  int pool_len, int window, const int32_t *slot_of, int F, int32_t *counts,
                                  uint64_t *seg_count, void *ws, size_t ws_bytes, void *stream) {
-  if (B < 0 || S < 0 || (B > 0 && S > MSAE_STATS_MAX_T / B)) return MSAE_EINVAL;
-  const int T = B * S;
-  if (!co_shape_ok(T, k, N) || F < 1 || F > CO_MAX_F) return MSAE_EINVAL;
-  if (mode == MSAE_POOL_IMAGE) {
-    if (pool_len <= 0 || pool_len > 2880) return MSAE_EINVAL;
-  } else if (mode == MSAE_POOL_WINDOW) {
-    if (window <= 0 || window > 4096) return MSAE_EINVAL;
-  } else if (mode != MSAE_POOL_TOKEN) {
-    return MSAE_EINVAL;
-  }
+  int T;
+  if (!pool_tokens(B, S, &T) || !pool_shape_ok(T, k, N) || F < 1 || F > CO_MAX_F) return MSAE_EINVAL;
+  if (!pool_mode_ok(mode, pool_len, window, true)) return MSAE_EINVAL;
   if (T == 0) return 0;
   if (!vals || !idx || !slot_of || !counts || !seg_count) return MSAE_EINVAL;
   hipStream_t st = (hipStream_t)stream;
@@ -290,32 +255,22 @@ extern "C" int msae_coact_update(const float *vals, const int32_t *idx, int B, i
                        (unsigned long long *)seg_count);
     return msae_launch_status();
   }
-  CoGeom g;
-  g.S = S;
-  g.k = k;
-  g.mode = mode;
-  g.P = pool_len;
-  g.W = window;
-  g.nw = mode == MSAE_POOL_WINDOW ? S / window : 1;
-  g.fb = co_bit_width((unsigned long long)(N - 1));
-  g.nseg = mode == MSAE_POOL_WINDOW ? B * g.nw : B;
+  const PoolGeom pg = pool_geom(T, S, mode, pool_len, window);
+  const CoGeom g{pg, k, pool_bit_width((unsigned long long)(N - 1)), mode == MSAE_POOL_WINDOW ? B * pg.nw : B};
   if (g.nseg == 0) return 0;                                // rows shorter than one window: nothing is pooled
   const long M = (long)T * k;
-  const CoLayout L = co_layout(T, M);
+  const PoolLayout L = co_layout(T, M);
   if (!ws || ws_bytes < L.total) return MSAE_EWS;
   char *w = (char *)ws;
-  unsigned long long *k0 = (unsigned long long *)(w + L.keys0), *k1 = (unsigned long long *)(w + L.keys1);
   int *starts = (int *)(w + L.starts), *ends = (int *)(w + L.ends);
   const unsigned blocks = (unsigned)((M + 255) / 256);
-  hipLaunchKernelGGL(coact_keys_kernel, dim3(blocks), dim3(256), 0, st, vals, idx, M, thresh, N, g, k0);
+  hipLaunchKernelGGL(coact_keys_kernel, dim3(blocks), dim3(256), 0, st, vals, idx, M, thresh, N, g,
+                     (unsigned long long *)(w + L.keys0));
   MSAE_HIP_TRY(hipMemsetAsync(ends, 0, (size_t)g.nseg * 4, st));
-  rocprim::double_buffer<unsigned long long> kb(k0, k1);
-  const unsigned end_bit = (unsigned)(g.fb + co_bit_width((unsigned long long)g.nseg));
-  size_t sort_bytes = 0;
-  MSAE_HIP_TRY(rocprim::radix_sort_keys(nullptr, sort_bytes, kb, (size_t)M, 0u, end_bit, st));
-  if (sort_bytes > co_sort_bound(M)) return MSAE_EWS;
-  MSAE_HIP_TRY(rocprim::radix_sort_keys((void *)(w + L.sort), sort_bytes, kb, (size_t)M, 0u, end_bit, st));
-  hipLaunchKernelGGL(coact_heads_kernel, dim3(blocks), dim3(256), 0, st, kb.current(), M, g, starts, ends,
+  PoolSorted sorted;
+  const unsigned end_bit = (unsigned)(g.fb + pool_bit_width((unsigned long long)g.nseg));
+  if (const int rc = pool_sort(w, L, M, end_bit, false, st, &sorted)) return rc;
+  hipLaunchKernelGGL(coact_heads_kernel, dim3(blocks), dim3(256), 0, st, sorted.keys, M, g, starts, ends,
                      (unsigned long long *)seg_count);
   // slices of a segment's member side: enough workgroups for the chip when the segments are few (image mode)
   int slices = (1024 + g.nseg - 1) / g.nseg;
@@ -323,13 +278,13 @@ extern "C" int msae_coact_update(const float *vals, const int32_t *idx, int B, i
   slices = slices < 1 ? 1 : slices > 64 ? 64 : slices;
   if (slices > max_slices) slices = max_slices;
   hipLaunchKernelGGL(coact_pairs_kernel, dim3((unsigned)g.nseg, (unsigned)slices), dim3(CO_PAIR_THREADS), 0, st,
-                     kb.current(), g, N, starts, ends, slot_of, F, counts);
+                     sorted.keys, g, N, starts, ends, slot_of, F, counts);
   return msae_launch_status();
 }
 
 static int coact_topk_impl(const int32_t *counts, const int64_t *seg_count, const int32_t *queries, int F, int N, int m,
                            int metric, int exclude_self, float *out_val, void *out_idx, bool wide, void *stream) {
-  if (F < 1 || F > CO_MAX_F || N <= 0 || N > CO_MAX_N || m < 1 || m > CO_MAX_M) return MSAE_EINVAL;
+  if (F < 1 || F > CO_MAX_F || N <= 0 || N > POOL_MAX_N || m < 1 || m > CO_MAX_M) return MSAE_EINVAL;
   if (metric != MSAE_COACT_JACCARD && metric != MSAE_COACT_COUNT) return MSAE_EINVAL;
   if (!counts || !seg_count || !queries || !out_val || !out_idx) return MSAE_EINVAL;
   hipStream_t st = (hipStream_t)stream;

@@ -6,13 +6,14 @@
 // pool_max_activations_windows_image -- there a dense [rows, seq] tensor per feature on the CPU).
 //
 // One update per batch of [B*S][k] top-k pairs:
-//   1. key build      every kept entry (|v| > thresh, sparsify's rule; no filter bitmap) becomes the key
-//                     (feature << tb | t) with its value; dropped entries get feature = N and sort last.
+//   1. key build      pool_segments.h's pool_keys_kernel: every kept entry (|v| > thresh, sparsify's rule; no filter bitmap)
+//                     becomes the key (feature << tb | t) with its value; dropped entries get feature = N and sort last.
 //   2. radix sort     rocPRIM's device radix sort over the used key bits: entries grouped by feature, and inside a
 //                     feature in token order (t is unique per feature: a token's top-k indices are distinct).
 //   3. group pass     a GROUP is the run of one feature inside one pooling segment (window mode: [w*W, (w+1)*W) of
 //                     a row, the ragged tail its own group; image mode: the row).  The thread on a group's first
-//                     entry walks it in ascending position: count / max / f64 sum -> ONE atomic each per (group,
+//                     entry walks it in ascending position (pool_segments.h's pool_walk_run, the walk the activation
+//                     histograms share): count / max / f64 sum -> ONE atomic each per (group,
 //                     feature), not one per token (a feature that fires on every token costs B*S/W atomics, not
 //                     B*S); the pooled value of the segment -> cand[i] (0 = no candidate).
 //   4. table merge    one wave per feature with records in this batch: the candidates of its run are ranked
@@ -23,21 +24,16 @@
 //                     under another order (FsSampleOrder: a hash of (seed, feature, id) ascending), and counts the
 //                     feature's candidates.
 // No host synchronisation, no allocation (workspace: msae_feature_stats_ws_bytes).
-#include <rocprim/device/device_radix_sort.hpp>
-
-#include "common.h"
+#include "pool_segments.h"
 #include "wave_ops.h"
 
 namespace {
 
 constexpr int FS_MAX_TOP = 256;
 
-struct FsGeom {      // where token t = b*S + s belongs
-  int S, mode, P, W, nw, tb;
+struct FsGeom : PoolGeom {      // ... and the global row of the call's first row
   long long row_base;
 };
-
-__device__ __forceinline__ int fs_group(const FsGeom &g, int s) { return g.mode == MSAE_POOL_WINDOW ? s / g.W : 0; }
 
 // the pooled candidate's id: image = global row, window = global row * (S / W) + w
 __device__ __forceinline__ long long fs_id(const FsGeom &g, int b, int grp) {
@@ -185,19 +181,6 @@ struct FsMergeLds<true, CAP> : FsMergeLds<false, CAP> {
   unsigned long long cp[64];
 };
 
-__global__ __launch_bounds__(256) void fs_keys_kernel(const float *__restrict__ vals, const int32_t *__restrict__ idx,
-                                                      long M, int k, float thresh, int N, int tb,
-                                                      unsigned long long *__restrict__ keys, float *__restrict__ kv) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= M) return;
-  const float v = vals[i];
-  const int f = idx[i];
-  const unsigned long long t = (unsigned long long)(i / k);
-  const bool keep = fabsf(v) > thresh && (unsigned)f < (unsigned)N;   // sparsify_count_kernel's rule, no bitmap
-  keys[i] = ((unsigned long long)(keep ? f : N) << tb) | t;
-  kv[i] = v;
-}
-
 // one thread per sorted entry: run boundaries of every feature, and the walk of every group from its first entry
 __global__ __launch_bounds__(256) void fs_group_kernel(const unsigned long long *__restrict__ keys,
                                                        const float *__restrict__ kv, long M, int N, FsGeom g,
@@ -206,54 +189,20 @@ __global__ __launch_bounds__(256) void fs_group_kernel(const unsigned long long 
                                                        float *__restrict__ act_max, double *__restrict__ act_sum) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= M) return;
-  const unsigned long long tmask = (1ull << g.tb) - 1ull;
-  const unsigned long long key = keys[i];
-  const int f = (int)(key >> g.tb);
+  const PoolEntry e = pool_entry(keys[i], g);
+  const int f = e.f;
   if (f >= N) return;                               // dropped entries: sorted behind every kept one
-  const int t = (int)(key & tmask), b = t / g.S, s = t - b * g.S, grp = fs_group(g, s);
-  bool first = true;
-  if (i == 0 || (int)(keys[i - 1] >> g.tb) != f) {
-    run_start[f] = (int)i;
-  } else {
-    const int pt = (int)(keys[i - 1] & tmask), pb = pt / g.S;
-    first = !(pb == b && fs_group(g, pt - pb * g.S) == grp);
-  }
-  if (i == M - 1 || (int)(keys[i + 1] >> g.tb) != f) run_end[f] = (int)i + 1;
-  if (!first) {
+  if (i == 0 || pool_key_feature(keys[i - 1], g) != f) run_start[f] = (int)i;
+  if (i == M - 1 || pool_key_feature(keys[i + 1], g) != f) run_end[f] = (int)i + 1;
+  if (!pool_run_head(keys, i, e, g)) {
     cand[i] = 0.f;
     return;
   }
-  int cnt = 0, pooled_n = 0;
-  float mx = -INFINITY, pool = 0.f;               // window: max; image: f32 sum in ascending s
-  double sum = 0.0;
-  for (long j = i; j < M; ++j) {
-    const unsigned long long kj = keys[j];
-    if ((int)(kj >> g.tb) != f) break;
-    const int tj = (int)(kj & tmask), bj = tj / g.S, sj = tj - bj * g.S;
-    if (bj != b || fs_group(g, sj) != grp) break;
-    const float v = kv[j];
-    ++cnt;
-    mx = fmaxf(mx, v);
-    sum += (double)v;
-    if (g.mode == MSAE_POOL_WINDOW) {
-      pool = pooled_n ? fmaxf(pool, v) : v;
-      ++pooled_n;
-    } else if (sj < g.P) {
-      pool += v;
-      ++pooled_n;
-    }
-  }
-  atomicAdd(count + f, (unsigned long long)cnt);
-  atomic_max_f32(act_max + f, mx);
-  atomicAdd(act_sum + f, sum);
-  float c = 0.f;
-  if (g.mode == MSAE_POOL_WINDOW) {
-    // max_pool1d over the dense row: a window with a position this feature did not fire on also holds a 0
-    if (grp < g.nw) c = cnt < g.W ? fmaxf(pool, 0.f) : pool;
-  } else if (pooled_n) {
-    c = pool / (float)g.P;                          // avg_pool1d over the first P positions
-  }
-  cand[i] = (c == c) ? c : 0.f;                     // NaN never enters a table
+  const PoolRun r = pool_walk_run<true>(keys, kv, M, i, e, g);
+  atomicAdd(count + f, (unsigned long long)r.cnt);    // the ragged tail has no candidate but counts here
+  atomic_max_f32(act_max + f, r.mx);
+  atomicAdd(act_sum + f, r.sum);
+  cand[i] = (r.cand == r.cand) ? r.cand : 0.f;      // NaN never enters a table
 }
 
 // one single-wave workgroup per feature (grid-stride): rank this batch's candidates against the feature's table(s), merge.
@@ -299,7 +248,7 @@ __global__ __launch_bounds__(64) void fs_merge_kernel(const unsigned long long *
       long long id = 0;
       if (is_c) {
         const int t = (int)(keys[i] & tmask), b = t / g.S;
-        id = fs_id(g, b, fs_group(g, t - b * g.S));
+        id = fs_id(g, b, g.group(t - b * g.S));
       }
       L.cv[lane] = c;
       L.ci[lane] = id;
@@ -379,41 +328,16 @@ __global__ __launch_bounds__(64) void fs_merge_tables_kernel(
   }
 }
 
-int bit_width(unsigned long long v) { return v ? 64 - __builtin_clzll(v) : 0; }
-
-struct FsLayout {
-  size_t keys0, keys1, vals0, vals1, starts, ends, sort, total;
-};
-
-size_t fs_sort_bound(long M) { return (size_t)M * 8 + (1u << 20); }
-
-FsLayout fs_layout(long M, int N) {
-  FsLayout L;
-  size_t o = 0;
-  auto take = [&](size_t b) { size_t r = o; o = msae_align_up(o + b, 256); return r; };
-  L.keys0 = take((size_t)M * 8);
-  L.keys1 = take((size_t)M * 8);
-  L.vals0 = take((size_t)M * 4);
-  L.vals1 = take((size_t)M * 4);
-  L.starts = take((size_t)N * 4);
-  L.ends = take((size_t)N * 4);
-  L.sort = take(fs_sort_bound(M));
-  L.total = o;
-  return L;
-}
+PoolLayout fs_layout(long M, int N) { return pool_layout(M, true, N); }
 
 bool fs_args_ok(int T, int k, int N, int n_top, int mode, int pool_len, int window) {
-  if (T < 0 || T > MSAE_STATS_MAX_T || k <= 0 || k > 256 || N <= 0 || N > 262144) return false;
-  if (n_top <= 0 || n_top > FS_MAX_TOP) return false;
-  if (mode == MSAE_POOL_IMAGE) return pool_len > 0 && pool_len <= 2880;
-  if (mode == MSAE_POOL_WINDOW) return window > 0 && window <= 4096;
-  return false;
+  return pool_shape_ok(T, k, N) && n_top > 0 && n_top <= FS_MAX_TOP && pool_mode_ok(mode, pool_len, window, false);
 }
 
 }  // namespace
 
 extern "C" size_t msae_feature_stats_ws_bytes(int T, int k, int N) {
-  if (T < 0 || T > MSAE_STATS_MAX_T || k <= 0 || k > 256 || N <= 0 || N > 262144) return 0;   // fs_args_ok's envelope
+  if (!pool_shape_ok(T, k, N)) return 0;
   return fs_layout((long)T * k, N).total;
 }
 
@@ -428,51 +352,39 @@ bool fs_sample_ok(const msae_feature_sample *sm) {
 int fs_update(const float *vals, const int32_t *idx, int B, int S, int k, float thresh, int N, int mode, int pool_len,
               int window, int64_t row_base, int n_top, uint64_t *count, float *act_max, double *act_sum, float *top_val,
               int64_t *top_id, const msae_feature_sample *sample, void *ws, size_t ws_bytes, void *stream) {
-  if (B < 0 || S < 0 || (B > 0 && S > MSAE_STATS_MAX_T / B)) return MSAE_EINVAL;
-  const int T = B * S;
+  int T;
+  if (!pool_tokens(B, S, &T)) return MSAE_EINVAL;
   if (!fs_args_ok(T, k, N, n_top, mode, pool_len, window) || row_base < 0) return MSAE_EINVAL;
   if (sample && !fs_sample_ok(sample)) return MSAE_EINVAL;
   if (T == 0) return 0;
   const long M = (long)T * k;
-  const FsLayout L = fs_layout(M, N);
+  const PoolLayout L = fs_layout(M, N);
   if (!ws || ws_bytes < L.total) return MSAE_EWS;
   hipStream_t st = (hipStream_t)stream;
   char *w = (char *)ws;
-  unsigned long long *k0 = (unsigned long long *)(w + L.keys0), *k1 = (unsigned long long *)(w + L.keys1);
-  float *v0 = (float *)(w + L.vals0), *v1 = (float *)(w + L.vals1);
   int *starts = (int *)(w + L.starts), *ends = (int *)(w + L.ends);
-  FsGeom g;
-  g.S = S;
-  g.mode = mode;
-  g.P = pool_len;
-  g.W = window;
-  g.nw = mode == MSAE_POOL_WINDOW ? S / window : 1;
-  g.tb = bit_width((unsigned long long)(T - 1));
-  g.row_base = row_base;
+  const FsGeom g{pool_geom(T, S, mode, pool_len, window), row_base};
   const unsigned blocks = (unsigned)((M + 255) / 256);
-  hipLaunchKernelGGL(fs_keys_kernel, dim3(blocks), dim3(256), 0, st, vals, idx, M, k, thresh, N, g.tb, k0, v0);
+  hipLaunchKernelGGL(pool_keys_kernel, dim3(blocks), dim3(256), 0, st, vals, idx, M, k, thresh, N, g.tb,
+                     (unsigned long long *)(w + L.keys0), (float *)(w + L.vals0));
   MSAE_HIP_TRY(hipMemsetAsync(ends, 0, (size_t)N * 4, st));
-  rocprim::double_buffer<unsigned long long> kb(k0, k1);
-  rocprim::double_buffer<float> vb(v0, v1);
-  const unsigned end_bit = (unsigned)(g.tb + bit_width((unsigned long long)N));
-  size_t sort_bytes = 0;
-  MSAE_HIP_TRY(rocprim::radix_sort_pairs(nullptr, sort_bytes, kb, vb, (size_t)M, 0u, end_bit, st));
-  if (sort_bytes > fs_sort_bound(M)) return MSAE_EWS;
-  MSAE_HIP_TRY(rocprim::radix_sort_pairs((void *)(w + L.sort), sort_bytes, kb, vb, (size_t)M, 0u, end_bit, st));
+  PoolSorted sorted;
+  const unsigned end_bit = (unsigned)(g.tb + pool_bit_width((unsigned long long)N));
+  if (const int rc = pool_sort(w, L, M, end_bit, true, st, &sorted)) return rc;
   // the group pass writes the candidates over the sort's other value buffer (dead after the sort)
-  float *cand = vb.current() == v0 ? v1 : v0;
-  hipLaunchKernelGGL(fs_group_kernel, dim3(blocks), dim3(256), 0, st, kb.current(), vb.current(), M, N, g, starts,
-                     ends, cand, (unsigned long long *)count, act_max, act_sum);
+  float *cand = sorted.spare;
+  hipLaunchKernelGGL(fs_group_kernel, dim3(blocks), dim3(256), 0, st, sorted.keys, sorted.vals, M, N, g, starts, ends,
+                     cand, (unsigned long long *)count, act_max, act_sum);
   const unsigned mblocks = (unsigned)(N < 8192 ? N : 8192);
   FsSampleArgs sa{};
   if (sample) {
     sa = FsSampleArgs{sample->n_sample, (unsigned long long)sample->seed, (unsigned long long *)sample->seg_count,
                       sample->smp_val, (long long *)sample->smp_id};
     auto kern = n_top <= 64 && sa.n <= 64 ? fs_merge_kernel<true, 64> : fs_merge_kernel<true, FS_MAX_TOP>;
-    hipLaunchKernelGGL(kern, dim3(mblocks), dim3(64), 0, st, kb.current(), cand, N, n_top, g, starts, ends, top_val,
+    hipLaunchKernelGGL(kern, dim3(mblocks), dim3(64), 0, st, sorted.keys, cand, N, n_top, g, starts, ends, top_val,
                        (long long *)top_id, sa);
   } else {
-    hipLaunchKernelGGL((fs_merge_kernel<false, FS_MAX_TOP>), dim3(mblocks), dim3(64), 0, st, kb.current(), cand, N, n_top, g, starts,
+    hipLaunchKernelGGL((fs_merge_kernel<false, FS_MAX_TOP>), dim3(mblocks), dim3(64), 0, st, sorted.keys, cand, N, n_top, g, starts,
                        ends, top_val, (long long *)top_id, sa);
   }
   return msae_launch_status();
@@ -502,7 +414,7 @@ extern "C" int msae_feature_stats_merge(int N, int n_top, uint64_t *count, float
                                         float *top_val, int64_t *top_id, const uint64_t *src_count,
                                         const float *src_max, const double *src_sum, const float *src_val,
                                         const int64_t *src_id, void *stream) {
-  if (N <= 0 || N > 262144 || n_top <= 0 || n_top > FS_MAX_TOP) return MSAE_EINVAL;
+  if (N <= 0 || N > POOL_MAX_N || n_top <= 0 || n_top > FS_MAX_TOP) return MSAE_EINVAL;
   const unsigned blocks = (unsigned)(N < 8192 ? N : 8192);
   hipLaunchKernelGGL(fs_merge_tables_kernel<FsTopOrder>, dim3(blocks), dim3(64), 0, (hipStream_t)stream, N, n_top,
                      FsTopOrder{}, (unsigned long long *)count, act_max, act_sum, top_val, (long long *)top_id,
@@ -513,7 +425,7 @@ extern "C" int msae_feature_stats_merge(int N, int n_top, uint64_t *count, float
 extern "C" int msae_feature_sample_merge(int N, int n_sample, uint64_t seed, uint64_t *seg_count, float *smp_val,
                                          int64_t *smp_id, const uint64_t *src_seg_count, const float *src_val,
                                          const int64_t *src_id, void *stream) {
-  if (N <= 0 || N > 262144 || n_sample <= 0 || n_sample > FS_MAX_TOP) return MSAE_EINVAL;
+  if (N <= 0 || N > POOL_MAX_N || n_sample <= 0 || n_sample > FS_MAX_TOP) return MSAE_EINVAL;
   if (!seg_count || !smp_val || !smp_id || !src_seg_count || !src_val || !src_id) return MSAE_EINVAL;
   const unsigned blocks = (unsigned)(N < 8192 ? N : 8192);
   hipLaunchKernelGGL(fs_merge_tables_kernel<FsSampleOrder>, dim3(blocks), dim3(64), 0, (hipStream_t)stream, N,

@@ -48,7 +48,8 @@ from __future__ import annotations
 import os
 import re
 from collections import defaultdict
-from typing import Dict, Optional, Sequence
+from types import SimpleNamespace
+from typing import Callable, Dict, NamedTuple, Optional, Sequence
 
 import torch
 import torch.distributed as dist
@@ -61,6 +62,39 @@ from .coact import CoactStats
 from .hist import ActHist
 from .recon import ReconStats
 from .stats import FeatureStats
+
+
+class _Accumulator(NamedTuple):
+    """One kind of per-module statistics the cache can keep next to the records."""
+    keyword: str        # the Cache keyword whose dict switches it on (kept as the attribute of that name; None: off)
+    attr: str           # the Cache attribute {module: accumulator}
+    stem: str           # files: Rank{r}_<stem>.safetensors per rank, <stem>.safetensors after the concat
+    cls: type
+    source: str         # "topk": fed by add_topk; "recon": fed by add_recon
+    make: Callable      # (cache, module_path, call) -> a new accumulator for the module
+    feed: Callable      # (accumulator, call) -> None; `call` holds the arguments of the add_* call
+
+
+def _new_recon(cache, module_path, c):
+    ks = cache.recon.get("ks")
+    return ReconStats(c.sae.d_in, c.sae.default_recon_ks() if ks is None else ks, cache.recon.get("position_edges") or (0,),
+                      b_dec=c.sae.b_dec, device=c.device)
+
+
+# add_topk feeds in this order: stats, coact, hist (then sparsify)
+ACCUMULATORS = (
+    _Accumulator("stats", "feature_stats", "feature_stats", FeatureStats, "topk",
+                 lambda cache, m, c: FeatureStats(c.num_latents, device=c.device, **cache.stats),
+                 lambda st, c: st.update(c.top_acts, c.top_indices, c.row_base)),
+    _Accumulator("coact", "coact_stats", "coact", CoactStats, "topk",
+                 lambda cache, m, c: cache._new_coact(m, c.num_latents, c.device),
+                 lambda co, c: co.update(c.top_acts, c.top_indices)),
+    _Accumulator("recon", "recon_stats", "recon_stats", ReconStats, "recon", _new_recon,
+                 lambda rs, c: rs.update(c.hidden, c.top_acts, c.top_indices, c.sae)),
+    _Accumulator("hist", "act_hists", "act_hist", ActHist, "topk",
+                 lambda cache, m, c: ActHist(c.num_latents, device=c.device, **cache.hist),
+                 lambda ah, c: ah.update(c.top_acts, c.top_indices)),
+)
 
 
 def generate_split_indices(width: int, n_splits: int):
@@ -109,18 +143,17 @@ class Cache:
         # groups of batches on their way to the host: (copy-done event, device buffers kept alive, pinned staging, layout)
         self._inflight = []
         self._copy_stream = None
-        self.stats = None if stats is None else dict(stats)
-        self.feature_stats: Dict[str, FeatureStats] = {}
-        self.coact = None if coact is None else dict(coact)
+        # per kind: self.stats / .coact / .recon / .hist (its keyword arguments, None: off) and the accumulators per module in
+        # self.feature_stats / .coact_stats / .recon_stats / .act_hists
+        given = dict(stats=stats, coact=coact, recon=recon, hist=hist)
+        for kind in ACCUMULATORS:
+            kw = given[kind.keyword]
+            setattr(self, kind.keyword, None if kw is None else dict(kw))
+            setattr(self, kind.attr, {})
         if self.coact is not None and self.coact.get("queries") is None and filters is None:
             raise ValueError("coact needs query features: pass coact['queries'] or a feature filter")
-        self.coact_stats: Dict[str, CoactStats] = {}
-        self.recon = None if recon is None else dict(recon)
         if self.recon is not None and set(self.recon) - {"ks", "position_edges"}:
             raise ValueError(f"recon takes the keys 'ks' and 'position_edges', got {sorted(self.recon)}")
-        self.recon_stats: Dict[str, ReconStats] = {}
-        self.hist = None if hist is None else dict(hist)
-        self.act_hists: Dict[str, ActHist] = {}
 
     def _bitmap(self, module_path: str, num_latents: int, device) -> Optional[Tensor]:
         if self.filters is None:
@@ -137,21 +170,8 @@ class Cache:
                  module_path: str):
         """Fused equivalent of scatter_ + Cache.add (cache.py:214-217, 42-57) for `[B,S,k]` pairs."""
         row_base = batch_number * self.batch_size + self.shard_size  # cache.py:55
-        if self.stats is not None:
-            st = self.feature_stats.get(module_path)
-            if st is None:
-                st = self.feature_stats[module_path] = FeatureStats(num_latents, device=top_acts.device, **self.stats)
-            st.update(top_acts, top_indices, row_base)
-        if self.coact is not None:
-            co = self.coact_stats.get(module_path)
-            if co is None:
-                co = self.coact_stats[module_path] = self._new_coact(module_path, num_latents, top_acts.device)
-            co.update(top_acts, top_indices)
-        if self.hist is not None:
-            ah = self.act_hists.get(module_path)
-            if ah is None:
-                ah = self.act_hists[module_path] = ActHist(num_latents, device=top_acts.device, **self.hist)
-            ah.update(top_acts, top_indices)
+        self._feed("topk", module_path, top_acts=top_acts, top_indices=top_indices, num_latents=num_latents,
+                   row_base=row_base, device=top_acts.device)
         loc, act, nnz = ops.sparsify(top_acts, top_indices, num_latents, row_base=row_base, thresh=1e-5,
                                      filter_bitmap=self._bitmap(module_path, num_latents, top_acts.device), sync=False)
         # stays on the device, stream-ordered (the reference does a nonzero() + two .cpu() per batch inside the
@@ -165,15 +185,19 @@ class Cache:
 
     def add_recon(self, hidden: Tensor, top_acts: Tensor, top_indices: Tensor, sae, module_path: str):
         """The batch's hidden state [B, S, d] and its top-k list into the module's `ReconStats` (a no-op without `recon=`)."""
-        if self.recon is None:
-            return
-        st = self.recon_stats.get(module_path)
-        if st is None:
-            ks = self.recon.get("ks")
-            st = self.recon_stats[module_path] = ReconStats(
-                sae.d_in, sae.default_recon_ks() if ks is None else ks, self.recon.get("position_edges") or (0,),
-                b_dec=sae.b_dec, device=hidden.device)
-        st.update(hidden, top_acts, top_indices, sae)
+        self._feed("recon", module_path, hidden=hidden, top_acts=top_acts, top_indices=top_indices, sae=sae,
+                   device=hidden.device)
+
+    def _feed(self, source: str, module_path: str, **call):
+        """The accumulators of `source` that are switched on, in table order: made at a module's first batch, then updated."""
+        call = SimpleNamespace(**call)
+        for kind in ACCUMULATORS:
+            if kind.source != source or getattr(self, kind.keyword) is None:
+                continue
+            accs = getattr(self, kind.attr)
+            if module_path not in accs:
+                accs[module_path] = kind.make(self, module_path, call)
+            kind.feed(accs[module_path], call)
 
     def _new_coact(self, module_path: str, num_latents: int, device) -> CoactStats:
         kw = dict(self.coact)
@@ -379,22 +403,11 @@ class FeatureCache:
                 mask = (feats >= start) & (feats < hi)
                 save_file({"locations": loc[mask].contiguous(), "activations": act[mask].contiguous()},
                           f"{module_dir}/Rank{rank}_{start}_{end}.safetensors")
-        for module_path, st in self.cache.feature_stats.items():
-            module_dir = f"{save_dir}/{module_path}"
-            os.makedirs(module_dir, exist_ok=True)
-            st.save(f"{module_dir}/Rank{rank}_feature_stats.safetensors")
-        for module_path, co in self.cache.coact_stats.items():
-            module_dir = f"{save_dir}/{module_path}"
-            os.makedirs(module_dir, exist_ok=True)
-            co.save(f"{module_dir}/Rank{rank}_coact.safetensors")
-        for module_path, rs in self.cache.recon_stats.items():
-            module_dir = f"{save_dir}/{module_path}"
-            os.makedirs(module_dir, exist_ok=True)
-            rs.save(f"{module_dir}/Rank{rank}_recon_stats.safetensors")
-        for module_path, ah in self.cache.act_hists.items():
-            module_dir = f"{save_dir}/{module_path}"
-            os.makedirs(module_dir, exist_ok=True)
-            ah.save(f"{module_dir}/Rank{rank}_act_hist.safetensors")
+        for kind in ACCUMULATORS:
+            for module_path, acc in getattr(self.cache, kind.attr).items():
+                module_dir = f"{save_dir}/{module_path}"
+                os.makedirs(module_dir, exist_ok=True)
+                acc.save(f"{module_dir}/Rank{rank}_{kind.stem}.safetensors")
 
     def concate_safetensors(self, n_splits: int, save_dir):
         for module_path in self.cache.feature_locations.keys():
@@ -411,87 +424,52 @@ class FeatureCache:
                     os.remove(os.path.join(module_dir, fname))
                 save_file({"locations": torch.cat(locs, dim=0), "activations": torch.cat(acts, dim=0)},
                           f"{module_dir}/{start}_{end}.safetensors")
-        for module_path, st in self.cache.feature_stats.items():
-            merge_rank_stats(f"{save_dir}/{module_path}", st.device)
-        for module_path, co in self.cache.coact_stats.items():
-            merge_rank_coact(f"{save_dir}/{module_path}", co.device)
-        for module_path, rs in self.cache.recon_stats.items():
-            merge_rank_recon(f"{save_dir}/{module_path}", rs.device)
-        for module_path, ah in self.cache.act_hists.items():
-            merge_rank_act_hist(f"{save_dir}/{module_path}", ah.device)
+        for kind in ACCUMULATORS:
+            for module_path, acc in getattr(self.cache, kind.attr).items():
+                merge_rank_files(f"{save_dir}/{module_path}", kind.stem, kind.cls, acc.device)
+
+
+def merge_rank_files(module_dir: str, stem: str, cls, device) -> Optional[str]:
+    """Merge `Rank{r}_<stem>.safetensors` of `module_dir` in rank order (`cls.load` on `device`, then `merge`) into
+    `<stem>.safetensors` and remove the rank files.  Returns the written path (None: no rank file)."""
+    pat = re.compile(r"^Rank(\d+)_{}\.safetensors$".format(re.escape(stem)))
+    parts = sorted((int(m.group(1)), f) for f in os.listdir(module_dir) if (m := pat.match(f)))
+    if not parts:
+        return None
+    total = None
+    for _, fname in parts:
+        acc = cls.load(os.path.join(module_dir, fname), device=device)
+        total = acc if total is None else total.merge(acc)
+    out = os.path.join(module_dir, f"{stem}.safetensors")
+    total.save(out)
+    for _, fname in parts:
+        os.remove(os.path.join(module_dir, fname))
+    return out
 
 
 def merge_rank_stats(module_dir: str, device) -> Optional[str]:
     """Merge `Rank{r}_feature_stats.safetensors` of `module_dir` in rank order (on `device`, a HIP device) into
     `feature_stats.safetensors` and remove the rank files.  Returns the written path (None: no rank file)."""
-    pat = re.compile(r"^Rank(\d+)_feature_stats\.safetensors$")
-    parts = sorted((int(m.group(1)), f) for f in os.listdir(module_dir) if (m := pat.match(f)))
-    if not parts:
-        return None
-    total = None
-    for _, fname in parts:
-        st = FeatureStats.load(os.path.join(module_dir, fname), device=device)
-        total = st if total is None else total.merge(st)
-    out = os.path.join(module_dir, "feature_stats.safetensors")
-    total.save(out)
-    for _, fname in parts:
-        os.remove(os.path.join(module_dir, fname))
-    return out
+    return merge_rank_files(module_dir, "feature_stats", FeatureStats, device)
 
 
 def merge_rank_coact(module_dir: str, device=None) -> Optional[str]:
     """Add `Rank{r}_coact.safetensors` of `module_dir` in rank order (on `device`; any device, the CPU included) into
     `coact.safetensors` and remove the rank files.  Returns the written path (None: no rank file)."""
-    pat = re.compile(r"^Rank(\d+)_coact\.safetensors$")
-    parts = sorted((int(m.group(1)), f) for f in os.listdir(module_dir) if (m := pat.match(f)))
-    if not parts:
-        return None
-    total = None
-    for _, fname in parts:
-        co = CoactStats.load(os.path.join(module_dir, fname), device=device)
-        total = co if total is None else total.merge(co)
-    out = os.path.join(module_dir, "coact.safetensors")
-    total.save(out)
-    for _, fname in parts:
-        os.remove(os.path.join(module_dir, fname))
-    return out
+    return merge_rank_files(module_dir, "coact", CoactStats, device)
 
 
 def merge_rank_act_hist(module_dir: str, device=None) -> Optional[str]:
     """Add `Rank{r}_act_hist.safetensors` of `module_dir` in rank order (on `device`; any device, the CPU included) into
     `act_hist.safetensors` and remove the rank files.  Returns the written path (None: no rank file)."""
-    pat = re.compile(r"^Rank(\d+)_act_hist\.safetensors$")
-    parts = sorted((int(m.group(1)), f) for f in os.listdir(module_dir) if (m := pat.match(f)))
-    if not parts:
-        return None
-    total = None
-    for _, fname in parts:
-        ah = ActHist.load(os.path.join(module_dir, fname), device=device)
-        total = ah if total is None else total.merge(ah)
-    out = os.path.join(module_dir, "act_hist.safetensors")
-    total.save(out)
-    for _, fname in parts:
-        os.remove(os.path.join(module_dir, fname))
-    return out
+    return merge_rank_files(module_dir, "act_hist", ActHist, device)
 
 
 def merge_rank_recon(module_dir: str, device=None) -> Optional[str]:
     """Add `Rank{r}_recon_stats.safetensors` of `module_dir` in rank order (on `device`; any device, the CPU included) into
     `recon_stats.safetensors` and remove the rank files.  Returns the written path (None: no rank file).  Float64 sums: the
     result equals a one-rank run to float64 rounding, not bit for bit."""
-    pat = re.compile(r"^Rank(\d+)_recon_stats\.safetensors$")
-    parts = sorted((int(m.group(1)), f) for f in os.listdir(module_dir) if (m := pat.match(f)))
-    if not parts:
-        return None
-    total = None
-    for _, fname in parts:
-        rs = ReconStats.load(os.path.join(module_dir, fname), device=device)
-        total = rs if total is None else total.merge(rs)
-    out = os.path.join(module_dir, "recon_stats.safetensors")
-    total.save(out)
-    for _, fname in parts:
-        os.remove(os.path.join(module_dir, fname))
-    return out
+    return merge_rank_files(module_dir, "recon_stats", ReconStats, device)
 
 
 class FeatureImageCache(FeatureCache):

@@ -20,41 +20,34 @@ order of the calls.  `neighbors` ranks the candidates of a query (counts > 0) by
 (score descending, feature ascending)."""
 from __future__ import annotations
 
-import json
-import struct
 from collections import defaultdict
 from typing import Dict, Optional, Tuple
 
 import torch
-from safetensors import safe_open
 from torch import Tensor
 
 from .. import _hip, ops
+from . import _pooled
+from ._pooled import POOL_MODES, _write_safetensors
 
-POOL_MODES = {"image": 0, "window": 1, "token": 2}
 METRICS = {"jaccard": 0, "count": 1}
 FORMAT = "msae.coact.v1"
-MAX_QUERIES, MAX_LATENTS, MAX_K, MAX_NEIGHBORS, MAX_CALL_TOKENS = 16384, 262144, 256, 64, 65536
+MAX_QUERIES, MAX_NEIGHBORS = 16384, 64
 
 
 @torch.library.custom_op("msae::coact_update", mutates_args=("counts", "seg_count"))
 def coact_update(top_acts: Tensor, top_indices: Tensor, thresh: float, mode: int, pool_len: int, window: int,
                  slot_of: Tensor, counts: Tensor, seg_count: Tensor) -> None:
     """One batch of `[B, S, k]` top-k pairs into the counters (in place, stream-ordered, no host read)."""
-    dev = _hip.require_device(top_acts, top_indices, slot_of, counts, seg_count)
-    lib = _hip.load()
-    assert top_acts.dim() == 3 and top_acts.shape == top_indices.shape
-    B, S, k = top_acts.shape
     F, N = counts.shape
     assert slot_of.shape == (N,) and slot_of.dtype == torch.int32 and seg_count.shape == (N,)
     assert counts.dtype == torch.int32 and seg_count.dtype == torch.int64
     assert counts.is_contiguous() and seg_count.is_contiguous() and slot_of.is_contiguous()
-    vals, idx = ops._f32c(top_acts), ops._idx32(top_indices)
+    dev, lib, vals, idx, Tk = _pooled.topk_inputs(top_acts, top_indices, slot_of, counts, seg_count)
     with torch.cuda.device(dev):
-        ws = ops._workspace(dev, lib.msae_coact_ws_bytes(B * S, k, N))
-        _hip.check(lib.msae_coact_update(
-            _hip.ptr(vals), _hip.ptr(idx), B, S, k, thresh, N, mode, pool_len, window, _hip.ptr(slot_of), F,
-            _hip.ptr(counts), _hip.ptr(seg_count), _hip.ptr(ws), ws.numel(), _hip.stream_of(vals)), "msae_coact_update")
+        ws = ops._workspace(dev, lib.msae_coact_ws_bytes(*Tk, N))
+        _pooled.pooled_update(lib, "msae_coact_update", vals, idx, thresh, N, mode, pool_len, window,
+                              (_hip.ptr(slot_of), F, _hip.ptr(counts), _hip.ptr(seg_count)), ws)
 
 
 @coact_update.register_fake
@@ -107,14 +100,8 @@ class CoactStats:
 
     def __init__(self, num_latents: int, queries, pool: str = "token", pool_len: int = 576, window: int = 64,
                  thresh: float = 1e-5, device=None, max_bytes: int = 8 << 30):
-        if pool not in POOL_MODES:
-            raise ValueError(f"pool must be one of {sorted(POOL_MODES)}, got {pool!r}")
-        if not 0 < num_latents <= MAX_LATENTS:
-            raise ValueError(f"num_latents must lie in [1, {MAX_LATENTS}], got {num_latents}")
-        if pool == "image" and not 0 < pool_len <= 2880:
-            raise ValueError(f"pool_len must lie in [1, 2880], got {pool_len}")
-        if pool == "window" and not 0 < window <= 4096:
-            raise ValueError(f"window must lie in [1, 4096], got {window}")
+        _pooled.check_pool(pool)
+        _pooled.check_pool_args(num_latents, pool, pool_len, window)
         q = _query_list(queries, num_latents)
         if len(q) * num_latents * 4 > max_bytes:
             raise ValueError(f"{len(q)} queries x {num_latents} features need {len(q) * num_latents * 4} bytes of counters, "
@@ -138,15 +125,7 @@ class CoactStats:
         return self.counts.shape[0]
 
     def _kind(self):
-        return (self.num_latents, self.pool, self.pool_len if self.pool == "image" else None,
-                self.window if self.pool == "window" else None, self.thresh)
-
-    def _segments_of(self, B: int, S: int) -> int:
-        if self.pool == "token":
-            return B * S
-        if self.pool == "window":
-            return B * (S // self.window)
-        return B
+        return (self.num_latents, *_pooled.pool_kind(self.pool, self.pool_len, self.window), self.thresh)
 
     def _device_lists(self) -> Tuple[Tensor, Tensor]:
         if self._slot_of is None or self._slot_of.device != self.device:
@@ -158,26 +137,16 @@ class CoactStats:
     def update(self, top_acts: Tensor, top_indices: Tensor) -> None:
         """Add one batch of `[B, S, k]` top-k pairs (complete rows only).  Every limit is checked on the host, from the
         shapes alone, before any device work; nothing is read back."""
-        if top_acts.dim() != 3 or top_acts.shape != top_indices.shape:
-            raise ValueError(f"top_acts / top_indices must be [B, S, k] of one shape, got {tuple(top_acts.shape)} and "
-                             f"{tuple(top_indices.shape)}")
-        B, S, k = top_acts.shape
-        if not 0 < k <= MAX_K:
-            raise ValueError(f"k must lie in [1, {MAX_K}], got {k}")
-        if S > MAX_CALL_TOKENS:
-            raise ValueError(f"rows of {S} positions exceed {MAX_CALL_TOKENS}")
-        total = self.n_segments + self._segments_of(B, S)
-        if total >= 1 << 31:
-            raise OverflowError(f"{total} segments: the int32 counters hold fewer than 2^31")
+        B, S, k = _pooled.topk_shape(top_acts, top_indices)
+        _pooled.check_call_limits(S, k)
+        total = _pooled.total_segments(self.n_segments, _pooled.segments_of(self.pool, B, S, self.window))
         _hip.require_device(top_acts, top_indices, self.counts)
         if B * S == 0:
             return
         slot_of, _ = self._device_lists()
-        rows = max(1, MAX_CALL_TOKENS // S)       # a row never spans two calls: any cut into whole rows is exact
-        for b0 in range(0, B, rows):
-            torch.ops.msae.coact_update(top_acts[b0:b0 + rows], top_indices[b0:b0 + rows], self.thresh,
-                                        POOL_MODES[self.pool], self.pool_len, self.window, slot_of, self.counts,
-                                        self.seg_count)
+        for rows in _pooled.row_chunks(B, S):
+            torch.ops.msae.coact_update(top_acts[rows], top_indices[rows], self.thresh, POOL_MODES[self.pool], self.pool_len,
+                                        self.window, slot_of, self.counts, self.seg_count)
         self.n_segments = total
 
     def merge(self, other: "CoactStats") -> "CoactStats":
@@ -186,9 +155,7 @@ class CoactStats:
             raise ValueError(f"cannot merge co-activation statistics of different kinds: {self._kind()} vs {other._kind()}")
         if self.queries.cpu().tolist() != other.queries.cpu().tolist():
             raise ValueError("cannot merge co-activation statistics of different query lists")
-        total = self.n_segments + other.n_segments
-        if total >= 1 << 31:
-            raise OverflowError(f"{total} segments: the int32 counters hold fewer than 2^31")
+        total = _pooled.total_segments(self.n_segments, other.n_segments)
         self.counts += other.counts.to(self.device)
         self.seg_count += other.seg_count.to(self.device)
         self.n_segments = total
@@ -230,11 +197,7 @@ class CoactStats:
 
     @classmethod
     def load(cls, path: str, device=None, max_bytes: int = 8 << 30) -> "CoactStats":
-        with safe_open(path, framework="pt") as fh:
-            meta = fh.metadata() or {}
-            if meta.get("format") != FORMAT:
-                raise ValueError(f"{path}: not a co-activation statistics file")
-            tensors = {k: fh.get_tensor(k) for k in fh.keys()}
+        meta, tensors = _pooled.open_stats_file(path, FORMAT, "a co-activation statistics")
         st = cls(int(meta["num_latents"]), tensors["queries"], pool=meta["pool"], pool_len=int(meta["pool_len"]),
                  window=int(meta["window"]), thresh=float(meta["thresh"]), device=device, max_bytes=max_bytes)
         dev = st.device
@@ -242,29 +205,6 @@ class CoactStats:
         st.seg_count.copy_(tensors["seg_count"])
         st.n_segments = int(meta["n_segments"])
         return st
-
-
-_ST_DTYPES = {torch.int64: "I64", torch.int32: "I32"}
-
-
-def _write_safetensors(tensors: Dict[str, Tensor], path: str, metadata: Dict[str, str]) -> None:
-    """A safetensors file with a canonical header (metadata keys sorted; tensors by item size, then name; padded to eight
-    bytes): equal state gives equal bytes, which `safetensors.torch.save_file` does not promise for several metadata
-    keys.  Any safetensors reader opens it."""
-    header, off, blobs = {"__metadata__": {k: metadata[k] for k in sorted(metadata)}}, 0, []
-    for name in sorted(tensors, key=lambda n: (-tensors[n].element_size(), n)):
-        t = tensors[name]
-        blob = t.numpy().tobytes()
-        header[name] = {"dtype": _ST_DTYPES[t.dtype], "shape": list(t.shape), "data_offsets": [off, off + len(blob)]}
-        off += len(blob)
-        blobs.append(blob)
-    head = json.dumps(header, separators=(",", ":")).encode()
-    head += b" " * (-len(head) % 8)
-    with open(path, "wb") as fh:
-        fh.write(struct.pack("<Q", len(head)))
-        fh.write(head)
-        for blob in blobs:
-            fh.write(blob)
 
 
 def _neighbors_host(counts: Tensor, seg_count: Tensor, queries: Tensor, m: int, metric: str, exclude_self: bool):

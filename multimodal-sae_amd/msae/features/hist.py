@@ -28,14 +28,14 @@ import math
 from typing import Sequence, Union
 
 import torch
-from safetensors import safe_open
 from torch import Tensor
 
 from .. import _hip, ops
-from .coact import POOL_MODES, _write_safetensors
+from . import _pooled
+from ._pooled import POOL_MODES, _write_safetensors
 
 FORMAT = "msae.act_hist.v1"
-MAX_LATENTS, MAX_K, MAX_BINS, MAX_Q, MAX_CALL_TOKENS = 262144, 256, 512, 64, 65536
+MAX_BINS, MAX_Q = 512, 64
 IS_ZERO, IS_EMPTY = -1, -2       # quantile_bins: the quantile is a zero / the feature has nothing to rank
 
 
@@ -43,18 +43,13 @@ IS_ZERO, IS_EMPTY = -1, -2       # quantile_bins: the quantile is a zero / the f
 def act_hist_update(top_acts: Tensor, top_indices: Tensor, thresh: float, mode: int, pool_len: int, window: int,
                     sub_bits: int, e_lo: int, octaves: int, hist: Tensor) -> None:
     """One batch of `[B, S, k]` top-k pairs into the histograms (in place, stream-ordered, no host read)."""
-    dev = _hip.require_device(top_acts, top_indices, hist)
-    lib = _hip.load()
-    assert top_acts.dim() == 3 and top_acts.shape == top_indices.shape
-    B, S, k = top_acts.shape
     N, n_bins = hist.shape
     assert hist.dtype == torch.int32 and hist.is_contiguous() and n_bins == octaves << sub_bits
-    vals, idx = ops._f32c(top_acts), ops._idx32(top_indices)
+    dev, lib, vals, idx, Tk = _pooled.topk_inputs(top_acts, top_indices, hist)
     with torch.cuda.device(dev):
-        ws = ops._workspace(dev, lib.msae_act_hist_ws_bytes(B * S, k, N))
-        _hip.check(lib.msae_act_hist_update(
-            _hip.ptr(vals), _hip.ptr(idx), B, S, k, thresh, N, mode, pool_len, window, sub_bits, e_lo, octaves,
-            _hip.ptr(hist), _hip.ptr(ws), ws.numel(), _hip.stream_of(vals)), "msae_act_hist_update")
+        ws = ops._workspace(dev, lib.msae_act_hist_ws_bytes(*Tk, N))
+        _pooled.pooled_update(lib, "msae_act_hist_update", vals, idx, thresh, N, mode, pool_len, window,
+                              (sub_bits, e_lo, octaves, _hip.ptr(hist)), ws)
 
 
 @act_hist_update.register_fake
@@ -121,14 +116,8 @@ class ActHist:
 
     def __init__(self, num_latents: int, pool: str = "token", pool_len: int = 576, window: int = 64, thresh: float = 1e-5,
                  sub_bits: int = 3, e_lo: int = -16, octaves: int = 32, device=None, max_bytes: int = 1 << 30):
-        if pool not in POOL_MODES:
-            raise ValueError(f"pool must be one of {sorted(POOL_MODES)}, got {pool!r}")
-        if not 0 < num_latents <= MAX_LATENTS:
-            raise ValueError(f"num_latents must lie in [1, {MAX_LATENTS}], got {num_latents}")
-        if pool == "image" and not 0 < pool_len <= 2880:
-            raise ValueError(f"pool_len must lie in [1, 2880], got {pool_len}")
-        if pool == "window" and not 0 < window <= 4096:
-            raise ValueError(f"window must lie in [1, 4096], got {window}")
+        _pooled.check_pool(pool)
+        _pooled.check_pool_args(num_latents, pool, pool_len, window)
         sub_bits, e_lo, octaves = int(sub_bits), int(e_lo), int(octaves)
         if not 0 <= sub_bits <= 4:
             raise ValueError(f"sub_bits must lie in [0, 4], got {sub_bits}")
@@ -154,47 +143,28 @@ class ActHist:
         return self.hist.device
 
     def _kind(self):
-        return (self.num_latents, self.pool, self.pool_len if self.pool == "image" else None,
-                self.window if self.pool == "window" else None, self.thresh, self.sub_bits, self.e_lo, self.octaves)
-
-    def _segments_of(self, B: int, S: int) -> int:
-        if self.pool == "token":
-            return B * S
-        if self.pool == "window":
-            return B * (S // self.window)
-        return B
+        return (self.num_latents, *_pooled.pool_kind(self.pool, self.pool_len, self.window), self.thresh, self.sub_bits,
+                self.e_lo, self.octaves)
 
     def update(self, top_acts: Tensor, top_indices: Tensor) -> None:
         """Add one batch of `[B, S, k]` top-k pairs (complete rows only).  Every limit is checked on the host, from the
         shapes alone, before any device work; nothing is read back.  Empty input is a no-op."""
-        if top_acts.dim() != 3 or top_acts.shape != top_indices.shape:
-            raise ValueError(f"top_acts / top_indices must be [B, S, k] of one shape, got {tuple(top_acts.shape)} and "
-                             f"{tuple(top_indices.shape)}")
-        B, S, k = top_acts.shape
+        B, S, k = _pooled.topk_shape(top_acts, top_indices)
         if B * S * k == 0:
             return
-        if k > MAX_K:
-            raise ValueError(f"k must lie in [1, {MAX_K}], got {k}")
-        if S > MAX_CALL_TOKENS:
-            raise ValueError(f"rows of {S} positions exceed {MAX_CALL_TOKENS}")
-        total = self.n_segments + self._segments_of(B, S)
-        if total >= 1 << 31:
-            raise OverflowError(f"{total} segments: the int32 counters hold fewer than 2^31")
+        _pooled.check_call_limits(S, k)
+        total = _pooled.total_segments(self.n_segments, _pooled.segments_of(self.pool, B, S, self.window))
         _hip.require_device(top_acts, top_indices, self.hist)
-        rows = max(1, MAX_CALL_TOKENS // S)       # a row never spans two calls: any cut into whole rows is exact
-        for b0 in range(0, B, rows):
-            torch.ops.msae.act_hist_update(top_acts[b0:b0 + rows], top_indices[b0:b0 + rows], self.thresh,
-                                           POOL_MODES[self.pool], self.pool_len, self.window, self.sub_bits, self.e_lo,
-                                           self.octaves, self.hist)
+        for rows in _pooled.row_chunks(B, S):
+            torch.ops.msae.act_hist_update(top_acts[rows], top_indices[rows], self.thresh, POOL_MODES[self.pool],
+                                           self.pool_len, self.window, self.sub_bits, self.e_lo, self.octaves, self.hist)
         self.n_segments = total
 
     def merge(self, other: "ActHist") -> "ActHist":
         """self += other (another rank's histograms of the same kind), on self's device, in plain torch."""
         if self._kind() != other._kind():
             raise ValueError(f"cannot merge activation histograms of different kinds: {self._kind()} vs {other._kind()}")
-        total = self.n_segments + other.n_segments
-        if total >= 1 << 31:
-            raise OverflowError(f"{total} segments: the int32 counters hold fewer than 2^31")
+        total = _pooled.total_segments(self.n_segments, other.n_segments)
         self.hist += other.hist.to(self.device)
         self.n_segments = total
         return self
@@ -252,11 +222,8 @@ class ActHist:
 
     @classmethod
     def load(cls, path: str, device=None, max_bytes: int = 1 << 30) -> "ActHist":
-        with safe_open(path, framework="pt") as fh:
-            meta = fh.metadata() or {}
-            if meta.get("format") != FORMAT:
-                raise ValueError(f"{path}: not an activation histogram file")
-            hist = fh.get_tensor("hist")
+        meta, tensors = _pooled.open_stats_file(path, FORMAT, "an activation histogram")
+        hist = tensors["hist"]
         st = cls(int(meta["num_latents"]), pool=meta["pool"], pool_len=int(meta["pool_len"]), window=int(meta["window"]),
                  thresh=float(meta["thresh"]), sub_bits=int(meta["sub_bits"]), e_lo=int(meta["e_lo"]),
                  octaves=int(meta["octaves"]), device=device, max_bytes=max_bytes)

@@ -36,11 +36,11 @@ import json
 from typing import Optional, Sequence
 
 import torch
-from safetensors import safe_open
 from safetensors.torch import save_file
 from torch import Tensor
 
 from .. import ops
+from ._pooled import open_stats_file
 
 FORMAT = "msae.recon_stats.v1"
 MAX_GROUPS = 8
@@ -211,11 +211,7 @@ class ReconStats:
 
     @classmethod
     def load(cls, path: str, device=None) -> "ReconStats":
-        with safe_open(path, framework="pt") as fh:
-            meta = fh.metadata() or {}
-            if meta.get("format") != FORMAT:
-                raise ValueError(f"{path}: not a reconstruction statistics file")
-            tensors = {k: fh.get_tensor(k) for k in fh.keys()}
+        meta, tensors = open_stats_file(path, FORMAT, "a reconstruction statistics")
         st = cls(int(meta["d"]), json.loads(meta["ks"]), json.loads(meta["position_edges"]), b_dec=tensors.get("b_dec"),
                  device=device)
         for name in ("sums", "xx_sum", "cos_sum", "x_sum"):

@@ -25,13 +25,15 @@ import json
 from typing import Optional, Tuple
 
 import torch
-from safetensors import safe_open
 from safetensors.torch import save_file
 from torch import Tensor
 
 from .. import _hip, ops
+from . import _pooled
+from ._pooled import POOL_MODES
 
-POOL_MODES = {"image": 0, "window": 1}
+FORMAT = "msae.feature_stats.v1"
+POOLS = ("image", "window")     # a token is no segment with examples to show
 MIN_TOP, MAX_TOP = 55, 256      # 55 = the README's --max_examples 5 + the image constructor's 50 spare ids
 MAX_SAMPLE = 256
 
@@ -42,18 +44,13 @@ def feature_stats_update(top_acts: Tensor, top_indices: Tensor, row_base: int, t
                          pool_len: int, window: int, count: Tensor, act_max: Tensor, act_sum: Tensor, top_val: Tensor,
                          top_id: Tensor) -> None:
     """One batch of `[B, S, k]` top-k pairs into the statistics (in place, stream-ordered, no host read)."""
-    dev = _hip.require_device(top_acts, top_indices, count, act_max, act_sum, top_val, top_id)
-    lib = _hip.load()
-    assert top_acts.dim() == 3 and top_acts.shape == top_indices.shape
-    B, S, k = top_acts.shape
     N, n = top_val.shape
-    vals, idx = ops._f32c(top_acts), ops._idx32(top_indices)
+    state = (count, act_max, act_sum, top_val, top_id)
+    dev, lib, vals, idx, Tk = _pooled.topk_inputs(top_acts, top_indices, *state)
     with torch.cuda.device(dev):
-        ws = ops._workspace(dev, lib.msae_feature_stats_ws_bytes(B * S, k, N))
-        _hip.check(lib.msae_feature_stats_update(
-            _hip.ptr(vals), _hip.ptr(idx), B, S, k, thresh, N, mode, pool_len, window, row_base, n,
-            _hip.ptr(count), _hip.ptr(act_max), _hip.ptr(act_sum), _hip.ptr(top_val), _hip.ptr(top_id),
-            _hip.ptr(ws), ws.numel(), _hip.stream_of(vals)), "msae_feature_stats_update")
+        ws = ops._workspace(dev, lib.msae_feature_stats_ws_bytes(*Tk, N))
+        _pooled.pooled_update(lib, "msae_feature_stats_update", vals, idx, thresh, N, mode, pool_len, window,
+                              (row_base, n, *[_hip.ptr(t) for t in state]), ws)
 
 
 @feature_stats_update.register_fake
@@ -69,21 +66,16 @@ def feature_stats_update_sampled(top_acts: Tensor, top_indices: Tensor, row_base
                                  smp_id: Tensor) -> None:
     """`feature_stats_update` that also merges the batch into the uniform sample tables (`seed`: the 64-bit sample seed,
     taken mod 2^64) -- one more table merge in the same launch."""
-    dev = _hip.require_device(top_acts, top_indices, count, act_max, act_sum, top_val, top_id, seg_count, smp_val, smp_id)
-    lib = _hip.load()
-    assert top_acts.dim() == 3 and top_acts.shape == top_indices.shape
-    B, S, k = top_acts.shape
     N, n = top_val.shape
     assert smp_val.shape == smp_id.shape and smp_val.shape[0] == N and seg_count.shape == (N,)
-    vals, idx = ops._f32c(top_acts), ops._idx32(top_indices)
+    state = (count, act_max, act_sum, top_val, top_id)
+    dev, lib, vals, idx, Tk = _pooled.topk_inputs(top_acts, top_indices, *state, seg_count, smp_val, smp_id)
     sample = _hip.MsaeFeatureSample(ctypes.sizeof(_hip.MsaeFeatureSample), smp_val.shape[1], seed % (1 << 64),
                                     seg_count.data_ptr(), smp_val.data_ptr(), smp_id.data_ptr())
     with torch.cuda.device(dev):
-        ws = ops._workspace(dev, lib.msae_feature_stats_ws_bytes(B * S, k, N))
-        _hip.check(lib.msae_feature_stats_update_sampled(
-            _hip.ptr(vals), _hip.ptr(idx), B, S, k, thresh, N, mode, pool_len, window, row_base, n,
-            _hip.ptr(count), _hip.ptr(act_max), _hip.ptr(act_sum), _hip.ptr(top_val), _hip.ptr(top_id),
-            ctypes.byref(sample), _hip.ptr(ws), ws.numel(), _hip.stream_of(vals)), "msae_feature_stats_update_sampled")
+        ws = ops._workspace(dev, lib.msae_feature_stats_ws_bytes(*Tk, N))
+        _pooled.pooled_update(lib, "msae_feature_stats_update_sampled", vals, idx, thresh, N, mode, pool_len, window,
+                              (row_base, n, *[_hip.ptr(t) for t in state], ctypes.byref(sample)), ws)
 
 
 @feature_stats_update_sampled.register_fake
@@ -100,16 +92,10 @@ class FeatureStats:
 
     def __init__(self, num_latents: int, n_top: int = 64, pool: str = "image", pool_len: int = 576, window: int = 64,
                  thresh: float = 1e-5, device=None, n_sample: int = 0, sample_seed: int = 22):
-        if pool not in POOL_MODES:
-            raise ValueError(f"pool must be one of {sorted(POOL_MODES)}, got {pool!r}")
+        _pooled.check_pool(pool, POOLS)
         if not MIN_TOP <= n_top <= MAX_TOP:
             raise ValueError(f"n_top must lie in [{MIN_TOP}, {MAX_TOP}], got {n_top}")
-        if not 0 < num_latents <= 262144:
-            raise ValueError(f"num_latents must lie in [1, 262144], got {num_latents}")
-        if pool == "image" and not 0 < pool_len <= 2880:
-            raise ValueError(f"pool_len must lie in [1, 2880], got {pool_len}")
-        if pool == "window" and not 0 < window <= 4096:
-            raise ValueError(f"window must lie in [1, 4096], got {window}")
+        _pooled.check_pool_args(num_latents, pool, pool_len, window)
         if not 0 <= n_sample <= MAX_SAMPLE:
             raise ValueError(f"n_sample must lie in [0, {MAX_SAMPLE}] (0: no sample), got {n_sample}")
         if not 0 <= sample_seed < 1 << 64:
@@ -211,7 +197,7 @@ class FeatureStats:
         return (self.n_sample / self.seg_count.double().clamp(min=1.0)).clamp(max=1.0)
 
     def metadata(self) -> dict:
-        meta = {"format": "msae.feature_stats.v1", "pool": self.pool, "pool_len": str(self.pool_len),
+        meta = {"format": FORMAT, "pool": self.pool, "pool_len": str(self.pool_len),
                 "window": str(self.window), "n_top": str(self.n_top), "thresh": repr(self.thresh),
                 "num_latents": str(self.num_latents), "tokens_seen": str(self.tokens_seen),
                 "windows_per_row": json.dumps(self.windows_per_row)}
@@ -228,11 +214,7 @@ class FeatureStats:
 
     @classmethod
     def load(cls, path: str, device=None) -> "FeatureStats":
-        with safe_open(path, framework="pt") as fh:
-            meta = fh.metadata() or {}
-            if meta.get("format") != "msae.feature_stats.v1":
-                raise ValueError(f"{path}: not a feature statistics file")
-            tensors = {k: fh.get_tensor(k) for k in fh.keys()}
+        meta, tensors = _pooled.open_stats_file(path, FORMAT, "a feature statistics")
         st = cls(int(meta["num_latents"]), n_top=int(meta["n_top"]), pool=meta["pool"],
                  pool_len=int(meta["pool_len"]), window=int(meta["window"]), thresh=float(meta["thresh"]),
                  device="cpu", n_sample=int(meta.get("n_sample", 0)), sample_seed=int(meta.get("sample_seed", 22)))

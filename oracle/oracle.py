@@ -17,6 +17,7 @@ Two restatements of the reference hot path live here:
 from __future__ import annotations
 
 import ctypes
+import fcntl
 import os
 import subprocess
 from pathlib import Path
@@ -33,11 +34,15 @@ _u8p = ctypes.POINTER(ctypes.c_uint8)
 
 
 def build(force: bool = False) -> Path:
-    """Compile the C oracle with gcc (oracle/Makefile)."""
+    """Compile the C oracle with gcc (oracle/Makefile).  The ranks of a multi-process test may all arrive here with a library
+    older than its source: the check and the compile run under one exclusive file lock, so one rank builds and the others
+    find it done -- none of them loads a file that another is still writing."""
     src = _HERE / "sae_oracle.c"
-    if force or not _LIB_PATH.exists() or _LIB_PATH.stat().st_mtime < src.stat().st_mtime:
-        subprocess.run(["make", "-C", str(_HERE), "-B", "libmsae_oracle.so"], check=True,
-                       capture_output=True)
+    with open(_HERE / "Makefile") as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)                # released when the file closes
+        if force or not _LIB_PATH.exists() or _LIB_PATH.stat().st_mtime < src.stat().st_mtime:
+            subprocess.run(["make", "-C", str(_HERE), "-B", "libmsae_oracle.so"], check=True,
+                           capture_output=True)
     return _LIB_PATH
 
 

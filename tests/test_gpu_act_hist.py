@@ -266,6 +266,80 @@ def test_agrees_with_the_feature_statistics(dev, pool, S):
     assert (top[on] > 0).all() and np.array_equal(highest[on], ref.bins_of(top[on]))
 
 
+def _case_shared_walk():
+    """B = 2, S = 150, k = 4, N = 37 for window 64 (two full windows and a ragged tail of 22) and pool_len 40.  Features
+    0 .. 19 are background (a token's four distinct, values +-2^[-6, 6): f32 sums depend on their order, f64 sums are exact in
+    any order); 20 .. 27 are planted, each in slots of its own:
+      20  a NaN (dropped) and one ordinary entry          21  -0.0 (dropped) and one negative entry
+      22  |v| = thresh and below (dropped), one just above  23  (row 1, s = 10) names it twice; also s = 12 and s = 45
+      24  row 0: all 64 positions of window 0, negative (cnt == W: the candidate stays negative); 63 positions of window 1,
+          negative (the implicit 0 wins); so it also lies on both sides of s = 40
+      25  only in the ragged tail (s >= 128)              26  s = 38 .. 41: both sides of pool_len
+      27  all of window 1 of row 1, positive
+    and two background slots carry the indices -1 and N."""
+    rng = np.random.default_rng(42)
+    B, S, k, N = 2, 150, 4, 37
+    idx = np.stack([rng.choice(20, size=k, replace=False) for _ in range(B * S)]).reshape(B, S, k).astype(np.int64)
+    vals = np.exp2(rng.uniform(-6, 6, size=(B, S, k))).astype(np.float32)
+    vals[rng.uniform(size=(B, S, k)) < 0.2] *= -1.0
+    plant = [((0, 5, 0), 20, np.nan), ((1, 3, 1), 20, 0.75), ((0, 6, 1), 21, -0.0), ((1, 4, 1), 21, -0.5),
+             ((0, 7, 0), 22, 1e-5), ((0, 8, 0), 22, 5e-6), ((0, 9, 0), 22, 1.25e-5),
+             ((1, 10, 0), 23, 1.5), ((1, 10, 3), 23, 2.25), ((1, 12, 0), 23, -3.0), ((1, 45, 0), 23, 0.625),
+             ((0, 20, 1), -1, 1.0), ((1, 70, 2), N, 1.0)]
+    plant += [((0, s, 2), 24, -(1.0 + s / 64.0)) for s in range(64)]
+    plant += [((0, s, 2), 24, -0.5) for s in range(64, 128) if s != 100]
+    plant += [((b, s, 1), 25, 2.0 + b + s / 256.0) for b in range(B) for s in range(130, 141)]
+    plant += [((1, s, 0), 26, x) for s, x in ((38, 3.0), (39, 2.0 ** -10), (40, 5.0), (41, -7.0))]
+    plant += [((1, s, 3), 27, x) for s, x in zip(range(64, 128), np.exp2(rng.uniform(-3, 3, size=64)))]
+    for at, f, x in plant:
+        idx[at], vals[at] = f, np.float32(x)
+    assert np.signbit(vals[0, 6, 1]) and vals[0, 6, 1] == 0 and vals[0, 7, 0] == np.float32(1e-5)
+    return vals, idx, N
+
+
+@pytest.mark.parametrize("index_dtype", [torch.int32, torch.int64])
+def test_shared_walk_special_values(dev, index_dtype):
+    """Every branch of the walk over a sorted (feature, row, group) run, on the planted input of `_case_shared_walk`:
+    FeatureStats bit for bit against feature_stats_ref.py (count, act_max, act_sum, top tables), ActHist bit for bit against
+    act_hist_ref.py, and the histogram's row totals equal to the positive candidates the statistics' restatement forms."""
+    import feature_stats_ref as fs_ref
+    from msae.features import FeatureStats
+
+    vals, idx, N = _case_shared_walk()
+    B, S, k = vals.shape
+    W, P, row_base, n_top = 64, 40, 11, 64
+    v, i = torch.from_numpy(vals).to(dev), torch.from_numpy(idx).to(dev).to(index_dtype)
+    with np.errstate(invalid="ignore"):
+        rb, rs, rf, rv = fs_ref.records(vals.reshape(B * S, k), idx.reshape(B * S, k), S, N=N)
+    count, mx, sm = fs_ref.basic_stats(rf, rv, N)
+    assert count[24] == 127 and mx[24] == -0.5 and count[23] == 4 and count[25] == 22 and count[22] == 1
+    for pool in ("window", "image"):
+        cf, cv, ci = fs_ref.candidates(rb, rs, rf, rv, S, pool, row_base, P=P, W=W)
+        tv, ti = fs_ref.top_tables(cf, cv, ci, N, n_top)
+        fs = FeatureStats(N, n_top=n_top, pool=pool, pool_len=P, window=W, device=dev)
+        fs.update(v, i, row_base)
+        assert np.array_equal(fs.count.cpu().numpy(), count)
+        assert np.array_equal(fs.act_max.cpu().numpy().view(np.uint32), mx.view(np.uint32))
+        assert np.array_equal(fs.act_sum.cpu().numpy().view(np.uint64), sm.view(np.uint64))
+        assert np.array_equal(fs.top_id.cpu().numpy(), ti)
+        assert np.array_equal(fs.top_val.cpu().numpy().view(np.uint32), tv.view(np.uint32))
+        exp = _ref([(vals, idx)], pool, N, pool_len=P, window=W)
+        st = _run([(vals, idx)], pool, N, dev, index_dtype=index_dtype, pool_len=P, window=W)
+        _assert_state(st, exp)
+        positive = np.bincount(cf[cv > 0], minlength=N)
+        assert np.array_equal(st.fired().cpu().numpy(), positive) and positive.sum() > 20
+        assert positive[25] == 0 and 25 not in cf                  # the ragged tail / s >= pool_len: no candidate
+        if pool == "window":
+            # window 0 of row 0 holds 24 on every position: the negative maximum stands; window 1 misses one: no candidate
+            assert cv[cf == 24].tolist() == [-1.0] and ci[cf == 24].tolist() == [row_base * 2] and positive[24] == 0
+            assert positive[27] == 1 and positive[23] == 1 and cv[cf == 23].tolist() == [2.25]
+            assert positive[20] == 1 and positive[21] == 0 and positive[22] == 1
+        else:
+            assert positive[24] == 0 and (cv[cf == 24] < 0).all() and positive[27] == 0
+            s26 = np.float32(np.float32(3.0) + np.float32(2.0 ** -10))
+            assert cv[cf == 26].tolist() == [s26 / np.float32(P)] and cv[cf == 23].tolist() == [np.float32(0.75) / np.float32(P)]
+
+
 # ---- quantiles -------------------------------------------------------------------------------------------------------
 def _planted_hist(rng, N, n_bins):
     hist = (rng.integers(0, 30, size=(N, n_bins)) * (rng.uniform(size=(N, n_bins)) < 0.3)).astype(np.int32)

@@ -132,6 +132,21 @@ def test_counter_helpers_at_the_envelope(lib):
         assert f(150, 8, 1000) > 0
 
 
+# (T, k, N) -> msae_feature_stats_ws_bytes, msae_coact_ws_bytes, msae_act_hist_ws_bytes: 256-byte aligned regions of two key
+# buffers (8 B per entry), two value buffers (4 B per entry; not the co-activation counters), starts / ends (4 B per feature /
+# per token; not the histograms) and the sort's (8 B per entry + 1 MiB)
+_COUNTER_SIZES = {(1, 1, 1): (1050368, 1049856, 1049856),
+                  (300, 5, 37): (1097472, 1087232, 1096960),
+                  (8192, 32, 131072): (10485760, 7405568, 9437184),
+                  (65536, 256, 262144): (540016640, 404226048, 537919488)}
+
+
+@pytest.mark.parametrize("shape", sorted(_COUNTER_SIZES))
+def test_counter_helper_sizes_are_pinned(lib, shape):
+    got = (lib.msae_feature_stats_ws_bytes(*shape), lib.msae_coact_ws_bytes(*shape), lib.msae_act_hist_ws_bytes(*shape))
+    assert got == _COUNTER_SIZES[shape]
+
+
 @pytest.mark.parametrize("M,N,k,chunks", [(-1, 1000, 8, 0), (130, 0, 8, 0), (130, 1000, 0, 0), (130, 1000, 65, 0),
                                           (130, 1000, 8, -1), (130, 4, 8, 0),       # k > N
                                           (130, 8192 * 128, 64, 129)])                # chunks * k > 8192

@@ -15,9 +15,14 @@ features, so hot features fire on most tokens).  Writes profiles/act_hist.txt:
   quantiles    quantile_bins for all 131072 features at Q = 7
 
 --out PATH   write there instead
+--parent_lib PATH  also time every pooled update of ANOTHER build of libmsae_hip.so (the parent commit's, built into a scratch
+             directory), loaded beside this build's and called through ctypes on the same buffers: the histograms', the feature
+             statistics' and the co-activation counters' update, per pool, this build, the parent's and the parent's again (the
+             twin: its difference from the first is the run-to-run spread the difference of the builds has to be read against)
 --loop-only  only the cache loop with the histograms off (and its twin); with --tree PATH the package and bench.py are taken
              from another checkout (a build of the parent commit: its loop must match this one's "off")"""
 import argparse
+import ctypes
 import statistics
 import sys
 from pathlib import Path
@@ -46,9 +51,67 @@ def alternate(variants):
     return {label: statistics.median(v) for label, v in ts.items()}
 
 
+def load_other(path, _hip):
+    """Another build of the library beside this one, with this build's prototypes (the ABI version must agree)."""
+    lib = ctypes.CDLL(str(path))
+    for name, (res, argtypes) in _hip.PROTOTYPES.items():
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype, fn.argtypes = res, argtypes
+    assert lib.msae_abi_version() == _hip.ABI_VERSION
+    return lib
+
+
+def against_parent(mine, parent, v, i, pool_len, pools=("token", "window", "image")):
+    """Lines: every pooled update at the shape of v / i [B, S, K] through the C ABI, the builds taking turns on ONE set of
+    buffers (the state's contents do not change what an update costs; window 64)."""
+    from msae import _hip
+    from msae.features.coact import POOL_MODES
+
+    B, S, k = v.shape
+    vals, idx = v.float().contiguous(), i.to(torch.int32).contiguous()
+    ws = torch.empty(max(f(B * S, k, N) for f in (mine.msae_feature_stats_ws_bytes, mine.msae_coact_ws_bytes,
+                                                   mine.msae_act_hist_ws_bytes)), dtype=torch.uint8, device=dev)
+    hist = torch.zeros(N, 256, dtype=torch.int32, device=dev)
+    count, act_max = torch.zeros(N, dtype=torch.int64, device=dev), torch.full((N,), float("-inf"), device=dev)
+    act_sum, top_val = torch.zeros(N, dtype=torch.float64, device=dev), torch.zeros(N, 64, device=dev)
+    top_id = torch.full((N, 64), -1, dtype=torch.int64, device=dev)
+    slot_of = torch.full((N,), -1, dtype=torch.int32, device=dev)
+    slot_of[torch.randperm(N, device=dev)[:F]] = torch.arange(F, dtype=torch.int32, device=dev)
+    counts, seg_count = torch.zeros(F, N, dtype=torch.int32, device=dev), torch.zeros(N, dtype=torch.int64, device=dev)
+    P, st, base = _hip.ptr, _hip.stream_of(vals), [0]
+    head = (P(vals), P(idx), B, S, k, 1e-5, N)
+    tail = (P(ws), ws.numel(), st)
+
+    def call(lib, what, pool):
+        pool_args = (POOL_MODES[pool], pool_len, 64)
+        if what == "act_hist":
+            rc = lib.msae_act_hist_update(*head, *pool_args, 3, -16, 32, P(hist), *tail)
+        elif what == "coact":
+            rc = lib.msae_coact_update(*head, *pool_args, P(slot_of), F, P(counts), P(seg_count), *tail)
+        else:
+            rc = lib.msae_feature_stats_update(*head, *pool_args, base[0], 64, P(count), P(act_max), P(act_sum), P(top_val),
+                                               P(top_id), *tail)
+            base[0] += B
+        assert rc == 0, (what, pool, rc)
+
+    lines = []
+    for what in ("act_hist", "feature_stats", "coact"):
+        for pool in pools:
+            if what == "feature_stats" and pool == "token":
+                continue
+            res = alternate([(label, lambda lib=lib: call(lib, what, pool))
+                             for label, lib in (("this", mine), ("parent", parent), ("parent'", parent))])
+            this, par, twin = res["this"], res["parent"], res["parent'"]
+            lines.append(f"    {what} update ({pool}, T={B * S})".ljust(42) + f"this {this:7.3f} ms  parent {par:7.3f} ms  parent' "
+                         f"{twin:7.3f} ms | this - parent {this - par:+.3f} ms, twin spread {abs(par - twin):.3f} ms")
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
+    ap.add_argument("--parent_lib", default=None)
     ap.add_argument("--loop-only", action="store_true")
     ap.add_argument("--tree", default=str(REPO))
     args = ap.parse_args()
@@ -118,6 +181,12 @@ def main():
     for label, t in alternate(variants).items():
         lines.append(f"    {label:40s} {t:7.3f} ms")
     lines.append(f"    ({int((hists['token'].hist > 0).sum())} nonzero token-pool counters after the run)")
+    parent = None
+    if args.parent_lib:
+        from msae import _hip
+        parent = load_other(args.parent_lib, _hip)
+        lines.append("  this build against the parent's (--parent_lib), through the C ABI on the same buffers")
+        lines += against_parent(_hip.load(), parent, v, i, 576)
 
     # ---- quantiles
     st = hists["token"]
@@ -157,6 +226,8 @@ def main():
     for label, t in alternate([("act_hist update (image)", lambda: him.update(v2, i2)),
                                ("feature statistics update (image)", fim_update)]).items():
         lines.append(f"    {label:40s} {t:7.3f} ms")
+    if parent is not None:
+        lines += against_parent(_hip.load(), parent, v2, i2, 576, pools=("image",))
     finish(lines, args.out or str(REPO / "profiles" / "act_hist.txt"))
 
 
