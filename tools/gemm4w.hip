@@ -3,6 +3,10 @@
 // ds_write_b128) instead of LDS-DMA.  tools/dma_depth.hip measured the register path delivering 58 GB/s per CU against
 // 43.5 for LDS-DMA at the same depth; this asks what a full k-loop makes of it.  int8, 256 x 256 x 128-byte k-tiles,
 // 2-slot LDS ring, T=8192 N=131072 d=4096; prints us per k-tile and checks a few outputs against a naive reference.
+// Variants 7-11 (gemm4w_dma_kernel) are the same four waves with the PRODUCT's LDS-DMA staging and 16x16x64 MFMAs
+// (profiles/gemm_wave_tile.txt).  G4W_ONLY=<variant> runs one of them G4W_REPS times, G4W_N sets N, G4W_SIGMA the operands,
+// G4W_READY=1 prints "ready" in front of the timed launches (tools/smi_sample.sh).
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/gemm4w.hip -o tools/bin/gemm4w
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
@@ -357,6 +361,228 @@ __global__ __launch_bounds__(256) void gemm4w_v2_kernel(const unsigned char *__r
   }
 }
 
+// ---- v3 ("7" / "8"): the combination the round-4 table never held -- four waves, 128 x 128 wave tiles, the PRODUCT's staging and
+// MFMA shape.  Tile-major operands (GemmOperands::packed) travel L2 -> LDS by gemm_stage_block, 16 one-KiB pieces per wave as four
+// groups of four (waves 0, 1: the halves of the A block, waves 2, 3: of the B block); v_mfma_i32_16x16x64_i8; the persistent
+// XCD-aware walk of gemm_map_tile, and like the product ONE flat k-sequence through the 2-slot ring across output tiles.  No
+// epilogue.  Accumulator block (fa, fb) -- rows 16 fa.., columns 16 fb.. of the wave tile -- is pinned to a[(8 fa + fb) * 4 .. + 3].
+//
+// One k-tile = two k-steps of 64 B = four half-steps of 32 MFMAs: one group of 4 A fragments against the 8 B fragments of the
+// k-step, B-outer.  Four fragment groups, 96 VGPRs: ga / gc = A rows 0-63 / 64-127, gb / gd = B of k-step 0 / 1; each is refilled
+// as soon as its last MFMA has issued, ONE ds_read_b128 behind an MFMA at a time (with one wave per SIMD nobody else fills a gap):
+//   HS0  ga x gb   behind its MFMAs: gc <- A high, k-step 0 (4);  gd <- B, k-step 1 (8)
+//   HS1  gc x gb                     ga <- A low, k-step 1 (4)
+//   HS2  ga x gd                     gc <- A high, k-step 1 (4)
+//   -- every read of this slot has landed, and this wave's pieces of the next k-tile: s_barrier --
+//   HS3  gc x gd                     the four LDS-DMA groups of the k-tile AFTER next into the slot just freed;
+//                                    ga, gb <- the next k-tile's first fragments (12), out of the other slot
+// so the DMA of a k-tile has a whole k-tile's time to land, as in the product, and the barrier sits in front of 32 MFMAs that
+// need nothing from LDS.  MODE 1: no staging in the loop (timing only: stale data, outputs wrong by construction).  MODE 2: a
+// second barrier per k-tile releases the B half of the slot early (see the body).  MODE 4: the same a quarter k-tile earlier.
+// MODE 3: the whole slot, through registers (body3).  (G4W_ONLY = 7, 8, 9, 10, 11 are MODE 0, 1, 2, 3, 4.)
+struct G4wDmaGroup { static constexpr int PPW = 4; };          // gemm_stage_block: one group of four 1-KiB pieces per call
+template <int BLK> __device__ __forceinline__ void g4d_mfma(const v4i &a, const v4i &b) {
+  asm volatile("v_mfma_i32_16x16x64_i8 a[%c2:%c3], %0, %1, a[%c2:%c3]" :: "v"(a), "v"(b), "i"(BLK * 4), "i"(BLK * 4 + 3) : G4W_CLOBBER);
+}
+template <int R> __device__ __forceinline__ int g4d_acc_read() {
+  int v; asm volatile("v_accvgpr_read_b32 %0, a%c1" : "=v"(v) : "i"(R)); return v;
+}
+// an MFMA's result -> any reader or writer but the next MFMA accumulating into it needs wait states of its own in inline asm
+__device__ __forceinline__ void g4d_mfma_drain() { asm volatile("s_nop 15\n\ts_nop 15" ::: "memory"); }
+template <int IMM> __device__ __forceinline__ void g4d_rd(v4i &v, unsigned addr) {
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(IMM) : "memory");
+}
+template <int N> __device__ __forceinline__ void g4d_wait4(v4i (&g)[4]) {
+  asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(g[0]), "+v"(g[1]), "+v"(g[2]), "+v"(g[3]) : "n"(N) : "memory");
+}
+template <int N> __device__ __forceinline__ void g4d_wait12(v4i (&g)[4], v4i (&h)[8]) {
+  asm volatile("s_waitcnt lgkmcnt(%12)" : "+v"(g[0]), "+v"(g[1]), "+v"(g[2]), "+v"(g[3]), "+v"(h[0]), "+v"(h[1]), "+v"(h[2]), "+v"(h[3]),
+               "+v"(h[4]), "+v"(h[5]), "+v"(h[6]), "+v"(h[7]) : "n"(N) : "memory");
+}
+template <int I> using G4I = std::integral_constant<int, I>;
+// half-step H (A rows 64 H ..): MFMA q = 4 j + s multiplies A fragment g[s] with B fragment b[j]; hook(G4I<q>) is called behind it
+template <int H, int Q = 0, class F>
+__device__ __forceinline__ void g4d_half(const v4i (&g)[4], const v4i (&b)[8], F &&hook) {
+  if constexpr (Q < 32) {
+    g4d_mfma<(4 * H + (Q & 3)) * 8 + (Q >> 2)>(g[Q & 3], b[Q >> 2]);
+    hook(G4I<Q>());
+    g4d_half<H, Q + 1>(g, b, hook);
+  }
+}
+template <int R = 0> __device__ __forceinline__ void g4d_zero() {
+  if constexpr (R < 256) {
+    asm volatile("v_accvgpr_write_b32 a%c0, 0\n\tv_accvgpr_write_b32 a%c1, 0\n\tv_accvgpr_write_b32 a%c2, 0\n\tv_accvgpr_write_b32 a%c3, 0"
+                 :: "i"(R), "i"(R + 1), "i"(R + 2), "i"(R + 3) : G4W_CLOBBER);
+    g4d_zero<R + 4>();
+  } else asm volatile("s_nop 3" ::: "memory");                 // accvgpr write -> MFMA reading it as C
+}
+// spot check: register lane & 3 of every accumulator block of every lane -> dst[blk * 64 + lane]
+template <int BLK = 0> __device__ __forceinline__ void g4d_dump(int *dst, int lane) {
+  if constexpr (BLK < 64) {
+    const int r0 = g4d_acc_read<BLK * 4>(), r1 = g4d_acc_read<BLK * 4 + 1>(), r2 = g4d_acc_read<BLK * 4 + 2>(), r3 = g4d_acc_read<BLK * 4 + 3>();
+    const int e = lane & 3;
+    dst[BLK * 64 + lane] = e == 0 ? r0 : (e == 1 ? r1 : (e == 2 ? r2 : r3));
+    g4d_dump<BLK + 1>(dst, lane);
+  }
+}
+constexpr int G4D_DUMP_INTS = 4 * 64 * 64;                     // per dumped output tile: 4 waves x 64 blocks x 64 lanes
+constexpr int G4D_DUMPS = 6;                                   // workgroups 0 and 1: their first, second and last output tile
+
+template <int MODE>
+__global__ __launch_bounds__(256) void gemm4w_dma_kernel(const unsigned char *__restrict__ A, const unsigned char *__restrict__ B,
+                                                         int nM, int nN, int nk, int *__restrict__ out) {
+  extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
+  constexpr unsigned SLOT = 512 * 128, BLOCK = 256 * 128;      // ring slot = A block | B block of one k-tile
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wr = wave >> 1, wc = wave & 1, l15 = lane & 15, kq = lane >> 4;
+  const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char *)smem;
+  // fragment f of the wave tile = 16 rows, lane l: row l % 16, 16-B chunk 4 ks + l / 16 at its swizzled position; fragments are
+  // 2 KiB apart (immediate offsets).  One address per operand, k-step and slot.
+  const unsigned sw = (unsigned)gemm_swz(l15);
+  const unsigned rowA = lds0 + (unsigned)(wr * 128 + l15) * 128u, rowB = lds0 + BLOCK + (unsigned)(wc * 128 + l15) * 128u;
+  const unsigned off0 = ((unsigned)kq ^ sw) << 4, off1 = ((unsigned)(4 + kq) ^ sw) << 4;
+  // staging: this wave's 16 KiB of the k-tile's 64: waves 0, 1 the halves of the A block, waves 2, 3 of the B block
+  const bool wa = wave < 2;
+  const unsigned char *opbase = (wa ? A : B) + (size_t)(wave & 1) * 16384;
+  unsigned char *wdst = smem + wave * 16384;
+  const int ntile = nM * nN;
+  const int my_tiles = (ntile - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;   // (host: grid <= ntile)
+  // DMA cursor: runs two k-tiles ahead of the MFMAs through the workgroup's flat (output tile, k-tile) sequence
+  int d_tile = blockIdx.x, d_kt = 0, d_left = my_tiles * nk;
+  const unsigned char *d_src = opbase;
+  auto d_enter = [&]() {
+    int tm, tn;
+    gemm_map_tile(d_tile, nM, nN, tm, tn);
+    d_src = opbase + (size_t)(wa ? tm : tn) * (size_t)nk * BLOCK;
+  };
+  auto d_group = [&](unsigned so, auto gtag) {
+    constexpr int g = decltype(gtag)::value;
+    gemm_stage_block<G4wDmaGroup>(d_src + g * 4096, wdst + so + g * 4096, lane);
+  };
+  auto d_advance = [&]() {
+    --d_left;
+    d_src += BLOCK;
+    if (++d_kt == nk) { d_kt = 0; d_tile += gridDim.x; if (d_left > 0) d_enter(); }
+  };
+  // the MFMAs' own position
+  int c_kt = 0, c_idx = 0;
+  v4i ga[4], gc[4], gb[8], gd[8];
+  auto read_first = [&](unsigned sn, auto qtag) {              // fragment q of the 12 first ones of a k-tile: ga (4) then gb (8)
+    constexpr int q = decltype(qtag)::value;
+    if constexpr (q < 4) g4d_rd<q * 2048>(ga[q], rowA + off0 + sn);
+    else g4d_rd<(q - 4) * 2048>(gb[q - 4], rowB + off0 + sn);
+  };
+  auto body = [&](auto slot_tag) {
+    constexpr unsigned so = decltype(slot_tag)::value * SLOT, sn = SLOT - so;
+    g4d_wait12<0>(ga, gb);
+    g4d_half<0>(ga, gb, [&](auto qt) {
+      constexpr int q = decltype(qt)::value;
+      if constexpr (q < 4) g4d_rd<8192 + q * 2048>(gc[q], rowA + off0 + so);
+      else if constexpr (q < 20 && (q & 1) == 0) g4d_rd<((q - 4) >> 1) * 2048>(gd[(q - 4) >> 1], rowB + off1 + so);
+    });
+    const bool more = MODE != 1 && d_left > 0;                  // wave-uniform
+    if constexpr (MODE == 4) {                                  // MODE 2's barrier a quarter k-tile earlier: gd has landed here too
+      g4d_wait12<0>(gc, gd);
+      __builtin_amdgcn_s_barrier();
+    } else g4d_wait4<8>(gc);                                    // younger: the 8 reads of gd
+    g4d_half<1>(gc, gb, [&](auto qt) {
+      constexpr int q = decltype(qt)::value;
+      if constexpr (q < 4) g4d_rd<q * 2048>(ga[q], rowA + off1 + so);
+      else if constexpr (MODE == 4 && q < 8) { if (more && !wa) d_group(so, G4I<q - 4>()); }
+    });
+    g4d_wait12<0>(ga, gd);
+    // MODE 2: behind this wait a wave has read its last B fragment of slot so.  One more barrier, and the B block of the slot is
+    // free half a k-tile before the A block: waves 2, 3 issue their pieces now, waves 0, 1 behind the barrier below as before, so
+    // the L2 -> LDS stream has two half-slots in flight instead of pausing at every barrier.
+    if constexpr (MODE == 2) __builtin_amdgcn_s_barrier();
+    g4d_half<0>(ga, gd, [&](auto qt) {
+      constexpr int q = decltype(qt)::value;
+      if constexpr (q < 4) g4d_rd<8192 + q * 2048>(gc[q], rowA + off1 + so);
+      else if constexpr (MODE == 2 && q < 8) { if (more && !wa) d_group(so, G4I<q - 4>()); }
+    });
+    g4d_wait4<0>(gc);                                           // the last read of slot so ...
+    // ... and this wave's pieces of the next k-tile (slot sn).  MODE 2, waves 2, 3: the 16 pieces just issued are younger
+    if ((MODE == 2 || MODE == 4) && more && !wa) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();                               // everybody's: sn is complete, so is free
+    g4d_half<1>(gc, gd, [&](auto qt) {
+      constexpr int q = decltype(qt)::value;
+      if constexpr (q < 4) { if (more && ((MODE != 2 && MODE != 4) || wa)) d_group(so, G4I<q>()); }
+      else if constexpr (q < 16) read_first(sn, G4I<q - 4>());
+    });
+    if (more) d_advance();
+    if (++c_kt == nk) {                                         // output tile complete: (no epilogue) spot check, then zero
+      c_kt = 0;
+      g4d_mfma_drain();
+      const int which = c_idx == 0 ? 0 : (c_idx == 1 ? 1 : (c_idx == my_tiles - 1 ? 2 : -1));
+      if (blockIdx.x < 2 && which >= 0)
+        g4d_dump(out + ((size_t)(blockIdx.x * 3 + which) * 4 + wave) * (64 * 64), lane);
+      ++c_idx;
+      g4d_zero();
+    }
+  };
+  // MODE 3: the whole k-tile's fragments are in registers (or in flight) by the end of HS0 -- ge / gf hold the A halves of k-step 1,
+  // 128 fragment VGPRs -- so the WHOLE slot is free a quarter into the k-tile.  Barrier A there, then every wave issues its pieces
+  // of the k-tile after next; barrier B in front of HS3 publishes the NEXT k-tile, whose pieces were issued a k-tile and a half
+  // earlier (vmcnt(16): the 16 just issued are younger).  Two k-tiles of DMA are in flight half of the time.
+  v4i ge[4], gf[4];
+  auto body3 = [&](auto slot_tag) {
+    constexpr unsigned so = decltype(slot_tag)::value * SLOT, sn = SLOT - so;
+    g4d_wait12<0>(ga, gb);
+    g4d_half<0>(ga, gb, [&](auto qt) {
+      constexpr int q = decltype(qt)::value;
+      if constexpr (q < 4) g4d_rd<8192 + q * 2048>(gc[q], rowA + off0 + so);
+      else if constexpr (q < 12) g4d_rd<(q - 4) * 2048>(gd[q - 4], rowB + off1 + so);
+      else if constexpr (q < 16) g4d_rd<(q - 12) * 2048>(ge[q - 12], rowA + off1 + so);
+      else if constexpr (q < 20) g4d_rd<8192 + (q - 16) * 2048>(gf[q - 16], rowA + off1 + so);
+    });
+    g4d_wait12<0>(gc, gd);
+    g4d_wait4<0>(ge);
+    g4d_wait4<0>(gf);
+    __builtin_amdgcn_s_barrier();                               // A: nobody reads slot so any more
+    const bool more = d_left > 0;
+    g4d_half<1>(gc, gb, [&](auto qt) {
+      constexpr int q = decltype(qt)::value;
+      if constexpr (q < 4) { if (more) d_group(so, G4I<q>()); }
+    });
+    g4d_half<0>(ge, gd, [&](auto) {});
+    if (more) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");  // this wave's pieces of the next k-tile (slot sn) ...
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();                               // B: ... and everybody's
+    g4d_half<1>(gf, gd, [&](auto qt) {
+      constexpr int q = decltype(qt)::value;
+      if constexpr (q < 12) read_first(sn, G4I<q>());
+    });
+    if (more) d_advance();
+    if (++c_kt == nk) {
+      c_kt = 0;
+      g4d_mfma_drain();
+      const int which = c_idx == 0 ? 0 : (c_idx == 1 ? 1 : (c_idx == my_tiles - 1 ? 2 : -1));
+      if (blockIdx.x < 2 && which >= 0)
+        g4d_dump(out + ((size_t)(blockIdx.x * 3 + which) * 4 + wave) * (64 * 64), lane);
+      ++c_idx;
+      g4d_zero();
+    }
+  };
+  // prologue: k-tiles 0 and 1 of the first output tile into slots 0 and 1, the first fragments of slot 0 in flight
+  d_enter();
+  d_group(0u, G4I<0>()); d_group(0u, G4I<1>()); d_group(0u, G4I<2>()); d_group(0u, G4I<3>());
+  d_advance();
+  d_group(SLOT, G4I<0>()); d_group(SLOT, G4I<1>()); d_group(SLOT, G4I<2>()); d_group(SLOT, G4I<3>());
+  d_advance();
+  g4d_zero();
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  read_first(0u, G4I<0>()); read_first(0u, G4I<1>()); read_first(0u, G4I<2>()); read_first(0u, G4I<3>());
+  read_first(0u, G4I<4>()); read_first(0u, G4I<5>()); read_first(0u, G4I<6>()); read_first(0u, G4I<7>());
+  read_first(0u, G4I<8>()); read_first(0u, G4I<9>()); read_first(0u, G4I<10>()); read_first(0u, G4I<11>());
+  for (int s = my_tiles * nk; s > 0; s -= 2) {                  // (host: nk even)
+    if constexpr (MODE == 3) { body3(G4I<0>()); body3(G4I<1>()); }
+    else { body(G4I<0>()); body(G4I<1>()); }
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(ga[0]), "+v"(gb[0]) :: "memory");   // the read-ahead behind the last k-tile
+}
+
 // sigma <= 0: small values -3 .. 3 (round 2's fill: hardly any switching activity); sigma > 0: round(N(0, sigma)) clamped to
 // +-127 -- what a quantised residual stream / encoder row looks like to the multipliers (round 4: the power / clock comparison
 // against the product's kernel, tools/gpu_r04_power.sh)
@@ -405,10 +631,63 @@ void run(const unsigned char *A, const unsigned char *B, int T, int N, int d, in
          ops / best / 1e9, best * 1e3 / ((double)nM * nN * nk / 256), bad ? "MISMATCH" : "ok");
 }
 
+// v3.  The operand buffers are READ as tile-major: byte k of row r of an operand with nk k-tiles lives in the 32-KB block of
+// (row tile r / 256, k-tile k / 128), row r % 256, at the swizzled position of its 16-B chunk -- the naive reference reads it there.
+static inline int tm_at(const signed char *X, int nk, int row, int k) {
+  const int r = row & 255, c = (k & 127) >> 4;
+  return X[((size_t)(row >> 8) * nk + (k >> 7)) * 32768 + (size_t)r * 128 + (size_t)((c ^ ((r >> 1) & 7)) << 4) + (k & 15)];
+}
+template <int MODE>
+void run_dma(const unsigned char *A, const unsigned char *B, int T, int N, int d, int *out, const signed char *hA, const signed char *hB) {
+  const int nM = T / 256, nN = N / 256, nk = d / 128, grid = 256;
+  if (nk < 2 || (nk & 1) || nM * nN < grid) { printf("4 waves, LDS-DMA: shape not supported\n"); return; }
+  const size_t smem = 2 * 512 * 128;
+  auto kern = gemm4w_dma_kernel<MODE>;
+  CK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+  hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+  for (int i = 0; i < 2; ++i) hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, 0, A, B, nM, nN, nk, out);
+  CK(hipDeviceSynchronize());
+  if (getenv("G4W_READY")) { printf("ready\n"); fflush(stdout); }
+  float best = 1e30f, sum = 0.f;
+  const int reps = getenv("G4W_REPS") ? atoi(getenv("G4W_REPS")) : 5;
+  for (int i = 0; i < reps; ++i) {
+    CK(hipEventRecord(e0, 0));
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, 0, A, B, nM, nN, nk, out);
+    CK(hipEventRecord(e1, 0)); CK(hipEventSynchronize(e1));
+    float ms; CK(hipEventElapsedTime(&ms, e0, e1)); if (ms < best) best = ms; sum += ms;
+  }
+  int *h = (int *)malloc((size_t)G4D_DUMPS * G4D_DUMP_INTS * 4);
+  CK(hipMemcpy(h, out, (size_t)G4D_DUMPS * G4D_DUMP_INTS * 4, hipMemcpyDeviceToHost));
+  const int ntile = nM * nN;
+  long bad = 0, checked = 0;
+  for (int b = 0; b < 2; ++b) for (int which = 0; which < 3; ++which) {
+    const int mine = (ntile - b + grid - 1) / grid, idx = which < 2 ? which : mine - 1;
+    const int tile = b + idx * grid;
+    int tm, tn;
+    if (nM % 8 == 0 && nN % 4 == 0 && ((nM / 8) * (nN / 4)) % 8 == 0) {     // gemm_map_tile, 8 x 4 super-tiles
+      const int xcd = tile & 7, slot = tile >> 3, st = (slot / 32) * 8 + xcd;
+      tm = (st % (nM / 8)) * 8 + (slot % 32) % 8; tn = (st / (nM / 8)) * 4 + (slot % 32) / 8;
+    } else { tm = tile % nM; tn = tile / nM; }
+    for (int wave = 0; wave < 4; ++wave) for (int blk = 0; blk < 64; ++blk) for (int lane = 0; lane < 64; ++lane) {
+      const int row = tm * 256 + (wave >> 1) * 128 + (blk >> 3) * 16 + 4 * (lane >> 4) + (lane & 3);
+      const int col = tn * 256 + (wave & 1) * 128 + (blk & 7) * 16 + (lane & 15);
+      int ref = 0;
+      for (int k = 0; k < d; ++k) ref += tm_at(hA, nk, row, k) * tm_at(hB, nk, col, k);
+      if (ref != h[((size_t)(b * 3 + which) * 4 + wave) * 4096 + blk * 64 + lane]) ++bad;
+      ++checked;
+    }
+  }
+  free(h);
+  const double ops = 2.0 * T * N * d;
+  printf("4 waves, LDS-DMA, 16x16x64%s: mean %7.3f ms  best %7.3f ms  %6.0f TOP/s  %5.2f us per k-tile   %ld outputs of 6 tiles checked: %s\n",
+         MODE == 1 ? ", no staging" : (MODE == 2 ? ", B half released early" : (MODE == 3 ? ", slot released at 1/4" : (MODE == 4 ? ", B half released at 1/4" : ""))), sum / reps, best, ops / best / 1e9, best * 1e3 / ((double)nM * nN * nk / grid), checked,
+         bad ? "MISMATCH" : "ok");
+}
+
 int main() {
-  const int T = 8192, N = 131072, d = 4096;
+  const int T = 8192, N = getenv("G4W_N") ? atoi(getenv("G4W_N")) : 131072, d = 4096;
   unsigned char *A, *B; int *out;
-  CK(hipMalloc(&A, (size_t)T * d)); CK(hipMalloc(&B, (size_t)N * d)); CK(hipMalloc(&out, 4096));
+  CK(hipMalloc(&A, (size_t)T * d)); CK(hipMalloc(&B, (size_t)N * d)); CK(hipMalloc(&out, (size_t)G4D_DUMPS * G4D_DUMP_INTS * 4));
   const float sigma = getenv("G4W_SIGMA") ? (float)atof(getenv("G4W_SIGMA")) : 0.f;
   fill<<<2048, 256>>>(A, (size_t)T * d, 1, sigma); fill<<<2048, 256>>>(B, (size_t)N * d, 2, sigma);
   if (sigma > 0.f) printf("int8 operands: round(N(0, %.0f))\n", sigma);
@@ -425,6 +704,11 @@ int main() {
       case 4: run<4>(A, B, T, N, d, out, hA, hBfull); break;
       case 5: run<5>(A, B, T, N, d, out, hA, hBfull); break;
       case 6: run<6>(A, B, T, N, d, out, hA, hBfull); break;
+      case 7: run_dma<0>(A, B, T, N, d, out, hA, hBfull); break;     // v3: LDS-DMA staging, 16x16x64 MFMAs, flat k-sequence
+      case 8: run_dma<1>(A, B, T, N, d, out, hA, hBfull); break;     // v3 without staging in the loop
+      case 9: run_dma<2>(A, B, T, N, d, out, hA, hBfull); break;     // v3 with the B half of a slot released half a k-tile early
+      case 11: run_dma<4>(A, B, T, N, d, out, hA, hBfull); break;    // as 9, the B half released a quarter into the k-tile
+      case 10: run_dma<3>(A, B, T, N, d, out, hA, hBfull); break;    // v3 with the whole slot released a quarter into the k-tile
       default: run<1>(A, B, T, N, d, out, hA, hBfull); break;
     }
     return 0;
@@ -436,6 +720,8 @@ int main() {
   run<5>(A, B, T, N, d, out, hA, hBfull);     // "5": v2 with the LDS writes but without the loads
   run<6>(A, B, T, N, d, out, hA, hBfull);     // "6": v2 with MFMAs only
   run<3>(A, B, T, N, d, out, hA, hBfull);
+  run_dma<0>(A, B, T, N, d, out, hA, hBfull);
+  run_dma<1>(A, B, T, N, d, out, hA, hBfull);
   (void)hB;
   return 0;
 }

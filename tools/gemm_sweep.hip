@@ -45,13 +45,14 @@ __global__ void max_diff(const float *a, const float *b, size_t n, float *res) {
   atomicMax((int *)res, __float_as_int(m));
 }
 
-struct Ctx { unsigned short *A, *B; float *tau, *dense, *ref, *res; f32x4 *rowc, *colc; float *refs; int *cnt; unsigned long long *cand; int T, d, N, Ns; };
+struct Ctx { unsigned short *A, *B; float *tau, *dense, *ref, *res; f32x4 *rowc, *colc; float *refs; int *cnt; unsigned long long *cand; int T, d, N, Ns, packed; };
 
 template <class C>
 void run(const char *name, Ctx &c, int reps) {
   GemmOperands op{};
   op.A = (const unsigned char *)c.A; op.B = (const unsigned char *)c.B;
   op.ldA = op.ldB = (size_t)c.d * 2; op.nk = c.d * 2 / C::ROWB;   // int8 configs read the same bytes as 2*d int8
+  op.packed = c.packed;                                           // SWEEP_PACKED: read the same bytes as tile-major operands (timing only)
   GemmEpilogue ep{};
   float md = -1.f;
   if (!C::I8) {  // correctness on the small problem (first Ns features) against the naive reference
@@ -69,6 +70,7 @@ void run(const char *name, Ctx &c, int reps) {
   hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
   for (int i = 0; i < 2; ++i) gemm_launch<C, false>(op, c.T, c.T, c.N, et, 0);
   CK(hipDeviceSynchronize());
+  if (getenv("SWEEP_READY")) { printf("ready\n"); fflush(stdout); }   // tools/smi_sample.sh: start sampling here
   float best = 1e30f, sum = 0.f;
   for (int i = 0; i < reps; ++i) {
     CK(hipEventRecord(e0, 0));
@@ -83,8 +85,9 @@ void run(const char *name, Ctx &c, int reps) {
 }
 
 int main(int argc, char **argv) {
-  Ctx c{}; c.T = 8192; c.d = getenv("SWEEP_D") ? atoi(getenv("SWEEP_D")) : 4096; c.N = 131072; c.Ns = 4096;
-  printf("d = %d\n", c.d);
+  Ctx c{}; c.T = 8192; c.d = getenv("SWEEP_D") ? atoi(getenv("SWEEP_D")) : 4096; c.N = getenv("SWEEP_N") ? atoi(getenv("SWEEP_N")) : 131072; c.Ns = 4096;
+  c.packed = getenv("SWEEP_PACKED") ? 1 : 0;
+  printf("d = %d  N = %d%s\n", c.d, c.N, c.packed ? "  tile-major" : "");
   int reps = argc > 1 ? atoi(argv[1]) : 5;
   CK(hipMalloc(&c.A, (size_t)c.T * c.d * 2)); CK(hipMalloc(&c.B, (size_t)c.N * c.d * 2));
   CK(hipMalloc(&c.tau, c.T * 4)); CK(hipMemset(c.tau, 0, c.T * 4));           // tau <= 0 -> nothing emitted
@@ -115,6 +118,7 @@ int main(int argc, char **argv) {
     if (which == 5) RUN(256, 256, 2, 2, 4, true, 8);                    // no fragment reads (staging + MFMA on constant registers)
     if (which == 6) RUN(256, 256, 2, 2, 4, true, 16);                   // no MFMA (staging + fragment reads)
     if (which == 7) RUN(256, 256, 2, 2, 4, true, 128);                  // int8 on 16x16x64 MFMAs (GemmCfg bit 7, MSAE_GEMM_MF = 16)
+    if (which == 8) RUN(256, 256, 2, 2, 4, true, 132);                  // ... without staging
   }
   return 0;
 }
