@@ -46,8 +46,8 @@ def f32(x) -> float:
     return float(np.float32(x))
 
 
-def _d(t) -> torch.Tensor:
-    return t.detach().to("cpu", F64)
+def _d(t, device="cpu") -> torch.Tensor:
+    return t.detach().to(device, F64)
 
 
 def kernel_rows(shape) -> Tuple[int, int]:
@@ -105,8 +105,10 @@ def unit_norm_rows(W, eps: float):
 
 
 def adam_rows(W, G, M, V, step: int, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, total_sumsq=None,
-              max_norm: float = 1.0, project: bool = False, renorm_eps: Optional[float] = None):
+              max_norm: float = 1.0, project: bool = False, renorm_eps: Optional[float] = None, device="cpu"):
     """One step of clip -> (projection) -> Adam -> (row renorm) -> ((W', M', V'), (dW, dM, dV)), float64, shaped like W.
+    `device`: where the float64 arithmetic runs (the same torch expressions; a trajectory test with 8M-element matrices
+    evaluates them next to its inputs).
 
         c  = min(1, max_norm / (sqrt(S) + 1e-6))          S = total_sumsq, the float32 value the kernel reads (None: c = 1)
         g  = c G ;  g -= <g, w> w  if project
@@ -131,7 +133,7 @@ def adam_rows(W, G, M, V, step: int, lr: float, betas=(0.9, 0.999), eps: float =
         renorm  _renorm(w', dw)"""
     shape = W.shape
     rows, d = kernel_rows(shape)
-    w, g_in, m, v = (_d(t).reshape(rows, d) for t in (W, G, M, V))
+    w, g_in, m, v = (_d(t, device).reshape(rows, d) for t in (W, G, M, V))
     assert not project or len(shape) == 2
     lr_, b1, b2, eps_, mn = f32(lr), f32(betas[0]), f32(betas[1]), f32(eps), f32(max_norm)
     if total_sumsq is None:
@@ -226,12 +228,12 @@ def weighted_row_sum(W, s, scale: float = 1.0):
 
 
 # ---- the check both files use ----------------------------------------------------------------------------------------------
-def assert_within(got, ref, bound, what: str = "") -> float:
+def assert_within(got, ref, bound, what: str = "", device="cpu") -> float:
     """Every element of `got` within its own bound of `ref` (nothing excluded; a zero bound demands equality) -> the largest
-    ratio of observed error to bound."""
-    got = torch.as_tensor(got).detach().to("cpu", F64)
-    ref = torch.as_tensor(ref, dtype=F64)
-    bound = torch.as_tensor(bound, dtype=F64).expand_as(ref)
+    ratio of observed error to bound.  `device`: where the comparison runs."""
+    got = torch.as_tensor(got).detach().to(device, F64)
+    ref = torch.as_tensor(ref, dtype=F64).to(device)
+    bound = torch.as_tensor(bound, dtype=F64).to(device).expand_as(ref)
     got = got.reshape(ref.shape)
     assert bool(torch.isfinite(got).all()), f"{what}: non-finite output"
     assert bool(torch.isfinite(bound).all()), f"{what}: non-finite bound"
@@ -243,7 +245,8 @@ def assert_within(got, ref, bound, what: str = "") -> float:
                              f"got {float(got.reshape(-1)[i])!r} ref {float(ref.reshape(-1)[i])!r} "
                              f"err {float(err.reshape(-1)[i]):.3e} bound {float(bound.reshape(-1)[i]):.3e}")
     pos = bound > 0
-    return float((err[pos] / bound[pos]).max()) if bool(pos.any()) else 0.0
+    return float(torch.where(pos, err / torch.where(pos, bound, torch.ones_like(bound)), torch.zeros_like(err)).max()) \
+        if bool(pos.any()) else 0.0
 
 
 # ---- the cases --------------------------------------------------------------------------------------------------------------
