@@ -9,7 +9,8 @@
  * features/cache.py:187-204, so ops must be stream-ordered).
  *
  * WORKSPACE CONTRACT (every entry that takes `void *ws, size_t ws_bytes`; tests/test_gpu_workspace_contract.py holds each of
- * them to it with exact-size, guarded and dirty buffers):
+ * them to it with exact-size, guarded and dirty buffers; tests/test_gpu_pos_profile.py does so for msae_pos_profile_update,
+ * whose helper asks for no bytes):
  *   - the contents of [ws, ws + ws_bytes) are UNSPECIFIED on entry and on return: a caller may hand over a fresh block, the
  *     block a different entry has just used, or one it shares between all entries of a stream; nothing is kept in it
  *     between calls;
@@ -41,6 +42,7 @@
  *   msae_feature_stats_*     per-feature counts + top examples  features/loader.py:103-106, constructors.py:28-141
  *   msae_coact_*             co-activation counters + neighbours (no reference counterpart)
  *   msae_act_hist_*          per-feature activation histograms + quantiles (no reference counterpart)
+ *   msae_pos_profile_*       per-feature position profiles + peak bins (no reference counterpart)
  *   msae_rows_topk_f32       cos + get_neighbors; logits   features/stats.py:76-120; stats.py:12-47
  *   msae_row_inv_norms_f32   F.normalize's norms in cos    features/stats.py:80-81
  *   msae_edit_topk_f32       hook edits with a feature LIST features/steering.py:113-114, patching/utils.py:43-48
@@ -536,6 +538,41 @@ int msae_act_hist_update(const float *vals, const int32_t *idx, int B, int S, in
                          size_t ws_bytes, void *stream);
 int msae_act_hist_quantiles(const int32_t *hist, int N, int n_bins, const double *qs, int Q, int64_t n_segments,
                             int zeros, int32_t *bins, void *stream);
+
+/* ---- per-feature position profiles, and the peak bin read from them (msae.features.PosProfile) -----------------------
+ * WHERE IN A ROW every feature fires, counted while the cache runs (no reference counterpart: the reference's only defence
+ * against positional features is a hard-coded window offset, features/constructors.py:204).  Input: one batch's top-k
+ * vals/idx[B*S][k], as the feature statistics take it; an entry is kept when |v| > thresh and 0 <= idx < N (no filter
+ * bitmap).  Per token: there are no pooling modes.
+ * The position table pos_bin[L] (i32, device; 1 <= L <= 65536) and tail_bin name the BIN of a position s of a row:
+ *   bin(s) = pos_bin[s] for s < L, tail_bin for s >= L;  bins are 0 .. P - 1 (1 <= P <= 1024), -1 = counted nowhere.
+ * tail_bin outside [-1, P) is MSAE_EINVAL; a table value outside [0, P) counts as -1 (the table is on the device and is
+ * not read back: nothing faults).
+ * A kept entry (v, f) at a position with bin b >= 0 is COUNTED iff v > 0 -- the histograms' rule: NaN, zero and negative
+ * values are counted nowhere; nothing is de-duplicated (a caller's repeat counts twice).  State, updated in place
+ * (initialise to 0):
+ *   count[N][P]  i32  count[f][b] += 1
+ *   mass[N][P]   u64  mass[f][b]  += q(v),  q(v) = llrint((double)v * 2^20) in round-half-to-even, saturated at 2^60 for
+ *                     v >= 2^40 (+inf included): the value in fixed point, 20 fractional bits.  The sum is mod 2^64.
+ *                     q(2^-21) = 0 (a tie, to even), q(3 * 2^-21) = 2, q(1.0) = 2^20, q(any subnormal) = 0.
+ * Every update is an integer atomic add: the state is bit-identical however the rows are cut into calls, in whatever
+ * order the calls arrive, and adds over ranks.  A counter wraps at 2^31: the caller keeps the number of positions below.
+ * Envelope: B*S <= 65536, k <= 256, N <= 262144, L and P as above (else MSAE_EINVAL).  No host synchronisation, no
+ * allocation.  msae_pos_profile_ws_bytes(B*S, k, N) is 0 for every shape: the update needs no workspace, ws / ws_bytes are
+ * not looked at, and MSAE_EWS is never returned.
+ * msae_pos_profile_summary: from count and bin_positions[P] (i64, device: positions seen per bin, each below 2^31)
+ *   fired[N]    i64  the row total of count
+ *   peak[N][2]  i32  (b, count[f][b]) of the bin with the highest firing RATE count[f][b] / bin_positions[b] among the bins
+ *                    with bin_positions[b] > 0, rates compared exactly (c1 * n2 against c2 * n1 in int64); equal rates:
+ *                    the lowest bin; (-1, 0) when no such bin has a count (fired = 0 for a state the update produced).
+ *   Envelope: N <= 262144, P <= 1024.  A pure function of its arguments; no scratch, no host synchronisation, no
+ *   allocation. */
+size_t msae_pos_profile_ws_bytes(int T, int k, int N);
+int msae_pos_profile_update(const float *vals, const int32_t *idx, int B, int S, int k, float thresh, int N,
+                            const int32_t *pos_bin, int L, int tail_bin, int P, int32_t *count, uint64_t *mass, void *ws,
+                            size_t ws_bytes, void *stream);
+int msae_pos_profile_summary(const int32_t *count, const int64_t *bin_positions, int N, int P, int64_t *fired,
+                             int32_t *peak, void *stream);
 
 /* ---- probe: segment-pooled feature ranking and activation maps (Sae.probe) ---------------------------------------
  * Replaces the dense probe of tools/probe_activations.py:109-126 (latents = pre_acts(h); latents.mean(0).topk(k);

@@ -111,6 +111,10 @@ PROTOTYPES = {
     "msae_act_hist_update": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_int, c_int, c_int, c_int,
                                      c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "msae_act_hist_quantiles": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p]),
+    "msae_pos_profile_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "msae_pos_profile_update": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_int, c_int, c_int,
+                                        c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "msae_pos_profile_summary": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "msae_pooled_acts_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int,
                                      c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "msae_probe_maps_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int,

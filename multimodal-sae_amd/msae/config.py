@@ -61,6 +61,10 @@ class CacheConfig:
     """Segments of the activation histograms: token, window or image (default: image on cache_image, token on cache)"""
     act_hist_bins: Optional[str] = None
     """Bins of the activation histograms as s,e_lo,octaves: 2^s bins per octave from 2^e_lo up (default: 3,-16,32)"""
+    pos_profile: bool = False
+    """Also count where in a row every feature fires (pos_profile.safetensors per module: counts and strength per position bin)"""
+    pos_profile_bins: Optional[str] = None
+    """Position bins: grid:SIDE:CELL, log2 or linear:P (default: the image grid in cells of 4 on cache_image, log2 on cache)"""
 
     def to_dict(self):
         return dataclasses.asdict(self)
@@ -130,6 +134,11 @@ def parse_cache_config(argv: Optional[Sequence[str]] = None) -> CacheConfig:
             act_hist_bins(cfg.act_hist_bins)
         except ValueError as e:
             p.error(str(e))
+    if cfg.pos_profile_bins is not None:
+        try:
+            pos_profile_spec(cfg.pos_profile_bins)
+        except ValueError as e:
+            p.error(str(e))
     return cfg
 
 
@@ -191,3 +200,62 @@ def act_hist_kwargs(cfg: CacheConfig, default_pool: str, pool_len: int = 576) ->
     if cfg.act_hist_bins is not None:
         kw.update(act_hist_bins(cfg.act_hist_bins))
     return kw
+
+
+def pos_profile_spec(text: str) -> tuple:
+    """'grid:SIDE:CELL' -> ("grid", SIDE, CELL), 'log2' -> ("log2",), 'linear:P' -> ("linear", P), within what the position
+    profiles take (include/msae.h): SIDE a positive multiple of CELL with SIDE^2 <= 65536, P in [1, 1024]."""
+    parts = text.split(":")
+    try:
+        nums = [int(t) for t in parts[1:]]
+    except ValueError:
+        nums = None
+    if nums is not None and parts[0] == "grid" and len(nums) == 2:
+        side, cell = nums
+        if not (cell >= 1 and 1 <= side <= 256 and side % cell == 0 and (side // cell) ** 2 < 1024):
+            raise ValueError(f"--pos_profile_bins grid:SIDE:CELL needs SIDE in [1, 256], a multiple of CELL, and fewer than "
+                             f"1024 cells, got {text!r}")
+        return ("grid", side, cell)
+    if nums == [] and parts[0] == "log2":
+        return ("log2",)
+    if nums is not None and parts[0] == "linear" and len(nums) == 1:
+        if not 1 <= nums[0] <= 1024:
+            raise ValueError(f"--pos_profile_bins linear:P needs P in [1, 1024], got {text!r}")
+        return ("linear", nums[0])
+    raise ValueError(f"--pos_profile_bins must be grid:SIDE:CELL, log2 or linear:P, got {text!r}")
+
+
+def pos_profile_grid_default(pool_len: int, cell: int = 4) -> str:
+    """The image launcher's default bins, 'grid:isqrt(pool_len):4': the base image's grid in cells of 4 x 4, one more bin for
+    the rest of the row.  A `pool_len` that is no such grid is a ValueError that names the flag to give instead."""
+    import math
+
+    side = math.isqrt(pool_len)
+    if side < 1 or side * side != pool_len or side % cell:
+        raise ValueError(f"--pos_profile: {pool_len} image positions are not a square grid with a side divisible by {cell}; "
+                         f"give --pos_profile_bins (grid:SIDE:CELL, log2 or linear:P)")
+    return f"grid:{side}:{cell}"
+
+
+def cache_config_error(message: str):
+    """End like the parser does on a bad flag (usage, the message, exit status 2): for what a launcher can only check once
+    the model is loaded."""
+    argparse.ArgumentParser(description="Cache SAE feature activations (MI355X HIP path)").error(message)
+
+
+def pos_profile_kwargs(cfg: CacheConfig, default_bins: str, length: int) -> Optional[dict]:
+    """The `pos=` argument of the feature caches for a parsed command line (None without --pos_profile): the bins of
+    --pos_profile_bins (the launcher's `default_bins` without it); log2 and linear bins span `length` positions, a grid gets
+    one more bin for everything behind it."""
+    if not cfg.pos_profile:
+        return None
+    from .features.pos import PosProfile
+
+    spec = pos_profile_spec(cfg.pos_profile_bins or default_bins)
+    if spec[0] == "grid":
+        table, tail_bin, n_bins, _ = PosProfile.grid_bins(spec[1], spec[2], rest=True)
+    elif spec[0] == "log2":
+        table, tail_bin, n_bins, _ = PosProfile.log2_bins(length)
+    else:
+        table, tail_bin, n_bins, _ = PosProfile.linear_bins(length, spec[1])
+    return dict(bins=table, tail_bin=tail_bin, n_bins=n_bins)

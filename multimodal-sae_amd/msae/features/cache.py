@@ -31,6 +31,11 @@ and, with `hist=` (opt-in; no reference counterpart), a histogram of every featu
     <save_dir>/<module>/Rank{r}_act_hist.safetensors           per rank
     <save_dir>/<module>/act_hist.safetensors                   the ranks added in rank order by the concat
 
+and, with `pos=` (opt-in; no reference counterpart), a profile of where in a row every feature fires (msae/features/pos.py):
+
+    <save_dir>/<module>/Rank{r}_pos_profile.safetensors        per rank
+    <save_dir>/<module>/pos_profile.safetensors                the ranks added in rank order by the concat
+
 The split files have keys `locations [nnz,3] int64 = (row, pos, feature)` and `activations [nnz] f32`, which is what
 `features/loader.py:143-196` (FeatureDataset) reads.
 
@@ -60,6 +65,7 @@ from .. import ops
 from ..sae import Sae
 from .coact import CoactStats
 from .hist import ActHist
+from .pos import PosProfile
 from .recon import ReconStats
 from .stats import FeatureStats
 
@@ -81,7 +87,7 @@ def _new_recon(cache, module_path, c):
                       b_dec=c.sae.b_dec, device=c.device)
 
 
-# add_topk feeds in this order: stats, coact, hist (then sparsify)
+# add_topk feeds in this order: stats, coact, hist, pos (then sparsify)
 ACCUMULATORS = (
     _Accumulator("stats", "feature_stats", "feature_stats", FeatureStats, "topk",
                  lambda cache, m, c: FeatureStats(c.num_latents, device=c.device, **cache.stats),
@@ -94,6 +100,9 @@ ACCUMULATORS = (
     _Accumulator("hist", "act_hists", "act_hist", ActHist, "topk",
                  lambda cache, m, c: ActHist(c.num_latents, device=c.device, **cache.hist),
                  lambda ah, c: ah.update(c.top_acts, c.top_indices)),
+    _Accumulator("pos", "pos_profiles", "pos_profile", PosProfile, "topk",
+                 lambda cache, m, c: PosProfile(c.num_latents, device=c.device, **cache.pos),
+                 lambda pp, c: pp.update(c.top_acts, c.top_indices)),
 )
 
 
@@ -110,7 +119,7 @@ class Cache:
     def __init__(self, shard_size: int, filters: Optional[Dict[str, Tensor]] = None,
                  batch_size: int = 64, spill_dir: Optional[str] = None, device_budget_bytes: int = 256 << 20,
                  stats: Optional[dict] = None, coact: Optional[dict] = None, recon: Optional[dict] = None,
-                 hist: Optional[dict] = None):
+                 hist: Optional[dict] = None, pos: Optional[dict] = None):
         """`spill_dir`: stream every batch's records to disk instead of holding the whole run in host
         RAM (the reference keeps everything in Python lists until save_splits, cache.py:56-57);
         `save()` reads them back in batch order, so the final tensors are identical.
@@ -128,7 +137,10 @@ class Cache:
         the loop already holds.  None (default): nothing of it is allocated, launched or written.
         `hist`: keyword arguments of `ActHist` (pool, pool_len, window, thresh, sub_bits, e_lo, octaves, max_bytes) -- one
         `ActHist` per module is then updated in `add_topk` from the same top-k pairs, over every feature.  None (default):
-        nothing of it is allocated, launched or written."""
+        nothing of it is allocated, launched or written.
+        `pos`: keyword arguments of `PosProfile` (bins, tail_bin, n_bins, thresh, max_bytes) -- one `PosProfile` per module is
+        then updated in `add_topk` from the same top-k pairs, over every feature.  None (default): nothing of it is
+        allocated, launched or written."""
         self.feature_locations = defaultdict(list)
         self.feature_activations = defaultdict(list)
         self.spill_dir = spill_dir
@@ -143,9 +155,9 @@ class Cache:
         # groups of batches on their way to the host: (copy-done event, device buffers kept alive, pinned staging, layout)
         self._inflight = []
         self._copy_stream = None
-        # per kind: self.stats / .coact / .recon / .hist (its keyword arguments, None: off) and the accumulators per module in
-        # self.feature_stats / .coact_stats / .recon_stats / .act_hists
-        given = dict(stats=stats, coact=coact, recon=recon, hist=hist)
+        # per kind: self.stats / .coact / .recon / .hist / .pos (its keyword arguments, None: off) and the accumulators per module
+        # in self.feature_stats / .coact_stats / .recon_stats / .act_hists / .pos_profiles
+        given = dict(stats=stats, coact=coact, recon=recon, hist=hist, pos=pos)
         for kind in ACCUMULATORS:
             kw = given[kind.keyword]
             setattr(self, kind.keyword, None if kw is None else dict(kw))
@@ -311,7 +323,8 @@ class Cache:
 class FeatureCache:
     def __init__(self, model, tokenizer, submodule_dict: Dict[str, Sae], batch_size: int,
                  shard_size: int, filters: Optional[Dict[str, Tensor]] = None, stats: Optional[dict] = None,
-                 coact: Optional[dict] = None, recon: Optional[dict] = None, hist: Optional[dict] = None):
+                 coact: Optional[dict] = None, recon: Optional[dict] = None, hist: Optional[dict] = None,
+                 pos: Optional[dict] = None):
         # LlavaNextForConditionalGeneration wraps the language model (cache.py:104-109)
         if hasattr(model, "language_model") and hasattr(model, "vision_tower"):
             self.llava_model, self.model = model, model.language_model
@@ -324,7 +337,8 @@ class FeatureCache:
         self.batch_size = batch_size
         first = next(iter(submodule_dict.values()))
         self.width = first.cfg.num_latents or first.d_in * first.cfg.expansion_factor
-        self.cache = Cache(shard_size, filters, batch_size=batch_size, stats=stats, coact=coact, recon=recon, hist=hist)
+        self.cache = Cache(shard_size, filters, batch_size=batch_size, stats=stats, coact=coact, recon=recon, hist=hist,
+                           pos=pos)
         if filters is not None:
             self.filter_submodules(filters)
 
@@ -465,6 +479,12 @@ def merge_rank_act_hist(module_dir: str, device=None) -> Optional[str]:
     return merge_rank_files(module_dir, "act_hist", ActHist, device)
 
 
+def merge_rank_pos_profile(module_dir: str, device=None) -> Optional[str]:
+    """Add `Rank{r}_pos_profile.safetensors` of `module_dir` in rank order (on `device`; any device, the CPU included) into
+    `pos_profile.safetensors` and remove the rank files.  Returns the written path (None: no rank file)."""
+    return merge_rank_files(module_dir, "pos_profile", PosProfile, device)
+
+
 def merge_rank_recon(module_dir: str, device=None) -> Optional[str]:
     """Add `Rank{r}_recon_stats.safetensors` of `module_dir` in rank order (on `device`; any device, the CPU included) into
     `recon_stats.safetensors` and remove the rank files.  Returns the written path (None: no rank file).  Float64 sums: the
@@ -478,9 +498,9 @@ class FeatureImageCache(FeatureCache):
 
     def __init__(self, model, tokenizer, submodule_dict, batch_size: int, shard_size: int,
                  filters=None, processor=None, stats: Optional[dict] = None, coact: Optional[dict] = None,
-                 recon: Optional[dict] = None, hist: Optional[dict] = None):
+                 recon: Optional[dict] = None, hist: Optional[dict] = None, pos: Optional[dict] = None):
         super().__init__(model, tokenizer, submodule_dict, batch_size, shard_size, filters, stats=stats, coact=coact,
-                         recon=recon, hist=hist)
+                         recon=recon, hist=hist, pos=pos)
         if processor is None:  # resolved lazily, not at import time as cache.py:321 does
             from transformers import LlavaNextProcessor
 

@@ -10,13 +10,15 @@ import os
 import torch
 import torch.distributed as dist
 
-from ...config import CacheConfig, act_hist_kwargs, coact_kwargs, parse_cache_config, recon_kwargs
+from ...config import (CacheConfig, act_hist_kwargs, cache_config_error, coact_kwargs, parse_cache_config, pos_profile_kwargs,
+                       recon_kwargs)
 from ...features import FeatureCache
 from ...utils import ddp_setup, load_filter, load_saes, maybe_load_llava_model, shard_offsets
 
 
 COACT_DEFAULT_POOL = "token"
 ACT_HIST_DEFAULT_POOL = "token"
+POS_PROFILE_DEFAULT_BINS = "log2"
 
 
 def chunk_and_tokenize(dataset, tokenizer, max_seq_len: int, text_key: str = "text", batch_docs: int = 2048,
@@ -109,10 +111,15 @@ def main(cfg: CacheConfig):
     if cfg.feature_stats:
         stats = dict(pool="window", window=cfg.example_ctx_len, n_top=cfg.stats_top, n_sample=cfg.stats_sample,
                      sample_seed=cfg.stats_seed)
+    try:
+        pos = pos_profile_kwargs(cfg, POS_PROFILE_DEFAULT_BINS, cfg.ctx_len)
+    except ValueError as e:       # a context length beyond what a position table holds
+        cache_config_error(f"--pos_profile: {e}")
     cache = FeatureCache(model, tokenizer, saes, batch_size=cfg.batch_size, shard_size=shard_size,
                          filters=filters, stats=stats, coact=coact_kwargs(cfg, COACT_DEFAULT_POOL, device=model.device),
                          recon=recon_kwargs(cfg),      # one position group
-                         hist=act_hist_kwargs(cfg, ACT_HIST_DEFAULT_POOL))
+                         hist=act_hist_kwargs(cfg, ACT_HIST_DEFAULT_POOL),
+                         pos=pos)
     if ddp:
         dist.barrier()
     cache.run(cfg.ctx_len, dataset)

@@ -5,7 +5,8 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
-from ...config import CacheConfig, act_hist_kwargs, coact_kwargs, parse_cache_config, recon_kwargs
+from ...config import (CacheConfig, act_hist_kwargs, cache_config_error, coact_kwargs, parse_cache_config,
+                       pos_profile_grid_default, pos_profile_kwargs, recon_kwargs)
 from ...features import FeatureImageCache
 from ...utils import ddp_setup, load_filter, load_saes, maybe_load_llava_model, shard_offsets
 
@@ -35,11 +36,18 @@ def main(cfg: CacheConfig):
     if cfg.feature_stats:   # the image constructor pools the processor's first num_image_tokens positions
         stats = dict(pool="image", pool_len=pool_len, n_top=cfg.stats_top,
                      n_sample=cfg.stats_sample, sample_seed=cfg.stats_seed)
+    pos = None
+    if cfg.pos_profile:     # the base image's grid in cells of 4 x 4 and the rest of the row; log2 / linear bins over ctx_len
+        try:
+            pos = pos_profile_kwargs(cfg, cfg.pos_profile_bins or pos_profile_grid_default(pool_len), cfg.ctx_len)
+        except ValueError as e:
+            cache_config_error(str(e))
     cache = FeatureImageCache(model, tokenizer, saes, batch_size=cfg.batch_size, shard_size=shard_size,
                               processor=processor, filters=filters, stats=stats,
                               coact=coact_kwargs(cfg, COACT_DEFAULT_POOL, pool_len=pool_len, device=model.device),
                               recon=recon_kwargs(cfg, (0, pool_len)),    # the base image against the rest
-                              hist=act_hist_kwargs(cfg, ACT_HIST_DEFAULT_POOL, pool_len=pool_len))
+                              hist=act_hist_kwargs(cfg, ACT_HIST_DEFAULT_POOL, pool_len=pool_len),
+                              pos=pos)
     if ddp:
         dist.barrier()
     cache.run(cfg.ctx_len, dataset)
