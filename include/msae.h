@@ -10,7 +10,7 @@
  *
  * WORKSPACE CONTRACT (every entry that takes `void *ws, size_t ws_bytes`; tests/test_gpu_workspace_contract.py holds each of
  * them to it with exact-size, guarded and dirty buffers; tests/test_gpu_pos_profile.py does so for msae_pos_profile_update,
- * whose helper asks for no bytes):
+ * whose helper asks for no bytes, tests/test_gpu_batch_select.py for msae_batch_kth_f32):
  *   - the contents of [ws, ws + ws_bytes) are UNSPECIFIED on entry and on return: a caller may hand over a fresh block, the
  *     block a different entry has just used, or one it shares between all entries of a stream; nothing is kept in it
  *     between calls;
@@ -49,6 +49,8 @@
  *   msae_edit_topk_rows_f32  the same with one table per token (a feature per batch row of one generate)
  *   msae_delta_decode_f32    x + decode(edited) - decode(plain): error-preserving hooks (no reference counterpart)
  *   msae_recon_curve_f32     reconstruction error at several sparsities in one pass (sae.py:190-202 per checkpoint)
+ *   msae_batch_kth_f32, msae_list_filter_f32, msae_decode_prefix_f32   BatchTopK on top-C lists: the batch threshold, the
+ *                            threshold filter, the decode with a row length (no reference counterpart)
  *
  * Numerics contract: all dot products are ascending-k f32 fused
  * multiply-add chains (v_mfma_f32_32x32x2_f32 / v_fma_f32), bit-identical to oracle/sae_oracle.c.
@@ -807,6 +809,57 @@ int msae_recon_curve_f32(const void *x, int x_dtype, const float *vals, const in
 int msae_recon_curve_i64_f32(const void *x, int x_dtype, const float *vals, const int64_t *idx, int ld, const float *W_dec,
                              const float *b_dec, int T, int k, int N, int d, const int32_t *ks, int C, float *mom, float *xx,
                              int32_t *status, void *stream);
+
+/* ---- batch-level selection: capped BatchTopK, threshold filter, length-aware decode -------------
+ * BatchTopK keeps the T*k largest pre-activations of a whole batch instead of k per token; inference replaces the batch's
+ * threshold by a learned one.  Here it is defined on LISTS, so it is exact by construction and needs no fallback and no
+ * host read.  T tokens, a target k, a cap C with k <= C:
+ *   1. L_t = the canonical top-C list of token t (msae_encode_topk with k = C: value descending, index ascending).
+ *   2. P = the multiset of list entries with v > 0 (false for NaN, -0.0 and negatives; +inf is the largest value), K = T*k.
+ *      theta = the K-th largest value of P; |P| < K: theta = min P; P empty: theta = +inf.
+ *   3. An entry is kept iff v > 0 && v >= theta: ALL ties at theta are kept, so the result does not depend on the order of
+ *      the tokens, and sum(len) >= min(K, |P|) with equality unless floats tie at theta.
+ *   4. On a value-descending row the kept entries are a prefix; len[t] is its length.  Dropped slots come out with
+ *      activation +0.0 and their own index (the indices of a row stay valid and distinct).
+ *   5. saturated[t] = (len[t] == C): the token may have had more latents at or above theta than the cap admits.  With no
+ *      saturated row the result equals uncapped BatchTopK over the dense [T, N] latents (an entry outside a list is at most
+ *      the list's last entry, which is below theta: no outside entry can enter the top K, and theta is the dense one).
+ *   6. Thresholded inference: the same keep rule with a given theta; with a per-feature table theta_feat[N] an entry is kept
+ *      iff its index lies in [0, N) && v > 0 && v >= theta_feat[idx] (the table is never read out of bounds).
+ *
+ * msae_batch_kth_f32: step 2.  vals [T][ld >= C] f32 (the [:, :C] view of a wider list is read in place), K >= 1;
+ *   *theta (f32) and *n_pos (int32, optional: |P|) are DEVICE scalars.  An exact radix select on the float bits (a positive
+ *   float's bits order like its value): four 8-bit passes over all T*C entries, one launch per pass, integer histograms
+ *   only -- per-workgroup LDS bins, one integer atomic per bin and workgroup -- so the result is bit-reproducible.  No data
+ *   is handed between the workgroups of a launch and nothing waits on a flag: every workgroup of a launch redoes the
+ *   earlier passes' digit picks from their complete 256-bin histograms.  Envelope: T, C >= 1, T*C <= 2^24 (else MSAE_EINVAL;
+ *   the helper returns 0).  ws: msae_batch_kth_ws_bytes(T, C) bytes under the workspace contract above (the call zeroes the
+ *   histograms itself; a short or missing workspace is MSAE_EWS before any launch).
+ * msae_list_filter_f32 / _i64_f32: steps 3-6.  vals_in / idx_in [T][ld >= C], *theta a DEVICE scalar, theta_feat f32 [N] or
+ *   NULL (then N is not looked at and indices are not checked); vals_out / idx_out [T][C] (not the inputs), len int32 [T].
+ *   Every row is partitioned STABLY: the kept entries first in list order, then the dropped ones in theirs with activation
+ *   +0.0 -- on a value-descending row in scalar mode that is the row itself with its tail zeroed.  *n_saturated (int32
+ *   device counter, optional) is ADDED to by the number of rows with v_last > 0 && v_last >= *theta, v_last the row's last
+ *   INPUT entry: in scalar mode on a descending row that is len == C; in table mode the host passes theta_feat's minimum as
+ *   *theta (the floor below which no feature keeps anything).  1 <= C <= 4096 (else MSAE_EINVAL); T == 0 returns 0.  One wave
+ *   per token for C <= 256 (ballot compaction in registers), one workgroup per token above.  No workspace.
+ * msae_decode_prefix_f32 / _i64_f32: msae_decode_f32 over the first clamp(len[a], 0, k) entries of every row.  The slots
+ *   behind that are not read at all -- neither index, nor activation, nor decoder row (they may hold anything) -- so the
+ *   cost follows sum(len), not A*k.  Same column slabs and the same fma chain in j order: on a filtered list the output is
+ *   bit-identical to msae_decode_f32's, which lets a zero activation contribute nothing. */
+size_t msae_batch_kth_ws_bytes(int T, int C);
+int msae_batch_kth_f32(const float *vals, int T, int C, int ld, long long K, float *theta, int32_t *n_pos, void *ws,
+                       size_t ws_bytes, void *stream);
+int msae_list_filter_f32(const float *vals_in, const int32_t *idx_in, int T, int C, int ld, const float *theta,
+                         const float *theta_feat, int N, float *vals_out, int32_t *idx_out, int32_t *len,
+                         int32_t *n_saturated, void *stream);
+int msae_list_filter_i64_f32(const float *vals_in, const int64_t *idx_in, int T, int C, int ld, const float *theta,
+                             const float *theta_feat, int N, float *vals_out, int64_t *idx_out, int32_t *len,
+                             int32_t *n_saturated, void *stream);
+int msae_decode_prefix_f32(const int32_t *idx, const float *acts, const int32_t *len, const float *W_dec,
+                           const float *b_dec, int A, int k, int N, int d, float *out, int32_t *status, void *stream);
+int msae_decode_prefix_i64_f32(const int64_t *idx, const float *acts, const int32_t *len, const float *W_dec,
+                               const float *b_dec, int A, int k, int N, int d, float *out, int32_t *status, void *stream);
 
 /* ---- merge of per-shard results (feature-sharded encode; no reference counterpart) ----
  * gathered: int32 [G][2][T][kl], the all-gather of each rank's packed block [2][T][kl]

@@ -144,6 +144,17 @@ PROTOTYPES = {
                                      c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "msae_recon_curve_i64_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
                                          c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "msae_batch_kth_ws_bytes": (c_size_t, [c_int, c_int]),
+    "msae_batch_kth_f32": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_size_t,
+                                   c_void_p]),
+    "msae_list_filter_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p]),
+    "msae_list_filter_i64_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p]),
+    "msae_decode_prefix_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                       c_void_p, c_void_p, c_void_p]),
+    "msae_decode_prefix_i64_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                           c_void_p, c_void_p, c_void_p]),
     "msae_merge_topk": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "msae_compact_flags": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "msae_merge_topk_masked": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -20,6 +20,13 @@ from ..sae import Sae
 from .edits import FeatureEdits, RowEdits, as_off_features
 
 
+def _topk_sae_only(sae, what: str) -> None:
+    """The steering and attribution hooks edit per-token top-k lists: not built for a "batchtopk" Sae."""
+    if getattr(getattr(sae, "cfg", None), "activation", "topk") == "batchtopk":
+        raise NotImplementedError(f"{what} is not built for an Sae with activation='batchtopk': the hooks edit per-token "
+                                  "top-k lists (Sae.encode(threshold=) + Sae.decode(lengths=) are its inference path)")
+
+
 def sae_reconstruct(sae, hidden: Tensor, *, set_feature: int = -1, set_value: float = 0.0,
                     zero_feature: int = -1, out_dtype: Optional[torch.dtype] = None,
                     differentiable: Optional[bool] = None, edits: Optional[FeatureEdits] = None,
@@ -39,6 +46,7 @@ def sae_reconstruct(sae, hidden: Tensor, *, set_feature: int = -1, set_value: fl
     when nothing is edited): the error term is a constant of the forward, so the gradients with respect to the latents and
     the SAE's parameters are exactly the reconstruct path's.  Its values agree with the fused path's within the derived
     bound of tests/intervene_ref.py (the cancelled entries round differently), not bitwise."""
+    _topk_sae_only(sae, "sae_reconstruct")
     if preserve_error:
         return _reconstruct_preserving(sae, hidden, set_feature, set_value, zero_feature, out_dtype, differentiable, edits,
                                        edit_group)
@@ -213,6 +221,7 @@ def clamp_features_max(sae, feature, hooked_module: torch.nn.Module, k: float = 
     dtype (`Sae.intervene`), the S = 1 steps return the layer output unchanged -- no SAE call, no captured graph."""
     import os
 
+    _topk_sae_only(sae, "clamp_features_max")
     if preserve_error:
         return _clamp_preserving(sae, hooked_module, _preserving_edits(sae, feature, k))
     if graph_step is None:
@@ -292,6 +301,7 @@ def clamp_features_rows(sae, features: Sequence, hooked_module: torch.nn.Module,
     if not isinstance(sae, Sae):
         raise NotImplementedError("clamp_features_rows runs on the single-GPU msae.Sae only: a feature-sharded engine takes "
                                   "one feature (clamp_features_max)")
+    _topk_sae_only(sae, "clamp_features_rows")
     if isinstance(features, (Mapping, Tensor, str)) or not hasattr(features, "__len__"):
         raise ValueError("clamp_features_rows: features must be a sequence with one element per batch row")
     if graph_step is None:
@@ -328,6 +338,8 @@ def attribution_sae_hook(sae_dict: Dict[str, Sae], module_to_name: Dict[torch.nn
     h + (decode(ablated) - decode(plain)) in h's own dtype -- the ablation's effect in the model itself, not in a model that
     runs on reconstructions; sae_reconstruct states the autograd rule."""
     per_module: dict = {}         # a list of features becomes one FeatureEdits per hooked Sae, built at its first call
+    for sae in sae_dict.values():
+        _topk_sae_only(sae, "attribution_sae_hook")
 
     def hook(module, inputs, outputs):
         h = outputs[0] if isinstance(outputs, tuple) else outputs

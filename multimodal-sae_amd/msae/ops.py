@@ -14,6 +14,7 @@ These are the operators the drop-in ``Sae`` module (msae/sae/sae.py) and the fea
     msae::rows_topk     torch.mm + torch.topk, fused         features/stats.py:35-37,83,107
     msae::pre_acts_features  pre_acts(x)[..., features]      sae/sae.py:207-225 (AuxK: the dead latents only)
     msae::recon_curve   decode + e.pow(2).sum() per checkpoint  sae/sae.py:190,201 (one pass for several sparsities)
+    batch_kth, list_filter, batch_select, decode(lengths=)   BatchTopK on top-C lists (no reference counterpart)
 
 All ops run on the tensor's device on the current stream, never synchronise (``sparsify`` reads one
 int64 back, as ``torch.nonzero`` does), and raise on CPU tensors.
@@ -1278,31 +1279,59 @@ def _idx32(top_indices: Tensor) -> Tensor:
     return top_indices.detach().to(torch.int32).contiguous()
 
 
+def _decode_prefix_host(top_indices: Tensor, top_acts: Tensor, W_dec: Tensor, b_dec: Optional[Tensor], lengths: Tensor) -> Tensor:
+    """The meaning of msae_decode_prefix_f32 in plain torch (not its bits): the slots behind a row's length count for nothing,
+    whatever they hold."""
+    C = top_acts.shape[-1]
+    live = torch.arange(C, device=top_acts.device) < lengths.reshape(*top_acts.shape[:-1], 1).clamp(0, C)
+    N = W_dec.shape[0]
+    ok = live & (top_indices >= 0) & (top_indices < N)
+    v = torch.where(ok, top_acts.detach().to(torch.float32), torch.zeros((), dtype=torch.float32, device=top_acts.device))
+    i = torch.where(ok, top_indices, torch.zeros_like(top_indices)).long()
+    out = (v[..., None] * W_dec.detach().to(torch.float32)[i]).sum(-2)
+    return out if b_dec is None else out + b_dec.detach().to(torch.float32)
+
+
 @torch.library.custom_op("msae::decode", mutates_args=())
-def decode(top_indices: Tensor, top_acts: Tensor, W_dec: Tensor, b_dec: Optional[Tensor]) -> Tensor:
-    """sum_j top_acts[:, j] * W_dec[top_indices[:, j]] (+ b_dec);  W_dec is [N, d] row-major."""
-    dev = _hip.require_device(top_indices, top_acts, W_dec, b_dec)
-    lib = _hip.load()
+def decode(top_indices: Tensor, top_acts: Tensor, W_dec: Tensor, b_dec: Optional[Tensor],
+           lengths: Optional[Tensor] = None) -> Tensor:
+    """sum_j top_acts[:, j] * W_dec[top_indices[:, j]] (+ b_dec);  W_dec is [N, d] row-major.  `lengths` (int32, one per row;
+    clamped to [0, k]): only the first lengths[a] entries of row a are read -- msae_decode_prefix_f32, whose cost follows
+    sum(lengths); on a filtered list (ops.list_filter / ops.batch_select) the same bits as without it.  With `lengths`, host
+    tensors take a plain-torch path with the same meaning."""
     assert top_indices.shape == top_acts.shape, "indices / acts shape mismatch"  # kernels.py:193
+    if lengths is not None and not top_acts.is_cuda:
+        return _decode_prefix_host(top_indices, top_acts, W_dec, b_dec, lengths)
+    dev = _hip.require_device(top_indices, top_acts, W_dec, b_dec, lengths)
+    lib = _hip.load()
     acts, W, bd = _f32c(top_acts), _f32c(W_dec), _f32c(b_dec)
+    pre = "msae_decode" if lengths is None else "msae_decode_prefix"
     if top_indices.dtype == torch.int64:      # Tensor.topk's index type: read as it is, no narrowing copy
-        idx, fn, name = top_indices.detach().contiguous(), lib.msae_decode_i64_f32, "msae_decode_i64_f32"
+        idx, name = top_indices.detach().contiguous(), pre + "_i64_f32"
     else:
-        idx, fn, name = _idx32(top_indices), lib.msae_decode_f32, "msae_decode_f32"
+        idx, name = _idx32(top_indices), pre + "_f32"
+    fn = getattr(lib, name)
     N, d = W.shape
     k = idx.shape[-1]
     A = idx.numel() // k
     out = torch.empty(*idx.shape[:-1], d, dtype=torch.float32, device=dev)
     flag = _bounds_flag(dev)
     with torch.cuda.device(dev):
-        _hip.check(fn(_hip.ptr(idx), _hip.ptr(acts), _hip.ptr(W), _hip.ptr(bd), A, k, N, d, _hip.ptr(out),
-                      _hip.ptr(flag), _hip.stream_of(acts)), "%s" % name)
+        if lengths is None:
+            _hip.check(fn(_hip.ptr(idx), _hip.ptr(acts), _hip.ptr(W), _hip.ptr(bd), A, k, N, d, _hip.ptr(out),
+                          _hip.ptr(flag), _hip.stream_of(acts)), "%s" % name)
+        else:
+            if lengths.numel() != A:
+                raise ValueError(f"decode: lengths must hold one entry per row ({A}), got {tuple(lengths.shape)}")
+            ln = lengths.detach().to(torch.int32).contiguous()
+            _hip.check(fn(_hip.ptr(idx), _hip.ptr(acts), _hip.ptr(ln), _hip.ptr(W), _hip.ptr(bd), A, k, N, d, _hip.ptr(out),
+                          _hip.ptr(flag), _hip.stream_of(acts)), "%s" % name)
     _check_bounds(flag, name)
     return out
 
 
 @decode.register_fake
-def _(top_indices, top_acts, W_dec, b_dec):
+def _(top_indices, top_acts, W_dec, b_dec, lengths=None):
     return top_acts.new_empty(*top_acts.shape[:-1], W_dec.shape[1], dtype=torch.float32)
 
 
@@ -1375,9 +1404,30 @@ def _(top_indices, top_acts, W_dec, grad_out, need_acts, need_w):
 
 
 def _decode_setup(ctx, inputs, output):
-    top_indices, top_acts, W_dec, b_dec = inputs
+    top_indices, top_acts, W_dec, b_dec, lengths = inputs
+    if lengths is not None:
+        # the slots behind a row's length were not read and may hold anything: the backward kernels (width C) get them as
+        # activation 0 on feature 0, and their activation gradient is 0
+        C = top_acts.shape[-1]
+        live = torch.arange(C, device=top_acts.device) < lengths.reshape(*top_acts.shape[:-1], 1).clamp(0, C)
+        top_acts = torch.where(live, top_acts.detach(), torch.zeros((), dtype=top_acts.dtype, device=top_acts.device))
+        top_indices = torch.where(live, top_indices, torch.zeros_like(top_indices))
+        ctx.live = live
+    else:
+        ctx.live = None
     ctx.save_for_backward(top_indices, top_acts, W_dec)
     ctx.has_bdec = b_dec is not None
+
+
+def _decode_bwd_host(top_indices: Tensor, top_acts: Tensor, W_dec: Tensor, grad_out: Tensor, need_acts: bool, need_w: bool):
+    """decode_bwd's meaning in plain torch, for the host path of decode(lengths=)."""
+    i = top_indices.long()
+    g_acts = (grad_out[..., None, :] * W_dec[i]).sum(-1) if need_acts else None
+    g_w = None
+    if need_w:
+        g_w = torch.zeros_like(W_dec)
+        g_w.index_add_(0, i.reshape(-1), (top_acts[..., None] * grad_out[..., None, :]).reshape(-1, W_dec.shape[1]))
+    return g_acts, g_w
 
 
 def _decode_backward(ctx, grad_out):
@@ -1385,15 +1435,179 @@ def _decode_backward(ctx, grad_out):
     need_acts, need_w = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
     g_acts = g_w = g_b = None
     if need_acts or need_w:
-        ga, gw = decode_bwd(top_indices, top_acts, W_dec, grad_out.contiguous(), need_acts, need_w)
+        if grad_out.is_cuda:
+            ga, gw = decode_bwd(top_indices, top_acts, W_dec, grad_out.contiguous(), need_acts, need_w)
+        else:
+            ga, gw = _decode_bwd_host(top_indices, top_acts, W_dec.detach(), grad_out, need_acts, need_w)
         g_acts = ga.to(top_acts.dtype) if need_acts else None
+        if g_acts is not None and ctx.live is not None:
+            g_acts = torch.where(ctx.live, g_acts, torch.zeros((), dtype=g_acts.dtype, device=g_acts.device))
         g_w = gw.to(W_dec.dtype) if need_w else None
     if ctx.has_bdec and ctx.needs_input_grad[3]:
         g_b = grad_out.reshape(-1, grad_out.shape[-1]).sum(0)
-    return None, g_acts, g_w, g_b
+    return None, g_acts, g_w, g_b, None
 
 
 decode.register_autograd(_decode_backward, setup_context=_decode_setup)
+
+
+# ---- batch-level selection: capped BatchTopK and threshold filters on top-C lists (csrc/batch_select.hip) ------
+BATCH_KTH_MAX_VALUES = 1 << 24      # msae_batch_kth_f32's envelope: T * C
+LIST_FILTER_MAX_C = 4096            # the encoder's own limit on a list's width
+
+
+def _list2d(vals: Tensor, idx: Optional[Tensor], what: str) -> Tuple[Tensor, Optional[Tensor], int, int, int]:
+    """A list [..., C] -> ([T, C] views whose rows are read in place where the last dimension is dense, T, C, ld)."""
+    if vals.dim() < 1 or vals.shape[-1] < 1:
+        raise ValueError(f"{what}: the list must be [..., C] with C >= 1, got {tuple(vals.shape)}")
+    if vals.dtype != torch.float32:
+        raise ValueError(f"{what}: the list's values must be float32, got {vals.dtype}")
+    C = vals.shape[-1]
+    T = vals.numel() // C
+    if idx is not None:
+        if idx.shape != vals.shape:
+            raise ValueError(f"{what}: values and indices must share one shape, got {tuple(vals.shape)} and {tuple(idx.shape)}")
+        if idx.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"{what}: indices must be int32 or int64, got {idx.dtype}")
+        if idx.device != vals.device:
+            raise ValueError(f"{what}: values and indices must be on one device")
+    v = vals.detach()
+    strided = v.dim() == 2 and v.stride(1) == 1 and v.stride(0) >= C and (
+        idx is None or (idx.stride(1) == 1 and idx.stride(0) == v.stride(0)))
+    if strided and T > 0:                 # the [:, :C] view of a wider list
+        return v, idx, T, C, v.stride(0)
+    v = v.reshape(T, C).contiguous()
+    return v, (None if idx is None else idx.detach().reshape(T, C).contiguous()), T, C, C
+
+
+def _batch_kth_host(v: Tensor, K: int) -> Tuple[Tensor, Tensor]:
+    pos = v[v > 0]
+    n = pos.numel()
+    n_pos = torch.tensor(n, dtype=torch.int32, device=v.device)
+    if n == 0:
+        return torch.full((), float("inf"), dtype=torch.float32, device=v.device), n_pos
+    return torch.sort(pos, descending=True).values[min(K, n) - 1].clone(), n_pos
+
+
+def batch_kth(vals: Tensor, K: int) -> Tuple[Tensor, Tensor]:
+    """theta of capped BatchTopK (include/msae.h, "batch-level selection", step 2) -> (theta f32 scalar, n_pos int32 scalar),
+    both on vals' device: the K-th largest of the entries with v > 0 of the list vals [..., C] (a [:, :C] view of a wider
+    2-d list is read in place), the smallest of them when there are fewer than K, +inf when there are none; n_pos = how
+    many there are.  Exact and bit-reproducible (an integer radix select); nothing is read back.  On a HIP device T * C may
+    be at most 2^24; host tensors take a torch.sort."""
+    K = int(K)
+    if K < 1:
+        raise ValueError(f"batch_kth: K must be positive, got {K}")
+    v, _, T, C, ld = _list2d(vals, None, "batch_kth")
+    if not v.is_cuda:
+        return _batch_kth_host(v, K)
+    theta = torch.empty((), dtype=torch.float32, device=v.device)
+    n_pos = torch.empty((), dtype=torch.int32, device=v.device)
+    if T == 0:
+        return theta.fill_(float("inf")), n_pos.zero_()
+    if T * C > BATCH_KTH_MAX_VALUES:
+        raise ValueError(f"batch_kth: T * C = {T * C} exceeds {BATCH_KTH_MAX_VALUES}: select over chunks of the batch")
+    lib = _hip.load()
+    ws = _workspace(v.device, lib.msae_batch_kth_ws_bytes(T, C))
+    with torch.cuda.device(v.device):
+        _hip.check(lib.msae_batch_kth_f32(_hip.ptr(v), T, C, ld, K, _hip.ptr(theta), _hip.ptr(n_pos), _hip.ptr(ws), ws.numel(),
+                                          _hip.stream_of(v)), "msae_batch_kth_f32")
+    return theta, n_pos
+
+
+def _list_filter_host(v: Tensor, i: Tensor, theta: Tensor, theta_feat: Optional[Tensor], N: int):
+    if theta_feat is None:
+        keep = (v > 0) & (v >= theta)
+    else:
+        ok = (i >= 0) & (i < N)
+        keep = ok & (v > 0) & (v >= theta_feat[torch.where(ok, i, torch.zeros_like(i)).long()])
+    order = torch.sort((~keep).to(torch.int8), dim=1, stable=True).indices         # kept first, each part in list order
+    lengths = keep.sum(1).to(torch.int32)
+    live = torch.arange(v.shape[1], device=v.device) < lengths[:, None]
+    vo = torch.where(live, torch.gather(v, 1, order), torch.zeros((), dtype=v.dtype, device=v.device))
+    n_sat = ((v[:, -1] > 0) & (v[:, -1] >= theta)).sum().to(torch.int32)
+    return vo, torch.gather(i, 1, order), lengths, n_sat
+
+
+def list_filter(vals: Tensor, idx: Tensor, theta, theta_feat: Optional[Tensor] = None,
+                n_saturated: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """Steps 3-6 of include/msae.h, "batch-level selection" -> (vals_out [..., C] f32, idx_out [..., C], lengths int32 [...],
+    n_saturated int32 scalar).  An entry of the list vals / idx [..., C] (C <= 4096; a [:, :C] view is read in place) is
+    kept iff v > 0 && v >= theta, or with a per-feature table theta_feat f32 [N] iff 0 <= idx < N && v > 0 &&
+    v >= theta_feat[idx]; every row is partitioned stably, kept entries first, and the dropped slots come out with
+    activation +0.0 and their own index.  theta: a float or a one-element tensor (kept on the device); in table mode it is
+    the FLOOR of the saturation test and defaults (None) to theta_feat.min().  n_saturated: an int32 device scalar to ADD
+    this call's count of rows with v_last > 0 && v_last >= theta to (None: a fresh zero).  Not differentiable; nothing is
+    read back."""
+    v, i, T, C, ld = _list2d(vals, idx, "list_filter")
+    if C > LIST_FILTER_MAX_C:
+        raise ValueError(f"list_filter: C must be at most {LIST_FILTER_MAX_C}, got {C}")
+    dev = v.device
+    N = 0
+    if theta_feat is not None:
+        if not isinstance(theta_feat, Tensor) or theta_feat.dim() != 1 or theta_feat.numel() < 1:
+            raise ValueError("list_filter: theta_feat must be a 1-d tensor [N]")
+        theta_feat = theta_feat.detach().to(dev, torch.float32).contiguous()
+        N = theta_feat.numel()
+        if theta is None:
+            theta = theta_feat.min()
+    if theta is None:
+        raise ValueError("list_filter: theta is required without a per-feature table")
+    if isinstance(theta, Tensor):
+        if theta.numel() != 1:
+            raise ValueError(f"list_filter: theta must hold one element, got {tuple(theta.shape)}")
+        th = theta.detach().to(dev, torch.float32).reshape(())
+    else:
+        th = torch.full((), float(theta), dtype=torch.float32, device=dev)
+    if n_saturated is not None and (n_saturated.dtype != torch.int32 or n_saturated.numel() != 1 or n_saturated.device != dev):
+        raise ValueError("list_filter: n_saturated must be an int32 scalar on the list's device")
+    lead = tuple(vals.shape[:-1])
+    if not v.is_cuda:
+        vo, io, lengths, n_sat = _list_filter_host(v, i, th, theta_feat, N)
+        if n_saturated is not None:
+            n_sat = n_saturated.add_(n_sat.reshape(n_saturated.shape))
+        return vo.view(*lead, C), io.view(*lead, C), lengths.view(lead), n_sat
+    lib = _hip.load()
+    vo = torch.empty(T, C, dtype=torch.float32, device=dev)
+    io = torch.empty(T, C, dtype=i.dtype, device=dev)
+    lengths = torch.empty(T, dtype=torch.int32, device=dev)
+    n_sat = n_saturated if n_saturated is not None else torch.zeros((), dtype=torch.int32, device=dev)
+    fn, name = (lib.msae_list_filter_i64_f32, "msae_list_filter_i64_f32") if i.dtype == torch.int64 else \
+        (lib.msae_list_filter_f32, "msae_list_filter_f32")
+    with torch.cuda.device(dev):
+        _hip.check(fn(_hip.ptr(v), _hip.ptr(i), T, C, ld, _hip.ptr(th), _hip.ptr(theta_feat), N, _hip.ptr(vo), _hip.ptr(io),
+                      _hip.ptr(lengths), _hip.ptr(n_sat), _hip.stream_of(v)), name)
+    return vo.view(*lead, C), io.view(*lead, C), lengths.view(lead), n_sat
+
+
+class _BatchSelect(torch.autograd.Function):
+    """batch_kth + list_filter as one autograd node: the gradient of a kept entry passes, a dropped slot's is 0."""
+
+    @staticmethod
+    def forward(ctx, acts, idx, k):
+        C = acts.shape[-1]
+        theta, _ = batch_kth(acts, max((acts.numel() // C) * k, 1))
+        kept, _, lengths, n_sat = list_filter(acts, idx, theta)
+        ctx.save_for_backward(kept)
+        ctx.mark_non_differentiable(lengths, theta, n_sat)
+        return kept, lengths, theta, n_sat
+
+    @staticmethod
+    def backward(ctx, g, _gl, _gt, _gn):
+        kept, = ctx.saved_tensors
+        return torch.where(kept > 0, g, torch.zeros((), dtype=g.dtype, device=g.device)), None, None
+
+
+def batch_select(acts: Tensor, idx: Tensor, k: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """Capped BatchTopK over canonical top-C lists (include/msae.h, "batch-level selection"): of the T rows of acts / idx
+    [..., C] (value descending, as ops.encode_topk / ops.sparse_encode return them) keep the entries at or above the
+    (T * k)-th largest positive value of the whole batch -> (acts_kept [..., C], lengths int32 [...], theta f32 scalar,
+    n_saturated int32 scalar), all on the device, no host synchronisation.  The kept entries are a prefix of every row, so
+    `idx` serves acts_kept unchanged; the dropped slots hold +0.0.  One autograd node: the backward is the gradient times
+    the keep mask."""
+    if int(k) < 1 or int(k) > acts.shape[-1]:
+        raise ValueError(f"batch_select: k must be in [1, C = {acts.shape[-1]}], got {k}")
+    return _BatchSelect.apply(acts, idx, int(k))
 
 
 # ---- cache sparsify ---------------------------------------------------------------------------------

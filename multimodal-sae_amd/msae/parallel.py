@@ -359,10 +359,14 @@ class ShardedSae:
         return join, (vals[: hi - lo], idx[: hi - lo]), pack
 
     def encode(self, x: Tensor, set_feature: int = -1, set_value: float = 0.0, zero_feature: int = -1, edits=None,
-               edit_group=None):
+               edit_group=None, threshold=None):
         """-> (top_acts [T,k] f32, top_indices [T,k] int64 GLOBAL feature ids, status [T]).  The optional edits are
         the hooks' (`latents[:, set_feature] = set_value`, `latents[:, zero_feature] = 0` before the TopK), by global
-        feature id.  A SET of edits (`edits=`, msae.features.FeatureEdits) is not implemented on sharded engines."""
+        feature id.  A SET of edits (`edits=`, msae.features.FeatureEdits) is not implemented on sharded engines, and
+        neither is a threshold encode (`threshold=`, Sae.encode's: DESIGN.md section 8)."""
+        if threshold is not None:
+            raise NotImplementedError("threshold= (the BatchTopK / per-feature-threshold encode) runs on the single-GPU msae.Sae "
+                                      "only: filter the merged list with ops.list_filter")
         if edits is not None or edit_group is not None:   # FeatureEdits, or RowEdits with its per-token groups
             raise NotImplementedError("edits= (a set of edited features) runs on the single-GPU msae.Sae only: a feature-sharded "
                                       "engine takes the scalar set_feature / zero_feature arguments")

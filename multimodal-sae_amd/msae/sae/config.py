@@ -37,6 +37,41 @@ class SaeConfig(_Serializable):
     """Use Multi-TopK loss."""
     signed: bool = False
     """Kept so older checkpoints' cfg.json load."""
+    activation: str = "topk"
+    """"topk": k latents per token.  "batchtopk": the T*k largest of the batch in training, a learned threshold in inference
+    (DESIGN.md section 7n)."""
+    batch_cap: int = 0
+    """"batchtopk" only: the most latents one token may keep (the width C of the lists the selection works on).
+    0: min(4k, 256)."""
+
+    ACTIVATIONS = ("topk", "batchtopk")
+
+    def __post_init__(self):
+        if self.activation not in self.ACTIVATIONS:
+            raise ValueError(f"activation must be one of {self.ACTIVATIONS}, got {self.activation!r}")
+        if self.batch_cap < 0:
+            raise ValueError(f"batch_cap must not be negative, got {self.batch_cap}")
+        if self.activation == "batchtopk":
+            if self.multi_topk:
+                raise ValueError("multi_topk is a per-token TopK loss term: it does not go with activation='batchtopk'")
+            if not self.k <= self.cap <= 4096:
+                raise ValueError(f"batch_cap must lie in [k = {self.k}, 4096], got {self.cap}")
+
+    @property
+    def cap(self) -> int:
+        """The list width of the main selection: k for "topk", batch_cap (0: min(4k, 256)) for "batchtopk"."""
+        if self.activation != "batchtopk":
+            return self.k
+        return self.batch_cap or min(4 * self.k, 256)
+
+    def to_dict(self) -> dict:
+        """The two BatchTopK fields are written only where they differ from the defaults: a TopK cfg.json is the reference's."""
+        d = super().to_dict()
+        if d["activation"] == "topk":
+            del d["activation"]
+        if d["batch_cap"] == 0:
+            del d["batch_cap"]
+        return d
 
 
 @dataclass
@@ -59,3 +94,6 @@ class TrainConfig(_Serializable):
     log_to_wandb: bool = True
     run_name: Union[str, None] = None
     wandb_log_frequency: int = 1
+
+    def to_dict(self) -> dict:
+        return {**super().to_dict(), "sae": self.sae.to_dict()}

@@ -16,6 +16,8 @@ unchanged.  What differs is underneath:
                      latents); `forward(..., auxk_path="subset")` builds the AuxK selection on it
 * `neighbors`, `top_logits` -> torch.ops.msae.row_inv_norms + rows_topk (features/stats.py:12-47,76-120 as one fused
                      f32 GEMM + per-row top-k: DESIGN.md section 7c)
+* `SaeConfig(activation="batchtopk")` -> ops.batch_select + ops.decode(lengths=): the T*k largest latents of the batch in
+                     `forward`, a learned or given threshold in `encode(threshold=)` (new, opt-in: DESIGN.md section 7n)
 
 SAE math is f32 whatever dtype the LLM hands over, as in the reference (sae.py:140,174).
 There is no CPU implementation: calling a compute method with CPU tensors raises.
@@ -53,6 +55,18 @@ class ForwardOutput(NamedTuple):
     fvu: Tensor
     auxk_loss: Tensor
     multi_topk_fvu: Tensor
+
+
+class BatchForwardOutput(ForwardOutput):
+    """The ForwardOutput of a "batchtopk" Sae: the same six fields -- latent_acts / latent_indices are the [T, C] lists, the
+    dropped slots with activation +0.0 -- and three attributes from the batch-level selection, all
+    device tensors: `lengths` (int32 [T], the kept prefix of every row), `theta` (f32 scalar, this batch's threshold) and
+    `n_saturated` (int32 scalar, the rows that kept all C slots)."""
+
+    def __new__(cls, *fields, lengths: Tensor, theta: Tensor, n_saturated: Tensor):
+        self = super().__new__(cls, *fields)
+        self.lengths, self.theta, self.n_saturated = lengths, theta, n_saturated
+        return self
 
 
 class ReconOutput(NamedTuple):
@@ -133,6 +147,11 @@ class Sae(nn.Module):
         if decoder and self.cfg.normalize_decoder:
             self.set_decoder_norm_to_unit_norm()
         self.b_dec = nn.Parameter(torch.zeros(d_in, dtype=dtype, device=device))
+        if cfg.activation == "batchtopk":
+            # the inference threshold BatchTopK learns in training (msae.train.SaeTrainStep folds every batch's theta into it);
+            # -1 = not learned yet.  Saved and loaded with the model; a TopK Sae has no such key.
+            self.register_buffer("threshold", torch.tensor(-1.0, dtype=torch.float32, device=device))
+            self._threshold_checked = None     # the buffer's _version at which a host read last found it learned
         self._prepared: Optional[Tensor] = None
         self._prepared_key = None
 
@@ -252,7 +271,7 @@ class Sae(nn.Module):
     def encode(self, x: Tensor, *, set_feature: int = -1, set_value: float = 0.0,
                zero_feature: int = -1, return_status: bool = False, resolve: bool = True,
                differentiable: Optional[bool] = None, exact: bool = False, certified: bool = False, edits=None,
-               edit_group: Optional[Tensor] = None):
+               edit_group: Optional[Tensor] = None, threshold=None, cap: Optional[int] = None, return_lengths: bool = False):
         """Fused encode + TopK (sae.py:183-185).  `set_feature/set_value` and `zero_feature` apply
         the steering / attribution hooks' edits of the dense latents (steering.py:113-114,
         patching/utils.py:43-48) inside the kernel, before TopK.  `edits` (a msae.features.FeatureEdits) applies a SET of
@@ -279,7 +298,23 @@ class Sae(nn.Module):
         node (sparse backward through the selected latents) when gradients are enabled and `x` requires grad (the attribution
         hooks: the LLM's hidden states do), or the module is in TRAINING mode and a parameter requires grad (a loaded module is,
         as in the reference, until `.eval()` / `.requires_grad_(False)`), or `differentiable=True` is passed.  The detached fast
-        path is what runs under `torch.no_grad()` (the cache and steering hooks) and in `eval()` mode."""
+        path is what runs under `torch.no_grad()` (the cache and steering hooks) and in `eval()` mode.
+
+        Threshold encode: with `threshold=` -- a float, a one-element tensor, or a per-feature table
+        [N] such as `ActHist.threshold_at_rate(...)` -- the call is "top-`cap`, then drop what lies below its (feature's)
+        threshold": an EncoderOutput of width `cap` (default cfg.k) whose rows hold the kept entries first, in list order, and
+        +0.0 behind them (`return_lengths=True` adds the int32 row lengths as a last result).  A "batchtopk" Sae ALWAYS
+        encodes this way: `threshold` defaults to its learned buffer (RuntimeError while that is still -1; checking costs
+        one host read per change of the buffer, none with an explicit threshold or after `set_threshold`) and `cap` to
+        cfg.cap.  No edits here (ValueError); autograd through a scalar threshold is the mask's, through a table
+        NotImplementedError."""
+        if threshold is not None or self.cfg.activation == "batchtopk":
+            if edits is not None or edit_group is not None or set_feature >= 0 or zero_feature >= 0:
+                raise ValueError("Sae.encode: a threshold encode takes no edits, set_feature or zero_feature (edit a per-token "
+                                 "TopK encode instead)")
+            return self._encode_threshold(x, threshold, cap, return_lengths, return_status, differentiable, exact, certified)
+        if cap is not None or return_lengths:
+            raise ValueError("Sae.encode: cap= and return_lengths= belong to a threshold encode (threshold=, or a 'batchtopk' Sae)")
         if edits is not None:
             if set_feature >= 0 or zero_feature >= 0:
                 raise ValueError("Sae.encode: pass either edits= or the scalar set_feature / zero_feature arguments, not both")
@@ -326,6 +361,76 @@ class Sae(nn.Module):
         out = EncoderOutput(acts, idx)
         return (out, status) if return_status else out
 
+    # ---- threshold encode ------------------------------------------------------
+    @torch.no_grad()
+    def set_threshold(self, value: float) -> None:
+        """Set the inference threshold of a "batchtopk" Sae from a host number (finite, >= 0): no device read."""
+        if self.cfg.activation != "batchtopk":
+            raise ValueError("Sae.set_threshold: only a 'batchtopk' Sae has a threshold buffer")
+        value = float(value)
+        if not (value >= 0.0 and value != float("inf")):
+            raise ValueError(f"Sae.set_threshold: the threshold must be finite and not negative, got {value}")
+        self.threshold.fill_(value)
+        self._threshold_checked = self.threshold._version
+
+    def _learned_threshold(self) -> Tensor:
+        """The threshold buffer, once a host read (one per change of the buffer) has found it learned."""
+        if self._threshold_checked != self.threshold._version:
+            if float(self.threshold) < 0:
+                raise RuntimeError("Sae.encode: this 'batchtopk' Sae has not learned its threshold yet (the buffer holds -1): "
+                                   "train it (msae.train.SaeTrainStep), call set_threshold(), or pass threshold=")
+            self._threshold_checked = self.threshold._version
+        return self.threshold
+
+    def _encode_threshold(self, x: Tensor, threshold, cap: Optional[int], return_lengths: bool, return_status: bool,
+                          differentiable: Optional[bool], exact: bool, certified: bool):
+        N = self.num_latents
+        dev = self.encoder.weight.device
+        if cap is None:
+            cap = self.cfg.cap
+        if not 1 <= int(cap) <= min(N, ops.LIST_FILTER_MAX_C):
+            raise ValueError(f"Sae.encode: cap must be in [1, {min(N, ops.LIST_FILTER_MAX_C)}], got {cap}")
+        cap = int(cap)
+        table = None
+        if threshold is None:
+            theta = self._learned_threshold()
+        elif isinstance(threshold, Tensor):
+            if threshold.numel() == 1:
+                theta = threshold.detach().to(dev, torch.float32).reshape(())
+            elif threshold.dim() == 1 and threshold.shape[0] == N:
+                table = threshold.detach().to(dev, torch.float32).contiguous()
+                theta = table.min()                      # the floor of the saturation count; stays on the device
+            else:
+                raise ValueError(f"Sae.encode: threshold must be a number, a one-element tensor or a table [{N}], got "
+                                 f"{tuple(threshold.shape)}")
+        else:
+            theta = torch.full((), float(threshold), dtype=torch.float32, device=dev)
+        if differentiable is None:
+            params = self.encoder.weight.requires_grad or self.encoder.bias.requires_grad or self.b_dec.requires_grad
+            differentiable = x.requires_grad or (self.training and params and not (exact or certified or return_status))
+        want_grad = torch.is_grad_enabled() and differentiable
+        if want_grad and table is not None:
+            raise NotImplementedError("Sae.encode: autograd through a per-feature threshold table is not built (the kept "
+                                      "entries move inside their row): call it under torch.no_grad(), or use a scalar threshold")
+        if want_grad and (exact or certified or return_status):
+            raise RuntimeError("Sae.encode(exact / certified / return_status) are inference switches: call them under "
+                               "torch.no_grad()")
+        status = None
+        if want_grad:
+            (acts, idx), = ops.sparse_encode(x, self.encoder.weight, self.encoder.bias, self.b_dec, cap,
+                                             prepared=self._prepared_weights())
+            with torch.no_grad():
+                kept, _, lengths, _ = ops.list_filter(acts, idx, theta)
+            # a canonical row is value-descending: the kept entries are its prefix, the indices stay, the gradient is the mask's
+            acts = torch.where(kept > 0, acts, torch.zeros((), dtype=acts.dtype, device=acts.device))
+        else:
+            with torch.no_grad():
+                acts, idx, status = ops.encode_topk(x, self.encoder.weight, self.encoder.bias, self.b_dec,
+                                                    self._prepared_weights(), cap, exact=exact, certified=certified)
+                acts, idx, lengths, _ = ops.list_filter(acts, idx, theta, table)
+        out = (EncoderOutput(acts, idx),) + ((status,) if return_status else ()) + ((lengths,) if return_lengths else ())
+        return out[0] if len(out) == 1 else out
+
     @staticmethod
     def _token_groups(x: Tensor, edits, edit_group: Optional[Tensor]) -> Tensor:
         """`edit_group` of encode -> one group id per token, shape x.shape[:-1] (device work only: nothing is read back)."""
@@ -354,6 +459,7 @@ class Sae(nn.Module):
         include/msae.h, "error-preserving interventions".  Inference only: no host synchronisation, allocations through torch
         alone (capturable in a HIP graph); with gradients enabled on x it raises RuntimeError -- the hooks' autograd path is
         `msae.features.hooks.sae_reconstruct(preserve_error=True)`."""
+        self._topk_only("intervene")
         if edits is None or not (hasattr(edits, "check") and (hasattr(edits, "offsets") or hasattr(edits, "E"))):
             raise ValueError("Sae.intervene: edits must be a msae.features.FeatureEdits or RowEdits")
         if self.W_dec is None:
@@ -397,6 +503,7 @@ class Sae(nn.Module):
         error of `decode` over an Sae with cfg.k = kappa.  `top`: the list of x (an EncoderOutput or (top_acts, top_indices))
         when the caller holds it already; None: `self.encode(x, exact=exact)`.  `chunk`: tokens per kernel call (None: one
         call); the per-token outputs do not depend on it.  Inference only; nothing is read back."""
+        self._topk_only("recon_error")
         if self.W_dec is None:
             raise ValueError("Sae.recon_error: this Sae has no decoder")
         if x.dim() < 1 or x.shape[-1] != self.d_in:
@@ -438,8 +545,18 @@ class Sae(nn.Module):
         return ReconOutput(tuple(ks), mom[..., 0].reshape(*lead, C), mom[..., 1].reshape(*lead, C),
                            mom[..., 2].reshape(*lead, C), xx.reshape(lead), tv, self.d_in)
 
-    def decode(self, top_acts: Tensor, top_indices: Tensor) -> Tensor:
+    def _topk_only(self, what: str) -> None:
+        """The paths that read a per-token top-k list are not built for a "batchtopk" Sae."""
+        if self.cfg.activation == "batchtopk":
+            raise NotImplementedError(f"Sae.{what} is not built for activation='batchtopk': it works on per-token top-k lists "
+                                      "(encode with threshold= and decode with lengths= are the BatchTopK inference path)")
+
+    def decode(self, top_acts: Tensor, top_indices: Tensor, lengths: Optional[Tensor] = None) -> Tensor:
+        """`lengths` (int32, one per row: what a threshold encode or ops.batch_select returned): only the kept prefix of every
+        row is read (ops.decode(lengths=)); the same bits as without it on such a list, at the cost of sum(lengths)."""
         assert self.W_dec is not None, "Decoder weight was not initialized."
+        if lengths is not None:
+            return ops.decode(top_indices, top_acts.to(self.dtype), self.W_dec, self.b_dec, lengths)
         # the module-level seam, as the reference (sae.py:190): `decoder_impl(top_indices, top_acts, W_dec.mT) + b_dec`.  The
         # default implementation is called with the bias inside the kernel (same bits: the kernel adds b_dec behind the
         # chain; one pass over the [A, d] output instead of two); a rebound decoder_impl gets the reference's call.
@@ -589,14 +706,22 @@ class Sae(nn.Module):
                 scale = min(num_dead / k_aux, 1.0)
                 k_aux = min(k_aux, num_dead)
         k_multi = 4 * self.cfg.k if self.cfg.multi_topk else 0
+        batch = self.cfg.activation == "batchtopk"
+        k_main = self.cfg.cap                     # cfg.k, or the list width C of the batch-level selection
         if auxk_path == "subset":
-            sel = ops.sparse_encode(x, self.encoder.weight, self.encoder.bias, self.b_dec, self.cfg.k,
+            sel = ops.sparse_encode(x, self.encoder.weight, self.encoder.bias, self.b_dec, k_main,
                                     dead_mask, k_aux, k_multi, auxk_path="subset", dead_list=dead_list)
         else:
-            sel = ops.sparse_encode(x, self.encoder.weight, self.encoder.bias, self.b_dec, self.cfg.k,
+            sel = ops.sparse_encode(x, self.encoder.weight, self.encoder.bias, self.b_dec, k_main,
                                     dead_mask, k_aux, k_multi)
         top_acts, top_indices = sel[0]
-        sae_out = self.decode(top_acts, top_indices)
+        if batch:
+            # BatchTopK: the T*k largest entries of the batch's top-C lists, and a decode that reads
+            # the kept prefix of every row only; theta, the lengths and the saturation count stay on the device
+            top_acts, lengths, theta, n_saturated = ops.batch_select(top_acts, top_indices, self.cfg.k)
+            sae_out = self.decode(top_acts, top_indices, lengths)
+        else:
+            sae_out = self.decode(top_acts, top_indices)
         # the loss terms in as few T x d sweeps as autograd allows (each elementwise torch op on [T, d] is a 45-us kernel at
         # C2; the reference's expression is ~10 of them forward + backward): squared error and its gradient through _SqErr,
         # the total variance as one column-variance kernel.  An input that itself requires grad keeps the plain expressions.
@@ -617,7 +742,7 @@ class Sae(nn.Module):
             e_t = e if not lean else (sae_out - x)
             auxk_loss = scale * (e_hat - e_t).pow(2).sum() / total_variance
         else:
-            auxk_loss = sae_out.new_tensor(0.0)
+            auxk_loss = sae_out.new_zeros(())           # (built on the device: no host-to-device copy)
 
         fvu = sq_err / total_variance
         if k_multi > 0:
@@ -625,7 +750,10 @@ class Sae(nn.Module):
             sae_out = self.decode(top_acts, top_indices)
             multi_topk_fvu = (_SqErr.apply(sae_out, x)[0] if lean else (sae_out - x).pow(2).sum()) / total_variance
         else:
-            multi_topk_fvu = sae_out.new_tensor(0.0)
+            multi_topk_fvu = sae_out.new_zeros(())
+        if batch:
+            return BatchForwardOutput(sae_out, top_acts, top_indices, fvu, auxk_loss, multi_topk_fvu, lengths=lengths,
+                                      theta=theta, n_saturated=n_saturated)
         return ForwardOutput(sae_out, top_acts, top_indices, fvu, auxk_loss, multi_topk_fvu)
 
     # ---- decoder-norm utilities (sae.py:249-271) ------------------------------------------------------

@@ -73,7 +73,8 @@ class SaeTrainStep:
     def __init__(self, sae: Sae, lr: Optional[float] = None, auxk_alpha: float = 0.0,
                  dead_feature_threshold: int = 10_000_000, group=None, grad_acc_steps: int = 1,
                  micro_acc_steps: int = 1, lr_warmup_steps: int = 0, total_steps: Optional[int] = None,
-                 init_b_dec: bool = False, fuse_next_step: bool = True, optim_bits: int = 32, auxk_path: str = "dense"):
+                 init_b_dec: bool = False, fuse_next_step: bool = True, optim_bits: int = 32, auxk_path: str = "dense",
+                 threshold_lr: float = 0.01):
         from .parallel import _unpinned
 
         group = _unpinned(group)          # (the default group is addressed as None: nothing here keeps it alive past its destroy)
@@ -94,6 +95,10 @@ class SaeTrainStep:
         if auxk_path not in ops.AUXK_PATHS:
             raise ValueError(f"auxk_path must be one of {ops.AUXK_PATHS}, got {auxk_path!r}")
         self.auxk_path = auxk_path        # how Sae.forward builds the AuxK selection ("subset": no dense [T, N] latents)
+        # "batchtopk" (DESIGN.md section 7n): every micro-chunk's theta is folded into sae.threshold at this rate (a
+        # hyper-parameter: the running average inference will encode with), on the device
+        self.batch_topk = sae.cfg.activation == "batchtopk"
+        self.threshold_lr = threshold_lr
         # per parameter: an ops.Adam8State where the 8-bit format takes the shape, else None and float32 moments
         self.state8 = [ops.adam8_state(p) if optim_bits == 8 else None for p in self.params]
         self.exp_avg = [torch.zeros_like(p) if s8 is None else None for p, s8 in zip(self.params, self.state8)]   # torch.optim.Adam state
@@ -177,6 +182,36 @@ class SaeTrainStep:
             dist.all_reduce(t, op=op or dist.ReduceOp.SUM, group=self.group)
         return t
 
+    # ---- BatchTopK bookkeeping (device work only: nothing is read back) -----------------------------------------
+    @torch.no_grad()
+    def _fold_threshold(self, theta: Tensor) -> Tensor:
+        """This chunk's theta, averaged over the ranks (each takes it from its local batch, as data-parallel BatchTopK does),
+        into sae.threshold: the first value is copied, after that thr += lr * (theta - thr); a non-finite theta (an empty
+        or overflowed batch) is skipped.  Returns the averaged theta."""
+        th = theta.detach().to(torch.float32).clone()
+        if self.world > 1:
+            self._all_reduce(th).div_(self.world)
+        thr = self.sae.threshold
+        moved = torch.where(thr < 0, th, thr + self.threshold_lr * (th - thr))
+        thr.copy_(torch.where(torch.isfinite(th), moved, thr))
+        return th
+
+    @torch.no_grad()
+    def _note_fired(self, out) -> None:
+        """did_fire of one chunk.  TopK: every listed feature, as the reference.  BatchTopK: a dropped slot still names a
+        feature, so only the kept prefix of every row counts -- an integer index_add_ of the keep mask (repeated indices add
+        up in integers: deterministic, and no host read)."""
+        idx = out.latent_indices
+        lengths = getattr(out, "lengths", None)
+        if lengths is None:
+            self._did_fire[idx.flatten()] = True
+            return
+        C = idx.shape[-1]
+        keep = torch.arange(C, device=idx.device) < lengths.reshape(-1, 1)
+        hits = torch.zeros(self._did_fire.shape[0], dtype=torch.int32, device=idx.device)
+        hits.index_add_(0, idx.reshape(-1).long(), keep.reshape(-1).to(torch.int32))
+        self._did_fire |= hits > 0
+
     # ---- compute (overridden with torch-CPU restatements by the gloo tests) ----------------------------------
     def _forward(self, hiddens: Tensor, dead_mask: Optional[Tensor]):
         return self.sae(hiddens, dead_mask, auxk_path=self.auxk_path)
@@ -235,7 +270,9 @@ class SaeTrainStep:
     def step(self, hiddens: Tensor) -> dict:
         """One global step (one batch of activations of this rank).  Returns device tensors (no host
         synchronisation): {"fvu", "auxk_loss", "multi_topk_fvu"} averaged over micro-batches and ranks,
-        "stepped": whether the optimizer moved (every `grad_acc_steps`-th call)."""
+        "stepped": whether the optimizer moved (every `grad_acc_steps`-th call).  A "batchtopk" Sae adds "theta" (the mean of
+        the micro-chunks' rank-averaged thresholds) and "n_saturated" (this rank's rows that kept all C slots), device tensors
+        as well."""
         sae = self.sae
         if self.global_step == 0 and self.init_b_dec:            # trainer.py:325-332
             pts = hiddens.float()
@@ -250,6 +287,7 @@ class SaeTrainStep:
         acc_steps = self.grad_acc_steps * self.micro_acc_steps
         stats = torch.zeros(3, dtype=torch.float32, device=hiddens.device)
         chunks = hiddens.chunk(self.micro_acc_steps)
+        theta_sum = n_saturated = 0
         for ci, chunk in enumerate(chunks):
             self._reduce_now = self.world > 1 and ci == len(chunks) - 1
             self._chunk_tokens = chunk.shape[0]
@@ -261,7 +299,10 @@ class SaeTrainStep:
             else:
                 loss.div(acc_steps).backward()
             stats += torch.stack([out.fvu.detach(), out.auxk_loss.detach(), out.multi_topk_fvu.detach()])
-            self._did_fire[out.latent_indices.flatten()] = True
+            self._note_fired(out)
+            if self.batch_topk:
+                theta_sum = theta_sum + self._fold_threshold(out.theta)
+                n_saturated = n_saturated + out.n_saturated
         self._reduce_now = False
         if self.world > 1:
             fired = self._did_fire.to(torch.int32)
@@ -285,4 +326,7 @@ class SaeTrainStep:
         stats /= len(chunks)
         if self.world > 1:
             self._all_reduce(stats).div_(self.world)
-        return {"fvu": stats[0], "auxk_loss": stats[1], "multi_topk_fvu": stats[2], "stepped": stepped}
+        res = {"fvu": stats[0], "auxk_loss": stats[1], "multi_topk_fvu": stats[2], "stepped": stepped}
+        if self.batch_topk:
+            res.update(theta=theta_sum / len(chunks), n_saturated=n_saturated)
+        return res
