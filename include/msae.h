@@ -51,6 +51,8 @@
  *   msae_recon_curve_f32     reconstruction error at several sparsities in one pass (sae.py:190-202 per checkpoint)
  *   msae_batch_kth_f32, msae_list_filter_f32, msae_decode_prefix_f32   BatchTopK on top-C lists: the batch threshold, the
  *                            threshold filter, the decode with a row length (no reference counterpart)
+ *   msae_nested_decode_f32, msae_nested_combine_f32, msae_decode_bwd_*_grouped_f32   Matryoshka prefixes: every prefix's
+ *                            reconstruction error in one decode pass, and its backward (no reference counterpart)
  *
  * Numerics contract: all dot products are ascending-k f32 fused
  * multiply-add chains (v_mfma_f32_32x32x2_f32 / v_fma_f32), bit-identical to oracle/sae_oracle.c.
@@ -860,6 +862,60 @@ int msae_decode_prefix_f32(const int32_t *idx, const float *acts, const int32_t 
                            const float *b_dec, int A, int k, int N, int d, float *out, int32_t *status, void *stream);
 int msae_decode_prefix_i64_f32(const int64_t *idx, const float *acts, const int32_t *len, const float *W_dec,
                                const float *b_dec, int A, int k, int N, int d, float *out, int32_t *status, void *stream);
+
+/* ---- nested decode: Matryoshka prefixes of the dictionary (ops.nested_reconstruct) ----------------
+ * A Matryoshka SAE asks the first m_0 features to reconstruct x alone, the first m_1 too, ... up to m_{G-1} = N, under ONE
+ * sparse selection over all N features.  Forward: every prefix's reconstruction error from one pass over a token's decoder
+ * rows.  Backward: the per-prefix loss gradients folded into G planes, and the two decoder backward kernels reading the
+ * plane of each feature's group.
+ *   Bounds and groups.  m[0] < m[1] < ... < m[G-1] = N, 1 <= G <= MSAE_NESTED_MAX_GROUPS, m[0] >= 1.  group(n) = the number
+ *     of g with m[g] <= n: 0 .. G-1 for 0 <= n < N.
+ *   Live entries.  Token t has the list (v_j, i_j), j < k; with `lengths`, j < clamp(len[t], 0, k) and the slots behind
+ *     are not read.  An entry is live iff 0 <= i_j < N and v_j != 0.  An out-of-range index ORs 1 into `status`, as
+ *     msae_decode_f32 does, and the entry is dead.
+ *   Group-major order.  The live entries ordered by (group(i_j), j): a stable partition of the list by group.
+ *   The chain, per column c.  acc = +0; for the live entries in group-major order acc = fmaf(v, W_dec[i][c], acc); after the
+ *     last entry of group g -- at once if the group has none -- r_g[c] = acc + b_dec[c] and e_g[c] = r_g[c] - (float)x[t][c].
+ *   Outputs.  out[t] = r_{G-1}.  E[g][t][c] = e_g[c], f32 [G][T][d]; E may be NULL, then nothing is written.
+ *     sq[t][g] = sum_c e_g[c]^2 in msae_recon_curve_f32's order of a moment (step 4 there): lane fmaf chain over its
+ *     ascending columns from +0, xor butterfly over the wave, ((w0 + w1) + w2) + w3, slabs in ascending order.  No
+ *     floating-point atomics: token t's outputs are the same bits alone or in any batch.
+ *   Consequences.  G = 1: out is bit-identical to msae_decode_f32 on the same list.  r_g is bit-identical to msae_decode_f32
+ *     on the group-major list with the entries of the groups above g set to 0.
+ * msae_nested_decode_f32 / _i64_f32: x [T][d] (MSAE_F32 / MSAE_BF16 / MSAE_F16), vals / idx [T][ld >= k], lengths int32 [T]
+ *   or NULL, bounds a HOST int32 [G] (copied into the launch arguments), W_dec f32 [N][d], b_dec f32 [d], out f32 [T][d],
+ *   E f32 [G][T][d] or NULL, sq f32 [T][G], status int32 [1] or NULL.  One workgroup of 256 threads per token; the live
+ *   entries in LDS (9 k bytes), partitioned by one workgroup scan per group; slabs of 1024 columns (256, one column per lane,
+ *   when d % 4 != 0 or a pointer is not aligned to 4 elements).  MSAE_EINVAL before any launch: a null pointer (lengths, E,
+ *   status may be null), k < 1, k > 4096, ld < k, T < 0, N < 1, d < 1, G outside [1, MSAE_NESTED_MAX_GROUPS], bounds not
+ *   strictly ascending, below 1 or not ending at N, a bad dtype code.  T == 0 returns 0.  No workspace, never synchronises.
+ * msae_nested_combine_f32: elementwise and in place on E (16-byte accesses when T*d % 4 == 0 and the pointers are aligned --
+ *   the planes lie T*d floats apart --, one element per lane otherwise; the same bits either way).  s = grad_full[t][c] (+0 when grad_full is NULL); for g = G-1
+ *   down to 0: s = fmaf(coef[g], E[g][t][c], s), S[g][t][c] = s (stored over E[g]).  coef: a DEVICE f32 [G].  With
+ *   coef[g] = 2 dL/d(sum_t sq[t][g]) and grad_full = dL/d(out), S[g] is the gradient that reaches r_g and everything the
+ *   chain added before it: the gradient of every decoder row and activation of group g.
+ * msae_decode_bwd_acts_grouped_f32 / msae_decode_bwd_wdec_grouped_f32: msae_decode_bwd_acts_f32 / msae_decode_bwd_wdec_f32
+ *   -- the same kernels, chains, reductions, pair order, row_sumsq / row_act_sum outputs and workspace
+ *   (msae_decode_bwd_wdec_ws_bytes(A, k, N)) -- with the gradient row of a pair or feature row taken from plane group(i) of
+ *   grad_planes f32 [G][A][d]:
+ *     g_acts[t][j] = S[group(i_j)][t] . W_dec[i_j]                          (0 and flagged for an out-of-range index)
+ *     g_W[n]       = sum over the pairs with i = n and v != 0, in ascending pair order, of v * S[group(n)][t]
+ *   bounds: a DEVICE int32 [G] (the caller passes N = bounds[G-1]; a group count past G-1 is clamped, so no bounds array
+ *   can index outside the planes).  The choice of plane is uniform over a wave. */
+#define MSAE_NESTED_MAX_GROUPS 8
+int msae_nested_decode_f32(const void *x, int x_dtype, const float *vals, const int32_t *idx, int ld, const int32_t *lengths,
+                           const int32_t *bounds, int G, const float *W_dec, const float *b_dec, int T, int k, int N, int d,
+                           float *out, float *E, float *sq, int32_t *status, void *stream);
+int msae_nested_decode_i64_f32(const void *x, int x_dtype, const float *vals, const int64_t *idx, int ld,
+                               const int32_t *lengths, const int32_t *bounds, int G, const float *W_dec, const float *b_dec,
+                               int T, int k, int N, int d, float *out, float *E, float *sq, int32_t *status, void *stream);
+int msae_nested_combine_f32(float *E, const float *coef, const float *grad_full, int T, int d, int G, void *stream);
+int msae_decode_bwd_acts_grouped_f32(const int32_t *idx, const float *grad_planes, const int32_t *bounds, int G,
+                                     const float *W_dec, int A, int k, int N, int d, float *g_acts, int32_t *status,
+                                     void *stream);
+int msae_decode_bwd_wdec_grouped_f32(const int32_t *idx, const float *acts, const float *grad_planes, const int32_t *bounds,
+                                     int G, int A, int k, int N, int d, float *g_W_dec, float *row_sumsq, float *row_act_sum,
+                                     int32_t *status, void *ws, size_t ws_bytes, void *stream);
 
 /* ---- merge of per-shard results (feature-sharded encode; no reference counterpart) ----
  * gathered: int32 [G][2][T][kl], the all-gather of each rank's packed block [2][T][kl]

@@ -106,12 +106,22 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_fwd_scalar_kernel(
   out[(size_t)a * d + col] = acc;
 }
 
+// The "grouped" form of the two backward kernels (nested decode, include/msae.h): grad_out is G planes [G][A][d], `plane`
+// floats apart, and feature n reads plane group(n) = the number of g with bounds[g] <= n (device bounds, ascending, the last
+// one N; clamped to G - 1 so that no bounds array can index past the planes).  Wave-uniform: a wave serves one feature.
+__device__ __forceinline__ int bwd_group(const int32_t *__restrict__ bounds, int G, int n) {
+  int g = 0;
+  for (int i = 0; i < G; ++i) g += bounds[i] <= n ? 1 : 0;
+  return g < G ? g : G - 1;
+}
+
 // g_acts[a][j] = grad_out[a][:] . W_dec[idx[a][j]][:]      (kernels.py:341-400)
 // one wave per (a, j); lanes stride the row in float4s, then a wave reduction.
+template <bool GROUPED>
 __global__ __launch_bounds__(256) void decode_bwd_acts_kernel(
     const int32_t *__restrict__ idx, const float *__restrict__ grad_out,
     const float *__restrict__ W_dec, int A, int k, int N, int d, float *__restrict__ g_acts,
-    int32_t *__restrict__ status) {
+    int32_t *__restrict__ status, const int32_t *__restrict__ bounds, int G, size_t plane) {
   const int lane = threadIdx.x & 63;
   const long pair = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (pair >= (long)A * k) return;
@@ -125,6 +135,7 @@ __global__ __launch_bounds__(256) void decode_bwd_acts_kernel(
     return;
   }
   const float *g = grad_out + (size_t)a * d;
+  if constexpr (GROUPED) g += (size_t)bwd_group(bounds, G, i) * plane;
   const float *w = W_dec + (size_t)i * d;
   float acc = 0.f;
   if ((d & 3) == 0) {
@@ -250,16 +261,19 @@ __device__ __forceinline__ void wave_sort_asc(int *a, int L, int lane, Sync &&sy
 constexpr int WGRAD_LDS_SEG = 1024;   // pair ids a wave can sort in its LDS slice
 
 // one wave per feature row n; lane owns float4 columns lane, lane+64, ... ; d % 4 == 0
+template <bool GROUPED>
 __global__ __launch_bounds__(256) void wgrad_accum_kernel(const float *__restrict__ acts,
                                                           const float *__restrict__ grad_out,
                                                           const int *__restrict__ offsets,
                                                           int *__restrict__ perm, int k, int N, int d,
                                                           float *__restrict__ g_W, float *__restrict__ rowsq,
-                                                          float *__restrict__ rowsum) {
+                                                          float *__restrict__ rowsum,
+                                                          const int32_t *__restrict__ bounds, int G, size_t plane) {
   __shared__ int s_seg[4][WGRAD_LDS_SEG];
   const int lane = threadIdx.x & 63;
   const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (n >= N) return;
+  if constexpr (GROUPED) grad_out += (size_t)bwd_group(bounds, G, n) * plane;      // this row's gradient plane
   const int beg = offsets[n], end = offsets[n + 1];
   const int L = end - beg;
   // deterministic summation order: the segment (filled through an atomic cursor, i.e. in any order) is sorted
@@ -404,16 +418,35 @@ extern "C" int msae_decode_i64_f32(const int64_t *idx, const float *acts, const 
   return decode_launch<int64_t>(idx, acts, W_dec, b_dec, A, k, N, d, out, status, stream);
 }
 
+// bounds == nullptr: the plain form
+static int decode_bwd_acts_launch(const int32_t *idx, const float *grad_out, const float *W_dec, int A, int k, int N, int d,
+                                  float *g_acts, int32_t *status, const int32_t *bounds, int G, void *stream) {
+  if (A < 0 || k <= 0 || N <= 0 || d <= 0) return MSAE_EINVAL;
+  if (A == 0) return 0;
+  const size_t plane = (size_t)A * d;
+  if (d % 4 == 0 && (!msae_aligned(W_dec, 16) || !msae_aligned(grad_out, 16) || (bounds && plane % 4 != 0))) return MSAE_EALIGN;
+  const long pairs = (long)A * k;
+  const dim3 grid((unsigned)((pairs + 3) / 4));
+  if (bounds)
+    hipLaunchKernelGGL(decode_bwd_acts_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, idx, grad_out, W_dec, A, k, N,
+                       d, g_acts, status, bounds, G, plane);
+  else
+    hipLaunchKernelGGL(decode_bwd_acts_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, idx, grad_out, W_dec, A, k, N,
+                       d, g_acts, status, nullptr, 0, (size_t)0);
+  return msae_launch_status();
+}
+
 extern "C" int msae_decode_bwd_acts_f32(const int32_t *idx, const float *grad_out,
                                         const float *W_dec, int A, int k, int N, int d,
                                         float *g_acts, int32_t *status, void *stream) {
-  if (A < 0 || k <= 0 || N <= 0 || d <= 0) return MSAE_EINVAL;
-  if (A == 0) return 0;
-  if (d % 4 == 0 && (!msae_aligned(W_dec, 16) || !msae_aligned(grad_out, 16))) return MSAE_EALIGN;
-  const long pairs = (long)A * k;
-  hipLaunchKernelGGL(decode_bwd_acts_kernel, dim3((unsigned)((pairs + 3) / 4)), dim3(256), 0,
-                     (hipStream_t)stream, idx, grad_out, W_dec, A, k, N, d, g_acts, status);
-  return msae_launch_status();
+  return decode_bwd_acts_launch(idx, grad_out, W_dec, A, k, N, d, g_acts, status, nullptr, 0, stream);
+}
+
+extern "C" int msae_decode_bwd_acts_grouped_f32(const int32_t *idx, const float *grad_planes, const int32_t *bounds, int G,
+                                                const float *W_dec, int A, int k, int N, int d, float *g_acts,
+                                                int32_t *status, void *stream) {
+  if (!bounds || G < 1 || G > MSAE_NESTED_MAX_GROUPS) return MSAE_EINVAL;
+  return decode_bwd_acts_launch(idx, grad_planes, W_dec, A, k, N, d, g_acts, status, bounds, G, stream);
 }
 
 extern "C" size_t msae_decode_bwd_wdec_ws_bytes(int A, int k, int N) {
@@ -421,10 +454,10 @@ extern "C" size_t msae_decode_bwd_wdec_ws_bytes(int A, int k, int N) {
   return msae_align_up((size_t)(N + 1) * 4, 256) * 3 + msae_align_up((size_t)A * k * 4, 256);
 }
 
-extern "C" int msae_decode_bwd_wdec_f32(const int32_t *idx, const float *acts,
-                                        const float *grad_out, int A, int k, int N, int d,
-                                        float *g_W_dec, float *row_sumsq, float *row_act_sum, int32_t *status, void *ws,
-                                        size_t ws_bytes, void *stream) {
+// bounds == nullptr: the plain form
+static int decode_bwd_wdec_launch(const int32_t *idx, const float *acts, const float *grad_out, int A, int k, int N, int d,
+                                  float *g_W_dec, float *row_sumsq, float *row_act_sum, int32_t *status, void *ws,
+                                  size_t ws_bytes, const int32_t *bounds, int G, void *stream) {
   if (A < 0 || k <= 0 || N <= 0 || d <= 0 || d % 4 != 0) return MSAE_EINVAL;
   if (!ws || ws_bytes < msae_decode_bwd_wdec_ws_bytes(A, k, N)) return MSAE_EWS;
   if (!msae_aligned(grad_out, 16) || !msae_aligned(g_W_dec, 16) || !msae_aligned(ws, 256)) return MSAE_EALIGN;
@@ -444,7 +477,28 @@ extern "C" int msae_decode_bwd_wdec_f32(const int32_t *idx, const float *acts,
   } else {
     hipLaunchKernelGGL(wgrad_zero_kernel, dim3(256), dim3(256), 0, s, offsets, N + 1);
   }
-  hipLaunchKernelGGL(wgrad_accum_kernel, dim3((N + 3) / 4), dim3(256), 0, s, acts, grad_out, offsets, perm,
-                     k, N, d, g_W_dec, row_sumsq, row_act_sum);
+  if (bounds)
+    hipLaunchKernelGGL(wgrad_accum_kernel<true>, dim3((N + 3) / 4), dim3(256), 0, s, acts, grad_out, offsets, perm,
+                       k, N, d, g_W_dec, row_sumsq, row_act_sum, bounds, G, (size_t)A * d);
+  else
+    hipLaunchKernelGGL(wgrad_accum_kernel<false>, dim3((N + 3) / 4), dim3(256), 0, s, acts, grad_out, offsets, perm,
+                       k, N, d, g_W_dec, row_sumsq, row_act_sum, nullptr, 0, (size_t)0);
   return msae_launch_status();
+}
+
+extern "C" int msae_decode_bwd_wdec_f32(const int32_t *idx, const float *acts,
+                                        const float *grad_out, int A, int k, int N, int d,
+                                        float *g_W_dec, float *row_sumsq, float *row_act_sum, int32_t *status, void *ws,
+                                        size_t ws_bytes, void *stream) {
+  return decode_bwd_wdec_launch(idx, acts, grad_out, A, k, N, d, g_W_dec, row_sumsq, row_act_sum, status, ws, ws_bytes,
+                                nullptr, 0, stream);
+}
+
+extern "C" int msae_decode_bwd_wdec_grouped_f32(const int32_t *idx, const float *acts, const float *grad_planes,
+                                                const int32_t *bounds, int G, int A, int k, int N, int d, float *g_W_dec,
+                                                float *row_sumsq, float *row_act_sum, int32_t *status, void *ws,
+                                                size_t ws_bytes, void *stream) {
+  if (!bounds || G < 1 || G > MSAE_NESTED_MAX_GROUPS) return MSAE_EINVAL;
+  return decode_bwd_wdec_launch(idx, acts, grad_planes, A, k, N, d, g_W_dec, row_sumsq, row_act_sum, status, ws, ws_bytes,
+                                bounds, G, stream);
 }

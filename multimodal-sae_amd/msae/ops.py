@@ -1451,6 +1451,284 @@ def _decode_backward(ctx, grad_out):
 decode.register_autograd(_decode_backward, setup_context=_decode_setup)
 
 
+# ---- nested decode: Matryoshka prefixes (csrc/nested_decode.hip) ------------------------------------------
+NESTED_MAX_GROUPS = 8
+NESTED_MAX_K = 4096
+
+
+def nested_bounds(bounds, N: int, what: str = "nested_decode") -> tuple:
+    """The prefix sizes as validated Python ints: 1 to 8 of them, at least 1, strictly ascending, the last one N."""
+    if isinstance(bounds, Tensor):
+        bounds = bounds.detach().cpu().reshape(-1).tolist()
+    try:
+        out = tuple(int(b) for b in bounds)
+        same = all(float(b) == float(o) for b, o in zip(bounds, out))
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: bounds must be a sequence of integers, got {bounds!r}") from None
+    if not same:
+        raise ValueError(f"{what}: bounds must be integers, got {list(bounds)!r}")
+    if not 1 <= len(out) <= NESTED_MAX_GROUPS:
+        raise ValueError(f"{what}: between 1 and {NESTED_MAX_GROUPS} prefix sizes, got {len(out)}")
+    if out[0] < 1 or any(a >= b for a, b in zip(out, out[1:])):
+        raise ValueError(f"{what}: prefix sizes must be at least 1 and strictly ascending, got {list(out)}")
+    if out[-1] != N:
+        raise ValueError(f"{what}: the last prefix size must be the number of latents {N}, got {out[-1]}")
+    return out
+
+
+def _nested_bounds_dev(bounds: tuple, dev: torch.device) -> Tensor:
+    """The bounds as an int32 tensor on `dev`: a pinned staging copy and an asynchronous transfer on the current stream (no
+    host synchronisation; the caching host allocator keeps the staging block until the copy has run)."""
+    host = torch.tensor(bounds, dtype=torch.int32)
+    return host.pin_memory().to(dev, non_blocking=True) if dev.type == "cuda" else host
+
+
+def _nested_check(what: str, x: Tensor, top_acts: Tensor, top_indices: Tensor, W_dec: Tensor, b_dec: Tensor, bounds,
+                  lengths: Optional[Tensor]) -> tuple:
+    if x.dim() < 1 or W_dec.dim() != 2 or x.shape[-1] != W_dec.shape[1] or x.shape[-1] < 1:
+        raise ValueError(f"{what}: x [..., d] and W_dec [N, d] must share d, got {tuple(x.shape)} and {tuple(W_dec.shape)}")
+    if b_dec is None or b_dec.dim() != 1 or b_dec.shape[0] != W_dec.shape[1]:
+        raise ValueError(f"{what}: b_dec must be [d] = [{W_dec.shape[1]}], got {None if b_dec is None else tuple(b_dec.shape)}")
+    if x.dtype not in _hip.DTYPE_CODE:
+        raise ValueError(f"{what}: x must be float32, bfloat16 or float16, got {x.dtype}")
+    if top_acts.shape != top_indices.shape or top_acts.dim() < 1:
+        raise ValueError(f"{what}: top_acts and top_indices must share one shape [..., k], got {tuple(top_acts.shape)} and "
+                         f"{tuple(top_indices.shape)}")
+    k = top_acts.shape[-1]
+    if not 1 <= k <= NESTED_MAX_K:
+        raise ValueError(f"{what}: k must be in [1, {NESTED_MAX_K}], got {k}")
+    T = x.numel() // x.shape[-1]
+    if top_acts.numel() != T * k or (top_acts.dim() != 2 and tuple(top_acts.shape[:-1]) != tuple(x.shape[:-1])):
+        raise ValueError(f"{what}: the list must hold one row per token of x {tuple(x.shape)}, got {tuple(top_acts.shape)}")
+    if top_indices.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{what}: top_indices must be int32 or int64, got {top_indices.dtype}")
+    if top_acts.dtype != torch.float32:
+        raise ValueError(f"{what}: the list's values must be float32, got {top_acts.dtype}")
+    if lengths is not None and lengths.numel() != T:
+        raise ValueError(f"{what}: lengths must hold one entry per token ({T}), got {tuple(lengths.shape)}")
+    devs = {t.device for t in (x, top_acts, top_indices, W_dec, b_dec) + (() if lengths is None else (lengths,))}
+    if len(devs) != 1:
+        raise ValueError(f"{what}: all tensors must be on one device, got {sorted(str(d) for d in devs)}")
+    return nested_bounds(bounds, W_dec.shape[0], what)
+
+
+def nested_group_major(top_acts: Tensor, top_indices: Tensor, bounds: tuple, lengths: Optional[Tensor] = None):
+    """The group-major order of include/msae.h ("nested decode") in plain torch -> (vals [T, k], idx [T, k] int64,
+    group [T, k] int64, order [T, k]): each row stably sorted by group(index); an entry behind the row's length or with an
+    index outside [0, N) comes last with value 0, index 0 and group G.  `vals` is a differentiable function of top_acts."""
+    k = top_acts.shape[-1]
+    N, G = bounds[-1], len(bounds)
+    v, i = top_acts.reshape(-1, k), top_indices.detach().reshape(-1, k).long()
+    ok = (i >= 0) & (i < N)
+    if lengths is not None:
+        ok = ok & (torch.arange(k, device=v.device) < lengths.detach().reshape(-1, 1).clamp(0, k))
+    edges = torch.tensor(bounds, dtype=torch.int64) if not v.is_cuda else _nested_bounds_dev(bounds, v.device).long()
+    grp = torch.where(ok, torch.bucketize(i, edges, right=True), torch.full_like(i, G))
+    order = torch.sort(grp, dim=1, stable=True).indices
+    v = torch.where(ok, v, torch.zeros((), dtype=v.dtype, device=v.device))
+    i = torch.where(ok, i, torch.zeros_like(i))
+    return torch.gather(v, 1, order), torch.gather(i, 1, order), torch.gather(grp, 1, order), order
+
+
+def nested_composed(x: Tensor, top_acts: Tensor, top_indices: Tensor, W_dec: Tensor, b_dec: Tensor, bounds: tuple,
+                    lengths: Optional[Tensor] = None):
+    """The nested decode composed of existing differentiable pieces -> (out [T, d], sq [T, G], [e_0 .. e_{G-1}]): the stable
+    sort of the group key, then one masked decode of the reordered list per prefix (ops.decode on a HIP device -- r_g then
+    has the fused kernel's bits --, plain torch on the host) and one squared-error pass each.  Ordinary autograd reaches
+    top_acts, W_dec, b_dec and x.  The fallback of ops.nested_reconstruct and the second opinion of its tests."""
+    d = W_dec.shape[1]
+    xf = x.reshape(-1, d).to(torch.float32)
+    v, i, grp, _ = nested_group_major(top_acts, top_indices, bounds, lengths)
+    zero = torch.zeros((), dtype=v.dtype, device=v.device)
+    rs, es, sqs = [], [], []
+    for g in range(len(bounds)):
+        vg = torch.where(grp <= g, v, zero)
+        if v.is_cuda:
+            r = decode(i, vg, W_dec, b_dec)
+        else:
+            r = (vg[..., None] * W_dec.to(torch.float32)[i]).sum(-2) + b_dec.to(torch.float32)
+        e = r - xf
+        rs.append(r)
+        es.append(e)
+        sqs.append((e * e).sum(-1))
+    return rs[-1], torch.stack(sqs, 1), es
+
+
+def _nested_decode_device(x: Tensor, top_acts: Tensor, top_indices: Tensor, W_dec: Tensor, b_dec: Tensor, bounds: tuple,
+                          lengths: Optional[Tensor], want_residuals: bool):
+    dev = _hip.require_device(x, top_acts, top_indices, W_dec, b_dec, lengths)
+    lib = _hip.load()
+    N, d = W_dec.shape
+    G = len(bounds)
+    k = top_acts.shape[-1]
+    xa, W, bd = x.detach().reshape(-1, d).contiguous(), _f32c(W_dec), _f32c(b_dec)
+    T = xa.shape[0]
+    out = torch.empty(T, d, dtype=torch.float32, device=dev)
+    sq = torch.empty(T, G, dtype=torch.float32, device=dev)
+    E = torch.empty(G, T, d, dtype=torch.float32, device=dev) if want_residuals else None
+    if T == 0:
+        return out, sq, E
+    v, i, ld = _list_rows(top_acts, top_indices, k)
+    ln = None if lengths is None else lengths.detach().reshape(-1).to(torch.int32).contiguous()
+    wide = i.dtype == torch.int64
+    fn, name = (lib.msae_nested_decode_i64_f32, "msae_nested_decode_i64_f32") if wide else \
+        (lib.msae_nested_decode_f32, "msae_nested_decode_f32")
+    b_host = (ctypes.c_int32 * G)(*bounds)             # read during the call: copied into the launch arguments
+    flag = _bounds_flag(dev)
+    with torch.cuda.device(dev):
+        _hip.check(fn(_hip.ptr(xa), _hip.DTYPE_CODE[xa.dtype], _hip.ptr(v), _hip.ptr(i), ld, _hip.ptr(ln), b_host, G,
+                      _hip.ptr(W), _hip.ptr(bd), T, k, N, d, _hip.ptr(out), _hip.ptr(E), _hip.ptr(sq), _hip.ptr(flag),
+                      _hip.stream_of(xa)), name)
+    _check_bounds(flag, name)
+    return out, sq, E
+
+
+def nested_decode(x: Tensor, top_acts: Tensor, top_indices: Tensor, W_dec: Tensor, b_dec: Tensor, bounds,
+                  lengths: Optional[Tensor] = None, want_residuals: bool = False):
+    """Every prefix's reconstruction error in one pass (include/msae.h, "nested decode") -> (out [T, d] f32, sq [T, G] f32,
+    E [G, T, d] f32 or None).  bounds: the prefix sizes m_0 < ... < m_{G-1} = N, G <= 8.  r_g decodes the entries of the
+    list with index < m_g (in group-major order: a stable partition of the list by group), out = r_{G-1}, E[g] = r_g - x,
+    sq[:, g] = |E[g]|^2 per token.  x [..., d] f32 / bf16 / f16; top_acts / top_indices [..., k] (k <= 4096; int32 or int64;
+    a `[:, :k]` view is read in place); lengths (int32 per token): only the first lengths[t] entries of a row are read.  On
+    a HIP device the fused kernel (bit-defined per token); on the host `nested_composed`, the same meaning in plain torch.
+    Not differentiable (ops.nested_reconstruct is); nothing is read back."""
+    bounds = _nested_check("nested_decode", x, top_acts, top_indices, W_dec, b_dec, bounds, lengths)
+    _no_grad_inputs("ops.nested_decode", x, top_acts)
+    if not x.is_cuda:
+        with torch.no_grad():
+            out, sq, es = nested_composed(x, top_acts, top_indices, W_dec, b_dec, bounds, lengths)
+        return out, sq, (torch.stack(es) if want_residuals else None)
+    return _nested_decode_device(x, top_acts, top_indices, W_dec.detach(), b_dec.detach(), bounds, lengths, want_residuals)
+
+
+def nested_combine_(E: Tensor, coef: Tensor, grad_full: Optional[Tensor] = None) -> Tensor:
+    """In place on E [G, T, d] (msae_nested_combine_f32): S[g] = coef[g] E[g] + S[g + 1] from the last plane down, with
+    S[G] = grad_full [T, d] or +0, every step one fmaf.  coef: a device f32 [G].  Returns E."""
+    G, T, d = E.shape
+    if E.dtype != torch.float32 or not E.is_contiguous() or not 1 <= G <= NESTED_MAX_GROUPS:
+        raise ValueError(f"nested_combine_: E must be a contiguous float32 [G <= {NESTED_MAX_GROUPS}, T, d], got "
+                         f"{E.dtype} {tuple(E.shape)}")
+    if coef.numel() != G or (grad_full is not None and grad_full.numel() != T * d):
+        raise ValueError("nested_combine_: coef must be [G] and grad_full [T, d]")
+    dev = _hip.require_device(E, coef, grad_full)
+    lib = _hip.load()
+    cf, gf = _f32c(coef), _f32c(grad_full)
+    with torch.cuda.device(dev):
+        _hip.check(lib.msae_nested_combine_f32(_hip.ptr(E), _hip.ptr(cf), _hip.ptr(gf), T, d, G, _hip.stream_of(E)),
+                   "msae_nested_combine_f32")
+    return E
+
+
+def nested_decode_bwd(top_indices: Tensor, top_acts: Tensor, W_dec: Tensor, planes: Tensor, bounds: tuple,
+                      need_acts: bool, need_w: bool) -> Tuple[Tensor, Tensor]:
+    """ops.decode_bwd with the gradient row taken from plane group(index) of planes [G, T, d] (include/msae.h, "nested
+    decode"): the same two kernels in their grouped form, the same workspace, and the same part in collect_wgrad_sumsq
+    and the encoder backward's row sums."""
+    dev = _hip.require_device(top_indices, top_acts, W_dec, planes)
+    lib = _hip.load()
+    idx, acts, W, g = _idx32(top_indices), _f32c(top_acts), _f32c(W_dec), _f32c(planes)
+    N, d = W.shape
+    G = len(bounds)
+    k = idx.shape[-1]
+    A = idx.numel() // k
+    if tuple(g.shape) != (G, A, d) or bounds[-1] != N:
+        raise ValueError(f"nested_decode_bwd: planes must be [G, T, d] = [{G}, {A}, {d}] and the last bound {N}, got "
+                         f"{tuple(g.shape)} and {bounds[-1]}")
+    bdev = _nested_bounds_dev(bounds, dev)
+    g_acts = torch.empty_like(acts) if need_acts else acts.new_empty(0)
+    g_w = torch.empty_like(W) if need_w else W.new_empty(0)   # the kernel writes every row
+    flag = _bounds_flag(dev)
+    with torch.cuda.device(dev):
+        st = _hip.stream_of(g)
+        if need_acts:
+            _hip.check(lib.msae_decode_bwd_acts_grouped_f32(_hip.ptr(idx), _hip.ptr(g), _hip.ptr(bdev), G, _hip.ptr(W), A, k,
+                                                            N, d, _hip.ptr(g_acts), _hip.ptr(flag), st),
+                       "msae_decode_bwd_acts_grouped_f32")
+        if need_w:
+            ws = _workspace(dev, lib.msae_decode_bwd_wdec_ws_bytes(A, k, N))
+            rowsq = torch.empty(N, dtype=torch.float32, device=dev) if _WGRAD_COLLECT is not None else None
+            rowsum = torch.empty(N, dtype=torch.float32, device=dev) if _WGRAD_ROWSUM is not None else None
+            d4 = (d + 3) // 4 * 4           # whole f32x4 columns, as decode_bwd: zero columns add exactly 0
+            g4 = g if d4 == d else torch.nn.functional.pad(g, (0, d4 - d))
+            g_w4 = g_w if d4 == d else torch.empty(N, d4, dtype=torch.float32, device=dev)
+            _hip.check(lib.msae_decode_bwd_wdec_grouped_f32(_hip.ptr(idx), _hip.ptr(acts), _hip.ptr(g4), _hip.ptr(bdev), G, A,
+                                                            k, N, d4, _hip.ptr(g_w4), _hip.ptr(rowsq), _hip.ptr(rowsum),
+                                                            _hip.ptr(flag), _hip.ptr(ws), ws.numel(), st),
+                       "msae_decode_bwd_wdec_grouped_f32")
+            if d4 != d:
+                g_w.copy_(g_w4[:, :d])
+            if rowsum is not None:
+                _WGRAD_ROWSUM.append(rowsum)
+            if rowsq is not None:
+                ent = _WGRAD_COLLECT.setdefault(W_dec.data_ptr(), [0, 0, None])
+                ent[0] += 1
+                ent[1], ent[2] = g_w.data_ptr(), rowsq
+    _check_bounds(flag, "msae_decode_bwd_grouped")
+    return g_acts, g_w
+
+
+class _NestedReconstruct(torch.autograd.Function):
+    """nested decode + per-prefix squared error as ONE node: forward msae_nested_decode_f32 (the residual planes E are
+    kept only when a gradient is needed), backward msae_nested_combine_f32 on E in place and the two grouped decoder
+    backward kernels.  x is a constant."""
+
+    @staticmethod
+    def forward(ctx, x, top_acts, top_indices, W_dec, b_dec, bounds, lengths):
+        need = any(ctx.needs_input_grad[n] for n in (1, 3, 4))
+        out, sq, E = _nested_decode_device(x, top_acts, top_indices, W_dec.detach(), b_dec.detach(), bounds, lengths, need)
+        ctx.bounds = bounds
+        ctx.set_materialize_grads(False)
+        if need:
+            acts, idx = top_acts.detach(), top_indices
+            live = None
+            if lengths is not None:
+                # as ops.decode: the slots behind a row's length reach the backward kernels as activation 0 on feature 0
+                k = acts.shape[-1]
+                live = torch.arange(k, device=acts.device) < lengths.reshape(*acts.shape[:-1], 1).clamp(0, k)
+                acts = torch.where(live, acts, torch.zeros((), dtype=acts.dtype, device=acts.device))
+                idx = torch.where(live, idx, torch.zeros_like(idx))
+            ctx.save_for_backward(E, _idx32(idx), acts, W_dec, live)
+            ctx.spent = False
+        return out, sq.sum(0)
+
+    @staticmethod
+    def backward(ctx, g_out, g_sq):
+        E, idx, acts, W_dec, live = ctx.saved_tensors
+        if ctx.spent:
+            raise RuntimeError("ops.nested_reconstruct: the backward folds the gradients into the saved residuals in place; "
+                               "a second backward through the same node is not supported")
+        ctx.spent = True
+        G = len(ctx.bounds)
+        coef = torch.zeros(G, dtype=torch.float32, device=E.device) if g_sq is None else g_sq.to(torch.float32) * 2.0
+        S = nested_combine_(E, coef, g_out)
+        need_acts, need_w = ctx.needs_input_grad[1], ctx.needs_input_grad[3]
+        g_acts = g_w = g_b = None
+        if need_acts or need_w:
+            ga, gw = nested_decode_bwd(idx, acts, W_dec, S, ctx.bounds, need_acts, need_w)
+            if need_acts:
+                g_acts = ga.to(acts.dtype)
+                if live is not None:
+                    g_acts = torch.where(live, g_acts, torch.zeros((), dtype=g_acts.dtype, device=g_acts.device))
+            g_w = gw.to(W_dec.dtype) if need_w else None
+        if ctx.needs_input_grad[4]:
+            g_b = S[0].sum(0)
+        return None, g_acts, None, g_w, g_b, None, None
+
+
+def nested_reconstruct(x: Tensor, top_acts: Tensor, top_indices: Tensor, W_dec: Tensor, b_dec: Tensor, bounds,
+                       lengths: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """The Matryoshka reconstruction as one differentiable step -> (sae_out [T, d], sq_sum [G]): sae_out decodes the whole
+    list, sq_sum[g] = sum over the tokens of |r_g - x|^2 for the reconstruction r_g from the entries with index < bounds[g]
+    (include/msae.h, "nested decode").  Gradients reach top_acts, W_dec and b_dec, from sq_sum and from sae_out.  For a HIP
+    float32 x that does not require grad this is ONE autograd node over the fused kernels; otherwise (x requires grad, another
+    dtype, the host) the composed expression `nested_composed` under ordinary autograd."""
+    bounds = _nested_check("nested_reconstruct", x, top_acts, top_indices, W_dec, b_dec, bounds, lengths)
+    if x.is_cuda and x.dtype == torch.float32 and not (torch.is_grad_enabled() and x.requires_grad):
+        return _NestedReconstruct.apply(x, top_acts, top_indices, W_dec, b_dec, bounds, lengths)
+    out, sq, _ = nested_composed(x, top_acts, top_indices, W_dec, b_dec, bounds, lengths)
+    return out, sq.sum(0)
+
+
 # ---- batch-level selection: capped BatchTopK and threshold filters on top-C lists (csrc/batch_select.hip, DESIGN.md 7n) ------
 BATCH_KTH_MAX_VALUES = 1 << 24      # msae_batch_kth_f32's envelope: T * C
 LIST_FILTER_MAX_C = 4096            # the encoder's own limit on a list's width

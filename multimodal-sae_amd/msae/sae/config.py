@@ -4,6 +4,7 @@ same keys the reference writes into cfg.json (sae.py:150-162)."""
 from __future__ import annotations
 
 import dataclasses
+import math
 from dataclasses import dataclass, field
 from typing import List, Union
 
@@ -43,8 +44,14 @@ class SaeConfig(_Serializable):
     batch_cap: int = 0
     """"batchtopk" only: the most latents one token may keep (the width C of the lists the selection works on).
     0: min(4k, 256)."""
+    matryoshka: List[int] = field(default_factory=list)
+    """Matryoshka prefix sizes m_0 < m_1 < ... < m_{G-1} = num_latents (at most 8): the first m_g latents must reconstruct
+    the input on their own, under one selection over all latents (DESIGN.md section 7o).  Empty: a plain SAE."""
+    matryoshka_weights: List[float] = field(default_factory=list)
+    """One loss weight per prefix (finite, not negative, a positive sum).  Empty: 1 / G each."""
 
     ACTIVATIONS = ("topk", "batchtopk")
+    MATRYOSHKA_MAX_GROUPS = 8
 
     def __post_init__(self):
         if self.activation not in self.ACTIVATIONS:
@@ -56,6 +63,33 @@ class SaeConfig(_Serializable):
                 raise ValueError("multi_topk is a per-token TopK loss term: it does not go with activation='batchtopk'")
             if not self.k <= self.cap <= 4096:
                 raise ValueError(f"batch_cap must lie in [k = {self.k}, 4096], got {self.cap}")
+        self.matryoshka = list(self.matryoshka or [])
+        self.matryoshka_weights = list(self.matryoshka_weights or [])
+        if self.matryoshka_weights and not self.matryoshka:
+            raise ValueError("matryoshka_weights needs the prefix sizes in matryoshka")
+        if self.matryoshka:
+            sizes = self.matryoshka
+            if any(isinstance(m, bool) or not isinstance(m, int) for m in sizes):
+                raise ValueError(f"matryoshka must hold integers, got {sizes!r}")
+            if len(sizes) > self.MATRYOSHKA_MAX_GROUPS:
+                raise ValueError(f"matryoshka takes at most {self.MATRYOSHKA_MAX_GROUPS} prefix sizes, got {len(sizes)}")
+            if sizes[0] < 1 or any(a >= b for a, b in zip(sizes, sizes[1:])):
+                raise ValueError(f"matryoshka prefix sizes must be at least 1 and strictly ascending, got {sizes}")
+            if self.num_latents and sizes[-1] != self.num_latents:
+                raise ValueError(f"the last matryoshka prefix size must be num_latents = {self.num_latents}, got {sizes[-1]}")
+            if self.multi_topk:
+                raise ValueError("multi_topk is a loss term of the full dictionary alone: it does not go with matryoshka")
+            w = self.matryoshka_weights
+            if w:
+                if len(w) != len(sizes):
+                    raise ValueError(f"matryoshka_weights must hold one weight per prefix size ({len(sizes)}), got {len(w)}")
+                try:
+                    w = [float(v) for v in w]
+                except (TypeError, ValueError):
+                    raise ValueError(f"matryoshka_weights must hold numbers, got {self.matryoshka_weights!r}") from None
+                if any(not math.isfinite(v) or v < 0 for v in w) or not sum(w) > 0:
+                    raise ValueError(f"matryoshka_weights must be finite, not negative and have a positive sum, got {w}")
+                self.matryoshka_weights = w
 
     @property
     def cap(self) -> int:
@@ -64,13 +98,23 @@ class SaeConfig(_Serializable):
             return self.k
         return self.batch_cap or min(4 * self.k, 256)
 
+    @property
+    def nested_weights(self) -> List[float]:
+        """The loss weight of every prefix: matryoshka_weights, or 1 / G each."""
+        G = len(self.matryoshka)
+        return list(self.matryoshka_weights) or [1.0 / G] * G
+
     def to_dict(self) -> dict:
-        """The two BatchTopK fields are written only where they differ from the defaults: a TopK cfg.json is the reference's."""
+        """The BatchTopK and Matryoshka fields are written only where they differ from the defaults: a TopK cfg.json is the
+        reference's."""
         d = super().to_dict()
         if d["activation"] == "topk":
             del d["activation"]
         if d["batch_cap"] == 0:
             del d["batch_cap"]
+        for name in ("matryoshka", "matryoshka_weights"):
+            if not d[name]:
+                del d[name]
         return d
 
 

@@ -69,6 +69,39 @@ class BatchForwardOutput(ForwardOutput):
         return self
 
 
+class NestedForwardOutput(ForwardOutput):
+    """The ForwardOutput of a Matryoshka Sae (SaeConfig.matryoshka): the same six fields -- fvu is the
+    full dictionary's -- and, as attributes, `nested_fvu` ([G]: the FVU of every prefix), `nested_loss` (the weighted sum the
+    trainer descends on) and `bounds` (the prefix sizes, a tuple).  For a "batchtopk" Sae it also carries `lengths`, `theta`
+    and `n_saturated` as a BatchForwardOutput does; they are None otherwise."""
+
+    def __new__(cls, *fields, nested_fvu: Tensor, nested_loss: Tensor, bounds: tuple, lengths: Optional[Tensor] = None,
+                theta: Optional[Tensor] = None, n_saturated: Optional[Tensor] = None):
+        self = super().__new__(cls, *fields)
+        self.nested_fvu, self.nested_loss, self.bounds = nested_fvu, nested_loss, bounds
+        self.lengths, self.theta, self.n_saturated = lengths, theta, n_saturated
+        return self
+
+
+class NestedErrorOutput(NamedTuple):
+    """Per-token squared error of every dictionary prefix (Sae.nested_error; include/msae.h, "nested decode").  The tensor
+    fields are f32; `fvu` is float64."""
+    bounds: tuple
+    """The prefix sizes: entry g of the G axis reconstructs from the listed features below bounds[g]."""
+    err2: Tensor
+    """|r_g - x|^2, [..., G]."""
+    xnorm2: Tensor
+    """|x|^2, [...]."""
+    total_variance: Tensor
+    """(x - x.mean(0)).pow(2).sum() over this call's tokens, a float64 scalar."""
+    d_in: int
+
+    @property
+    def fvu(self) -> Tensor:
+        """Fraction of variance unexplained of this call, [G]."""
+        return self.err2.to(torch.float64).reshape(-1, self.err2.shape[-1]).sum(0) / self.total_variance
+
+
 class ReconOutput(NamedTuple):
     """Per-token moments of the reconstruction at several sparsities (Sae.recon_error; include/msae.h, "reconstruction
     error against sparsity").  The tensor fields are the kernel's f32 outputs; the properties are float64."""
@@ -152,6 +185,14 @@ class Sae(nn.Module):
             # -1 = not learned yet.  Saved and loaded with the model; a TopK Sae has no such key.
             self.register_buffer("threshold", torch.tensor(-1.0, dtype=torch.float32, device=device))
             self._threshold_checked = None     # the buffer's _version at which a host read last found it learned
+        if cfg.matryoshka:
+            # only here is d_in known, and with it the width of the dictionary the prefixes must end at
+            if cfg.matryoshka[-1] != self.num_latents:
+                raise ValueError(f"the last matryoshka prefix size must be the number of latents {self.num_latents}, got "
+                                 f"{cfg.matryoshka[-1]}")
+            # the loss weights live on the device from the start (not saved: cfg.json holds them)
+            self.register_buffer("_nested_w", torch.tensor(cfg.nested_weights, dtype=torch.float32, device=device),
+                                 persistent=False)
         self._prepared: Optional[Tensor] = None
         self._prepared_key = None
 
@@ -545,6 +586,95 @@ class Sae(nn.Module):
         return ReconOutput(tuple(ks), mom[..., 0].reshape(*lead, C), mom[..., 1].reshape(*lead, C),
                            mom[..., 2].reshape(*lead, C), xx.reshape(lead), tv, self.d_in)
 
+    def nested_error(self, x: Tensor, bounds=None, *, top=None, exact: bool = False) -> NestedErrorOutput:
+        """How well the first m features alone explain x, GIVEN the selection over all N features: the per-token squared
+        error |r_g - x|^2 of the reconstruction r_g from the listed features below bounds[g], for every prefix size at once
+        (include/msae.h, "nested decode"; one pass over each token's decoder rows, no residual planes).  x [..., d_in] in
+        f32 / bf16 / f16.  `bounds`: prefix sizes, strictly ascending, at most 8, the last one num_latents; None:
+        cfg.matryoshka (ValueError when the Sae has none).  `top`: the list of x when the caller holds it -- an EncoderOutput,
+        (top_acts, top_indices) or (top_acts, top_indices, lengths); None: `self.encode(x, exact=exact)`.  Available on any
+        Sae; inference only, nothing is read back.  Not the same question as `truncate(m)`, which RE-SELECTS the top-k
+        among the first m features."""
+        if bounds is None:
+            bounds = self.cfg.matryoshka
+            if not bounds:
+                raise ValueError("Sae.nested_error: give bounds= (this Sae's cfg.matryoshka is empty)")
+        bounds = ops.nested_bounds(bounds, self.num_latents, "Sae.nested_error")
+        if self.W_dec is None:
+            raise ValueError("Sae.nested_error: this Sae has no decoder")
+        if x.dim() < 1 or x.shape[-1] != self.d_in:
+            raise ValueError(f"Sae.nested_error: x must be [..., {self.d_in}], got {tuple(x.shape)}")
+        if x.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+            raise ValueError(f"Sae.nested_error: x must be float32, bfloat16 or float16, got {x.dtype}")
+        if top is not None and len(top) not in (2, 3):
+            raise ValueError("Sae.nested_error: top must be (top_acts, top_indices) or (top_acts, top_indices, lengths)")
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise RuntimeError("Sae.nested_error is an inference path: call it under torch.no_grad() or on a detached input")
+        with torch.no_grad():
+            flat = x.reshape(-1, self.d_in)
+            T = flat.shape[0]
+            if top is None:
+                if self.cfg.activation == "batchtopk":
+                    enc, lengths = self.encode(flat, exact=exact, return_lengths=True)
+                    top = (enc.top_acts, enc.top_indices, lengths)
+                else:
+                    top = self.encode(flat, exact=exact)
+            k = top[0].shape[-1]
+            lengths = top[2].reshape(T) if len(top) == 3 and top[2] is not None else None
+            _, sq, _ = ops.nested_decode(flat, top[0].reshape(T, k), top[1].reshape(T, k), self.W_dec, self.b_dec, bounds,
+                                         lengths)
+            xf = flat.to(torch.float32)
+            xx = (xf * xf).sum(-1)
+            tv = flat.new_zeros((), dtype=torch.float64)
+            if T:
+                rows = max(1, (32 << 20) // self.d_in)
+                mean = sum(flat[a:a + rows].sum(0, dtype=torch.float64) for a in range(0, T, rows)) / T
+                for a in range(0, T, rows):
+                    tv += (flat[a:a + rows].to(torch.float64) - mean).square().sum()
+        lead = tuple(x.shape[:-1])
+        return NestedErrorOutput(bounds, sq.reshape(*lead, len(bounds)), xx.reshape(lead), tv, self.d_in)
+
+    def truncate(self, m: int, copy: bool = False) -> "Sae":
+        """An Sae over the first m features: how a trained Matryoshka prefix is used on its own (steering, probes, neighbours
+        on a 16k dictionary cut from a 131k one).  By default its parameters are row-slice VIEWS that share storage with this
+        Sae's (copy=True: its own copies); its prepared encoder operands are its own.  cfg.num_latents becomes m,
+        cfg.matryoshka is cut to the sizes <= m (with m itself as the last size; the weights are cut along where m is one of
+        the sizes and reset to uniform otherwise), and a "batchtopk" threshold buffer is carried over.  m need not be a
+        multiple of 8192: the encoder takes whatever path it takes for such a width.
+
+        `truncate(m)` RE-SELECTS the top-k among the first m features; `nested_error` keeps the selection over all N features
+        and restricts it to those below m.  The two agree only where the full selection already lies inside the prefix."""
+        import dataclasses
+
+        m = int(m)
+        if not self.cfg.cap <= m <= self.num_latents:
+            raise ValueError(f"Sae.truncate: m must lie in [{self.cfg.cap}, {self.num_latents}], got {m}")
+        sizes = [s for s in self.cfg.matryoshka if s <= m]
+        weights = list(self.cfg.matryoshka_weights[:len(sizes)]) if self.cfg.matryoshka_weights else []
+        if self.cfg.matryoshka and (not sizes or sizes[-1] != m):
+            sizes, weights = sizes + [m], []
+        if weights and not sum(weights) > 0:
+            weights = []
+        cfg = dataclasses.replace(self.cfg, num_latents=m, matryoshka=sizes, matryoshka_weights=weights)
+        new = Sae(self.d_in, cfg, device="meta", decoder=self.W_dec is not None)     # the shell: no storage of its own
+
+        def part(t: Tensor) -> Tensor:
+            t = t.detach()[:m]
+            return t.clone() if copy else t
+
+        new.encoder.weight = nn.Parameter(part(self.encoder.weight), requires_grad=self.encoder.weight.requires_grad)
+        new.encoder.bias = nn.Parameter(part(self.encoder.bias), requires_grad=self.encoder.bias.requires_grad)
+        if self.W_dec is not None:
+            new.W_dec = nn.Parameter(part(self.W_dec), requires_grad=self.W_dec.requires_grad)
+        b = self.b_dec.detach()
+        new.b_dec = nn.Parameter(b.clone() if copy else b, requires_grad=self.b_dec.requires_grad)
+        if cfg.activation == "batchtopk":
+            new.threshold = self.threshold.detach().clone()
+        if cfg.matryoshka:
+            new._nested_w = torch.tensor(cfg.nested_weights, dtype=torch.float32, device=self.device)
+        new.train(self.training)
+        return new
+
     def _topk_only(self, what: str) -> None:
         """The paths that read a per-token top-k list are not built for a "batchtopk" Sae."""
         if self.cfg.activation == "batchtopk":
@@ -715,10 +845,20 @@ class Sae(nn.Module):
             sel = ops.sparse_encode(x, self.encoder.weight, self.encoder.bias, self.b_dec, k_main,
                                     dead_mask, k_aux, k_multi)
         top_acts, top_indices = sel[0]
+        nested = bool(self.cfg.matryoshka)
+        lengths = theta = n_saturated = None
         if batch:
             # BatchTopK: the T*k largest entries of the batch's top-C lists, and a decode that reads
             # the kept prefix of every row only; theta, the lengths and the saturation count stay on the device
             top_acts, lengths, theta, n_saturated = ops.batch_select(top_acts, top_indices, self.cfg.k)
+        if nested:
+            # Matryoshka: the full reconstruction and every prefix's squared error from one pass over
+            # the decoder rows, one autograd node
+            bounds = tuple(self.cfg.matryoshka)
+            sae_out, sq_sum = ops.nested_reconstruct(x, top_acts.to(self.dtype), top_indices, self.W_dec, self.b_dec, bounds,
+                                                     lengths)
+            sae_out = sae_out.view(x.shape)
+        elif batch:
             sae_out = self.decode(top_acts, top_indices, lengths)
         else:
             sae_out = self.decode(top_acts, top_indices)
@@ -726,7 +866,10 @@ class Sae(nn.Module):
         # C2; the reference's expression is ~10 of them forward + backward): squared error and its gradient through _SqErr,
         # the total variance as one column-variance kernel.  An input that itself requires grad keeps the plain expressions.
         lean = x.is_cuda and x.dim() == 2 and not x.requires_grad and x.dtype == torch.float32
-        if lean:
+        if nested:
+            sq_err, e = sq_sum[-1], None if lean else sae_out - x
+            total_variance = _total_variance(x) if lean else (x - x.mean(0)).pow(2).sum()
+        elif lean:
             sq_err, e = _SqErr.apply(sae_out, x)
             total_variance = _total_variance(x)
         else:
@@ -751,6 +894,11 @@ class Sae(nn.Module):
             multi_topk_fvu = (_SqErr.apply(sae_out, x)[0] if lean else (sae_out - x).pow(2).sum()) / total_variance
         else:
             multi_topk_fvu = sae_out.new_zeros(())
+        if nested:
+            nested_fvu = sq_sum / total_variance
+            return NestedForwardOutput(sae_out, top_acts, top_indices, fvu, auxk_loss, multi_topk_fvu, nested_fvu=nested_fvu,
+                                       nested_loss=(nested_fvu * self._nested_w).sum(), bounds=bounds, lengths=lengths,
+                                       theta=theta, n_saturated=n_saturated)
         if batch:
             return BatchForwardOutput(sae_out, top_acts, top_indices, fvu, auxk_loss, multi_topk_fvu, lengths=lengths,
                                       theta=theta, n_saturated=n_saturated)

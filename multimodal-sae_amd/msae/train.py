@@ -270,7 +270,9 @@ class SaeTrainStep:
     def step(self, hiddens: Tensor) -> dict:
         """One global step (one batch of activations of this rank).  Returns device tensors (no host
         synchronisation): {"fvu", "auxk_loss", "multi_topk_fvu"} averaged over micro-batches and ranks,
-        "stepped": whether the optimizer moved (every `grad_acc_steps`-th call).  A "batchtopk" Sae adds "theta" (the mean of
+        "stepped": whether the optimizer moved (every `grad_acc_steps`-th call).  A Matryoshka Sae (cfg.matryoshka) descends on
+        the forward's `nested_loss` in place of its fvu and adds "nested_fvu" ([G], averaged like the others).  A
+        "batchtopk" Sae adds "theta" (the mean of
         the micro-chunks' rank-averaged thresholds) and "n_saturated" (this rank's rows that kept all C slots), device tensors
         as well."""
         sae = self.sae
@@ -287,18 +289,23 @@ class SaeTrainStep:
         acc_steps = self.grad_acc_steps * self.micro_acc_steps
         stats = torch.zeros(3, dtype=torch.float32, device=hiddens.device)
         chunks = hiddens.chunk(self.micro_acc_steps)
-        theta_sum = n_saturated = 0
+        theta_sum = n_saturated = nested_sum = 0
         for ci, chunk in enumerate(chunks):
             self._reduce_now = self.world > 1 and ci == len(chunks) - 1
             self._chunk_tokens = chunk.shape[0]
             out = self._forward(chunk, dead_mask)
-            loss = out.fvu + self.auxk_alpha * out.auxk_loss + out.multi_topk_fvu / 8
+            # a Matryoshka Sae descends on the weighted sum of its prefixes' FVUs; fvu stays a statistic
+            nested_loss = getattr(out, "nested_loss", None)
+            main = out.fvu if nested_loss is None else nested_loss
+            loss = main + self.auxk_alpha * out.auxk_loss + out.multi_topk_fvu / 8
             if hiddens.is_cuda:
                 with ops.collect_wgrad_sumsq() as self._wgrad_sumsq:
                     loss.div(acc_steps).backward()
             else:
                 loss.div(acc_steps).backward()
             stats += torch.stack([out.fvu.detach(), out.auxk_loss.detach(), out.multi_topk_fvu.detach()])
+            if nested_loss is not None:
+                nested_sum = nested_sum + out.nested_fvu.detach().to(torch.float32)
             self._note_fired(out)
             if self.batch_topk:
                 theta_sum = theta_sum + self._fold_threshold(out.theta)
@@ -329,4 +336,9 @@ class SaeTrainStep:
         res = {"fvu": stats[0], "auxk_loss": stats[1], "multi_topk_fvu": stats[2], "stepped": stepped}
         if self.batch_topk:
             res.update(theta=theta_sum / len(chunks), n_saturated=n_saturated)
+        if isinstance(nested_sum, Tensor):
+            nested_sum = nested_sum / len(chunks)
+            if self.world > 1:
+                self._all_reduce(nested_sum).div_(self.world)
+            res["nested_fvu"] = nested_sum
         return res
