@@ -27,21 +27,57 @@ the float32 side's ReLU mask where |p64| <= b_t (elsewhere the masks must agree)
 trajectory.  `tie_share` is the share of tokens whose float64 gap at rank k is below 2 b_t (ties among zeros aside: they
 carry neither value nor gradient).
 
+BatchTopK (TrainerConfig.activation = "batchtopk"; msae: SaeConfig(activation="batchtopk")).  The main
+selection has the list width C = cap.  Standalone: the float64 top-C lists; theta64 = the (T_chunk k)-th largest positive list
+entry (the smallest positive one when there are fewer, +inf when none); an entry is kept iff v > 0 and v >= theta.  Adopting: the
+caller also hands over, per chunk, what ops.batch_select returned for the list (kept values, lengths, theta, n_saturated).  (i)
+the list passes `_adopt` with kk = C; (ii) the four results equal, BIT FOR BIT, batch_select_ref.batch_select of the float32
+list (the list itself must descend); (iii) over the whole chunk min over kept (lat64 + b_t) >= max over dropped positive list
+entries (lat64 - b_t), and at least min(T k, positives) entries are kept; (iv) the keep mask and the ReLU mask are adopted.
+The decode, every gradient, the statistics and did_fire see the kept entries only; AuxK's target is the residual of the kept
+reconstruction.  Per CHUNK theta is folded into `threshold` (from -1: the first finite theta is copied, then thr +=
+threshold_lr (theta - thr); a non-finite theta is skipped); per batch BatchResult carries theta (the mean over the chunks),
+threshold, n_saturated and lengths.  `tie_share` of this selection is the share of the chunk's T k kept slots that float64
+leaves undecided: positive list entries within 2 b_t of theta64, plus rows saturated in float64 whose gap at rank C is below
+2 b_t (a tie at rank C of an unsaturated row forks nothing -- its tail is dropped -- and does not count).
+
+Matryoshka (TrainerConfig.matryoshka / matryoshka_weights).  out_g decodes the selected (kept) entries
+with idx < bounds[g], e_g = out_g - x, nested_fvu[g] = sum e_g^2 / tv; the descended main term is sum_g w_g nested_fvu[g] and
+fvu = nested_fvu[-1] is a statistic.  The decode output of group h receives S_h = grad_full + sum_{g >= h} c_g e_g with
+c_g = weight 2 w_g / tv (nested_ref's combine); W_dec row n gets sum v S_group(n)[t], a latent S_group(i)[t] . W_dec[i], b_dec
+sum_t S_0[t]; grad_full is the AuxK term's gradient into the full reconstruction.
+
 Error model (u = 2^-24; to first order, ONE factor SAFETY at the end).  Every intermediate is a pair (value, bound):
   * an elementwise float32 operation adds u |result|; a scalar coefficient built from a handful of float32 scalar operations
     (2 / total_variance / acc_steps, alpha, scale, 1 / 8) carries 6 u plus the relative bound of the total variance;
   * a float32 sum adds depth * u * sum |terms| on top of the propagated input intervals.  `depth` where the order is ours:
         decode (sae_out, e_hat)        k + 1        the j-ordered fma chain and the bias add, csrc/decode.hip:33-79
+        decode of a kept prefix        len + 1      decode_prefix_v4_kernel walks the first len entries of a row, one fma each,
+                                                    then the bias add (csrc/batch_select.hip:229-277): <= C + 1
+        prefix decode r_g              n_g + 1      the live entries of the groups 0 .. g in group-major order, one fma each
+                                                    (nd_walk, csrc/nested_decode.hip:79, walked to the checkpoint s_ck[g],
+                                                    :162-169) and the bias add (:173); e_g = r_g - x is one subtract (:174)
+        combine S_h                    G + 1        one fma per plane from the last plane down, from grad_full or +0
+                                                    (csrc/nested_decode.hip:247-255; nested_ref states the same G + 1)
         decoder backward, g_acts       d / 64 + 7   the lane's fma chain (d / 64 terms, own product), 6 shuffle levels,
                                                     csrc/decode.hip:131-143
         weight gradients (both)        L + 1        wgrad_accum_kernel's ascending pair order: one fma chain over the row's L
-                                                    pairs, csrc/decode.hip:308-341 (L counts every selected pair of the call)
+                                                    pairs, csrc/decode.hip:308-341 (L counts every selected pair of the call;
+                                                    "batchtopk": the KEPT pairs -- wgrad_count_kernel and wgrad_fill_kernel
+                                                    leave a pair with activation 0 out of the segment, csrc/decode.hip:177,
+                                                    235, and a dropped slot reaches them as 0).  The grouped forms
+                                                    (csrc/decode.hip:138, 276) only choose the plane a row is read from
         b_dec through the encoder      train_ref.weighted_row_sum's depth (csrc/train.hip, msae_weighted_row_sum_f32)
     and depth = the number of terms where the order is not ours (valid for ANY order):
         encoder bias gradient          L            (row_act_sum, csrc/decode.hip:355-358, is shallower: ceil(L / 64) + 6)
         b_dec through a decode         T            grad_out.sum(0), a torch reduction
         total variance                 T + d + 8    torch.var over the tokens, the sum over d, the product with T
-        squared-error sums             T d          torch.linalg.vector_norm
+        squared-error sums             T d          torch.linalg.vector_norm; the nested node's sq (lane fma chain, wave
+                                                    butterfly, four waves, slabs: csrc/nested_decode.hip:175-187, then
+                                                    sq.sum(0) over the tokens) is one order among those
+        theta's mean, the threshold    chunks; 4    the float32 running sum of the chunks' thetas and its division; one fold is a
+                                                    subtract, a product with the float32 rate and an add: 4 u (|thr| + |theta|)
+                                                    per fold on top of the state's own bound (msae/train.py, _fold_threshold)
         clip_grad_norm_'s total        all parameter elements (torch._foreach_norm and the norm of the four norms)
     autograd adding two contributions of one parameter (the three decodes, the chunks of a window) is one u each;
   * W_dec as the float32 side holds it after its own renormalisation differs from the float64 renormalisation by
@@ -62,7 +98,11 @@ NAMES = ("W_enc", "b_enc", "W_dec", "b_dec")
 
 MUTATIONS = ("bias_correction_t_plus_1", "lr_of_next_step", "no_clip_on_non_stepping", "dead_ge_threshold",
              "did_fire_from_k", "chunk_weight_by_token_share", "tokens_in_step_reset_every_batch", "scale_uncapped",
-             "project_before_clip", "no_renorm")
+             "project_before_clip", "no_renorm",
+             # "batchtopk"  and matryoshka (section 7o)
+             "fired_from_listed_slots", "theta_rank_plus_1", "keep_strictly_above_theta", "threshold_folded_once_per_batch",
+             "threshold_first_value_averaged", "descend_on_full_fvu", "prefix_boundary_off_by_one", "suffix_as_prefix",
+             "nested_coef_without_weight", "auxk_target_ignores_kept_mask")
 
 
 def linear_schedule_with_warmup(step: int, warmup: int, total: Optional[int]) -> float:
@@ -90,6 +130,27 @@ class TrainerConfig:
     betas: Tuple[float, float] = (0.9, 0.999)
     eps: float = 1e-8
     max_norm: float = 1.0
+    activation: str = "topk"                  # "topk" or "batchtopk"
+    cap: int = 0                              # "batchtopk": the list width C of the main selection
+    threshold_lr: float = 0.01                # "batchtopk": the rate every chunk's theta is folded into the threshold at
+    matryoshka: Tuple[int, ...] = ()          # prefix sizes, the last one N; empty: the plain loss
+    matryoshka_weights: Tuple[float, ...] = ()    # one loss weight per prefix, explicit
+
+    def __post_init__(self):
+        assert self.activation in ("topk", "batchtopk"), self.activation
+        if self.multi_topk and (self.activation == "batchtopk" or self.matryoshka):
+            raise ValueError("multi_topk goes with neither activation='batchtopk' nor matryoshka")
+        if self.activation == "batchtopk" and not self.k <= self.cap:
+            raise ValueError(f"cap must be at least k = {self.k}, got {self.cap}")
+        if len(self.matryoshka_weights) != len(self.matryoshka):
+            raise ValueError("matryoshka_weights holds one weight per prefix size")
+        if any(a >= b for a, b in zip(self.matryoshka, self.matryoshka[1:])):
+            raise ValueError(f"matryoshka prefix sizes must ascend strictly, got {self.matryoshka}")
+
+    @property
+    def width(self) -> int:
+        """The width of the main selection's lists."""
+        return self.cap if self.activation == "batchtopk" else self.k
 
 
 @dataclass
@@ -111,6 +172,16 @@ class BatchResult:
     tie_share: float               # worst selection of the batch
     sel_ratio: float               # largest |float32 value - float64 latent| / b_t over the adopted selections
     num_tokens_since_fired: torch.Tensor = field(default=None)    # after the batch
+    theta: float = 0.0             # "batchtopk": the mean of the chunks' thresholds, and the bound of its float32 mean
+    dtheta: float = 0.0
+    threshold: float = -1.0        # "batchtopk": the folded threshold state after the batch
+    dthreshold: float = 0.0
+    n_saturated: int = 0           # "batchtopk": rows that kept all C slots, summed over the chunks
+    lengths: torch.Tensor = field(default=None)                   # "batchtopk": the kept prefix of every row, chunks in order
+    nested_fvu: Tuple[float, ...] = ()                            # matryoshka: the FVU of every prefix, averaged like stats
+    dnested_fvu: Tuple[float, ...] = ()
+    groups_min: Tuple[int, ...] = ()                              # matryoshka: per group the fewest live entries of a chunk
+    empty_first: int = 0                                          # matryoshka: tokens whose first group holds no live entry
 
 
 class TrainerRef:
@@ -133,6 +204,9 @@ class TrainerRef:
         self.G: Optional[Dict[str, torch.Tensor]] = None      # the window's accumulated gradients and their raw bounds
         self.dG: Optional[Dict[str, torch.Tensor]] = None
         self.dWd = torch.zeros_like(self.p["W_dec"])           # |float32 W_dec - self.p["W_dec"]| (raw)
+        self.threshold, self.dthreshold = -1.0, 0.0            # "batchtopk": the folded theta and its raw bound
+        if cfg.matryoshka:
+            assert cfg.matryoshka[-1] == self.N, (cfg.matryoshka, self.N)
 
     # ---- synchronisation with the side under test ---------------------------------------------------------------------------
     def load_state(self, params, exp_avg, exp_avg_sq) -> None:
@@ -197,10 +271,84 @@ class TrainerRef:
         pos = b_sel > 0
         return torch.where(near, m32, m64), float((err[pos] / b_sel[pos]).max()) if bool(pos.any()) else 0.0
 
+    # ---- "batchtopk": the batch-level selection over the top-C lists ----------------------------------------------------------
+    def _theta64(self, v, K: int) -> float:
+        """The K-th largest positive entry of the lists v; the smallest positive one when there are fewer, +inf when none."""
+        pos = v[v > 0]
+        if pos.numel() == 0:
+            return float("inf")
+        if "theta_rank_plus_1" in self.mut:
+            K = K + 1
+        return float(pos.sort(descending=True).values[min(K, pos.numel()) - 1])
+
+    def _keep64(self, v, theta: float):
+        if "keep_strictly_above_theta" in self.mut:
+            return (v > 0) & (v > theta)
+        return (v > 0) & (v >= theta)
+
+    def _batch_tie_share(self, lat, bt) -> float:
+        """The share of the chunk's T k kept slots that float64 leaves undecided: positive list entries within 2 b_t of
+        theta64, and rows saturated in float64 whose gap at rank C is below 2 b_t.  A tie at rank C of an unsaturated row
+        forks nothing (its tail is dropped) and does not count."""
+        T, N = lat.shape
+        C, K = self.cfg.cap, T * self.cfg.k
+        v, i = lat.topk(min(C + 1, N), dim=1)
+        b = bt.gather(1, i)
+        vC, bC = v[:, :C], b[:, :C]
+        theta = self._theta64(vC, K)
+        undecided = int(((vC > 0) & ((vC - theta).abs() < 2 * bC)).sum())
+        if N > C:
+            saturated = (vC[:, -1] > 0) & (vC[:, -1] >= theta)
+            undecided += int((saturated & (v[:, C - 1] - v[:, C] < 2 * b[:, C - 1:C + 1].amax(1))).sum())
+        return undecided / K
+
+    def _select_batch64(self, lat):
+        """Standalone mode -> (idx [T, C], keep [T, C], theta64, lengths, n_saturated) from the float64 top-C lists."""
+        v, idx = lat.topk(self.cfg.cap, dim=1)
+        theta = self._theta64(v, lat.shape[0] * self.cfg.k)
+        keep = self._keep64(v, theta)
+        sat = (v[:, -1] > 0) & (v[:, -1] >= theta)
+        return idx, keep, theta, keep.sum(1).to(torch.int32), int(sat.sum())
+
+    def _adopt_batch(self, pre, bt, vals32, idx, returned, what: str):
+        """Adopting mode.  (vals32, idx): the top-C list ops.sparse_encode returned (already through _adopt); returned:
+        (kept values, lengths, theta, n_saturated) of ops.batch_select for it.  (ii) those four equal, bit for bit,
+        batch_select_ref.batch_select of the float32 list; (iii) the kept set is a valid batch-level selection of the float64
+        latents: over the whole chunk min over kept (lat64 + b_t) >= max over dropped positive list entries (lat64 - b_t), and
+        at least min(T k, positives) entries are kept.  -> (keep [T, C], theta as a float, lengths, n_saturated)."""
+        import batch_select_ref as bs
+
+        T, C = idx.shape
+        kept32, lengths, theta32, n_sat = returned
+        v_np = vals32.detach().cpu().float().numpy()
+        assert bool((v_np[:, :-1] >= v_np[:, 1:]).all()), f"{what}: a top-C list is not in descending order"
+        vo, io, ln, th, sat = bs.batch_select(v_np, idx.cpu().numpy(), self.cfg.k)
+        kept32 = kept32.detach().cpu().float().reshape(T, C)
+        lengths = lengths.detach().cpu().to(torch.int32).reshape(T)
+        theta32 = float(theta32)
+        assert theta32 == float(th), f"{what}: theta {theta32!r} is not the restated {float(th)!r}"
+        assert torch.equal(lengths, torch.from_numpy(ln)), f"{what}: lengths differ from the restated filter"
+        assert torch.equal(kept32, torch.from_numpy(vo)) and bool((io == idx.cpu().numpy()).all()), \
+            f"{what}: kept values differ from the restated filter"
+        assert int(n_sat) == int(sat.sum()), f"{what}: n_saturated {int(n_sat)} against {int(sat.sum())}"
+        keep = torch.arange(C)[None, :] < lengths[:, None].long()
+        lat_sel, b_sel = torch.relu(pre).gather(1, idx), bt.gather(1, idx)
+        lo_kept = float(torch.where(keep, lat_sel + b_sel, torch.full_like(lat_sel, torch.inf)).min())
+        dropped = ~keep & (lat_sel > 0)
+        hi_drop = float(torch.where(dropped, lat_sel - b_sel, torch.full_like(lat_sel, -torch.inf)).max())
+        assert lo_kept >= hi_drop, f"{what}: a dropped entry lies more than 2 b_t above a kept one in float64"
+        positives = int((tr._d(vals32) > 0).sum())
+        assert int(keep.sum()) >= min(T * self.cfg.k, positives), f"{what}: {int(keep.sum())} entries kept of {positives} positive"
+        return keep, theta32, lengths, int(n_sat)
+
     # ---- forward and backward of one micro-chunk ----------------------------------------------------------------------------
-    def _chunk(self, x, weight: float, dead: Optional[torch.Tensor], num_dead: int, sel):
-        """-> (G, dG raw, stats, dstats raw, fired indices, tie share, selection ratio) of `weight` * loss on chunk x."""
+    def _chunk(self, x, weight: float, dead: Optional[torch.Tensor], num_dead: int, sel, bsel=None):
+        """-> (G, dG raw, stats, dstats raw, fired indices, tie share, selection ratio, k_aux, scale, extra) of `weight` *
+        loss on chunk x.  extra: theta, lengths, n_saturated ("batchtopk"), nested_fvu with raw bounds and the live entries
+        per group (matryoshka)."""
         cfg, d, N = self.cfg, self.d, self.N
+        batch, nested = cfg.activation == "batchtopk", bool(cfg.matryoshka)
+        extra = {}
         We, be, Wd, bd = (self.p[n] for n in NAMES)
         dWd = self.dWd
         T = x.shape[0]
@@ -216,15 +364,21 @@ class TrainerRef:
             k_aux = d // 2
             scale = num_dead / k_aux if "scale_uncapped" in self.mut else min(num_dead / k_aux, 1.0)
             k_aux = min(k_aux, num_dead)
-        widths = [(cfg.k, None)] + ([(k_aux, dead)] if k_aux else []) + ([(4 * cfg.k, None)] if cfg.multi_topk else [])
+        widths = [(cfg.width, None)] + ([(k_aux, dead)] if k_aux else []) + ([(4 * cfg.k, None)] if cfg.multi_topk else [])
         picks, tie, ratio = [], 0.0, 0.0
+        fire_main = listed_mask = None
         if sel is not None:
             assert len(sel) == len(widths), ("selections handed over", len(sel), "expected", len(widths))
+            assert (bsel is not None) == batch, "what ops.batch_select returned goes with activation='batchtopk', and only with it"
         for j, (kk, universe) in enumerate(widths):
-            tie = max(tie, self._tie_share(lat, bt, kk, universe))
+            main_batch = batch and j == 0
+            tie = max(tie, self._batch_tie_share(lat, bt) if main_batch else self._tie_share(lat, bt, kk, universe))
             if sel is None:
-                src = lat if universe is None else torch.where(universe[None], lat, torch.full_like(lat, -torch.inf))
-                idx = src.topk(kk, dim=1, sorted=False).indices
+                if main_batch:
+                    idx, keep, theta, lengths, n_sat = self._select_batch64(lat)
+                else:
+                    src = lat if universe is None else torch.where(universe[None], lat, torch.full_like(lat, -torch.inf))
+                    idx = src.topk(kk, dim=1, sorted=False).indices
                 mask = pre.gather(1, idx) > 0
             else:
                 vals32, idx = sel[j]
@@ -232,9 +386,20 @@ class TrainerRef:
                 idx = idx.to("cpu", torch.long)
                 mask, r = self._adopt(pre, bt, idx, vals32, universe, f"selection {j} (k = {kk})")
                 ratio = max(ratio, r)
+                if main_batch:
+                    keep, theta, lengths, n_sat = self._adopt_batch(pre, bt, vals32, idx, bsel, "batch selection")
+            depth = kk + 1
+            if main_batch:
+                # the decode, every gradient and the statistics see the kept entries only; the decode's chain has one fma per
+                # kept entry and the bias add behind it: len + 1 <= C + 1 (csrc/batch_select.hip:229-277)
+                extra.update(theta=theta, lengths=lengths, n_saturated=n_sat)
+                fire_main = idx[keep]
+                listed_mask = mask
+                mask = mask & keep
+                depth = mask.sum(1, keepdim=True).to(F64) + 1
             v = pre.gather(1, idx) * mask
             dv = bt.gather(1, idx) / SAFETY * mask
-            picks.append((idx, mask, v, dv, kk))
+            picks.append((idx, mask, v, dv, depth))
 
         # three sparse products, each as a dense [T, N] matmul (wide selections) or over the selected pairs (narrow ones)
         def dense(idx):
@@ -255,11 +420,14 @@ class TrainerRef:
             return torch.zeros(N, rows.shape[1], dtype=F64).index_add_(
                 0, idx.reshape(-1), (coef[:, :, None] * rows[:, None, :]).reshape(-1, rows.shape[1]))
 
-        def decode(pick):                     # sum_j v_j W_dec[idx_j] + b_dec
-            idx, _, v, dv, kk = pick
+        def decode_of(idx, v, dv, depth):     # sum_j v_j W_dec[idx_j] + b_dec, a chain of `depth` rounded operations
             av = v.abs()
             return (lin(idx, v, Wd) + bd,
-                    lin(idx, dv, aWd) + lin(idx, av, dWd) + (kk + 1) * U * (lin(idx, av, aWd) + bd.abs()))
+                    lin(idx, dv, aWd) + lin(idx, av, dWd) + depth * U * (lin(idx, av, aWd) + bd.abs()))
+
+        def decode(pick):
+            idx, _, v, dv, depth = pick
+            return decode_of(idx, v, dv, depth)
 
         mean = x.mean(0)
         tv = float(((x - mean) ** 2).sum())
@@ -267,9 +435,6 @@ class TrainerRef:
         rc = 6 * U + dtv / tv                                     # relative bound of a loss coefficient
         cf = weight * 2.0 / tv
 
-        out0, dout0 = decode(picks[0])
-        e = out0 - x
-        de = dout0 + U * e.abs()
         nterm = T * d
 
         def sq_stat(r, dr, coef):
@@ -278,16 +443,48 @@ class TrainerRef:
             return val, abs(coef) * (float((2 * r.abs() * dr + dr * dr).sum()) + nterm * U * s) / tv + abs(val) * rc
 
         stats, dstats = {}, {}
-        stats["fvu"], dstats["fvu"] = sq_stat(e, de, 1.0)
+        idx0, mask0, v0, dv0, _ = picks[0]
+        if nested:
+            # every prefix g decodes the live entries with idx < bounds[g]: group-major, one fma per live entry of the groups
+            # 0 .. g and the bias add (csrc/nested_decode.hip:79, 167-173), e_g = r_g - x one subtract (:174)
+            Gn = len(cfg.matryoshka)
+            grp = torch.searchsorted(torch.tensor(cfg.matryoshka, dtype=torch.long), idx0,
+                                     right="prefix_boundary_off_by_one" not in self.mut)
+            E, dE, nf, dnf = [], [], [], []
+            for g in range(Gn):
+                mg = mask0 & ((grp >= Gn - 1 - g) if "suffix_as_prefix" in self.mut else (grp <= g))
+                out_g, dout_g = decode_of(idx0, v0 * mg, dv0 * mg, mg.sum(1, keepdim=True).to(F64) + 1)
+                e_g = out_g - x
+                E.append(e_g)
+                dE.append(dout_g + U * e_g.abs())
+                val, dval = sq_stat(E[-1], dE[-1], 1.0)
+                nf.append(val)
+                dnf.append(dval)
+            e, de = E[-1], dE[-1]
+            stats["fvu"], dstats["fvu"] = nf[-1], dnf[-1]         # a statistic only: the descent is on sum_g w_g nested_fvu[g]
+            live_g = [mask0 & (grp == h) for h in range(Gn)]
+            extra.update(nested_fvu=nf, dnested_fvu=dnf, groups=[int(m.sum()) for m in live_g],
+                         empty_first=int((live_g[0].sum(1) == 0).sum()))
+        else:
+            out0, dout0 = decode(picks[0])
+            e = out0 - x
+            de = dout0 + U * e.abs()
+            stats["fvu"], dstats["fvu"] = sq_stat(e, de, 1.0)
         g_outs = [None] * len(picks)          # (g_out, dg_out) of each decode
         gf = cf * e
         dgf = abs(cf) * de + (rc + U) * gf.abs()
         j = 1
         stats["auxk_loss"], dstats["auxk_loss"] = 0.0, 0.0
+        ga = dga = None
         if k_aux:
             out1, dout1 = decode(picks[1])
-            r = out1 - e
-            dr = dout1 + de + U * r.abs()
+            e_t, de_t = e, de                 # AuxK's target: the residual of the (kept) reconstruction
+            if batch and "auxk_target_ignores_kept_mask" in self.mut:
+                o, do = decode_of(idx0, pre.gather(1, idx0) * listed_mask, bt.gather(1, idx0) / SAFETY * listed_mask, cfg.cap + 1)
+                e_t = o - x
+                de_t = do + U * e_t.abs()
+            r = out1 - e_t
+            dr = dout1 + de_t + U * r.abs()
             stats["auxk_loss"], dstats["auxk_loss"] = sq_stat(r, dr, scale)
             ca = cf * cfg.auxk_alpha * scale
             ga = ca * r
@@ -298,6 +495,26 @@ class TrainerRef:
             j = 2
         else:
             g_outs[0] = (gf, dgf)
+        S = None
+        if nested:
+            # the combine (csrc/nested_decode.hip:247-255): S_h = grad_full + sum_{g >= h} c_g e_g, one fma per plane from the
+            # last plane down, from grad_full = the AuxK term's gradient into the full reconstruction (or +0): a chain of at
+            # most G + 1 rounded operations.  c_g = weight 2 w_g / tv: the loss coefficient's handful of float32 operations,
+            # the float32 value of w_g and the product with it
+            w = list(cfg.matryoshka_weights)
+            if "descend_on_full_fvu" in self.mut:
+                w = [0.0] * (Gn - 1) + [1.0]
+            s = torch.zeros_like(e) if ga is None else -ga
+            ds = torch.zeros_like(e) if ga is None else dga
+            sabs = s.abs()
+            S = [None] * Gn
+            for g in range(Gn - 1, -1, -1):
+                cg = cf if "nested_coef_without_weight" in self.mut else cf * w[g]
+                term = cg * E[g]
+                s = s + term
+                ds = ds + abs(cg) * dE[g] + (rc + 2 * U) * term.abs()
+                sabs = sabs + term.abs()
+                S[g] = (s, ds + (Gn + 1) * U * sabs)
         stats["multi_topk_fvu"], dstats["multi_topk_fvu"] = 0.0, 0.0
         if cfg.multi_topk:
             out2, dout2 = decode(picks[j])
@@ -336,13 +553,34 @@ class TrainerRef:
         depth_acts = -(-d // 64) + 7
         L = torch.zeros(N, dtype=F64)
         idx_all, gc_all, dgc_all = [], [], []
-        for (idx, mask, v, dv, kk), (g, dg) in zip(picks, g_outs):
+        for pj, ((idx, mask, v, dv, _), (g, dg)) in enumerate(zip(picks, g_outs)):
             ag = g.abs()
-            Ls = torch.bincount(idx.reshape(-1), minlength=N).to(F64)
-            add("W_dec", *wgrad(idx, v, dv, g, dg, Ls))
-            add("b_dec", g.sum(0), dg.sum(0) + T * U * ag.sum(0))
-            gc = dots(idx, g, Wd) * mask
-            dgc = (dots(idx, dg, aWd) + dots(idx, ag, dWd) + depth_acts * U * dots(idx, ag, aWd)) * mask
+            if batch and pj == 0:
+                # a dropped slot reaches the weight-gradient kernels as activation 0, and wgrad_count_kernel / wgrad_fill_kernel
+                # leave a zero activation out of the row's segment (csrc/decode.hip:177, 235): the chain counts kept pairs
+                Ls = torch.bincount(idx.reshape(-1), weights=mask.reshape(-1).to(F64), minlength=N).to(F64)
+            else:
+                Ls = torch.bincount(idx.reshape(-1), minlength=N).to(F64)
+            if nested and pj == 0:
+                # the grouped backward kernels (csrc/decode.hip:138, 276): feature n reads plane group(n), the chains are
+                # those of the plain kernels.  A row of W_dec lies in ONE group: the per-group sums meet no rounded add
+                gw, dgw = torch.zeros(N, d, dtype=F64), torch.zeros(N, d, dtype=F64)
+                gc, dgc = torch.zeros(T, idx.shape[1], dtype=F64), torch.zeros(T, idx.shape[1], dtype=F64)
+                for h, (sh, dsh) in enumerate(S):
+                    mh = (grp == h).to(F64)
+                    gw_h, dgw_h = wgrad(idx, v * mh, dv * mh, sh, dsh, Ls)
+                    gw, dgw = gw + gw_h, dgw + dgw_h
+                    ash = sh.abs()
+                    gc = gc + dots(idx, sh, Wd) * mask * mh
+                    dgc = dgc + (dots(idx, dsh, aWd) + dots(idx, ash, dWd) + depth_acts * U * dots(idx, ash, aWd)) * mask * mh
+                add("W_dec", gw, dgw)
+                s0, ds0 = S[0]
+                add("b_dec", s0.sum(0), ds0.sum(0) + T * U * s0.abs().sum(0))
+            else:
+                add("W_dec", *wgrad(idx, v, dv, g, dg, Ls))
+                add("b_dec", g.sum(0), dg.sum(0) + T * U * ag.sum(0))
+                gc = dots(idx, g, Wd) * mask
+                dgc = (dots(idx, dg, aWd) + dots(idx, ag, dWd) + depth_acts * U * dots(idx, ag, aWd)) * mask
             idx_all.append(idx); gc_all.append(gc); dgc_all.append(dgc)
             L += Ls
         idx_cat, gc, dgc = torch.cat(idx_all, 1), torch.cat(gc_all, 1), torch.cat(dgc_all, 1)
@@ -357,14 +595,17 @@ class TrainerRef:
         _, wrs_bound = tr.weighted_row_sum(We, s, -1.0)
         add("b_dec", -(s @ We), (ds + U * s.abs()) @ aWe + wrs_bound / SAFETY)
         fire = picks[0][0] if ("did_fire_from_k" in self.mut or not cfg.multi_topk) else picks[-1][0]
-        return G, dG, stats, dstats, fire, tie, ratio, k_aux, scale
+        if batch and "fired_from_listed_slots" not in self.mut:
+            fire = fire_main                  # a dropped slot still names a feature: only the kept entries have fired
+        return G, dG, stats, dstats, fire, tie, ratio, k_aux, scale, extra
 
     # ---- one batch --------------------------------------------------------------------------------------------------------------
-    def batch(self, x, selections=None, update: bool = True) -> BatchResult:
+    def batch(self, x, selections=None, update: bool = True, batch_selects=None) -> BatchResult:
         """x: [T, d] float32 (or float64 holding float32 values).  selections: None, or per micro-chunk the list of
-        (values, indices) pairs the float32 side selected.  update=False: a caller that hands the parameters and moments
-        over before every optimiser step (load_state) skips the restatement's own Adam arithmetic; t, the schedule and
-        the dead-feature bookkeeping advance all the same."""
+        (values, indices) pairs the float32 side selected; batch_selects ("batchtopk", with selections): per micro-chunk what
+        ops.batch_select returned for the main list (kept values, lengths, theta, n_saturated).  update=False: a caller that
+        hands the parameters and moments over before every optimiser step (load_state) skips the restatement's own Adam
+        arithmetic; t, the schedule and the dead-feature bookkeeping advance all the same."""
         cfg = self.cfg
         x = tr._d(x)
         if cfg.normalize_decoder and "no_renorm" not in self.mut:
@@ -378,13 +619,33 @@ class TrainerRef:
         stats = {n: 0.0 for n in ("fvu", "auxk_loss", "multi_topk_fvu")}
         dstats = dict(stats)
         tie = ratio = scale = 0.0
+        batch_mode, Gn = cfg.activation == "batchtopk", len(cfg.matryoshka)
+        th_sum = dth_sum = 0.0
+        n_sat, lengths = 0, []
+        nf, dnf = [0.0] * Gn, [0.0] * Gn
+        groups_min, empty_first = [x.shape[0] * cfg.width] * Gn, 0
         for ci, chunk in enumerate(chunks):
             weight = 1.0 / acc_steps
             if "chunk_weight_by_token_share" in self.mut:
                 weight = chunk.shape[0] / x.shape[0] / cfg.grad_acc_steps
-            G, dG, st, dst, fire, tie_c, ratio_c, _, scale = self._chunk(
-                chunk, weight, dead, num_dead, None if selections is None else selections[ci])
+            G, dG, st, dst, fire, tie_c, ratio_c, _, scale, extra = self._chunk(
+                chunk, weight, dead, num_dead, None if selections is None else selections[ci],
+                None if batch_selects is None else batch_selects[ci])
             tie, ratio = max(tie, tie_c), max(ratio, ratio_c)
+            if batch_mode:
+                th = extra["theta"]
+                th_sum += th
+                dth_sum += U * abs(th_sum)                      # the float32 running sum of the chunks' thetas
+                n_sat += extra["n_saturated"]
+                lengths.append(extra["lengths"])
+                if "threshold_folded_once_per_batch" not in self.mut:
+                    self._fold(th)
+            for g in range(Gn):
+                nf[g] += extra["nested_fvu"][g]
+                dnf[g] += extra["dnested_fvu"][g] + U * abs(nf[g])
+                groups_min[g] = min(groups_min[g], extra["groups"][g])
+            if Gn:
+                empty_first += extra["empty_first"]
             for n in stats:
                 stats[n] += st[n]
                 dstats[n] += dst[n] + U * abs(stats[n])
@@ -398,6 +659,12 @@ class TrainerRef:
         for n in stats:
             stats[n] /= len(chunks)
             dstats[n] = SAFETY * (dstats[n] / len(chunks) + U * abs(stats[n]))
+        for g in range(Gn):
+            nf[g] /= len(chunks)
+            dnf[g] = SAFETY * (dnf[g] / len(chunks) + U * abs(nf[g]))
+        theta = th_sum / len(chunks) if batch_mode else 0.0
+        if batch_mode and "threshold_folded_once_per_batch" in self.mut:
+            self._fold(theta)
         if "tokens_in_step_reset_every_batch" in self.mut:
             self.num_tokens_in_step = 0
         self.num_tokens_in_step += x.shape[0]
@@ -428,6 +695,13 @@ class TrainerRef:
                           dsumsq=SAFETY * dS, clip=c, stats=stats, dstats=dstats,
                           dead_mask=dead if dead is not None else torch.zeros(self.N, dtype=torch.bool), num_dead=num_dead,
                           scale=scale, tie_share=tie, sel_ratio=ratio)
+        if batch_mode:
+            res.theta, res.dtheta = theta, SAFETY * (dth_sum / len(chunks) + U * abs(theta))
+            res.threshold, res.dthreshold = self.threshold, SAFETY * self.dthreshold
+            res.n_saturated, res.lengths = n_sat, torch.cat(lengths)
+        if Gn:
+            res.nested_fvu, res.dnested_fvu = tuple(nf), tuple(dnf)
+            res.groups_min, res.empty_first = tuple(groups_min), empty_first
         if stepped:
             res.G, res.dG = G_in, {n: SAFETY * g for n, g in dG_in.items()}
             if cfg.normalize_decoder and not proj_first and update:
@@ -447,6 +721,20 @@ class TrainerRef:
             res.dG = {n: SAFETY * g for n, g in self.dG.items()}
         res.num_tokens_since_fired = self.num_tokens_since_fired.clone()
         return res
+
+    def _fold(self, theta: float) -> None:
+        """One chunk's theta into the threshold state: the first finite theta is copied (the state starts at -1), after that
+        thr += threshold_lr * (theta - thr); a non-finite theta is skipped.  Bound: the subtract, the product with the float32
+        value of the rate and the add are one rounding each, 4 u (|thr| + |theta|) on top of the state's own bound (which
+        the update contracts by 1 - rate: carried uncontracted)."""
+        if theta != theta or theta in (float("inf"), float("-inf")):
+            return
+        if self.threshold < 0 and "threshold_first_value_averaged" not in self.mut:
+            self.threshold, self.dthreshold = theta, 0.0
+            return
+        thr = self.threshold + self.cfg.threshold_lr * (theta - self.threshold)
+        self.dthreshold += 4 * U * (abs(thr) + abs(theta) + abs(self.threshold))
+        self.threshold = thr
 
     def _project(self) -> None:
         """remove_gradient_parallel_to_decoder_directions (sae.py:257-271) on the window's W_dec gradient."""
@@ -478,6 +766,7 @@ class Scenario:
     nnz: int = 8                       # nonzero coordinates per token
     weak: int = 0                      # features (the last ones) too short ever to fire
     start_dead: int = 0                # of those, how many start above the dead threshold
+    start_old: int = 0                 # ordinary features that start ONE token into their count: one silent window kills them
 
 
 def make_params(sc: Scenario) -> Dict[str, torch.Tensor]:
@@ -521,10 +810,17 @@ def start_dead_features(sc: Scenario) -> torch.Tensor:
     return sc.N - sc.weak + torch.randperm(sc.weak, generator=g)[:sc.start_dead]
 
 
-def _sc(name, d, N, tokens, scales, seed, nnz, weak, start_dead=0, **cfg) -> Scenario:
+def start_old_features(sc: Scenario) -> torch.Tensor:
+    """Ordinary (not weak) features whose count starts at 1: with dead_feature_threshold = one window's tokens they cross it
+    after the first optimiser step unless they fire before it -- while a feature that starts at 0 needs two silent windows."""
+    g = torch.Generator().manual_seed(sc.seed + 3)
+    return torch.randperm(sc.N - sc.weak, generator=g)[:sc.start_old]
+
+
+def _sc(name, d, N, tokens, scales, seed, nnz, weak, start_dead=0, start_old=0, **cfg) -> Scenario:
     cfg.setdefault("k", 16)
     cfg.setdefault("lr", 2e-4)
-    return Scenario(name, d, N, TrainerConfig(**cfg), tuple(tokens), tuple(scales), seed, nnz, weak, start_dead)
+    return Scenario(name, d, N, TrainerConfig(**cfg), tuple(tokens), tuple(scales), seed, nnz, weak, start_dead, start_old)
 
 
 def scenario(name: str, normalize_decoder: bool = True, small: bool = False) -> Scenario:
@@ -546,14 +842,39 @@ def scenario(name: str, normalize_decoder: bool = True, small: bool = False) -> 
     if name == "batch_sizes":
         assert not small
         return _sc(name, 1024, 8192, [512, 200, 512, 8, 300], [1, 0.03, 1, 1, 1], 404, 8, 40, k=k)
+    # "batchtopk" and matryoshka.  The small forms keep the ratios: C = 4 k and C = 2 k, bounds off the multiples of 64
+    bounds, wts = ((20, 65, N), (0.5, 0.0, 0.25)) if small else ((300, 2049, N), (0.5, 0.0, 0.25))
+    if name == "batchtopk":
+        return _sc(name, d, N, [T] * 5, [1, 0.03, 1, 1, 0.03], 101, nnz, weak, k=k, lr_warmup_steps=2, total_steps=6,
+                   activation="batchtopk", cap=4 * k)
+    if name == "batchtopk_saturated":
+        Ta = T + 3
+        return _sc(name, d, N, [Ta] * 4, [1, 0.03, 0.03, 1], 303, nnz, weak, start_dead=5 if small else 50,
+                   start_old=12 if small else 240, k=k, activation="batchtopk", cap=2 * k, auxk_alpha=1.0 / 32,
+                   dead_feature_threshold=2 * Ta, micro_acc_steps=2, grad_acc_steps=2, lr_warmup_steps=1, total_steps=4)
+    if name == "matryoshka":
+        return _sc(name, d, N, [T] * 5, [1, 0.03, 1, 1, 0.03], 101, nnz, weak, k=k, lr_warmup_steps=2, total_steps=6,
+                   normalize_decoder=normalize_decoder, matryoshka=bounds, matryoshka_weights=wts)
+    if name == "matryoshka_auxk":
+        return _sc(name, d, N, [T] * 5, [1, 1, 0.03, 1, 0.03], 303, nnz, weak, start_dead=5 if small else 50, k=k,
+                   auxk_alpha=1.0 / 32, dead_feature_threshold=8 * T, lr_warmup_steps=2, total_steps=6, matryoshka=bounds,
+                   matryoshka_weights=wts)
+    if name == "matryoshka_batchtopk":
+        Ta = T + 3
+        return _sc(name, d, N, [Ta] * 6, [1, 0.01, 1, 1, 0.01, 1], 202, nnz, weak, k=k, micro_acc_steps=2, grad_acc_steps=2,
+                   lr_warmup_steps=1, total_steps=4, activation="batchtopk", cap=4 * k, matryoshka=bounds,
+                   matryoshka_weights=wts)
     raise ValueError(name)
 
 
 def initial_counts(sc: Scenario) -> torch.Tensor:
-    """num_tokens_since_fired at the start: three batches' worth on the features that start dead."""
+    """num_tokens_since_fired at the start: one batch above the threshold on the features that start dead (three batches'
+    worth where the threshold is two), 1 on the old ones."""
     c = torch.zeros(sc.N, dtype=torch.long)
     if sc.start_dead:
-        c[start_dead_features(sc)] = 3 * sc.tokens[0]
+        c[start_dead_features(sc)] = sc.cfg.dead_feature_threshold + sc.tokens[0]
+    if sc.start_old:
+        c[start_old_features(sc)] = 1
     return c
 
 
