@@ -689,7 +689,8 @@ int msae_topk_map_i64_f32(const float *latents, int T, int M, int k, int ld, con
  *   5. Only the first k + E entries of a row are read: the result does not depend on kk beyond kk >= k + E, nor on T or
  *      on the other tokens of the call.
  *   6. The `status` of the underlying encode describes the result unchanged (the kernel does not touch it). */
-enum { MSAE_EDIT_SET = 0, MSAE_EDIT_ZERO = 1 };
+enum { MSAE_EDIT_SET = 0, MSAE_EDIT_ZERO = 1,
+       MSAE_EDIT_SCALE = 2, MSAE_EDIT_ADD = 3, MSAE_EDIT_FLOOR = 4, MSAE_EDIT_CAP = 5 };   /* the valued forms below only */
 int msae_edit_topk_f32(const float *vals_in, const int32_t *idx_in, int T, int kk, const int32_t *edit_feat,
                        const float *edit_val, const int32_t *edit_kind, int E, int N, int k, float *vals, int32_t *idx,
                        void *stream);
@@ -731,6 +732,60 @@ int msae_edit_topk_rows_i64_f32(const float *vals_in, const int64_t *idx_in, int
                                 const int32_t *group_off, int G, const int32_t *edit_feat, const float *edit_val,
                                 const int32_t *edit_kind, int E_total, int E_max, int N, int k, float *vals, int64_t *idx,
                                 uint8_t *edited, void *stream);
+
+/* ---- value-dependent edits (FeatureEdits(scale=, add=, floor=, cap=)) ------------------------------
+ * SET and ZERO ignore the feature's activation.  The four kinds below are functions of it: amplify a feature where it
+ * fires, add to it, keep it above or below a bound.  With c = L[t][f] the exact post-ReLU latent (msae_pre_acts_f32's bits)
+ * and v = edit_val[e]:
+ *   kind               L'[t][f]                      gain = dL'/dL * [c > 0]
+ *   MSAE_EDIT_SET      v                             0
+ *   MSAE_EDIT_ZERO     +0                            0
+ *   MSAE_EDIT_SCALE    c * v   (one f32 multiply)    v * [c > 0]
+ *   MSAE_EDIT_ADD      c + v   (one f32 add)         [c > 0]
+ *   MSAE_EDIT_FLOOR    fmaxf(c, v)                   [c > 0 && c >= v]
+ *   MSAE_EDIT_CAP      fminf(c, v)                   [c > 0 && c <= v]      (torch.clamp's convention at the tie)
+ * The list alone cannot supply c: a feature outside a token's first k + E entries has an unknown value <= the last entry's,
+ * and an increasing edit can lift it into the top-k.  The valued forms therefore take, beside the arguments of
+ * msae_edit_topk_f32 / msae_edit_topk_rows_f32 (same meaning, same MSAE_EINVAL cases):
+ *   cur f32 [T][ld_cur]           the edited features' exact latents: msae_pre_acts_features_f32's output (relu = 1) over
+ *                                 the table's features; ld_cur >= 1
+ *   edit_col int32 [E] / [E_total] or NULL   the column of `cur` that table entry e reads (rows form: e counts through the
+ *                                 concatenated arrays); NULL: entry e reads column e.  Clamped into [0, ld_cur) before use.
+ *   gain f32 [T][k] or NULL       per output slot: 1.0 for a slot that came from an unedited list entry, the table's gain
+ *                                 (above) for a slot that came from a table entry
+ * Asynchronous on `stream`; allocates nothing, never synchronises, needs no workspace.  MSAE_EINVAL in addition: cur null,
+ * ld_cur < 1.
+ * Contract:
+ *   1. The output is the canonical top-k (value descending, index ascending) of L' -- bit-identical to msae_topk_f32 on
+ *      the edited dense latents for finite pre-activations.  A result <= 0 follows point 3 of "set-valued hook edits": it
+ *      ranks by the key rule and a negative one is never selected, so a negative ADD or SCALE ablates the feature wherever
+ *      it drives the value to 0 or below.
+ *   2. A table holding only SET / ZERO entries gives msae_edit_topk_f32's / msae_edit_topk_rows_f32's bits; `cur` is then
+ *      not read (gain: 0 at the table's slots, 1 elsewhere).
+ *   3. Only the first k + E (k + E_g) entries of a row are read.  Of `cur`, only row t's columns named by the
+ *      value-dependent entries of token t's own table are read: other columns, and the padding up to ld_cur, may hold
+ *      anything.
+ *   4. Nothing is indexed by a list entry's feature.  No device id, offset or column is trusted: a hostile one can give a
+ *      wrong row for that token, not an out-of-bounds access.
+ *   5. A kind outside [0, 5] reads as SET, as the unvalued kernels read any kind but ZERO.
+ *   6. Rows form: an unedited token (group id outside [0, G), or an empty group) copies its first k entries, gain 1.
+ *   7. Layout, LDS and launch shapes are the unvalued kernels': the same three kernels instantiated with VALUED = true. */
+int msae_edit_topk_valued_f32(const float *vals_in, const int32_t *idx_in, int T, int kk, const int32_t *edit_feat,
+                              const float *edit_val, const int32_t *edit_kind, int E, int N, int k, const float *cur,
+                              int ld_cur, const int32_t *edit_col, float *vals, int32_t *idx, float *gain, void *stream);
+int msae_edit_topk_valued_i64_f32(const float *vals_in, const int64_t *idx_in, int T, int kk, const int32_t *edit_feat,
+                                  const float *edit_val, const int32_t *edit_kind, int E, int N, int k, const float *cur,
+                                  int ld_cur, const int32_t *edit_col, float *vals, int64_t *idx, float *gain, void *stream);
+int msae_edit_topk_rows_valued_f32(const float *vals_in, const int32_t *idx_in, int T, int kk, const int32_t *group_of,
+                                   const int32_t *group_off, int G, const int32_t *edit_feat, const float *edit_val,
+                                   const int32_t *edit_kind, int E_total, int E_max, int N, int k, const float *cur,
+                                   int ld_cur, const int32_t *edit_col, float *vals, int32_t *idx, uint8_t *edited,
+                                   float *gain, void *stream);
+int msae_edit_topk_rows_valued_i64_f32(const float *vals_in, const int64_t *idx_in, int T, int kk, const int32_t *group_of,
+                                       const int32_t *group_off, int G, const int32_t *edit_feat, const float *edit_val,
+                                       const int32_t *edit_kind, int E_total, int E_max, int N, int k, const float *cur,
+                                       int ld_cur, const int32_t *edit_col, float *vals, int64_t *idx, uint8_t *edited,
+                                       float *gain, void *stream);
 
 /* ---- error-preserving interventions (Sae.intervene) ------------------------------------------------
  * out = x + (decode(edited list) - decode(plain list)): the hidden state keeps the SAE's reconstruction error and moves by

@@ -33,6 +33,16 @@
 //     n_sort = next_pow2(k + 2 E_g) <= the launch's; LDS 8 n_sort + 4 E_max bytes, 80 KiB at the envelope as above.
 // `edited` (optional) marks the output slots whose feature is in the token's table: every surviving list entry's is not, so
 // those are exactly the slots that came from an edit entry.
+//
+// VALUE-DEPENDENT EDITS (msae_edit_topk_valued_f32 / msae_edit_topk_rows_valued_f32): SCALE, ADD, FLOOR
+// and CAP are functions of the feature's own latent c = L[t][f].  The list cannot supply c -- a feature outside the first
+// k + E entries has an unknown value, and an increasing edit may lift it into the top-k -- so the caller passes the edited
+// features' exact latents `cur` (msae_pre_acts_features_f32's columns).  With them the set above becomes
+//     {list entries whose feature is not edited}  u  {(L'[t][f], f): every table entry},
+// the same k + 2 E keys, and the argument stands word for word: it never used what an edit's value IS, only that every
+// edited feature's value is known.  The three kernels are templated on VALUED; <false> is the code above, <true> reads
+// `cur` at the entries whose kind depends on it and (optionally) writes each slot's gain dL'/dL * [c > 0], 1 for a slot that
+// came from the list.
 #include <algorithm>
 
 #include "common.h"
@@ -53,11 +63,55 @@ __device__ __forceinline__ int edit_find(const int32_t *feat, int E, int f) {
   return (lo < E && feat[lo] == f) ? lo : -1;
 }
 
-template <typename IDX>
+// the valued forms' extra arguments; the <false> instantiations get an empty one and never look at it
+struct EditCur {
+  const float *cur = nullptr;          // [T][ld_cur] the edited features' exact latents
+  int ld_cur = 0;
+  const int32_t *col = nullptr;        // [E] / [E_total] the column of `cur` entry e reads; null: column e
+  float *gain = nullptr;               // [T][k] or null
+};
+
+__device__ __forceinline__ bool edit_kind_valued(int kind) {
+  return (unsigned)(kind - MSAE_EDIT_SCALE) <= (unsigned)(MSAE_EDIT_CAP - MSAE_EDIT_SCALE);
+}
+
+// c = L[t][feature of table entry e] for a kind that depends on it (the column clamped into [0, ld_cur)); other kinds
+// read nothing
+template <bool VALUED>
+__device__ __forceinline__ float edit_current(const EditCur &a, size_t t, int e, int kind) {
+  if (!VALUED || !edit_kind_valued(kind)) return 0.f;
+  const int c = min(max(a.col ? a.col[e] : e, 0), a.ld_cur - 1);
+  return a.cur[t * (size_t)a.ld_cur + c];
+}
+
+// L'[t][f] of a table entry: one f32 operation on c (include/msae.h); a kind outside the known ones reads as SET
+template <bool VALUED>
+__device__ __forceinline__ float edit_value(int kind, float v, float c) {
+  if (kind == MSAE_EDIT_ZERO) return 0.f;
+  if (VALUED) {
+    if (kind == MSAE_EDIT_SCALE) return c * v;
+    if (kind == MSAE_EDIT_ADD) return c + v;
+    if (kind == MSAE_EDIT_FLOOR) return fmaxf(c, v);
+    if (kind == MSAE_EDIT_CAP) return fminf(c, v);
+  }
+  return v;
+}
+
+// dL'/dL * [c > 0] of a table entry (torch.clamp's convention at the tie)
+__device__ __forceinline__ float edit_gain(int kind, float v, float c) {
+  const bool on = c > 0.f;
+  if (kind == MSAE_EDIT_SCALE) return on ? v : 0.f;
+  if (kind == MSAE_EDIT_ADD) return on ? 1.f : 0.f;
+  if (kind == MSAE_EDIT_FLOOR) return (on && c >= v) ? 1.f : 0.f;
+  if (kind == MSAE_EDIT_CAP) return (on && c <= v) ? 1.f : 0.f;
+  return 0.f;
+}
+
+template <typename IDX, bool VALUED>
 __global__ __launch_bounds__(ET_MAX_THREADS) void edit_topk_kernel(
     const float *__restrict__ vals_in, const IDX *__restrict__ idx_in, int kk, const int32_t *__restrict__ edit_feat,
     const float *__restrict__ edit_val, const int32_t *__restrict__ edit_kind, int E, int k, int n_sort,
-    float *__restrict__ vals, IDX *__restrict__ idx) {
+    float *__restrict__ vals, IDX *__restrict__ idx, EditCur ec) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long et_smem[];
   unsigned long long *keys = et_smem;                               // [n_sort]
   int32_t *feat = reinterpret_cast<int32_t *>(keys + n_sort);       // [E]
@@ -72,34 +126,41 @@ __global__ __launch_bounds__(ET_MAX_THREADS) void edit_topk_kernel(
       const int f = (int)idx_in[t * kk + j];
       if (edit_find(feat, E, f) < 0) key = rank_key(vals_in[t * kk + j], f);
     } else if (j < L + E) {
-      const int e = j - L;
-      key = rank_key(edit_kind[e] == MSAE_EDIT_ZERO ? 0.f : edit_val[e], feat[e]);
+      const int e = j - L, kind = edit_kind[e];
+      key = rank_key(edit_value<VALUED>(kind, edit_val[e], edit_current<VALUED>(ec, t, e, kind)), feat[e]);
     }
     keys[j] = key;
   }
   bitonic_sort_desc_u64<0>(keys, n_sort, threadIdx.x);              // run-time thread count (barriers before and after)
   for (int j = threadIdx.x; j < k; j += blockDim.x) {
     const unsigned long long key = keys[j];
+    const int f = rank_key_index(key);
     vals[t * k + j] = rank_key_value(key);
-    idx[t * k + j] = (IDX)rank_key_index(key);
+    idx[t * k + j] = (IDX)f;
+    if (VALUED && ec.gain) {
+      const int e = edit_find(feat, E, f);
+      const int kind = e < 0 ? 0 : edit_kind[e];
+      ec.gain[t * k + j] = e < 0 ? 1.f : edit_gain(kind, edit_val[e], edit_current<VALUED>(ec, t, e, kind));
+    }
   }
 }
 
-template <typename IDX>
+template <typename IDX, bool VALUED>
 int edit_topk_impl(const float *vals_in, const IDX *idx_in, int T, int kk, const int32_t *edit_feat, const float *edit_val,
-                   const int32_t *edit_kind, int E, int N, int k, float *vals, IDX *idx, void *stream) {
+                   const int32_t *edit_kind, int E, int N, int k, float *vals, IDX *idx, const EditCur &ec, void *stream) {
   if (T < 0 || N <= 0 || k < 1 || E < 1) return MSAE_EINVAL;
+  if (VALUED && (!ec.cur || ec.ld_cur < 1)) return MSAE_EINVAL;
   if ((long long)k + E > ET_MAX_SEL || (long long)k + E > N || kk < k + E) return MSAE_EINVAL;
   if (!vals_in || !idx_in || !edit_feat || !edit_val || !edit_kind || !vals || !idx) return MSAE_EINVAL;
   if (T == 0) return 0;
   const int n_sort = next_pow2(k + 2 * E);                          // <= 8192
   const int threads = std::min(ET_MAX_THREADS, std::max(MSAE_WAVE, n_sort / 2));
   const size_t smem = (size_t)n_sort * sizeof(unsigned long long) + (size_t)E * sizeof(int32_t);
-  auto kern = edit_topk_kernel<IDX>;
+  auto kern = edit_topk_kernel<IDX, VALUED>;
   if (smem > 64 * 1024)
     MSAE_HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
   hipLaunchKernelGGL(kern, dim3(T), dim3(threads), smem, (hipStream_t)stream, vals_in, idx_in, kk, edit_feat, edit_val,
-                     edit_kind, E, k, n_sort, vals, idx);
+                     edit_kind, E, k, n_sort, vals, idx, ec);
   return msae_launch_status();
 }
 
@@ -128,30 +189,41 @@ __device__ __forceinline__ bool edit_has(const int32_t *feat, int E, int f) {
   return edit_find(feat, E, f) >= 0;
 }
 
+// position of f in feat[0 .. E) (strictly ascending), or -1: edit_has's two routes
+__device__ __forceinline__ int edit_pos(const int32_t *feat, int E, int f) {
+  if (E <= ET_SCAN_MAX) {
+    int pos = -1;
+    for (int e = 0; e < E; ++e) pos = (feat[e] == f) ? e : pos;
+    return pos;
+  }
+  return edit_find(feat, E, f);
+}
+
 template <typename IDX>
 __device__ __forceinline__ void edit_copy_row(const float *__restrict__ vals_in, const IDX *__restrict__ idx_in, size_t t, int kk,
                                               int k, float *__restrict__ vals, IDX *__restrict__ idx,
-                                              uint8_t *__restrict__ edited, int tid, int nt) {
+                                              uint8_t *__restrict__ edited, float *__restrict__ gain, int tid, int nt) {
   for (int j = tid; j < k; j += nt) {
     vals[t * k + j] = vals_in[t * kk + j];
     idx[t * k + j] = idx_in[t * kk + j];
     if (edited) edited[t * k + j] = 0;
+    if (gain) gain[t * k + j] = 1.f;
   }
 }
 
-template <typename IDX, int R>
+template <typename IDX, int R, bool VALUED>
 __global__ __launch_bounds__(ET_ROWS_WAVES * MSAE_WAVE) void edit_topk_rows_wave_kernel(
     const float *__restrict__ vals_in, const IDX *__restrict__ idx_in, int T, int kk, const int32_t *__restrict__ group_of,
     const int32_t *__restrict__ group_off, int G, const int32_t *__restrict__ edit_feat, const float *__restrict__ edit_val,
     const int32_t *__restrict__ edit_kind, int E_total, int E_max, int k, float *__restrict__ vals, IDX *__restrict__ idx,
-    uint8_t *__restrict__ edited) {
+    uint8_t *__restrict__ edited, EditCur ec) {
   const int lane = threadIdx.x & (MSAE_WAVE - 1);
   const size_t t = (size_t)blockIdx.x * ET_ROWS_WAVES + (size_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / MSAE_WAVE));
   if (t >= (size_t)T) return;                                       // (no barrier anywhere in this kernel)
   int first;
   const int E = __builtin_amdgcn_readfirstlane(edit_slice(group_of, group_off, t, G, E_total, E_max, first));
   if (E == 0) {
-    edit_copy_row(vals_in, idx_in, t, kk, k, vals, idx, edited, lane, MSAE_WAVE);
+    edit_copy_row(vals_in, idx_in, t, kk, k, vals, idx, edited, VALUED ? ec.gain : nullptr, lane, MSAE_WAVE);
     return;
   }
   first = __builtin_amdgcn_readfirstlane(first);
@@ -166,8 +238,8 @@ __global__ __launch_bounds__(ET_ROWS_WAVES * MSAE_WAVE) void edit_topk_rows_wave
       const int f = (int)idx_in[t * kk + j];
       if (!edit_has(feat, E, f)) key = rank_key(vals_in[t * kk + j], f);
     } else if (j < L + E) {
-      const int e = first + (j - L);
-      key = rank_key(edit_kind[e] == MSAE_EDIT_ZERO ? 0.f : edit_val[e], edit_feat[e]);
+      const int e = first + (j - L), kind = edit_kind[e];
+      key = rank_key(edit_value<VALUED>(kind, edit_val[e], edit_current<VALUED>(ec, t, e, kind)), edit_feat[e]);
     }
     v[r] = key;
   }
@@ -180,16 +252,21 @@ __global__ __launch_bounds__(ET_ROWS_WAVES * MSAE_WAVE) void edit_topk_rows_wave
       vals[t * k + j] = rank_key_value(v[r]);
       idx[t * k + j] = (IDX)f;
       if (edited) edited[t * k + j] = edit_has(feat, E, f) ? 1 : 0;
+      if (VALUED && ec.gain) {
+        const int p = edit_pos(feat, E, f), e = first + max(p, 0);
+        const int kind = p < 0 ? 0 : edit_kind[e];
+        ec.gain[t * k + j] = p < 0 ? 1.f : edit_gain(kind, edit_val[e], edit_current<VALUED>(ec, t, e, kind));
+      }
     }
   }
 }
 
-template <typename IDX>
+template <typename IDX, bool VALUED>
 __global__ __launch_bounds__(ET_MAX_THREADS) void edit_topk_rows_wg_kernel(
     const float *__restrict__ vals_in, const IDX *__restrict__ idx_in, int kk, const int32_t *__restrict__ group_of,
     const int32_t *__restrict__ group_off, int G, const int32_t *__restrict__ edit_feat, const float *__restrict__ edit_val,
     const int32_t *__restrict__ edit_kind, int E_total, int E_max, int k, int n_sort, float *__restrict__ vals,
-    IDX *__restrict__ idx, uint8_t *__restrict__ edited) {
+    IDX *__restrict__ idx, uint8_t *__restrict__ edited, EditCur ec) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long et_smem[];
   unsigned long long *keys = et_smem;                               // [n_sort]
   int32_t *feat = reinterpret_cast<int32_t *>(keys + n_sort);       // [E_max]
@@ -197,7 +274,7 @@ __global__ __launch_bounds__(ET_MAX_THREADS) void edit_topk_rows_wg_kernel(
   int first;
   const int E = edit_slice(group_of, group_off, t, G, E_total, E_max, first);   // uniform over the workgroup
   if (E == 0) {
-    edit_copy_row(vals_in, idx_in, t, kk, k, vals, idx, edited, threadIdx.x, blockDim.x);
+    edit_copy_row(vals_in, idx_in, t, kk, k, vals, idx, edited, VALUED ? ec.gain : nullptr, threadIdx.x, blockDim.x);
     return;
   }
   const int L = k + E;
@@ -210,8 +287,8 @@ __global__ __launch_bounds__(ET_MAX_THREADS) void edit_topk_rows_wg_kernel(
       const int f = (int)idx_in[t * kk + j];
       if (edit_find(feat, E, f) < 0) key = rank_key(vals_in[t * kk + j], f);
     } else if (j < L + E) {
-      const int e = j - L;
-      key = rank_key(edit_kind[first + e] == MSAE_EDIT_ZERO ? 0.f : edit_val[first + e], feat[e]);
+      const int e = j - L, kind = edit_kind[first + e];
+      key = rank_key(edit_value<VALUED>(kind, edit_val[first + e], edit_current<VALUED>(ec, t, first + e, kind)), feat[e]);
     }
     keys[j] = key;
   }
@@ -221,16 +298,23 @@ __global__ __launch_bounds__(ET_MAX_THREADS) void edit_topk_rows_wg_kernel(
     const int f = rank_key_index(key);
     vals[t * k + j] = rank_key_value(key);
     idx[t * k + j] = (IDX)f;
-    if (edited) edited[t * k + j] = edit_find(feat, E, f) >= 0 ? 1 : 0;
+    const int p = edit_find(feat, E, f);
+    if (edited) edited[t * k + j] = p >= 0 ? 1 : 0;
+    if (VALUED && ec.gain) {
+      const int e = first + max(p, 0);
+      const int kind = p < 0 ? 0 : edit_kind[e];
+      ec.gain[t * k + j] = p < 0 ? 1.f : edit_gain(kind, edit_val[e], edit_current<VALUED>(ec, t, e, kind));
+    }
   }
 }
 
-template <typename IDX>
+template <typename IDX, bool VALUED>
 int edit_topk_rows_impl(const float *vals_in, const IDX *idx_in, int T, int kk, const int32_t *group_of,
                         const int32_t *group_off, int G, const int32_t *edit_feat, const float *edit_val,
                         const int32_t *edit_kind, int E_total, int E_max, int N, int k, float *vals, IDX *idx, uint8_t *edited,
-                        void *stream) {
+                        const EditCur &ec, void *stream) {
   if (T < 0 || G < 1 || k < 1 || E_max < 1 || E_total < 0) return MSAE_EINVAL;
+  if (VALUED && (!ec.cur || ec.ld_cur < 1)) return MSAE_EINVAL;
   if ((long long)k + E_max > ET_MAX_SEL || (long long)k + E_max > N || kk < k + E_max) return MSAE_EINVAL;
   if (!vals_in || !idx_in || !group_of || !group_off || !edit_feat || !edit_val || !edit_kind || !vals || !idx)
     return MSAE_EINVAL;
@@ -240,8 +324,8 @@ int edit_topk_rows_impl(const float *vals_in, const IDX *idx_in, int T, int kk, 
   if (n_sort <= 256) {
     const dim3 grid((unsigned)(((long long)T + ET_ROWS_WAVES - 1) / ET_ROWS_WAVES)), block(ET_ROWS_WAVES * MSAE_WAVE);
 #define ET_ROWS_LAUNCH(R)                                                                                                 \
-  hipLaunchKernelGGL((edit_topk_rows_wave_kernel<IDX, R>), grid, block, 0, st, vals_in, idx_in, T, kk, group_of, group_off, G, \
-                     edit_feat, edit_val, edit_kind, E_total, E_max, k, vals, idx, edited)
+  hipLaunchKernelGGL((edit_topk_rows_wave_kernel<IDX, R, VALUED>), grid, block, 0, st, vals_in, idx_in, T, kk, group_of,   \
+                     group_off, G, edit_feat, edit_val, edit_kind, E_total, E_max, k, vals, idx, edited, ec)
     if (n_sort <= 64) ET_ROWS_LAUNCH(1);
     else if (n_sort <= 128) ET_ROWS_LAUNCH(2);
     else ET_ROWS_LAUNCH(4);
@@ -250,11 +334,11 @@ int edit_topk_rows_impl(const float *vals_in, const IDX *idx_in, int T, int kk, 
   }
   const int threads = std::min(ET_MAX_THREADS, std::max(MSAE_WAVE, n_sort / 2));
   const size_t smem = (size_t)n_sort * sizeof(unsigned long long) + (size_t)E_max * sizeof(int32_t);
-  auto kern = edit_topk_rows_wg_kernel<IDX>;
+  auto kern = edit_topk_rows_wg_kernel<IDX, VALUED>;
   if (smem > 64 * 1024)
     MSAE_HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
   hipLaunchKernelGGL(kern, dim3(T), dim3(threads), smem, st, vals_in, idx_in, kk, group_of, group_off, G, edit_feat, edit_val,
-                     edit_kind, E_total, E_max, k, n_sort, vals, idx, edited);
+                     edit_kind, E_total, E_max, k, n_sort, vals, idx, edited, ec);
   return msae_launch_status();
 }
 
@@ -264,26 +348,67 @@ extern "C" int msae_edit_topk_rows_f32(const float *vals_in, const int32_t *idx_
                                        const int32_t *group_off, int G, const int32_t *edit_feat, const float *edit_val,
                                        const int32_t *edit_kind, int E_total, int E_max, int N, int k, float *vals,
                                        int32_t *idx, uint8_t *edited, void *stream) {
-  return edit_topk_rows_impl<int32_t>(vals_in, idx_in, T, kk, group_of, group_off, G, edit_feat, edit_val, edit_kind, E_total,
-                                      E_max, N, k, vals, idx, edited, stream);
+  return edit_topk_rows_impl<int32_t, false>(vals_in, idx_in, T, kk, group_of, group_off, G, edit_feat, edit_val, edit_kind,
+                                             E_total, E_max, N, k, vals, idx, edited, EditCur{}, stream);
 }
 
 extern "C" int msae_edit_topk_rows_i64_f32(const float *vals_in, const int64_t *idx_in, int T, int kk, const int32_t *group_of,
                                            const int32_t *group_off, int G, const int32_t *edit_feat, const float *edit_val,
                                            const int32_t *edit_kind, int E_total, int E_max, int N, int k, float *vals,
                                            int64_t *idx, uint8_t *edited, void *stream) {
-  return edit_topk_rows_impl<int64_t>(vals_in, idx_in, T, kk, group_of, group_off, G, edit_feat, edit_val, edit_kind, E_total,
-                                      E_max, N, k, vals, idx, edited, stream);
+  return edit_topk_rows_impl<int64_t, false>(vals_in, idx_in, T, kk, group_of, group_off, G, edit_feat, edit_val, edit_kind,
+                                             E_total, E_max, N, k, vals, idx, edited, EditCur{}, stream);
 }
 
 extern "C" int msae_edit_topk_f32(const float *vals_in, const int32_t *idx_in, int T, int kk, const int32_t *edit_feat,
                                   const float *edit_val, const int32_t *edit_kind, int E, int N, int k, float *vals,
                                   int32_t *idx, void *stream) {
-  return edit_topk_impl<int32_t>(vals_in, idx_in, T, kk, edit_feat, edit_val, edit_kind, E, N, k, vals, idx, stream);
+  return edit_topk_impl<int32_t, false>(vals_in, idx_in, T, kk, edit_feat, edit_val, edit_kind, E, N, k, vals, idx, EditCur{},
+                                        stream);
 }
 
 extern "C" int msae_edit_topk_i64_f32(const float *vals_in, const int64_t *idx_in, int T, int kk, const int32_t *edit_feat,
                                       const float *edit_val, const int32_t *edit_kind, int E, int N, int k, float *vals,
                                       int64_t *idx, void *stream) {
-  return edit_topk_impl<int64_t>(vals_in, idx_in, T, kk, edit_feat, edit_val, edit_kind, E, N, k, vals, idx, stream);
+  return edit_topk_impl<int64_t, false>(vals_in, idx_in, T, kk, edit_feat, edit_val, edit_kind, E, N, k, vals, idx, EditCur{},
+                                        stream);
+}
+
+// ---- value-dependent edits: the same kernels with the edited features' exact latents ---------------------------------------
+extern "C" int msae_edit_topk_valued_f32(const float *vals_in, const int32_t *idx_in, int T, int kk, const int32_t *edit_feat,
+                                         const float *edit_val, const int32_t *edit_kind, int E, int N, int k,
+                                         const float *cur, int ld_cur, const int32_t *edit_col, float *vals, int32_t *idx,
+                                         float *gain, void *stream) {
+  return edit_topk_impl<int32_t, true>(vals_in, idx_in, T, kk, edit_feat, edit_val, edit_kind, E, N, k, vals, idx,
+                                       EditCur{cur, ld_cur, edit_col, gain}, stream);
+}
+
+extern "C" int msae_edit_topk_valued_i64_f32(const float *vals_in, const int64_t *idx_in, int T, int kk,
+                                             const int32_t *edit_feat, const float *edit_val, const int32_t *edit_kind, int E,
+                                             int N, int k, const float *cur, int ld_cur, const int32_t *edit_col, float *vals,
+                                             int64_t *idx, float *gain, void *stream) {
+  return edit_topk_impl<int64_t, true>(vals_in, idx_in, T, kk, edit_feat, edit_val, edit_kind, E, N, k, vals, idx,
+                                       EditCur{cur, ld_cur, edit_col, gain}, stream);
+}
+
+extern "C" int msae_edit_topk_rows_valued_f32(const float *vals_in, const int32_t *idx_in, int T, int kk,
+                                              const int32_t *group_of, const int32_t *group_off, int G,
+                                              const int32_t *edit_feat, const float *edit_val, const int32_t *edit_kind,
+                                              int E_total, int E_max, int N, int k, const float *cur, int ld_cur,
+                                              const int32_t *edit_col, float *vals, int32_t *idx, uint8_t *edited, float *gain,
+                                              void *stream) {
+  return edit_topk_rows_impl<int32_t, true>(vals_in, idx_in, T, kk, group_of, group_off, G, edit_feat, edit_val, edit_kind,
+                                            E_total, E_max, N, k, vals, idx, edited, EditCur{cur, ld_cur, edit_col, gain},
+                                            stream);
+}
+
+extern "C" int msae_edit_topk_rows_valued_i64_f32(const float *vals_in, const int64_t *idx_in, int T, int kk,
+                                                  const int32_t *group_of, const int32_t *group_off, int G,
+                                                  const int32_t *edit_feat, const float *edit_val, const int32_t *edit_kind,
+                                                  int E_total, int E_max, int N, int k, const float *cur, int ld_cur,
+                                                  const int32_t *edit_col, float *vals, int64_t *idx, uint8_t *edited,
+                                                  float *gain, void *stream) {
+  return edit_topk_rows_impl<int64_t, true>(vals_in, idx_in, T, kk, group_of, group_off, G, edit_feat, edit_val, edit_kind,
+                                            E_total, E_max, N, k, vals, idx, edited, EditCur{cur, ld_cur, edit_col, gain},
+                                            stream);
 }

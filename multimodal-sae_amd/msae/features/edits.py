@@ -7,7 +7,9 @@ The reference's hooks edit the dense latents with torch indexing, so the feature
 
 `Sae.encode(x, edits=FeatureEdits(...))` applies such a set without the dense [T, N] latents: the unedited fused encode
 over-fetches k + E entries per token and `ops.edit_topk` (csrc/edit_topk.hip) drops the edited features from each list,
-adds the edits' own (value, feature) pairs and re-ranks -- exact, DESIGN.md section 7d.
+adds the edits' own (value, feature) pairs and re-ranks -- exact, DESIGN.md section 7d.  Beside SET and ZERO an entry
+may SCALE, ADD to, FLOOR or CAP the feature's own latent (section 7p): the encode then passes the edited features' exact
+latents (`ops.pre_acts_features`) to the same kernels' valued form.
 
 Everything host-side happens ONCE, here: range checks, duplicates, the merge of the two lists (a feature in both is
 zeroed: the oracle applies set, then zero), the sort, and one upload of the three device arrays.  Afterwards nothing is
@@ -22,6 +24,9 @@ import torch
 from torch import Tensor
 
 EDIT_SET, EDIT_ZERO = 0, 1          # include/msae.h: MSAE_EDIT_SET / MSAE_EDIT_ZERO
+EDIT_SCALE, EDIT_ADD, EDIT_FLOOR, EDIT_CAP = 2, 3, 4, 5     # MSAE_EDIT_SCALE ..: functions of the feature's own latent
+VALUE_KINDS = {"scale": EDIT_SCALE, "add": EDIT_ADD, "floor": EDIT_FLOOR, "cap": EDIT_CAP}
+EDIT_MODES = ("set",) + tuple(VALUE_KINDS)                  # the hooks' `mode`
 MAX_SELECTED = 4096                 # k + E: msae_encode_topk's own limit on k
 
 
@@ -52,45 +57,61 @@ def _float_list(values) -> list:
     return [float(v) for v in values]
 
 
+def _valued_pairs(spec, what: str) -> Tuple[list, list]:
+    """A mapping feature -> parameter, or a (features, values) pair -> (features, values) of one length."""
+    if isinstance(spec, Mapping):
+        feats, vals = _int_list(list(spec.keys()), what), _float_list(list(spec.values()))
+    else:
+        try:
+            f_in, v_in = spec
+        except (TypeError, ValueError):
+            raise ValueError(f"FeatureEdits: {what} must be a mapping feature -> value or a (features, values) pair") from None
+        feats, vals = _int_list(f_in, what), _float_list(v_in)
+    if len(feats) != len(vals):
+        raise ValueError(f"FeatureEdits: {what} has {len(feats)} features and {len(vals)} values")
+    return feats, vals
+
+
 class FeatureEdits:
-    """FeatureEdits(num_latents, set=None, zero=None, device="cuda")
+    """FeatureEdits(num_latents, set=None, zero=None, device="cuda", scale=None, add=None, floor=None, cap=None)
 
     set   a mapping feature -> value, or a (features, values) pair of equal-length sequences / tensors
     zero  an int, or any iterable / tensor of features
-    A feature named in both is zeroed.  Errors (ValueError): a feature outside [0, num_latents), a feature twice in `set`,
-    a non-finite set value, nothing to edit, more than 4095 distinct features.  Duplicates inside `zero` are harmless (the
-    reference's `mask[:, off_features] = 0` accepts them) and collapse.
+    scale / add / floor / cap   like `set`; the parameter v of an edit that depends on the feature's own latent c:
+          c * v, c + v, max(c, v), min(c, v) -- amplify a feature where it fires, instead of
+          lighting it up at every position
+    A feature named in `zero` and anywhere else is zeroed.  Errors (ValueError): a feature outside [0, num_latents), a
+    feature twice among set / scale / add / floor / cap (inside one of them or across two), a non-finite value, nothing to
+    edit, more than 4095 distinct features.  Duplicates inside `zero` are harmless (the reference's
+    `mask[:, off_features] = 0` accepts them) and collapse.
 
     Attributes: E (distinct edited features), features (their sorted tuple), num_latents, device; the device arrays
-    feat / val / kind [E] that ops.edit_topk takes; mask (bool [num_latents], True at every edited feature, built on the
-    device at first use: the backward of the differentiable encode masks those latents' gradients)."""
+    feat / val / kind [E] that ops.edit_topk takes; value_dependent (does any entry need the feature's latent?); mask (bool
+    [num_latents], True at every edited feature, built on the device at first use: the backward of the differentiable
+    encode masks those latents' gradients)."""
 
     def __init__(self, num_latents: int, set: Union[Mapping, Tuple, None] = None, zero: Optional[Iterable] = None,
-                 device: Union[str, torch.device] = "cuda"):
+                 device: Union[str, torch.device] = "cuda", scale: Union[Mapping, Tuple, None] = None,
+                 add: Union[Mapping, Tuple, None] = None, floor: Union[Mapping, Tuple, None] = None,
+                 cap: Union[Mapping, Tuple, None] = None):
         self.num_latents = int(num_latents)
-        table = {}
-        if set is not None:
-            if isinstance(set, Mapping):
-                feats, vals = _int_list(list(set.keys()), "set"), _float_list(list(set.values()))
-            else:
-                try:
-                    f_in, v_in = set
-                except (TypeError, ValueError):
-                    raise ValueError("FeatureEdits: set must be a mapping feature -> value or a (features, values) pair") from None
-                feats, vals = _int_list(f_in, "set"), _float_list(v_in)
-            if len(feats) != len(vals):
-                raise ValueError(f"FeatureEdits: set has {len(feats)} features and {len(vals)} values")
-            for f, v in zip(feats, vals):
+        table, named = {}, {}
+        for what, kind, spec in (("set", EDIT_SET, set), ("scale", EDIT_SCALE, scale), ("add", EDIT_ADD, add),
+                                 ("floor", EDIT_FLOOR, floor), ("cap", EDIT_CAP, cap)):
+            if spec is None:
+                continue
+            for f, v in zip(*_valued_pairs(spec, what)):
                 if f in table:
-                    raise ValueError(f"FeatureEdits: feature {f} appears twice in set")
+                    raise ValueError(f"FeatureEdits: feature {f} appears twice in {what}" if named[f] == what else
+                                     f"FeatureEdits: feature {f} appears in both {named[f]} and {what}")
                 if not np.isfinite(v):
-                    raise ValueError(f"FeatureEdits: set value of feature {f} is not finite ({v})")
-                table[f] = (EDIT_SET, v)
+                    raise ValueError(f"FeatureEdits: {what} value of feature {f} is not finite ({v})")
+                table[f], named[f] = (kind, v), what
         if zero is not None:
             for f in _int_list(zero, "zero"):
-                table[f] = (EDIT_ZERO, 0.0)                      # ZERO over SET
+                table[f] = (EDIT_ZERO, 0.0)                      # ZERO over everything else
         if not table:
-            raise ValueError("FeatureEdits: nothing to edit (set and zero are both empty)")
+            raise ValueError("FeatureEdits: nothing to edit (every argument is empty)")
         bad = [f for f in table if not 0 <= f < self.num_latents]
         if bad:
             raise ValueError(f"FeatureEdits: features must lie in [0, {self.num_latents}), got {sorted(bad)[:8]}")
@@ -100,6 +121,7 @@ class FeatureEdits:
         self.E = len(self.features)
         self.kinds = tuple(table[f][0] for f in self.features)       # host copies: tests, repr
         self.values = tuple(table[f][1] for f in self.features)
+        self.value_dependent = any(kd >= EDIT_SCALE for kd in self.kinds)
         # one buffer, one copy: int32 [3, E] = features, value bits, kinds
         host = np.empty((3, self.E), dtype=np.int32)
         host[0] = self.features
@@ -138,7 +160,9 @@ class FeatureEdits:
 
     def __repr__(self) -> str:
         n_zero = sum(1 for kd in self.kinds if kd == EDIT_ZERO)
-        return f"FeatureEdits(num_latents={self.num_latents}, E={self.E}: {self.E - n_zero} set, {n_zero} zero)"
+        n_dep = sum(1 for kd in self.kinds if kd >= EDIT_SCALE)
+        return (f"FeatureEdits(num_latents={self.num_latents}, E={self.E}: {self.E - n_zero - n_dep} set, {n_zero} zero" +
+                (f", {n_dep} value-dependent)" if n_dep else ")"))
 
 
 class RowEdits:
@@ -155,7 +179,10 @@ class RowEdits:
 
     Attributes: G, E_max (the longest group), E_total, num_latents, device, tables (host copy: per group a
     (features, values, kinds) triple of tuples, features ascending); the device arrays offsets int32 [G + 1], feat int32 / val f32 / kind int32 [E_total] that
-    ops.edit_topk_rows takes."""
+    ops.edit_topk_rows takes.  A spec also takes FeatureEdits' scale / add / floor / cap; for those entries: value_dependent,
+    union (int32 device tensor: the sorted distinct features of the value-dependent entries of all groups -- the columns of
+    the one ops.pre_acts_features pass an encode runs) and col (int32 [E_total]: each entry's position in union, 0 for an
+    entry that reads no latent)."""
 
     def __init__(self, num_latents: int, groups, device: Union[str, torch.device] = "cuda"):
         self.num_latents = int(num_latents)
@@ -170,9 +197,10 @@ class RowEdits:
                     raise ValueError(f"RowEdits: group {g} was built for num_latents = {spec.num_latents}, not {self.num_latents}")
                 fe = spec
             elif isinstance(spec, Mapping):
-                if not set(spec) <= {"set", "zero"}:
-                    raise ValueError(f"RowEdits: group {g}: a spec has the keys 'set' and 'zero', got {sorted(map(str, spec))}")
-                fe = FeatureEdits(self.num_latents, set=spec.get("set"), zero=spec.get("zero"), device="cpu")
+                if not set(spec) <= {"set", "zero", *VALUE_KINDS}:
+                    raise ValueError(f"RowEdits: group {g}: a spec has the keys 'set', 'zero', 'scale', 'add', 'floor' and "
+                                     f"'cap', got {sorted(map(str, spec))}")
+                fe = FeatureEdits(self.num_latents, device="cpu", **{key: spec.get(key) for key in spec})
             else:
                 raise ValueError(f"RowEdits: group {g} must be a FeatureEdits, a dict(set=..., zero=...) or None, got "
                                  f"{type(spec).__name__}")
@@ -187,20 +215,27 @@ class RowEdits:
         self.E_total = len(feats)
         self.E_max = max(b - a for a, b in zip(offsets[:-1], offsets[1:]))
         self.tables = tuple((tuple(feats[a:b]), tuple(vals[a:b]), tuple(kinds[a:b])) for a, b in zip(offsets[:-1], offsets[1:]))
-        # one buffer, one copy: int32 [G + 1 + 3 E_total] = offsets, features, value bits, kinds
-        G1, E = self.G + 1, self.E_total
-        host = np.empty(G1 + 3 * E, dtype=np.int32)
+        # the value-dependent entries' features, once each: the columns of the one `cur` pass an encode runs for all groups
+        union = sorted({f for f, kd in zip(feats, kinds) if kd >= EDIT_SCALE})
+        where = {f: c for c, f in enumerate(union)}
+        self.value_dependent = bool(union)
+        # one buffer, one copy: int32 [G + 1 + 4 E_total + U] = offsets, features, value bits, kinds, columns, union
+        G1, E, U = self.G + 1, self.E_total, len(union)
+        host = np.empty(G1 + 4 * E + U, dtype=np.int32)
         host[:G1] = offsets
         host[G1:G1 + E] = feats
         host[G1 + E:G1 + 2 * E] = np.asarray(vals, dtype=np.float32).view(np.int32)
-        host[G1 + 2 * E:] = kinds
+        host[G1 + 2 * E:G1 + 3 * E] = kinds
+        host[G1 + 3 * E:G1 + 4 * E] = [where[f] if kd >= EDIT_SCALE else 0 for f, kd in zip(feats, kinds)]
+        host[G1 + 4 * E:] = union
         self.device = torch.device(device)
         buf = torch.from_numpy(host)
         if self.device.type == "cuda":
             buf = buf.pin_memory().to(self.device, non_blocking=True)
         self._buf = buf
-        self.offsets, self.feat, self.kind = buf[:G1], buf[G1:G1 + E], buf[G1 + 2 * E:]
+        self.offsets, self.feat, self.kind = buf[:G1], buf[G1:G1 + E], buf[G1 + 2 * E:G1 + 3 * E]
         self.val = buf[G1 + E:G1 + 2 * E].view(torch.float32)
+        self.col, self.union = buf[G1 + 3 * E:G1 + 4 * E], buf[G1 + 4 * E:]
 
     def check(self, num_latents: int, k: int, device=None) -> None:
         """Raise ValueError unless this object fits an encode of `num_latents` features selecting k."""

@@ -17,7 +17,7 @@ import torch
 from torch import Tensor
 
 from ..sae import Sae
-from .edits import FeatureEdits, RowEdits, as_off_features
+from .edits import EDIT_MODES, FeatureEdits, RowEdits, as_off_features
 
 
 def _topk_sae_only(sae, what: str) -> None:
@@ -189,8 +189,17 @@ class _DecodeStepGraph:
         self.keep = (sae._prepared_weights(), ops._WS.get((h.device, side.cuda_stream)), side)
 
 
-def _steering_edits(sae, feature, k: float):
-    """`feature` of clamp_features_max -> (set_feature for the in-kernel scalar route or -1, FeatureEdits or None)."""
+def _check_mode(mode, what: str) -> str:
+    if mode not in EDIT_MODES:
+        raise ValueError(f"{what}: mode must be one of {EDIT_MODES}, got {mode!r}")
+    return mode
+
+
+def _steering_edits(sae, feature, k: float, mode: str = "set"):
+    """`feature` of clamp_features_max -> (set_feature for the in-kernel scalar route or -1, FeatureEdits or None).  A mode
+    other than "set" (scale / add / floor / cap: `k` is the edit's parameter) always takes the
+    FeatureEdits route: the in-kernel scalar edit is a SET."""
+    _check_mode(mode, "clamp_features_max")
     if isinstance(feature, FeatureEdits):
         return -1, feature
     if isinstance(feature, Mapping):
@@ -199,16 +208,18 @@ def _steering_edits(sae, feature, k: float):
         table = {int(f): float(k) for f in feature.reshape(-1).tolist()}
     elif isinstance(feature, (list, tuple, range)) or (hasattr(feature, "__iter__") and not isinstance(feature, Tensor)):
         table = {int(f): float(k) for f in feature}
-    else:
+    elif mode == "set":
         return int(feature), None                   # today's path, unchanged
+    else:
+        table = {int(feature): float(k)}
     if not isinstance(sae, Sae):
-        raise NotImplementedError("clamping a set of features runs on the single-GPU msae.Sae only: a feature-sharded "
-                                  "engine takes one feature")
-    return -1, FeatureEdits(sae.num_latents, set=table, device=sae.device)
+        raise NotImplementedError("clamping a set of features, and every mode but 'set', runs on the single-GPU msae.Sae "
+                                  "only: a feature-sharded engine sets one feature")
+    return -1, FeatureEdits(sae.num_latents, device=sae.device, **{mode: table})
 
 
 def clamp_features_max(sae, feature, hooked_module: torch.nn.Module, k: float = 10, graph_step: Optional[bool] = None,
-                       preserve_error: bool = False):
+                       preserve_error: bool = False, mode: str = "set"):
     """Register the steering hook (steering.py:102-128): on prefill (S != 1) the feature's latent
     is set to `k` before TopK; every call replaces the layer output by the fp16 reconstruction.
     `feature`: an int (the in-kernel edit), a sequence or tensor of ints (`latents[:, :, f] = k` with a list: all
@@ -218,16 +229,19 @@ def clamp_features_max(sae, feature, hooked_module: torch.nn.Module, k: float = 
     `graph_step`: replay the S = 1 step from a captured HIP graph (_DecodeStepGraph); default: on for a single-GPU `Sae`
     under no_grad unless MSAE_HOOK_GRAPH=0.
     `preserve_error` (single-GPU `Sae` only): the prefill output is h + the decoded EDIT in h's own
-    dtype (`Sae.intervene`), the S = 1 steps return the layer output unchanged -- no SAE call, no captured graph."""
+    dtype (`Sae.intervene`), the S = 1 steps return the layer output unchanged -- no SAE call, no captured graph.
+    `mode` (single-GPU `Sae` only unless "set"): what `k`, or a mapping's value, does to the feature's
+    own latent c on prefill -- "set" (c := k, the reference's clamp), "scale" (c k), "add" (c + k), "floor" (max(c, k)),
+    "cap" (min(c, k)); it applies to an int, a sequence or a mapping, not to a prebuilt FeatureEdits."""
     import os
 
     _topk_sae_only(sae, "clamp_features_max")
     if preserve_error:
-        return _clamp_preserving(sae, hooked_module, _preserving_edits(sae, feature, k))
+        return _clamp_preserving(sae, hooked_module, _preserving_edits(sae, feature, k, mode))
     if graph_step is None:
         graph_step = os.environ.get("MSAE_HOOK_GRAPH", "1") not in ("0", "")
     step_graph = _DecodeStepGraph() if (graph_step and isinstance(sae, Sae)) else None
-    set_feature, edits = _steering_edits(sae, feature, k)
+    set_feature, edits = _steering_edits(sae, feature, k, mode)
 
     def hook(module, _, outputs):
         h = outputs[0] if isinstance(outputs, tuple) else outputs
@@ -246,12 +260,12 @@ def clamp_features_max(sae, feature, hooked_module: torch.nn.Module, k: float = 
     return [handle]
 
 
-def _preserving_edits(sae, feature, k: float) -> FeatureEdits:
+def _preserving_edits(sae, feature, k: float, mode: str = "set") -> FeatureEdits:
     """`feature` of clamp_features_max(preserve_error=True) -> the FeatureEdits of the prefill, built once."""
     if not isinstance(sae, Sae):
         raise NotImplementedError("preserve_error runs on the single-GPU msae.Sae only: a feature-sharded engine "
                                   "reconstructs (preserve_error=False)")
-    set_feature, edits = _steering_edits(sae, feature, k)
+    set_feature, edits = _steering_edits(sae, feature, k, mode)
     return edits if edits is not None else _scalar_edits(sae, set_feature, float(k), -1)
 
 
@@ -273,21 +287,21 @@ def _clamp_preserving(sae, hooked_module: torch.nn.Module, edits):
     return [handle]
 
 
-def _row_spec(element, k: float):
+def _row_spec(element, k: float, mode: str = "set"):
     """One element of clamp_features_rows' `features` -> a RowEdits group (None, a FeatureEdits or a dict spec)."""
     if element is None or isinstance(element, FeatureEdits):
         return element
     if isinstance(element, Mapping):
-        return {"set": element}
+        return {mode: element}
     if isinstance(element, Tensor):
         element = element.reshape(-1).tolist()
     if isinstance(element, (list, tuple, range)):
-        return {"set": {int(f): float(k) for f in element}} if len(element) else None
-    return {"set": {int(element): float(k)}}
+        return {mode: {int(f): float(k) for f in element}} if len(element) else None
+    return {mode: {int(element): float(k)}}
 
 
 def clamp_features_rows(sae, features: Sequence, hooked_module: torch.nn.Module, k: float = 10,
-                        graph_step: Optional[bool] = None, preserve_error: bool = False):
+                        graph_step: Optional[bool] = None, preserve_error: bool = False, mode="set"):
     """The steering hook for a BATCH whose rows steer different features: `features` has one element
     per batch row -- an int, a list of ints (all clamped to `k`), a mapping feature -> value, or None for an unedited row
     (the batch's baseline).  On prefill (S != 1) row b's latents are clamped per element b before TopK; every call replaces
@@ -295,7 +309,8 @@ def clamp_features_rows(sae, features: Sequence, hooked_module: torch.nn.Module,
     RowEdits.  The S = 1 step of the batch ([B, 1, d], no edit) replays from a captured HIP graph like clamp_features_max's
     (`graph_step`: default on under no_grad unless MSAE_HOOK_GRAPH=0).  Single-GPU `Sae` only.  The prefill's batch size
     must equal len(features) (ValueError).  `preserve_error`: as in clamp_features_max -- row b's prefill output is
-    h[b] + its decoded edit, a row of None and every S = 1 step keep the layer's output bit for bit."""
+    h[b] + its decoded edit, a row of None and every S = 1 step keep the layer's output bit for bit.  `mode`: as in
+    clamp_features_max, one string for every row or a sequence with one string per row."""
     import os
 
     if not isinstance(sae, Sae):
@@ -306,7 +321,13 @@ def clamp_features_rows(sae, features: Sequence, hooked_module: torch.nn.Module,
         raise ValueError("clamp_features_rows: features must be a sequence with one element per batch row")
     if graph_step is None:
         graph_step = os.environ.get("MSAE_HOOK_GRAPH", "1") not in ("0", "")
-    edits = RowEdits(sae.num_latents, [_row_spec(f, k) for f in features], device=sae.device)
+    if isinstance(mode, str):
+        modes = [_check_mode(mode, "clamp_features_rows")] * len(features)
+    else:
+        modes = [_check_mode(m, "clamp_features_rows") for m in mode]
+        if len(modes) != len(features):
+            raise ValueError(f"clamp_features_rows: {len(features)} rows of features, {len(modes)} modes")
+    edits = RowEdits(sae.num_latents, [_row_spec(f, k, m) for f, m in zip(features, modes)], device=sae.device)
     if preserve_error:
         return _clamp_preserving(sae, hooked_module, edits)
     step_graph = _DecodeStepGraph() if graph_step else None

@@ -10,6 +10,7 @@ from typing import List
 import torch
 
 from ..sae import Sae
+from .edits import EDIT_MODES
 from .hooks import clamp_features_max, clamp_features_rows
 
 
@@ -22,11 +23,20 @@ class SteeringController:
     the default B = 1, which runs the reference's loop unchanged.  The rows share one prompt.
     `preserve_error` (single-GPU `Sae` only): the hooks add the decoded clamp to the layer's own output
     instead of replacing it by the reconstruction, so `clamped_resps` differs from `original_resps` -- the un-hooked model --
-    by the edit alone."""
+    by the edit alone.
+    `mode` (single-GPU `Sae` only unless "set"): what `k` does to the steered feature's own latent c on
+    the prompt -- "set" (the reference's clamp, at every position), "scale" (c k: amplify it where it fires), "add",
+    "floor", "cap"."""
 
     def __init__(self, sae, module_name: str, feature_idx: List[int], model, processor,
                  prompt: str, image_path: str = None, k: float = 50, batch_features: int = 1,
-                 preserve_error: bool = False):
+                 preserve_error: bool = False, mode: str = "set"):
+        if mode not in EDIT_MODES:
+            raise ValueError(f"mode must be one of {EDIT_MODES}, got {mode!r}")
+        if mode != "set" and not isinstance(sae, Sae):
+            raise NotImplementedError(f"mode={mode!r} runs on the single-GPU msae.Sae only: a feature-sharded engine sets "
+                                      "one feature")
+        self.mode = mode
         if int(batch_features) < 1:
             raise ValueError(f"batch_features must be >= 1, got {batch_features}")
         if int(batch_features) > 1 and not isinstance(sae, Sae):
@@ -55,9 +65,10 @@ class SteeringController:
         self.inputs = processor(images=self.image, text=self.prompt, return_tensors="pt").to(model.device)
 
     def clamp_features_max(self, sae, feature: int, hooked_module, k: float = 10):
+        kw = {} if self.mode == "set" else {"mode": self.mode}
         if self.preserve_error:
-            return clamp_features_max(sae, feature, hooked_module, k=k, preserve_error=True)
-        return clamp_features_max(sae, feature, hooked_module, k=k)
+            return clamp_features_max(sae, feature, hooked_module, k=k, preserve_error=True, **kw)
+        return clamp_features_max(sae, feature, hooked_module, k=k, **kw)
 
     def _generate(self) -> str:
         kw = {}
@@ -103,7 +114,8 @@ class SteeringController:
         for lo in range(0, len(feats), B):
             chunk = feats[lo:lo + B]                 # (a short last chunk generates a smaller batch)
             handles = clamp_features_rows(self.sae, chunk, self.hooked_module, k=self.k,
-                                          **({"preserve_error": True} if self.preserve_error else {}))
+                                          **({"preserve_error": True} if self.preserve_error else {}),
+                                          **({} if self.mode == "set" else {"mode": self.mode}))
             try:
                 texts = self._generate_rows(len(chunk))
             finally:

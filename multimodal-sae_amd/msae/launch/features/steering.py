@@ -37,7 +37,13 @@ def parse_argument(argv=None):
                    help="(new) add the decoded clamp to the layer's own output instead of replacing it by the SAE "
                         "reconstruction: the steered generation differs from the original by the edit alone.  Not with "
                         "--shard-sae")
+    p.add_argument("--steer-mode", "--steer_mode", default="set", choices=["set", "scale", "add", "floor", "cap"],
+                   help="(new) what --clamp-value does to the steered feature's own activation c on the prompt: set (the "
+                        "reference's clamp, at every position), scale (c * value: amplify it where it fires), add, floor, "
+                        "cap.  Anything but set runs on the single-GPU Sae: not with --shard-sae")
     args = p.parse_args(argv)
+    if args.steer_mode != "set" and args.shard_sae:
+        p.error("--steer-mode other than set runs on the single-GPU Sae: it cannot be combined with --shard-sae")
     if args.batch_features < 1:
         p.error("--batch-features must be >= 1")
     if args.batch_features > 1 and args.shard_sae:
@@ -71,7 +77,8 @@ def main(argv=None):
         result = SteeringController(sae=engine, module_name=module_name, feature_idx=feature_idx,
                                     prompt=args.text, model=model, processor=processor,
                                     image_path=args.image_path, k=args.clamp_value,
-                                    batch_features=args.batch_features, preserve_error=args.preserve_error).run()
+                                    batch_features=args.batch_features, preserve_error=args.preserve_error,
+                                    **({} if args.steer_mode == "set" else {"mode": args.steer_mode})).run()
         if ddp and not shard:
             gathered = [None] * world
             dist.gather_object(result, gathered if rank == 0 else None, dst=0)

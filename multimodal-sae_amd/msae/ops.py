@@ -913,21 +913,155 @@ def _(vals_in, idx_in, edit_feat, edit_val, edit_kind, num_latents, k):
 
 
 def edit_topk(vals_in: Tensor, idx_in: Tensor, edit_feat: Tensor, edit_val: Tensor, edit_kind: Tensor, num_latents: int,
-              k: int) -> Tuple[Tensor, Tensor]:
+              k: int, *, cur: Optional[Tensor] = None, col: Optional[Tensor] = None, want_gain: bool = False):
     """The canonical top-k of the EDITED latents from an unedited top-kk list -> (vals f32 [..., k], idx [..., k] in
     idx_in's dtype, int32 or int64).  vals_in / idx_in [..., kk]: encode_topk's output for kk >= k + E without edits;
     edit_feat int [E] strictly ascending in [0, num_latents), edit_val f32 [E], edit_kind int [E] (0 set, 1 zero) -- the
     arrays of a msae.features.FeatureEdits.  Exact: include/msae.h, "set-valued hook edits".  Nothing is read back; the
-    arguments the library would refuse (kk < k + E, k + E > num_latents, k + E > 4096, E < 1) raise ValueError here."""
+    arguments the library would refuse (kk < k + E, k + E > num_latents, k + E > 4096, E < 1) raise ValueError here.
+    cur (f32 [..., C]: the edited features' exact latents, `pre_acts_features` over edit_feat) selects the VALUED form
+    (include/msae.h, "value-dependent edits"): kinds 2 scale, 3 add, 4 floor, 5 cap read column col[e] (int32 [E]; None:
+    column e) of their token's row; want_gain=True appends gain f32 [..., k], the factor of each slot's gradient.  CPU
+    tensors take a plain-torch host path in the valued form."""
     E, kk = edit_feat.numel(), vals_in.shape[-1]
     if E < 1 or k < 1 or kk < k + E or k + E > num_latents or k + E > EDIT_TOPK_MAX_SELECTED:
         raise ValueError(f"edit_topk: need E >= 1, k >= 1, kk >= k + E and k + E <= min(num_latents, {EDIT_TOPK_MAX_SELECTED}); "
                          f"got kk = {kk}, k = {k}, E = {E}, num_latents = {num_latents}")
     _no_grad_inputs("ops.edit_topk", vals_in, edit_val)
-    return _edit_topk(vals_in, idx_in, edit_feat, edit_val, edit_kind, num_latents, k)
+    if cur is None:
+        if col is not None or want_gain:
+            raise ValueError("edit_topk: col= and want_gain= belong to the valued form: pass cur= as well")
+        return _edit_topk(vals_in, idx_in, edit_feat, edit_val, edit_kind, num_latents, k)
+    _check_cur("edit_topk", vals_in, idx_in, cur, col, E)
+    _no_grad_inputs("ops.edit_topk", cur)
+    if not vals_in.is_cuda:
+        lead = vals_in.shape[:-1]
+        cols = torch.arange(E) if col is None else col.long()
+        v, i, g, _ = _edit_topk_valued_host(vals_in.reshape(-1, kk).float(), idx_in.reshape(-1, kk), edit_feat, edit_val,
+                                            edit_kind, cur.reshape(-1, cur.shape[-1]).float(), cols, k)
+        vals, idx, gain = v.reshape(*lead, k), i.reshape(*lead, k), g.reshape(*lead, k)
+    else:
+        vals, idx, gain = _edit_topk_valued(vals_in, idx_in, edit_feat, edit_val, edit_kind, cur, col, num_latents, k,
+                                            want_gain)
+    return (vals, idx, gain) if want_gain else (vals, idx)
+
+
+# ---- value-dependent edits: scale, add, floor, cap (msae_edit_topk_valued_*, DESIGN.md section 7p) ---------------------------
+def _check_cur(what: str, vals_in: Tensor, idx_in: Tensor, cur, col, n_entries: int) -> None:
+    if vals_in.shape != idx_in.shape:
+        raise ValueError(f"{what}: vals_in {tuple(vals_in.shape)} and idx_in {tuple(idx_in.shape)} must share a shape")
+    if idx_in.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{what}: idx_in must be int32 or int64, got {idx_in.dtype}")
+    if not isinstance(cur, Tensor) or cur.dtype != torch.float32:
+        raise ValueError(f"{what}: cur must be a float32 tensor (ops.pre_acts_features' output)")
+    if cur.dim() != vals_in.dim() or tuple(cur.shape[:-1]) != tuple(vals_in.shape[:-1]) or cur.shape[-1] < 1:
+        raise ValueError(f"{what}: cur must have shape {tuple(vals_in.shape[:-1])} + (C,) with C >= 1, got {tuple(cur.shape)}")
+    if cur.device != vals_in.device:
+        raise ValueError(f"{what}: cur lives on {cur.device}, the list on {vals_in.device}")
+    if col is not None and (not isinstance(col, Tensor) or col.dtype not in (torch.int32, torch.int64) or
+                            col.numel() != n_entries):
+        raise ValueError(f"{what}: col must be an int32 or int64 tensor with one column per table entry ({n_entries})")
+
+
+def _cur_rows(cur: Tensor) -> Tuple[Tensor, int]:
+    """cur [..., C] -> (a [T, C] tensor the kernels can read, its row stride): the column-sliced view that
+    pre_acts_features returns is passed as it is, anything else is copied."""
+    C = cur.shape[-1]
+    c2 = cur.detach()
+    try:
+        c2 = c2.view(-1, C)
+    except RuntimeError:
+        c2 = c2.reshape(-1, C).contiguous()
+    T = c2.shape[0]
+    ld = c2.stride(0) if T > 1 else C
+    room = c2.untyped_storage().nbytes() // 4 - c2.storage_offset()
+    if c2.stride(1) != 1 or ld < C or T * ld > room:
+        c2, ld = c2.contiguous(), C
+    return c2, ld
+
+
+def _edit_topk_valued_host(v_in: Tensor, i_in: Tensor, feat: Tensor, val: Tensor, kind: Tensor, cur: Tensor, cols: Tensor,
+                           k: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """The valued list edit of ONE table in plain torch: v_in / i_in [T, kk], feat / val / kind [E], cur [T, C], cols int64
+    [E] -> (vals [T, k], idx [T, k], gain [T, k], edited bool [T, k]).  The same candidate set as the kernel -- the first
+    k + E entries minus the edited features', plus one entry per table row -- ordered by three stable sorts (index
+    ascending, value descending with -0 folded onto +0, dropped entries last)."""
+    T, E, C = v_in.shape[0], feat.numel(), cur.shape[1]
+    feat, kind, val = feat.long(), kind.long(), val.float()
+    c = cur[:, cols.clamp(0, C - 1)]                                        # [T, E]
+    v = val[None].expand(T, E)
+    new = torch.where(kind == 1, torch.zeros_like(c), v)                    # ZERO, and SET for every other kind ...
+    new = torch.where(kind == 2, c * v, new)
+    new = torch.where(kind == 3, c + v, new)
+    new = torch.where(kind == 4, torch.maximum(c, v), new)
+    new = torch.where(kind == 5, torch.minimum(c, v), new)
+    on = c > 0
+    one, zero = torch.ones_like(c), torch.zeros_like(c)
+    gain = torch.where(kind == 2, torch.where(on, v, zero), zero)
+    gain = torch.where(kind == 3, torch.where(on, one, zero), gain)
+    gain = torch.where(kind == 4, torch.where(on & (c >= v), one, zero), gain)
+    gain = torch.where(kind == 5, torch.where(on & (c <= v), one, zero), gain)
+    L = k + E
+    lv, li = v_in[:, :L], i_in[:, :L].long()
+    dropped = torch.isin(li, feat)
+    cand_v = torch.cat([lv, new], 1)
+    cand_v = torch.where(cand_v == 0, torch.zeros_like(cand_v), cand_v)     # the rank key folds -0 onto +0
+    cand_i = torch.cat([li, feat[None].expand(T, E)], 1)
+    cand_g = torch.cat([torch.ones_like(lv), gain], 1)
+    cand_e = torch.cat([torch.zeros_like(dropped), torch.ones(T, E, dtype=torch.bool)], 1)
+    cand_d = torch.cat([dropped, torch.zeros(T, E, dtype=torch.bool)], 1)
+    order = torch.sort(cand_i, dim=1, stable=True).indices
+    order = order.gather(1, torch.sort(cand_v.gather(1, order), dim=1, descending=True, stable=True).indices)
+    order = order.gather(1, torch.sort(cand_d.gather(1, order).to(torch.uint8), dim=1, stable=True).indices)[:, :k]
+    return (cand_v.gather(1, order), cand_i.gather(1, order).to(i_in.dtype), cand_g.gather(1, order),
+            cand_e.gather(1, order))
+
+
+@torch.library.custom_op("msae::edit_topk_valued", mutates_args=())
+def _edit_topk_valued(vals_in: Tensor, idx_in: Tensor, edit_feat: Tensor, edit_val: Tensor, edit_kind: Tensor, cur: Tensor,
+                      col: Optional[Tensor], num_latents: int, k: int, want_gain: bool) -> Tuple[Tensor, Tensor, Tensor]:
+    dev = _hip.require_device(vals_in, idx_in, edit_feat, edit_val, edit_kind, cur, col)
+    lib = _hip.load()
+    E, kk = edit_feat.numel(), vals_in.shape[-1]
+    assert edit_val.numel() == E and edit_kind.numel() == E, "the edit table's three arrays must have one length"
+    v_in = _f32c(vals_in)
+    i_in = idx_in.detach().contiguous()
+    ef = edit_feat.detach().to(torch.int32).contiguous()
+    ev = _f32c(edit_val)
+    ek = edit_kind.detach().to(torch.int32).contiguous()
+    ec = None if col is None else col.detach().to(torch.int32).contiguous()
+    T = v_in.numel() // max(kk, 1)
+    c2, ld = _cur_rows(cur)
+    assert c2.shape[0] == T, f"cur must hold one row per token ({T}), got {tuple(cur.shape)}"
+    vals = torch.empty(*v_in.shape[:-1], k, dtype=torch.float32, device=dev)
+    idx = torch.empty(*v_in.shape[:-1], k, dtype=i_in.dtype, device=dev)
+    gain = torch.empty(*v_in.shape[:-1], k if want_gain else 0, dtype=torch.float32, device=dev)
+    wide = i_in.dtype == torch.int64
+    fn, name = (lib.msae_edit_topk_valued_i64_f32, "msae_edit_topk_valued_i64_f32") if wide else \
+        (lib.msae_edit_topk_valued_f32, "msae_edit_topk_valued_f32")
+    with torch.cuda.device(dev):
+        _hip.check(fn(_hip.ptr(v_in), _hip.ptr(i_in), T, kk, _hip.ptr(ef), _hip.ptr(ev), _hip.ptr(ek), E, num_latents, k,
+                      _hip.ptr(c2), ld, _hip.ptr(ec), _hip.ptr(vals), _hip.ptr(idx),
+                      _hip.ptr(gain) if want_gain else None, _hip.stream_of(v_in)), name)
+    return vals, idx, gain
+
+
+@_edit_topk_valued.register_fake
+def _(vals_in, idx_in, edit_feat, edit_val, edit_kind, cur, col, num_latents, k, want_gain):
+    return (vals_in.new_empty(*vals_in.shape[:-1], k, dtype=torch.float32),
+            idx_in.new_empty(*idx_in.shape[:-1], k),
+            vals_in.new_empty(*vals_in.shape[:-1], k if want_gain else 0, dtype=torch.float32))
 
 
 # ---- the same with one edit table per token (msae_edit_topk_rows_*, DESIGN.md section 7g) ------------------------------------
+def _group_ids(group_of: Tensor, G: int) -> Tensor:
+    """The tokens' group ids as the contiguous int32 the kernels read."""
+    go = group_of.detach()
+    if go.dtype != torch.int32:         # an id beyond int32 must stay outside [0, G): clamp on the device, then narrow
+        go = go.clamp(-1, G).to(torch.int32)
+    return go.contiguous()
+
+
 @torch.library.custom_op("msae::edit_topk_rows", mutates_args=())
 def _edit_topk_rows(vals_in: Tensor, idx_in: Tensor, group_of: Tensor, group_off: Tensor, edit_feat: Tensor,
                     edit_val: Tensor, edit_kind: Tensor, e_max: int, num_latents: int, k: int,
@@ -943,10 +1077,7 @@ def _edit_topk_rows(vals_in: Tensor, idx_in: Tensor, group_of: Tensor, group_off
     i_in = idx_in.detach().contiguous()
     T = v_in.numel() // max(kk, 1)
     assert group_of.numel() == T, f"group_of must hold one id per token ({T}), got {tuple(group_of.shape)}"
-    go = group_of.detach()
-    if go.dtype != torch.int32:         # an id beyond int32 must stay outside [0, G): clamp on the device, then narrow
-        go = go.clamp(-1, G).to(torch.int32)
-    go = go.contiguous()
+    go = _group_ids(group_of, G)
     gf = group_off.detach().to(torch.int32).contiguous()
     ef = edit_feat.detach().to(torch.int32).contiguous()
     ev = _f32c(edit_val)
@@ -971,14 +1102,82 @@ def _(vals_in, idx_in, group_of, group_off, edit_feat, edit_val, edit_kind, e_ma
             vals_in.new_empty(*vals_in.shape[:-1], k if want_mask else 0, dtype=torch.uint8))
 
 
+@torch.library.custom_op("msae::edit_topk_rows_valued", mutates_args=())
+def _edit_topk_rows_valued(vals_in: Tensor, idx_in: Tensor, group_of: Tensor, group_off: Tensor, edit_feat: Tensor,
+                           edit_val: Tensor, edit_kind: Tensor, cur: Tensor, col: Optional[Tensor], e_max: int,
+                           num_latents: int, k: int, want_mask: bool,
+                           want_gain: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    dev = _hip.require_device(vals_in, idx_in, group_of, group_off, edit_feat, edit_val, edit_kind, cur, col)
+    lib = _hip.load()
+    E_total, kk, G = edit_feat.numel(), vals_in.shape[-1], group_off.numel() - 1
+    assert edit_val.numel() == E_total and edit_kind.numel() == E_total, "the edit table's three arrays must have one length"
+    v_in = _f32c(vals_in)
+    i_in = idx_in.detach().contiguous()
+    T = v_in.numel() // max(kk, 1)
+    assert group_of.numel() == T, f"group_of must hold one id per token ({T}), got {tuple(group_of.shape)}"
+    go = _group_ids(group_of, G)
+    gf = group_off.detach().to(torch.int32).contiguous()
+    ef = edit_feat.detach().to(torch.int32).contiguous()
+    ev = _f32c(edit_val)
+    ek = edit_kind.detach().to(torch.int32).contiguous()
+    ec = None if col is None else col.detach().to(torch.int32).contiguous()
+    c2, ld = _cur_rows(cur)
+    assert c2.shape[0] == T, f"cur must hold one row per token ({T}), got {tuple(cur.shape)}"
+    vals = torch.empty(*v_in.shape[:-1], k, dtype=torch.float32, device=dev)
+    idx = torch.empty(*v_in.shape[:-1], k, dtype=i_in.dtype, device=dev)
+    edited = torch.empty(*v_in.shape[:-1], k if want_mask else 0, dtype=torch.uint8, device=dev)
+    gain = torch.empty(*v_in.shape[:-1], k if want_gain else 0, dtype=torch.float32, device=dev)
+    wide = i_in.dtype == torch.int64
+    fn, name = (lib.msae_edit_topk_rows_valued_i64_f32, "msae_edit_topk_rows_valued_i64_f32") if wide else \
+        (lib.msae_edit_topk_rows_valued_f32, "msae_edit_topk_rows_valued_f32")
+    with torch.cuda.device(dev):
+        _hip.check(fn(_hip.ptr(v_in), _hip.ptr(i_in), T, kk, _hip.ptr(go), _hip.ptr(gf), G, _hip.ptr(ef), _hip.ptr(ev),
+                      _hip.ptr(ek), E_total, e_max, num_latents, k, _hip.ptr(c2), ld, _hip.ptr(ec), _hip.ptr(vals),
+                      _hip.ptr(idx), _hip.ptr(edited) if want_mask else None, _hip.ptr(gain) if want_gain else None,
+                      _hip.stream_of(v_in)), name)
+    return vals, idx, edited, gain
+
+
+@_edit_topk_rows_valued.register_fake
+def _(vals_in, idx_in, group_of, group_off, edit_feat, edit_val, edit_kind, cur, col, e_max, num_latents, k, want_mask,
+      want_gain):
+    return (vals_in.new_empty(*vals_in.shape[:-1], k, dtype=torch.float32),
+            idx_in.new_empty(*idx_in.shape[:-1], k),
+            vals_in.new_empty(*vals_in.shape[:-1], k if want_mask else 0, dtype=torch.uint8),
+            vals_in.new_empty(*vals_in.shape[:-1], k if want_gain else 0, dtype=torch.float32))
+
+
+def _edit_topk_rows_valued_host(v_in: Tensor, i_in: Tensor, group_of: Tensor, row_edits, cur: Tensor, cols: Tensor, k: int):
+    """The valued per-token edit in plain torch: every group's tokens through `_edit_topk_valued_host` with that group's
+    slice; the others copy their first k entries (gain 1, edited 0).  v_in / i_in [T, kk], group_of [T], cols int64
+    [E_total]."""
+    T = v_in.shape[0]
+    vals, idx = v_in[:, :k].clone(), i_in[:, :k].clone()
+    gain, edited = torch.ones(T, k), torch.zeros(T, k, dtype=torch.uint8)
+    off = row_edits.offsets.tolist()
+    for g in range(len(off) - 1):
+        a, b = off[g], off[g + 1]
+        rows = torch.nonzero(group_of == g).flatten()
+        if b <= a or rows.numel() == 0:
+            continue
+        v, i, gn, ed = _edit_topk_valued_host(v_in[rows], i_in[rows], row_edits.feat[a:b], row_edits.val[a:b],
+                                              row_edits.kind[a:b], cur[rows], cols[a:b], k)
+        vals[rows], idx[rows], gain[rows], edited[rows] = v, i, gn, ed.to(torch.uint8)
+    return vals, idx, edited, gain
+
+
 def edit_topk_rows(vals_in: Tensor, idx_in: Tensor, group_of: Tensor, row_edits, num_latents: int, k: int,
-                   want_mask: bool = False):
+                   want_mask: bool = False, *, cur: Optional[Tensor] = None, col: Optional[Tensor] = None,
+                   want_gain: bool = False):
     """`edit_topk` with one edit table PER TOKEN -> (vals f32 [..., k], idx [..., k] in idx_in's dtype[, edited uint8
     [..., k]]).  vals_in / idx_in [..., kk]: encode_topk's output for kk >= k + E_max without edits; group_of int32 / int64
     [...]: the group of every token, any id outside [0, G) = unedited (the first k entries are copied); row_edits: a
     msae.features.RowEdits (offsets [G + 1], feat / val / kind [E_total], E_max).  `edited` (want_mask=True): 1 where the slot
     came from an edit entry.  Exact per token: include/msae.h, "per-token edit tables".  Nothing is read back; the arguments
-    the library would refuse raise ValueError here."""
+    the library would refuse raise ValueError here.  cur (f32 [..., C], `pre_acts_features` over row_edits.union) selects the
+    VALUED form as in `edit_topk`: col int32 [E_total] (row_edits.col; None: entry e of the concatenated table reads column
+    e), want_gain=True appends gain f32 [..., k] (1 on unedited tokens).  CPU tensors take a plain-torch host path in the
+    valued form."""
     kk, e_max, G = vals_in.shape[-1], int(row_edits.E_max), int(row_edits.G)
     if G < 1 or e_max < 1 or k < 1 or kk < k + e_max or k + e_max > min(num_latents, EDIT_TOPK_MAX_SELECTED):
         raise ValueError(f"edit_topk_rows: need G >= 1, E_max >= 1, k >= 1, kk >= k + E_max and k + E_max <= min(num_latents, "
@@ -994,9 +1193,25 @@ def edit_topk_rows(vals_in: Tensor, idx_in: Tensor, group_of: Tensor, row_edits,
         raise ValueError(f"edit_topk_rows: group_of must have one id per token, shape {tuple(vals_in.shape[:-1])}, got "
                          f"{tuple(group_of.shape)}")
     _no_grad_inputs("ops.edit_topk_rows", vals_in, row_edits.val)
-    vals, idx, edited = _edit_topk_rows(vals_in, idx_in, group_of, row_edits.offsets, row_edits.feat, row_edits.val,
-                                        row_edits.kind, e_max, num_latents, k, want_mask)
-    return (vals, idx, edited) if want_mask else (vals, idx)
+    if cur is None:
+        if col is not None or want_gain:
+            raise ValueError("edit_topk_rows: col= and want_gain= belong to the valued form: pass cur= as well")
+        vals, idx, edited = _edit_topk_rows(vals_in, idx_in, group_of, row_edits.offsets, row_edits.feat, row_edits.val,
+                                            row_edits.kind, e_max, num_latents, k, want_mask)
+        return (vals, idx, edited) if want_mask else (vals, idx)
+    _check_cur("edit_topk_rows", vals_in, idx_in, cur, col, int(row_edits.E_total))
+    _no_grad_inputs("ops.edit_topk_rows", cur)
+    if not vals_in.is_cuda:
+        lead = vals_in.shape[:-1]
+        cols = torch.arange(int(row_edits.E_total)) if col is None else col.long()
+        out = _edit_topk_rows_valued_host(vals_in.reshape(-1, kk).float(), idx_in.reshape(-1, kk), group_of.reshape(-1),
+                                          row_edits, cur.reshape(-1, cur.shape[-1]).float(), cols, k)
+        vals, idx, edited, gain = (o.reshape(*lead, k) for o in out)
+    else:
+        vals, idx, edited, gain = _edit_topk_rows_valued(vals_in, idx_in, group_of, row_edits.offsets, row_edits.feat,
+                                                         row_edits.val, row_edits.kind, cur, col, e_max, num_latents, k,
+                                                         want_mask, want_gain)
+    return (vals, idx) + ((edited,) if want_mask else ()) + ((gain,) if want_gain else ())
 
 
 # ---- error-preserving interventions (csrc/delta_decode.hip) -------------------------------------------
@@ -2008,7 +2223,8 @@ class _SparseEncode(torch.autograd.Function):
         vals, idxs = [], []
         edits = set_feature >= 0 or zero_feature >= 0 or edit_set is not None
         assert not (edits and (k_aux > 0 or k_multi > 0)), "hook edits apply to the plain top-k only"
-        row_mask = None
+        row_mask = gain = None
+        valued = edit_set is not None and getattr(edit_set, "value_dependent", False)
         if edit_set is not None and edit_group is not None:
             # one table per token (msae.features.RowEdits + the tokens' group ids): the same two steps, and the kernel says
             # which output slots hold an edit's own value -- a feature-wide mask is wrong once the tables differ per token
@@ -2016,7 +2232,12 @@ class _SparseEncode(torch.autograd.Function):
             v, i, _ = encode_topk(x, W_enc, b_enc, b_dec,
                                   prepared if prepared is not None else _refresh_train_operands(W_enc, x.shape[0]),
                                   k + edit_set.E_max)
-            v, i, row_mask = edit_topk_rows(v, i, edit_group, edit_set, W_enc.shape[0], k, want_mask=True)
+            if valued:  # scale / add / floor / cap: the kernel reads the features' exact latents and returns each slot's gain
+                cur = pre_acts_features(x, W_enc, b_enc, b_dec, edit_set.union)
+                v, i, row_mask, gain = edit_topk_rows(v, i, edit_group, edit_set, W_enc.shape[0], k, want_mask=True, cur=cur,
+                                                      col=edit_set.col, want_gain=True)
+            else:
+                v, i, row_mask = edit_topk_rows(v, i, edit_group, edit_set, W_enc.shape[0], k, want_mask=True)
             vals.append(v); idxs.append(i)
         elif edit_set is not None:
             # a SET of edits (msae.features.FeatureEdits): the unedited encode over-fetches k + E entries, edit_topk re-ranks
@@ -2025,7 +2246,12 @@ class _SparseEncode(torch.autograd.Function):
             v, i, _ = encode_topk(x, W_enc, b_enc, b_dec,
                                   prepared if prepared is not None else _refresh_train_operands(W_enc, x.shape[0]),
                                   k + edit_set.E)
-            v, i = edit_topk(v, i, edit_set.feat, edit_set.val, edit_set.kind, W_enc.shape[0], k)
+            if valued:
+                cur = pre_acts_features(x, W_enc, b_enc, b_dec, edit_set.feat)
+                v, i, gain = edit_topk(v, i, edit_set.feat, edit_set.val, edit_set.kind, W_enc.shape[0], k, cur=cur,
+                                       want_gain=True)
+            else:
+                v, i = edit_topk(v, i, edit_set.feat, edit_set.val, edit_set.kind, W_enc.shape[0], k)
             vals.append(v); idxs.append(i)
         elif k_aux == 0 and max(k, k_multi) <= 256:
             # no AuxK term: the fused encoder gives the canonical top-max(k, 4k); the top-k is its
@@ -2069,8 +2295,9 @@ class _SparseEncode(torch.autograd.Function):
         ctx.save_for_backward(x, W_enc, b_dec, torch.cat(idxs, -1), torch.cat(vals, -1))
         ctx.splits = [t.shape[-1] for t in vals]
         ctx.set_feature = set_feature
-        ctx.edit_mask = None if edit_set is None or row_mask is not None else edit_set.mask
-        ctx.row_mask = row_mask
+        ctx.edit_mask = None if edit_set is None or row_mask is not None or gain is not None else edit_set.mask
+        ctx.row_mask = row_mask if gain is None else None
+        ctx.gain = gain          # value-dependent edits: dL'/dL per slot -- 0 at SET / ZERO slots, 1 at unedited ones
         ctx.has_b_enc = b_enc is not None
         out = []
         for v, i in zip(vals, idxs):
@@ -2091,6 +2318,8 @@ class _SparseEncode(torch.autograd.Function):
             g_cat = g_cat * ~ctx.edit_mask[idx_cat]
         if ctx.row_mask is not None:                               # ... per token: the slots that came from an edit entry
             g_cat = g_cat * ~ctx.row_mask.bool()
+        if ctx.gain is not None:                                   # ... or scaled by the edit's own derivative
+            g_cat = g_cat * ctx.gain
         a = x.float() - b_dec
         need_x, need_W, need_be, need_bd = ctx.needs_input_grad[:4]
         g_x = g_W = g_be = g_bd = None

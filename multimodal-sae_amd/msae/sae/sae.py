@@ -389,12 +389,17 @@ class Sae(nn.Module):
                 acts, idx, status = ops.encode_topk(x, self.encoder.weight, self.encoder.bias, self.b_dec,
                                                     self._prepared_weights(), self.cfg.k + edits.E_max, exact=exact,
                                                     certified=certified)
-                acts, idx = ops.edit_topk_rows(acts, idx, edit_group, edits, self.num_latents, self.cfg.k)
+                if edits.value_dependent:  # scale / add / floor / cap: the edited features' exact latents, one pass
+                    acts, idx = ops.edit_topk_rows(acts, idx, edit_group, edits, self.num_latents, self.cfg.k,
+                                                   cur=self._edit_cur(x, edits.union), col=edits.col)
+                else:
+                    acts, idx = ops.edit_topk_rows(acts, idx, edit_group, edits, self.num_latents, self.cfg.k)
             elif edits is not None:  # over-fetch, then edit: `exact` / `certified` only change the first call
                 acts, idx, status = ops.encode_topk(x, self.encoder.weight, self.encoder.bias, self.b_dec,
                                                     self._prepared_weights(), self.cfg.k + edits.E, exact=exact,
                                                     certified=certified)
-                acts, idx = ops.edit_topk(acts, idx, edits.feat, edits.val, edits.kind, self.num_latents, self.cfg.k)
+                acts, idx = ops.edit_topk(acts, idx, edits.feat, edits.val, edits.kind, self.num_latents, self.cfg.k,
+                                          cur=self._edit_cur(x, edits.feat) if edits.value_dependent else None)
             else:
                 acts, idx, status = ops.encode_topk(x, self.encoder.weight, self.encoder.bias, self.b_dec,
                                                     self._prepared_weights(), self.cfg.k, set_feature,
@@ -472,6 +477,11 @@ class Sae(nn.Module):
         out = (EncoderOutput(acts, idx),) + ((status,) if return_status else ()) + ((lengths,) if return_lengths else ())
         return out[0] if len(out) == 1 else out
 
+    def _edit_cur(self, x: Tensor, feats: Tensor) -> Tensor:
+        """The exact latents of the features a value-dependent edit reads: the listed columns of
+        `pre_acts`, bit for bit, [..., len(feats)] f32."""
+        return ops.pre_acts_features(x, self.encoder.weight, self.encoder.bias, self.b_dec, feats)
+
     @staticmethod
     def _token_groups(x: Tensor, edits, edit_group: Optional[Tensor]) -> Tensor:
         """`edit_group` of encode -> one group id per token, shape x.shape[:-1] (device work only: nothing is read back)."""
@@ -524,10 +534,14 @@ class Sae(nn.Module):
             flat = x.reshape(-1, self.d_in)
             acts, idx, _ = ops.encode_topk(flat, self.encoder.weight, self.encoder.bias, self.b_dec, self._prepared_weights(),
                                            k + (edits.E_max if rows else edits.E), exact=exact, certified=certified)
-            if rows:
+            if rows and edits.value_dependent:
+                q_acts, q_idx = ops.edit_topk_rows(acts, idx, edit_group.reshape(-1), edits, self.num_latents, k,
+                                                   cur=self._edit_cur(flat, edits.union), col=edits.col)
+            elif rows:
                 q_acts, q_idx = ops.edit_topk_rows(acts, idx, edit_group.reshape(-1), edits, self.num_latents, k)
             else:
-                q_acts, q_idx = ops.edit_topk(acts, idx, edits.feat, edits.val, edits.kind, self.num_latents, k)
+                q_acts, q_idx = ops.edit_topk(acts, idx, edits.feat, edits.val, edits.kind, self.num_latents, k,
+                                              cur=self._edit_cur(flat, edits.feat) if edits.value_dependent else None)
             out = ops.delta_decode(flat, acts[:, :k], idx[:, :k], q_acts, q_idx, self.W_dec)
         return out.view(x.shape)
 
