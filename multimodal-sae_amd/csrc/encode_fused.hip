@@ -335,7 +335,12 @@ int run_exact_fallback(const EncodeCall &c, unsigned char *ws, const FallbackPla
 }
 
 inline int dot4_max_small() {   // largest T of the dot4 weight stream (tuning knob; the MFMA stream takes the rest of the small path)
-  static const int v = [] { const char *e = getenv("MSAE_SMALL_DOT4_MAX"); return e ? atoi(e) : SMALL_DOT4_PREF; }();
+  // (at most SMALL_T_DOT4: gemv_small_kernel is instantiated for 1, 2 and 4 tokens)
+  static const int v = [] {
+    const char *e = getenv("MSAE_SMALL_DOT4_MAX");
+    const int m = e ? atoi(e) : SMALL_DOT4_PREF;
+    return m < SMALL_T_DOT4 ? m : SMALL_T_DOT4;
+  }();
   return v;
 }
 
@@ -368,7 +373,9 @@ int run_small(const EncodeCall &c, const FusedCtx &fx) {
   prof_mark(co.prof, 2, s);
   prof_mark(co.prof, 3, s);
   const int skip_a = c.skip_a(), skip_b = c.skip_b();
+  // every case below is a member of small_kernel_for (encode_small.h), which is what the plan asked; `default` is a defence
 #define MSAE_GEMV(DSEG, TT)                                                                                        \
+  static_assert(small_kernel_for(DSEG, TT), "a dot4 stream kernel outside the small path's shape set");            \
   hipLaunchKernelGGL((gemv_small_kernel<DSEG, TT>), dim3(SMALL_GRID), dim3(256), 0, s, wq, wstat, b_enc, N, T, xhi, xlo, \
                      rowc, zzx, skip_a, skip_b, surv, bound)
   const int dseg = d / 1024;
@@ -384,6 +391,7 @@ int run_small(const EncodeCall &c, const FusedCtx &fx) {
     const size_t smem_m = (size_t)2 * 16 * (d + 16) + (size_t)16 * 8 * (SMALL_MF_EMIT + 1) * 8;
 #define MSAE_GEMV_M(DSEG)                                                                                          \
   do {                                                                                                             \
+    static_assert(small_kernel_for(DSEG, SMALL_T_MAX), "an MFMA stream kernel outside the small path's shape set"); \
     MSAE_HIP_TRY(hipFuncSetAttribute((const void *)gemv_mfma_kernel<DSEG>, hipFuncAttributeMaxDynamicSharedMemorySize, \
                                      (int)smem_m));                                                                \
     hipLaunchKernelGGL(gemv_mfma_kernel<DSEG>, dim3(grid_m), dim3(512), smem_m, s, wqf, wqsf, wstat, b_enc, N, T, xhi, xlo, rowc, \
@@ -406,6 +414,7 @@ int run_small(const EncodeCall &c, const FusedCtx &fx) {
   hipLaunchKernelGGL(select_small_kernel, dim3(T), dim3(1024), 0, s, surv, bound, cand, tau, n_surv, n_bound);
   prof_mark(co.prof, 4, s);
 #define MSAE_RESCORE(DSEG)                                                                                         \
+  static_assert(small_kernel_for(DSEG, 1), "a re-score kernel outside the small path's shape set");                \
   hipLaunchKernelGGL(rescore_small_kernel<DSEG>, dim3(SMALL_RMAX, T), dim3(64), 0, s, a32, c.W_enc, b_enc, c.k, cand, tau, wstat, \
                      rowc, zzx, z * z, guard_z_check2(co.seed != 0ull), c.set_feature, c.set_value, exact, viol, done, c.vals, \
                      c.idx, c.status, flagged, n_flagged)

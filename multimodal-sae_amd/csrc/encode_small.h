@@ -23,7 +23,10 @@ namespace {
 //                 rotate per step, ~6 cycles per element instead of ~15 for a one-lane chain out of LDS);
 //                 the LAST wave of a token to finish sorts the exact values and writes the outputs: verified
 //                 iff v_k lies above tau
-constexpr int SMALL_T_MAX = 16, SMALL_T_DOT4 = 4;      // small path: T <= 16 (d <= 4096), T <= 4 for wider inputs
+// small path: T <= 16 at d = 1024, 2048, 4096 (MFMA stream, or the dot4 stream up to SMALL_T_DOT4 tokens); d = 8192 has the
+// dot4 stream's one- and two-token kernels only (SMALL_T_WIDE).  Every other width (3072, 5120, 6144, 7168; 8192 from three
+// tokens on) takes the weight-stream kernel's 64-token tile (gemm_skinny.h), as under MSAE_NO_SMALL_PATH=1: small_kernel_for.
+constexpr int SMALL_T_MAX = 16, SMALL_T_DOT4 = 4, SMALL_T_WIDE = 2;
 constexpr int SMALL_DOT4_PREF = 1;                     // T = 1: dot4 stream (0.130 ms vs 0.154); T >= 2: MFMA stream
                                                        // (T = 2 / 3 / 4: 0.158 / 0.156 / 0.159 ms vs 0.165 / 0.205 / 0.213)
 constexpr int SMALL_R = 96, SMALL_RMAX = 127, SMALL_K_MAX = 64;   // candidates per token: R .. RMAX
@@ -33,9 +36,16 @@ constexpr int SMALL_EMIT = 3;                          // survivors per workgrou
 constexpr int SMALL_WG_ROWS = 128;                     // most rows of one workgroup (32 per wave)
 constexpr int SMALL_SURV = SMALL_GRID * SMALL_EMIT;    // 6144 keys per token
 static_assert(SMALL_RMAX < SMALL_SURV && SMALL_RMAX + 1 <= 128, "candidate list: 127 exact values + the hook's set_feature");
+// THE set of (d / 1024, T) run_small has kernels for (encode_fused.hip): its switch statements instantiate exactly these -- every
+// case asserts it here, and a (dseg, T) outside it reaches their `default` arms only if the plan and this predicate disagree.
+//   dseg 1, 2, 4: gemv_mfma_kernel<dseg>, gemv_small_kernel<dseg, 1 | 2 | 4>, rescore_small_kernel<dseg> -- every T <= 16
+//   dseg 8:       gemv_small_kernel<8, 1 | 2>, rescore_small_kernel<8>                                   -- T <= 2
+constexpr bool small_kernel_for(int dseg, int T) {
+  return T >= 1 && T <= SMALL_T_MAX && (dseg == 1 || dseg == 2 || dseg == 4 || (dseg == 8 && T <= SMALL_T_WIDE));
+}
 inline bool small_shape_ok(int T, int d, int N, int k) {
-  return T <= SMALL_T_MAX && (T <= SMALL_T_DOT4 || d <= 4096) && k <= SMALL_K_MAX && d % 1024 == 0 && d <= 8192 &&
-         N >= 4096 && N <= SMALL_GRID * SMALL_WG_ROWS && i8_shape_ok(N, d);
+  return d % 1024 == 0 && small_kernel_for(d / 1024, T) && k <= SMALL_K_MAX && N >= 4096 &&
+         N <= SMALL_GRID * SMALL_WG_ROWS && i8_shape_ok(N, d);
 }
 
 // ---- small-T path kernels ---------------------------------------------------------------------------------
@@ -232,7 +242,12 @@ __global__ __launch_bounds__(512) void gemv_mfma_kernel(const signed char *__res
   // B fragments from the FRAGMENT-major copies (frag_off: one k-step of a 16-row block = one contiguous kilobyte, this lane's 16 B
   // at byte 16 lane; the row-major copy's 16 rows x 64 B per instruction are half-line requests: 0.13 -> 0.09 ms of stream).  The
   // main copy holds the non-sample rows in main_row order, the sample rows have their own: blocks [0, n_main) | [n_main, N / 16).
-  const int n_blocks = N / 16, wave_g = blockIdx.x * 8 + wv, n_waves = gridDim.x * 8;
+  // Fewer blocks than waves (N < 128 x the grid: 32768 at 256 CUs): the blocks go to the waves WAVE-major, i.e. spread over all
+  // workgroups.  Workgroup-major, N = 8192 put its 512 blocks on 64 of the 256 workgroups, 128 features each of which a workgroup
+  // emits SMALL_MF_EMIT: at k = 64 some workgroup held more than that many of a token's ~100 best every tenth token, its bound
+  // became tau and the token went to the exact path (tests/test_gpu_encode_shape_lattice.py, NOTEBOOK.md).  Larger N: as before.
+  const int n_blocks = N / 16, n_waves = gridDim.x * 8;
+  const int wave_g = n_blocks < n_waves ? wv * (int)gridDim.x + (int)blockIdx.x : (int)blockIdx.x * 8 + wv;
   const int n_main = MAIN_SKIPS_SAMPLE ? (N - N / SAMPLE_STRIDE) / 16 : n_blocks;
   for (int blk = wave_g; blk < n_blocks; blk += n_waves) {
     const bool samp_blk = blk >= n_main;

@@ -200,7 +200,10 @@ def _opts(coarse_mode: int = -1, guard_z: float = 0.0, status_detail: bool = Fal
 def _encode_ws_bytes(lib, T: int, d: int, N: int, k: int, opts: _OptsRef) -> int:
     """msae_encode_topk_ws_bytes, memoised (a pure function of the shape and the coarse mode)."""
     key = (T, d, N, k, opts.struct.coarse_mode, os.environ.get("MSAE_COARSE") if opts.struct.coarse_mode < 0 else None,
-           os.environ.get("MSAE_FM"), opts.struct.certified)
+           os.environ.get("MSAE_FM"), opts.struct.certified,
+           # (the library reads the switch at every call, and the small-T plan is the larger one: a size memoised with the switch
+           # set would be too small for the same shape without it)
+           os.environ.get("MSAE_NO_SMALL_PATH") if T <= 16 else None)
     n = _WS_BYTES_CACHE.get(key)
     if n is None:
         if len(_WS_BYTES_CACHE) > 4096:
