@@ -1036,6 +1036,26 @@ int msae_adam_rows_f32(float *W, const float *G, float *M, float *V, int rows, i
                        const float *total_sumsq, float max_norm, int project, float lr, float beta1,
                        float beta2, float eps, int step, void *stream);
 
+/* ---- sign momentum: Lion (Chen et al. 2023, arXiv:2302.06675), and Signum (Bernstein et al. 2018) as its beta1 == beta2
+ * case.  One moment M, no second moment, no bias correction, no step count, no weight decay.  Per row r of the [rows][d]
+ * view msae_adam_rows_f32 takes, one workgroup:
+ *   c  = min(1, max_norm / (sqrtf(*total_sumsq) + 1e-6f))          (total_sumsq NULL: 1)   as msae_adam_rows_f32
+ *   g  = c * G[r][j];   if project: g -= <g, W[r]> * W[r][j]                                as msae_adam_rows_f32
+ *   u  = fmaf(g - m, 1.f - beta1, m)        the interpolated momentum that is signed
+ *   s  = (u > 0) - (u < 0)                  0 for u == 0, and for a NaN
+ *   w' = w - lr * s                         one float32 multiplication (exact: s is -1, 0 or 1), one float32 subtraction
+ *   m' = fmaf(g - m, 1.f - beta2, m)        the carried momentum
+ * Bit-level rules: g - m and 1.f - beta are float32 operations, u and m' are each ONE fused multiply-add of them (no other
+ * contraction anywhere), so given g the sign and the momentum are defined bit for bit, and with beta1 == beta2 u == m'.
+ * An element with s == 0 keeps its bits.  G is read only.
+ * renorm_eps (>= 0: on) and prepared / T_next / opts are the tails of msae_adam_rows_fused_f32, with its bits: a call with
+ * tails leaves the M, and before the renorm the W, of a call without.  d % 4 == 0 and d <= 8192 is one kernel (W, G, M
+ * 16-byte aligned, else MSAE_EALIGN); other shapes run a plain pass and then the separate tail passes.  Null W / G / M or a
+ * non-positive shape: MSAE_EINVAL.  No atomics, no workspace: two runs give the same bits.  20 bytes moved per element. */
+int msae_lion_rows_f32(float *W, const float *G, float *M, int rows, int d, const float *total_sumsq, float max_norm,
+                       int project, float lr, float beta1, float beta2, float renorm_eps, void *prepared, int T_next,
+                       const msae_options *opts, void *stream);
+
 /* ---- blockwise 8-bit Adam moments ("adam8"; the role of bitsandbytes' Adam8bit in train/sae/sae/trainer.py:139-147,
  * a format of this project's own: checkpoints are NOT interchangeable with bitsandbytes') ----
  * A parameter is the [rows][d] view msae_adam_rows_f32 takes.  A BLOCK is 256 consecutive elements of one row, the last

@@ -347,6 +347,99 @@ __global__ __launch_bounds__(256) void adam_rows_fused_kernel(float *__restrict_
   if constexpr (REFRESH != 0) refresh_row<REFRESH>(W, base, d, ft, red3);
 }
 
+// ---- sign momentum ("lion" / "signum", include/msae.h) ----------------------------------------------------------
+struct LionArgs {
+  float lr, omb1, omb2, max_norm;      // omb = 1.f - beta, rounded once on the host's float32 values as the device would
+  int project;
+};
+
+// u = lerp(m, g, 1 - beta1) is signed, m' = lerp(m, g, 1 - beta2) is carried: one subtraction and one explicit fma each, so
+// that every variant of the kernel takes the same sign from the same g.  beta1 == beta2: u and m' are the same bits.
+__device__ __forceinline__ void lion_update(float &w, float g, float &m, const LionArgs &a) {
+  const float dgm = g - m;
+  const float u = __builtin_fmaf(dgm, a.omb1, m);
+  const float s = (float)((u > 0.f) - (u < 0.f));          // 0 for u == 0 and for NaN
+  w = w - a.lr * s;
+  m = __builtin_fmaf(dgm, a.omb2, m);
+}
+
+// adam_rows_kernel's sibling for the shapes lion_rows_fused_kernel does not take (d % 4 != 0: scalar loop; d > 8192)
+__global__ __launch_bounds__(256) void lion_rows_kernel(float *__restrict__ W, const float *__restrict__ G,
+                                                        float *__restrict__ M, int d,
+                                                        const float *__restrict__ total_sumsq, LionArgs a) {
+  __shared__ float red[4];
+  const size_t base = (size_t)blockIdx.x * d;
+  const float clip = clip_coef(total_sumsq, a.max_norm);
+  if ((d & 3) == 0) {
+    const float along = a.project ? row_along(G, W, base, d, clip, red) : 0.f;
+    for (int c = threadIdx.x * 4; c < d; c += 1024) {
+      const f32x4 g = *reinterpret_cast<const f32x4 *>(G + base + c);     // L2 hit when projecting
+      f32x4 w = *reinterpret_cast<const f32x4 *>(W + base + c);
+      f32x4 m = *reinterpret_cast<const f32x4 *>(M + base + c);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float ge = g[e] * clip, we = w[e], me = m[e];
+        if (a.project) ge -= along * we;
+        lion_update(we, ge, me, a);
+        w[e] = we; m[e] = me;
+      }
+      *reinterpret_cast<f32x4 *>(W + base + c) = w;
+      *reinterpret_cast<f32x4 *>(M + base + c) = m;
+    }
+  } else {
+    float along = 0.f;
+    if (a.project) {
+      float dot = 0.f;
+      for (int c = threadIdx.x; c < d; c += 256) dot += (G[base + c] * clip) * W[base + c];
+      along = block_sum(dot, red);
+    }
+    for (int c = threadIdx.x; c < d; c += 256) {
+      float ge = G[base + c] * clip, w = W[base + c], m = M[base + c];
+      if (a.project) ge -= along * w;
+      lion_update(w, ge, m, a);
+      W[base + c] = w; M[base + c] = m;
+    }
+  }
+}
+
+// adam_rows_fused_kernel's sibling: one moment, no second-moment stream (d % 4 == 0, d <= 8192).  20 bytes per element.
+template <int REFRESH>
+__global__ __launch_bounds__(256) void lion_rows_fused_kernel(float *__restrict__ W, const float *__restrict__ G,
+                                                              float *__restrict__ M, int d,
+                                                              const float *__restrict__ total_sumsq, LionArgs a, FusedTail ft) {
+  __shared__ float red[4];
+  __shared__ float red3[3][4];
+  const size_t base = (size_t)blockIdx.x * d;
+  const float clip = clip_coef(total_sumsq, a.max_norm);
+  const float along = a.project ? row_along(G, W, base, d, clip, red) : 0.f;
+  const bool renorm = ft.renorm_eps >= 0.f;
+  f32x4 keep[KEEP];
+  float ss = 0.f;
+  int it = 0;
+  for (int c = threadIdx.x * 4; c < d; c += 1024, ++it) {
+    const f32x4 g = a.project ? *reinterpret_cast<const f32x4 *>(G + base + c)     // L2 hit when projecting
+                              : MSAE_ADAM_LOAD(reinterpret_cast<const f32x4 *>(G + base + c));
+    f32x4 w = *reinterpret_cast<const f32x4 *>(W + base + c);
+    f32x4 m = MSAE_ADAM_LOAD(reinterpret_cast<const f32x4 *>(M + base + c));
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float ge = g[e] * clip, we = w[e], me = m[e];
+      if (a.project) ge -= along * we;
+      lion_update(we, ge, me, a);
+      w[e] = we; m[e] = me;
+    }
+    MSAE_ADAM_STORE(m, reinterpret_cast<f32x4 *>(M + base + c));
+    if (renorm) {
+      keep_put(keep, it, w);
+      ss += w[0] * w[0] + w[1] * w[1] + w[2] * w[2] + w[3] * w[3];
+    } else {
+      *reinterpret_cast<f32x4 *>(W + base + c) = w;
+    }
+  }
+  if (renorm) renorm_store(W, base, d, keep, 1.f / (sqrtf(block_sum(ss, red)) + ft.renorm_eps));
+  if constexpr (REFRESH != 0) refresh_row<REFRESH>(W, base, d, ft, red3);
+}
+
 // ---- 8-bit moments ("adam8", include/msae.h) -------------------------------------------------------------------
 // M8 = e4m3 codes of m, R8 = e4m3 codes of sqrt(v), one float32 scale (absmax / 448) per block of ADAM8_BLOCK consecutive
 // elements of a row.  With one workgroup per row and one f32x4 per thread per trip, a block is what ONE WAVE holds in ONE TRIP:
@@ -608,6 +701,39 @@ extern "C" int msae_adam_rows_fused_f32(float *W, const float *G, float *M, floa
     hipLaunchKernelGGL(adam_rows_fused_kernel<2>, dim3(rows), dim3(256), 0, s, W, G, M, V, d, total_sumsq, a, ft);
   else
     hipLaunchKernelGGL(adam_rows_fused_kernel<0>, dim3(rows), dim3(256), 0, s, W, G, M, V, d, total_sumsq, a, ft);
+  return msae_launch_status();
+}
+
+// ---- sign momentum --------------------------------------------------------------------------------------------------------------
+// d % 4 == 0 and d <= 8192: lion_rows_fused_kernel, with or without tails (ONE kernel: a call without tails and a call with them
+// compute the same W before the renorm and the same M); other shapes: lion_rows_kernel and the separate passes.
+extern "C" int msae_lion_rows_f32(float *W, const float *G, float *M, int rows, int d, const float *total_sumsq,
+                                  float max_norm, int project, float lr, float beta1, float beta2, float renorm_eps,
+                                  void *prepared, int T_next, const msae_options *opts, void *stream) {
+  if (!W || !G || !M || rows <= 0 || d <= 0) return MSAE_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  LionArgs a{};
+  a.lr = lr; a.omb1 = 1.f - beta1; a.omb2 = 1.f - beta2; a.max_norm = max_norm;
+  a.project = project ? 1 : 0;
+  if ((d & 3) != 0 || d > 8192) {
+    if ((d & 3) == 0 && !(msae_aligned(W, 16) && msae_aligned(G, 16) && msae_aligned(M, 16))) return MSAE_EALIGN;
+    hipLaunchKernelGGL(lion_rows_kernel, dim3(rows), dim3(256), 0, s, W, G, M, d, total_sumsq, a);
+    if (int rc = msae_launch_status()) return rc;
+    if (renorm_eps >= 0.f) { if (int rc = msae_unit_norm_rows_f32(W, rows, d, renorm_eps, stream)) return rc; }
+    if (prepared) return T_next > 0 ? msae_encoder_refresh_for(W, rows, d, prepared, T_next, opts, stream)
+                                    : msae_encoder_refresh(W, rows, d, prepared, opts, stream);
+    return 0;
+  }
+  if (!(msae_aligned(W, 16) && msae_aligned(G, 16) && msae_aligned(M, 16))) return MSAE_EALIGN;
+  FusedTail ft;
+  int refresh;
+  if (int rc = fused_tail(rows, d, renorm_eps, prepared, T_next, opts, s, &ft, &refresh)) return rc;
+  if (refresh == 1)
+    hipLaunchKernelGGL(lion_rows_fused_kernel<1>, dim3(rows), dim3(256), 0, s, W, G, M, d, total_sumsq, a, ft);
+  else if (refresh == 2)
+    hipLaunchKernelGGL(lion_rows_fused_kernel<2>, dim3(rows), dim3(256), 0, s, W, G, M, d, total_sumsq, a, ft);
+  else
+    hipLaunchKernelGGL(lion_rows_fused_kernel<0>, dim3(rows), dim3(256), 0, s, W, G, M, d, total_sumsq, a, ft);
   return msae_launch_status();
 }
 

@@ -192,6 +192,8 @@ PROTOTYPES = {
                                          c_opts_p, c_void_p]),
     "msae_adam_rows_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_float,
                                    c_int, c_float, c_float, c_float, c_float, c_int, c_void_p]),
+    "msae_lion_rows_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_float, c_int, c_float, c_float,
+                                   c_float, c_float, c_void_p, c_int, c_opts_p, c_void_p]),
     "msae_adam8_blocks": (c_size_t, [c_int, c_int]),
     "msae_adam8_rows_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                     c_float, c_int, c_float, c_float, c_float, c_float, c_int, c_float, c_void_p, c_int,

@@ -2468,6 +2468,29 @@ def adam_rows_(p: Tensor, g: Tensor, m: Tensor, v: Tensor, step: int, lr: float,
             "msae_adam_rows_f32")
 
 
+def lion_rows_(p: Tensor, g: Tensor, m: Tensor, lr: float, *,
+               total_sumsq: Optional[Tensor] = None, max_norm: float = 1.0, project: bool = False,
+               betas: Tuple[float, float] = (0.9, 0.99), renorm_eps: Optional[float] = None,
+               refresh: Optional[Tensor] = None, tokens_next: int = 0) -> None:
+    """adam_rows_ with a sign-momentum update (msae_lion_rows_f32): same clip, projection, `renorm_eps` and `refresh` /
+    `tokens_next` tails; p -= lr * sign(lerp(m, g, 1 - betas[0])), m = lerp(m, g, 1 - betas[1]) in place.  Lion; with
+    betas[0] == betas[1] it is Signum.  One moment, no bias correction, no weight decay."""
+    dev = _hip.require_device(p, g, m, refresh)
+    for t in (p, g, m):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == p.shape
+    assert p.dim() == 2 or not project
+    if renorm_eps is not None or refresh is not None:
+        assert p.dim() == 2, "renorm / refresh are row operations on a [rows, d] matrix"
+    rows, d = _kernel_rows(p)
+    with torch.cuda.device(dev):
+        _hip.check(_hip.load().msae_lion_rows_f32(
+            _hip.ptr(p), _hip.ptr(g), _hip.ptr(m), rows, d,
+            _hip.ptr(total_sumsq) if total_sumsq is not None else None, float(max_norm), int(project),
+            float(lr), float(betas[0]), float(betas[1]),
+            float(renorm_eps) if renorm_eps is not None else -1.0, _hip.ptr(refresh), int(tokens_next),
+            _opts().ref(), _hip.stream_of(p)), "msae_lion_rows_f32")
+
+
 # ---- blockwise 8-bit Adam moments (the "adam8" format of include/msae.h, DESIGN.md 7e) ---------------------------------
 @dataclasses.dataclass
 class Adam8State:

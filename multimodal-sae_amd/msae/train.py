@@ -24,6 +24,9 @@ MI355X-side design:
   * `optim_bits=8` (the reference takes bitsandbytes' Adam8bit when it can import it, trainer.py:139-147): the Adam
     moments of every parameter the format takes are carried as blockwise 8-bit codes (ops.Adam8State) --
     2 bytes per element instead of 8, and 16 instead of 28 bytes moved per element by the Adam pass;
+  * `optimizer="lion"` / `"signum"` (no reference counterpart): a sign-momentum update in the same fused pass --
+    one moment instead of two (4 bytes of state per element, 20 instead of 28 bytes moved per element), a step of +-lr per
+    element; same clip, projection, renorm and operand refresh.  The default stays Adam;
   * data parallel: each parameter's gradient all-reduce (RCCL, ReduceOp.AVG -- no division pass) is
     launched ASYNCHRONOUSLY from a post-accumulate-grad hook the moment autograd has finished that
     parameter, so the 2 GiB W_dec exchange over xGMI overlaps the encoder backward, and the W_enc
@@ -36,7 +39,7 @@ trainer's outer loop and out of scope.
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import Optional, Tuple
 
 import torch
 import torch.distributed as dist
@@ -69,20 +72,40 @@ def linear_schedule_with_warmup(step: int, warmup_steps: int, total_steps: Optio
     return max(0.0, (total_steps - step) / max(1, total_steps - warmup_steps))
 
 
+OPTIMIZERS = ("adam", "lion", "signum")
+# "lion": Chen et al. 2023 (arXiv:2302.06675); "signum" (Bernstein et al. 2018) is its beta1 == beta2 case
+_DEFAULT_BETAS = {"adam": (0.9, 0.999), "lion": (0.9, 0.99), "signum": (0.9, 0.9)}
+
+
 class SaeTrainStep:
     def __init__(self, sae: Sae, lr: Optional[float] = None, auxk_alpha: float = 0.0,
                  dead_feature_threshold: int = 10_000_000, group=None, grad_acc_steps: int = 1,
                  micro_acc_steps: int = 1, lr_warmup_steps: int = 0, total_steps: Optional[int] = None,
                  init_b_dec: bool = False, fuse_next_step: bool = True, optim_bits: int = 32, auxk_path: str = "dense",
-                 threshold_lr: float = 0.01):
+                 threshold_lr: float = 0.01, optimizer: str = "adam", betas: Optional[Tuple[float, float]] = None):
         from .parallel import _unpinned
 
         group = _unpinned(group)          # (the default group is addressed as None: nothing here keeps it alive past its destroy)
         self.sae, self.auxk_alpha, self.group = sae, auxk_alpha, group
         self.dead_feature_threshold = dead_feature_threshold
+        if optimizer not in OPTIMIZERS:
+            raise ValueError(f"optimizer must be one of {OPTIMIZERS}, got {optimizer!r}")
+        self.optimizer = optimizer
+        sign = optimizer != "adam"         # "lion" / "signum": one moment, a step of +-lr per element
+        if sign and lr is None:
+            raise ValueError(f"optimizer={optimizer!r} needs an explicit lr: the default 2e-4 / sqrt(N / 2^14) is the reference's "
+                             "Adam value (trainer.py:131), and there is no sign-optimiser value to inherit from it")
+        if sign and optim_bits == 8:
+            raise ValueError(f"optim_bits=8 is the 8-bit Adam format; optimizer={optimizer!r} keeps a float32 momentum "
+                             "(an 8-bit momentum for the sign optimisers is a follow-up, DESIGN.md section 8)")
+        if betas is None:
+            betas = _DEFAULT_BETAS[optimizer]
+        betas = (float(betas[0]), float(betas[1]))
+        if optimizer == "signum" and betas[0] != betas[1]:
+            raise ValueError(f"optimizer='signum' is Lion with beta1 == beta2, got betas={betas}; use optimizer='lion'")
         if lr is None:  # trainer.py:131: 2e-4 scaled by 1/sqrt(N / 2^14)
             lr = 2e-4 / (sae.num_latents / (2 ** 14)) ** 0.5
-        self.lr, self.betas, self.eps, self.max_grad_norm = lr, (0.9, 0.999), 1e-8, 1.0
+        self.lr, self.betas, self.eps, self.max_grad_norm = lr, betas, 1e-8, 1.0
         self.grad_acc_steps, self.micro_acc_steps = grad_acc_steps, micro_acc_steps
         self.lr_warmup_steps, self.total_steps, self.init_b_dec = lr_warmup_steps, total_steps, init_b_dec
         self.params = [p for p in sae.parameters()]
@@ -102,7 +125,7 @@ class SaeTrainStep:
         # per parameter: an ops.Adam8State where the 8-bit format takes the shape, else None and float32 moments
         self.state8 = [ops.adam8_state(p) if optim_bits == 8 else None for p in self.params]
         self.exp_avg = [torch.zeros_like(p) if s8 is None else None for p, s8 in zip(self.params, self.state8)]   # torch.optim.Adam state
-        self.exp_avg_sq = [torch.zeros_like(p) if s8 is None else None for p, s8 in zip(self.params, self.state8)]
+        self.exp_avg_sq = [torch.zeros_like(p) if s8 is None and not sign else None for p, s8 in zip(self.params, self.state8)]
         self.t = 0                     # optimizer steps taken (= lr scheduler steps)
         self.global_step = 0           # batches seen (trainer.py:394)
         self._sumsq = torch.zeros(1, dtype=torch.float32, device=sae.device)
@@ -129,7 +152,7 @@ class SaeTrainStep:
 
     @property
     def optimizer_state_bytes(self) -> int:
-        """Bytes of Adam moments held (float32 tensors and 8-bit states together)."""
+        """Bytes of optimiser moments held (float32 tensors and 8-bit states together)."""
         f32 = sum(t.numel() * t.element_size() for t in self.exp_avg + self.exp_avg_sq if t is not None)
         return f32 + sum(s8.nbytes for s8 in self.state8 if s8 is not None)
 
@@ -139,11 +162,18 @@ class SaeTrainStep:
         if self.optim_bits == 8:        # (a float32 state dict is what it always was)
             sd["optim_bits"] = 8
             sd["adam8"] = [None if s8 is None else {"m8": s8.m8, "r8": s8.r8, "sm": s8.sm, "sr": s8.sr} for s8 in self.state8]
+        if self.optimizer != "adam":    # (an Adam state dict carries no optimiser key: it is what it always was)
+            sd["optimizer"], sd["betas"] = self.optimizer, self.betas
         return sd
 
     def load_state_dict(self, sd: dict) -> None:
         """Takes a checkpoint of either precision: float32 moments are quantised into an 8-bit state, an 8-bit state is
-        dequantised into float32 moments, per parameter."""
+        dequantised into float32 moments, per parameter.  A checkpoint of another optimiser is refused: the moments of
+        Adam and of a sign optimiser do not mean the same thing."""
+        theirs = sd.get("optimizer", "adam")
+        if theirs != self.optimizer:
+            raise ValueError(f"the checkpoint holds the state of optimizer={theirs!r}, this object runs "
+                             f"optimizer={self.optimizer!r}: nothing is converted between them")
         self.t = int(sd["step"])
         self.global_step = int(sd.get("global_step", self.t * self.grad_acc_steps))
         saved8 = sd.get("adam8") or [None] * len(self.params)
@@ -153,7 +183,8 @@ class SaeTrainStep:
                 if src8 is not None:
                     m, v = ops.adam8_dequantize(ops.Adam8State(*(t.to(self.params[i].device) for t in src8.tensors())))
                 self.exp_avg[i].copy_(m)
-                self.exp_avg_sq[i].copy_(v)
+                if self.exp_avg_sq[i] is not None:
+                    self.exp_avg_sq[i].copy_(v)
             else:
                 if src8 is None:
                     dev = self.params[i].device
@@ -204,7 +235,7 @@ class SaeTrainStep:
         idx = out.latent_indices
         lengths = getattr(out, "lengths", None)
         if lengths is None:
-            self._did_fire[idx.flatten()] = True
+            self._did_fire.index_fill_(0, idx.flatten().long(), True)    # (an indexed assignment copies its scalar to the device)
             return
         C = idx.shape[-1]
         keep = torch.arange(C, device=idx.device) < lengths.reshape(-1, 1)
@@ -227,7 +258,7 @@ class SaeTrainStep:
         torch.nn.utils.clip_grad_norm_(self.params, self.max_grad_norm)
 
     def _update(self, lr: float) -> None:
-        """clip_grad_norm_(1.0) -> remove_gradient_parallel_to_decoder_directions -> Adam, fused."""
+        """clip_grad_norm_(1.0) -> remove_gradient_parallel_to_decoder_directions -> Adam (or the sign update), fused."""
         sae = self.sae
         self._sumsq.zero_()
         # the squared norm of a weight gradient that came out of exactly ONE weight-gradient kernel call and was not
@@ -253,12 +284,14 @@ class SaeTrainStep:
                 kw["renorm_eps"] = torch.finfo(p.dtype).eps          # sae.py:252
             if fuse and is_enc and self._chunk_tokens > 0 and ops.coarse_in_force() != "fp8":   # (the fused pass builds int8 / bf16 operands; MSAE_COARSE=fp8 in the environment counts: ADVICE r5)
                 kw["refresh"], kw["tokens_next"] = ops.train_operand_buffer(p), self._chunk_tokens
-            kw.update(total_sumsq=self._sumsq, max_norm=self.max_grad_norm, betas=self.betas, eps=self.eps,
+            kw.update(total_sumsq=self._sumsq, max_norm=self.max_grad_norm, betas=self.betas,
                       project=sae.cfg.normalize_decoder and is_dec)
-            if s8 is None:
-                ops.adam_rows_(p.data, p.grad, m, v, self.t, lr, **kw)
+            if self.optimizer != "adam":
+                ops.lion_rows_(p.data, p.grad, m, lr, **kw)
+            elif s8 is None:
+                ops.adam_rows_(p.data, p.grad, m, v, self.t, lr, eps=self.eps, **kw)
             else:
-                ops.adam8_rows_(p.data, p.grad, s8, self.t, lr, **kw)
+                ops.adam8_rows_(p.data, p.grad, s8, self.t, lr, eps=self.eps, **kw)
             p.grad = None
             torch.autograd.graph.increment_version(p)    # p changed behind autograd's back: caches keyed on it go stale
             if "renorm_eps" in kw:
@@ -316,7 +349,7 @@ class SaeTrainStep:
             self._all_reduce(fired, dist.ReduceOp.MAX)             # max is boolean "any"
             self._did_fire = fired.bool()
             self._join_reductions()                               # DDP semantics: gradients averaged over the ranks
-        n_tok = torch.tensor(hiddens.shape[0], device=hiddens.device)
+        n_tok = torch.full((), hiddens.shape[0], dtype=torch.long, device=hiddens.device)   # (a fill: no host-to-device copy)
         self._tokens_in_step += self._all_reduce(n_tok)
         self.global_step += 1
         stepped = self.global_step % self.grad_acc_steps == 0
