@@ -15,6 +15,7 @@
 // LDS rows: 36 floats, the k of a tile permuted (f_kpos): fragment reads are one ds_read_b128 per four k-steps, bank-conflict-free.  MFMA issue is the bound: 4 MFMAs (256 cycles/SIMD) per
 // 4 ds_read_b32.
 #include "f32_tile.h"
+#include "tuning.h"
 
 namespace {
 
@@ -125,6 +126,10 @@ int launch_dt(const void *x, const float *W, const float *b_enc, const float *b_
   int tiles_n = (N + F_BN - 1) / F_BN;
   if (n_rows && tiles_m > 2) tiles_m = 2;   // device-side count: workgroups loop over the row tiles ...
   if (n_rows && tiles_n > 256) tiles_n = 256;   // ... and over the column tiles
+  if (n_rows) {                                  // (tuning.h MSAE_GRID_CAP: no cap in the product)
+    tiles_n = msae_tuning::grid_cap(tiles_n);
+    if (msae_tuning::GRID_CAP > 0) tiles_m = 1;
+  }
   dim3 grid(tiles_n, tiles_m);
   const size_t smem = F_LDS_FLOATS * sizeof(float);
   if (vec) {

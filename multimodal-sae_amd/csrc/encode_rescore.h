@@ -489,6 +489,7 @@ __global__ __launch_bounds__(64 * NW) void select_rescore_kernel(RescoreArgs p, 
   load_list<C>(p, tk);
   if constexpr (PHASE != 1) { for (int i = lane; i < tk.nrp; i += C::NT) tk.res[i] = 0ull; }
   MSAE_RTL(1);
+  MSAE_PERTURB_AT(RESCORE_LIST, 0);   // list, activations and zeroed results are in LDS: only the sorts' barriers publish them to the other waves
 
   KeyPrefix<C> pre(p, tk);
   if constexpr (PHASE == 2 && NW == 1) {       // PHASE 1's preselected + sorted prefix, as it left it in fm.keys
@@ -502,6 +503,7 @@ __global__ __launch_bounds__(64 * NW) void select_rescore_kernel(RescoreArgs p, 
   if (!pre.partial) pre.full_sort(p, tk);
   if constexpr (LEAN) { if (pre.deferred) { defer_token<C>(p, tk); return; } }
   MSAE_RTL(2);
+  MSAE_PERTURB_AT(RESCORE_SORTED, 0);   // the sorted prefix is read by every wave in first_round_target's LDS exchange
   const int has_set = p.set_feature >= 0 ? 1 : 0;
   if constexpr (PHASE != 1) { if (lane == 0 && has_set) tk.res[0] = rank_key(p.set_value, p.set_feature); }
 
@@ -511,6 +513,7 @@ __global__ __launch_bounds__(64 * NW) void select_rescore_kernel(RescoreArgs p, 
   else target = first_round_target<C>(p, tk, pre, has_set, lim);
   if constexpr (LEAN) { if (pre.deferred) { defer_token<C>(p, tk); return; } }
   MSAE_RTL(3);
+  MSAE_PERTURB_AT(RESCORE_TARGET, 0);   // first_round_target's shared picks are read; the round (or a full sort) rewrites keys[] / res[]
   const bool guarded = !EXT && tk.rc[3] != 0.f;  // the token's shape is outside the noise model (quant_x_kernel): exact path
   if (guarded) target = 0;                       // (no row is read for it here)
   if constexpr (PHASE == 1) {
@@ -546,6 +549,7 @@ __global__ __launch_bounds__(64 * NW) void select_rescore_kernel(RescoreArgs p, 
       else if (lpr == 2) my_viol = rescore_pass<C, 2>(p, tk, a, W_enc, has_set, done, target);
       else my_viol = rescore_pass<C, 1>(p, tk, a, W_enc, has_set, done, target);
     }
+    MSAE_PERTURB_AT(RESCORE_ROUND, rounds);   // this wave's results are in res[]: the barrier hands them to the result sort
     done = target;
     viol = viol || (__syncthreads_or(my_viol) != 0);
     MSAE_RTL(2 + 2 * rounds);
@@ -553,6 +557,7 @@ __global__ __launch_bounds__(64 * NW) void select_rescore_kernel(RescoreArgs p, 
     // one key per lane / four per thread of four waves (k = 256: ~350 results) hold it
     lds_sort_desc_u64<NW, NW == 1 ? 1 : 4>(tk.res, next_pow2(done + has_set > 2 ? done + has_set : 2), tk.nrp, lane);
     MSAE_RTL(3 + 2 * rounds);
+    MSAE_PERTURB_AT(RESCORE_VERIFY, rounds);   // the sorted results are read by verify on every wave
     int needed;
     bool last;
     ok = verify<C>(p, tk, pre, has_set, done, lim, viol, guarded, needed, last);
@@ -561,6 +566,7 @@ __global__ __launch_bounds__(64 * NW) void select_rescore_kernel(RescoreArgs p, 
     if constexpr (LEAN) { defer_token<C>(p, tk); return; }   // a follow-up round: the full-size launch (rows token-major, activations in LDS)
     target = needed > done ? needed : done + 1;
     if (target > lim) target = lim;
+    MSAE_PERTURB_AT(RESCORE_FOLLOWUP, rounds);   // a follow-up round appends to res[] behind this barrier while slower waves still verify
     __syncthreads();
   }
 
@@ -608,6 +614,7 @@ __global__ __launch_bounds__(256) void fm_scan_kernel(int *__restrict__ counts, 
 #pragma unroll
   for (int e = 0; e < 4; ++e) { c[e] = (i0 + e < N) ? counts[i0 + e] : 0; sum += fm_pad(c[e], G); }
   part[tid] = sum;
+  MSAE_PERTURB_AT(RESCORE_FM_SCAN, 0);   // the four waves' partial sums meet in the LDS scan
   __syncthreads();
   for (int off = 1; off < 256; off <<= 1) {
     const int v = tid >= off ? part[tid - off] : 0;
@@ -690,6 +697,7 @@ __global__ __launch_bounds__(64) void fm_dot_kernel(const void *__restrict__ x, 
                                                     float *__restrict__ fm_pre) {
   const int n_slots = *n_slots_p;                        // a multiple of G
   if ((int)blockIdx.x * 64 >= n_slots) return;
+  MSAE_PERTURB_AT(RESCORE_FM_DOT, 0);   // the pairs of one token are spread over workgroups that finish in any order (PHASE 2 picks them up)
   const int lane = threadIdx.x, slot = blockIdx.x * 64 + lane;
   // slots behind the last one: lanes of whole groups (n_slots % G == 0); they walk the last feature's row, without a token
   const int2 fo = slot < n_slots ? slots[slot] : make_int2(slots[n_slots - 1].x, -1);

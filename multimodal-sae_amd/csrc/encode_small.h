@@ -505,10 +505,12 @@ __global__ __launch_bounds__(64) void rescore_small_kernel(const float *__restri
     exact[(size_t)t * 128 + r] = 0ull;
   }
   // release our result, count this wave in; the last one acquires everybody's
+  MSAE_PERTURB_AT(SMALL_ARRIVE, 0);   // the token's waves arrive in any order: the counter's release / acquire is all that orders their results
   if (lane == 0)
     s_last = __hip_atomic_fetch_add(done + t, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1;
   __syncthreads();
   if (!s_last) return;
+  MSAE_PERTURB_AT(SMALL_FINAL, 0);   // the last wave to arrive reads every other wave's result behind this acquire
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // every lane reads the other waves' results below
   const int vi = __hip_atomic_load(viol + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   finalize_small(keys, exact, tau[t], t, k, set_feature, set_value, vi, vals, idx, status, flagged, n_flagged, lane);

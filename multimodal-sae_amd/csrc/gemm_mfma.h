@@ -780,8 +780,10 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[C::MI][C::NI], const
   constexpr int QCAP = C::QCAP;
   unsigned *q_count = reinterpret_cast<unsigned *>(smem + C::LDS_RING_BYTES + C::SIDE_BYTES);
   unsigned long long *queue = reinterpret_cast<unsigned long long *>(smem + C::LDS_RING_BYTES + C::SIDE_BYTES + 16);
+  MSAE_PERTURB_AT(GEMM_EPI_ENTER, m0 * 31 + n0);   // this wave's side-buffer words are written: the barrier publishes them and ends the last k-tile's reads
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();                        // side buffer written; previous tile's flush done
+  MSAE_PERTURB_AT(GEMM_EPI_BEHIND, m0 * 31 + n0);   // the queue count is reset behind the barrier, in front of the first reservation
   if constexpr (!DENSE) {
     if (threadIdx.x == 0) *q_count = 0u;
     __syncthreads();
@@ -919,6 +921,7 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[C::MI][C::NI], const
   }
   MSAE_TL(4);
   if constexpr (!DENSE) {
+    MSAE_PERTURB_AT(GEMM_EPI_FLUSH, m0 * 31 + n0);   // this wave's pushes are in the LDS queue: the barrier hands them to the flush
     __syncthreads();
     const unsigned nq = msae_tuning::ABL_NOFLUSH ? 0u : (*q_count < QCAP ? *q_count : QCAP);
     for (unsigned q = threadIdx.x; q < nq; q += C::NT) {
@@ -931,6 +934,7 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[C::MI][C::NI], const
       const int feat = gemm_feature(ep, n0 + col);
       gemm_push_candidate(ep, t, rank_key(u, feat));
     }
+    MSAE_PERTURB_AT(GEMM_EPI_FLUSHED, m0 * 31 + n0);   // a wave done flushing runs ahead into the next tile while others still read queue and side buffer
   }
   MSAE_TL(5);
 }
@@ -949,6 +953,7 @@ __global__ __launch_bounds__(C::NT) void gemm_kernel(GemmOperands op, int T, int
   for (int tile_id = blockIdx.x; tile_id < nM * nN; tile_id += gridDim.x) {
   ++tl_tile;
   MSAE_TL(0);
+  MSAE_PERTURB_AT(GEMM_TILE_ENTRY, tile_id);   // a wave starts the next tile while slower ones are still in the previous epilogue
   // the thread id is made opaque per tile: otherwise every lane-dependent address of the
   // prologue and the epilogue is hoisted out of this loop and lives across the k-loop (spills)
   int tid_ = threadIdx.x;
@@ -1045,10 +1050,12 @@ __global__ __launch_bounds__(C::NT) void gemm_kernel(GemmOperands op, int T, int
     MSAE_TLK(kt == 9, 5);
     wait_vmcnt<0>();               // this wave's pieces of k-tile kt (and the side constants) landed
     if (park_m) {                  // outlier multipliers (and -E) of the tile's rows -> LDS (read after this k-tile)
+      MSAE_PERTURB_AT(GEMM_PARK_EARLY, tile_id);   // the EARLY pair is written while the previous tile's epilogue may still read the side buffer
       side.park_early(tid_, side_regs);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
     MSAE_TLK(kt == 8, 1);
+    MSAE_PERTURB_AT_K(GEMM_KTILE_BARRIER, seq);   // this wave's pieces have landed: the barrier is all that publishes them to the others
     __builtin_amdgcn_s_barrier();  // ... and everybody's; the other slot is free again
     MSAE_TLK(kt == 8, 2);
     if (kt == 0) MSAE_TL(1);
@@ -1067,7 +1074,10 @@ __global__ __launch_bounds__(C::NT) void gemm_kernel(GemmOperands op, int T, int
     // counts now; behind k-step 2 costs 9 %, everybody at the top 2 %: profiles/r05_ab_stagger_at.txt.)
     const bool late = MSAE_GEMM_STAGGER != 0 && (MSAE_GEMM_STAGGER == 2 ? (wave & 1) != 0 : wave >= C::NWAVES / 2) && !park_m && nM > 1;
     if constexpr (!C::ABL_NOSTAGE) {
-      if (!late) stage_next();
+      if (!late) {
+        MSAE_PERTURB_AT_K(GEMM_STAGE_EARLY, seq);   // the slot staged into was read in the previous k-tile: only the barrier frees it
+        stage_next();
+      }
     }
     MSAE_TLK(kt == 8, 3);
     const unsigned char *sA = smem + (seq & 1) * C::STAGE_BYTES;
@@ -1077,7 +1087,10 @@ __global__ __launch_bounds__(C::NT) void gemm_kernel(GemmOperands op, int T, int
     }
     else if constexpr (!C::ABL_NOREAD && !C::ABL_NOMFMA && !C::ABL_NOSTAGE)
       gemm_compute_asm<C>(acc, sA, wr, wc, lane, [&](int pos) {
-        if (late && pos == MSAE_GEMM_STAGGER_AT) stage_next();
+        if (late && pos == MSAE_GEMM_STAGGER_AT) {
+          MSAE_PERTURB_AT_K(GEMM_STAGE_LATE, seq);   // the staggered waves stage into the free slot from inside the compute phase
+          stage_next();
+        }
       });
     else gemm_compute<C>(acc, sA, sA + C::A_BYTES, wr, wc, lane, abl_a, abl_b);
     MSAE_TLK(kt == 8, 4);
@@ -1128,11 +1141,13 @@ __global__ __launch_bounds__(C::NT) void gemm_kernel(GemmOperands op, int T, int
   }
 
   MSAE_TL(3);
+  MSAE_PERTURB_AT(GEMM_SIDE_PARK, tile_id);   // the side buffer is rewritten: every wave has left the previous epilogue's flush (k-tile barriers)
   side.template park<DENSE>(tid_, side_regs, ep.zz12);
   // behind the epilogue's first barrier every wave is done with the last k-tile's slot: the next tile's first main
   // k-tile lands there while the epilogue runs (its outlier tile is already in the other slot)
   gemm_epilogue<C, DENSE>(acc, ep, T, m0, n0, wr, wc, lane, smem, side, tl_tile);
   MSAE_TL(6);
+  MSAE_PERTURB_AT(GEMM_TILE_EXIT, tile_id);   // the waves leave a tile apart: the next tile's entry and EARLY park meet this one's flush
   }
 }
 
@@ -1152,7 +1167,8 @@ inline int gemm_launch(const GemmOperands &op, int T, int Tp, int N, const GemmE
   }();
   const char *np_env = getenv("MSAE_GEMM_NONPERSISTENT");
   const int per_cu = C::LDS_BYTES > 80 * 1024 ? 1 : 2;
-  const int grid = (np_env || nM * nN <= n_cu * per_cu) ? nM * nN : n_cu * per_cu;
+  const int grid = msae_tuning::grid_cap((np_env || nM * nN <= n_cu * per_cu) ? nM * nN : n_cu * per_cu);
+  MSAE_PERTURB_LAUNCH(DENSE ? 0 : 1, nM * nN, grid);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(C::NT), C::LDS_BYTES, s, op, T, Tp, N, nM, nN, ep);
   return (int)hipGetLastError();
 }

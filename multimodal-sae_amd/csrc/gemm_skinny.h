@@ -65,6 +65,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_skinny_kernel(GemmOperands op, i
   const GemmSide<C> side(smem);
   const typename GemmSide<C>::Regs side_regs = GemmSide<C>::template fetch<DENSE>(ep, tid, m0, n0, m0 + T, has_out);
   side.park_early(tid, side_regs);
+  MSAE_PERTURB_AT(SKINNY_ENTRY, 0);   // the EARLY pair is parked; the barrier behind the outlier tile publishes it
   const bool sub_e = ep.row_e != nullptr;              // (wave-uniform)
 
   // v_mfma_i32_16x16x64_i8: A = 16 tokens x 64 B of k, B = 16 features x 64 B of k (lane l: row l % 16, bytes 16 (l / 16) ..),
@@ -217,6 +218,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_skinny_kernel(GemmOperands op, i
         }
       }
       const bool last = c + 1 == nchunks && b + 1 == BPC;
+      MSAE_PERTURB_AT_K(SKINNY_BATCH, c * BPC + b);   // between the load batches: the waves drift apart inside a chunk of the shared A buffer
       if (!last && !(MSAE_SK_ABL & 2)) load_b(ba, b + 1 < BPC ? ks_of(c, b + 1) : ks_of(c + 1, 0));
 #pragma unroll
       for (int u = 0; u < UN; ++u) {
@@ -231,6 +233,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_skinny_kernel(GemmOperands op, i
       put_a((c + 1) & 1);                               // the other buffer: last read in iteration c - 1 (barrier below)
       // ADMA: the next chunk's pieces were issued at the top of this iteration; everything issued since is B loads, of which
       // only the last batch (2 UN loads: ba for the next iteration) may still be in flight -- vmcnt counts in order
+      MSAE_PERTURB_AT(SKINNY_CHUNK, c);   // the next A chunk is written beside slower waves' reads of this one: the raw barrier hands it over
       if constexpr (C::ADMA) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * UN) : "memory");
       // a raw barrier: __syncthreads() would also wait for vmcnt(0), i.e. drain the B batches in flight at every chunk
       // (measured: the stream ran at 3.3 TB/s with it)
@@ -249,6 +252,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_skinny_kernel(GemmOperands op, i
     constexpr int HR = C::ADMA ? 64 : (C::BM < 128 ? C::BM : 128), NH = C::BM / HR;   // (the unpadded ADMA ring holds 64 image rows)
     static_assert(HR * TP * 4 <= C::LDS_RING_BYTES, "tile image fits the A buffers");
     int *timg = reinterpret_cast<int *>(smem);
+    MSAE_PERTURB_AT(SKINNY_EPILOGUE, 0);   // the A buffers become the accumulator image while slower waves still read the last chunk
 #pragma unroll
     for (int h = 0; h < NH; ++h) {
       __syncthreads();                                   // every wave is done with the A buffers / the previous half

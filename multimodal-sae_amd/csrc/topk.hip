@@ -15,6 +15,7 @@
 
 #include "common.h"
 #include "sortsel.h"
+#include "tuning.h"
 #include "wave_ops.h"
 
 namespace {
@@ -534,7 +535,8 @@ int msae_topk_launch(const float *latents, int T, int N, int k, int ld, const in
     if (vec) MSAE_HIP_TRY(hipFuncSetAttribute((const void *)topk_rows_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     else MSAE_HIP_TRY(hipFuncSetAttribute((const void *)topk_rows_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
   }
-  const int grid = (n_rows && T > 128) ? 128 : T;   // device-side count: workgroups loop over the rows
+  int grid = (n_rows && T > 128) ? 128 : T;   // device-side count: workgroups loop over the rows
+  if (n_rows) grid = msae_tuning::grid_cap(grid);   // (tuning.h MSAE_GRID_CAP: no cap in the product)
   if (vec)
     hipLaunchKernelGGL(topk_rows_kernel<true>, dim3(grid), dim3(TK_THREADS), smem, s, latents, T, N, k, ld,
                        n_rows, vals, idx, ex);

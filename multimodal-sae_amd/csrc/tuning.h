@@ -136,3 +136,147 @@ __device__ unsigned long long g_rs_tl[64 * 16];
 #define MSAE_RTL(slot) do { } while (0)
 #define MSAE_RTL_VALUE(slot, v) do { } while (0)
 #endif
+
+// ---- perturbed-schedule build (csrc/build.sh: libmsae_hip_perturb.so; tests/test_gpu_perturbed_schedule.py) -------------------
+// MSAE_GRID_CAP (0 = none): the looping launches run at most this many workgroups, so that each walks several tiles at a test's
+// small shapes: the persistent grid of gemm_launch (a multiple of 8: gemm_map_tile's XCD super-tile), and the column-tile and row
+// grids of the in-call exact fallback (encode_f32.hip: launch_dt with n_rows, topk.hip: msae_topk_launch with n_rows).
+#ifndef MSAE_GRID_CAP
+#define MSAE_GRID_CAP 0
+#endif
+static_assert(MSAE_GRID_CAP >= 0 && MSAE_GRID_CAP % 8 == 0, "MSAE_GRID_CAP: 0 or a multiple of 8");
+namespace msae_tuning {
+constexpr int GRID_CAP = MSAE_GRID_CAP;
+constexpr int grid_cap(int grid) { return GRID_CAP > 0 && grid > GRID_CAP ? GRID_CAP : grid; }
+}  // namespace msae_tuning
+
+// MSAE_PERTURB: MSAE_PERTURB_AT(site, visit) delays the calling WAVE by a pseudo-random time on about one visit in four (per-k-tile
+// sites, MSAE_PERTURB_AT_K: one in sixteen), so that the waves of a workgroup -- and the workgroups of a launch -- meet every
+// hand-synchronised hand-over at relative speeds the product's one schedule never shows.  The delay is a hash of (run seed,
+// workgroup, wave, site, the wave's visit counter): no clock is read, a run repeats from its seed.  Up to MSAE_PERTURB_MAX
+// s_sleep units of 64 clocks: 32 (~2000 cycles) by default; build.sh builds the variant with 256, because a delay only shows a
+// missing barrier when it is longer than the path it races against (epilogue exit -> next tile's side fetch -> early park is a
+// global-load round trip, ~2000 cycles by itself: profiles/perturb_sensitivity.txt).  One site per hand-over; the
+// comment at each MSAE_PERTURB_AT says which.  X(enum name, hand-over)
+#define MSAE_PERTURB_SITES(X) \
+  X(GEMM_TILE_ENTRY, "gemm_kernel: a wave enters a tile while others may be in the previous tile's epilogue") \
+  X(GEMM_PARK_EARLY, "gemm_kernel: in front of GemmSide::park_early (EARLY pair vs the previous epilogue's side reads)") \
+  X(GEMM_KTILE_BARRIER, "gemm_kernel: in front of the k-tile barrier (vmcnt(0) of this wave vs the others' fragment reads)") \
+  X(GEMM_STAGE_EARLY, "gemm_kernel: behind the barrier, in front of stage_next() of the early waves (ring slot reuse)") \
+  X(GEMM_STAGE_LATE, "gemm_kernel: in front of stage_next() of the staggered waves, inside the compute phase") \
+  X(GEMM_SIDE_PARK, "gemm_kernel: behind the k-loop, in front of GemmSide::park (vs the previous epilogue's flush)") \
+  X(GEMM_EPI_ENTER, "gemm_epilogue: in front of its first barrier (side buffer written, previous flush done)") \
+  X(GEMM_EPI_BEHIND, "gemm_epilogue: behind its first barrier (queue count reset vs the first reservations)") \
+  X(GEMM_EPI_FLUSH, "gemm_epilogue: in front of the queue flush's barrier (pushes vs the flush's reads)") \
+  X(GEMM_EPI_FLUSHED, "gemm_epilogue: behind the flush loop (vs the next tile's reservations and side writes)") \
+  X(GEMM_TILE_EXIT, "gemm_kernel: tile exit") \
+  X(SKINNY_ENTRY, "gemm_skinny_kernel: behind park_early, in front of the first loads") \
+  X(SKINNY_BATCH, "gemm_skinny_kernel: between the two B load batches of a double-batch") \
+  X(SKINNY_CHUNK, "gemm_skinny_kernel: in front of the raw barrier that hands an A buffer over") \
+  X(SKINNY_EPILOGUE, "gemm_skinny_kernel: in front of the accumulator image's first barrier (A buffers become the image)") \
+  X(SMALL_ARRIVE, "rescore_small_kernel: in front of the token's device-scope arrival counter") \
+  X(SMALL_FINAL, "rescore_small_kernel: the finalising wave, in front of its acquire") \
+  X(RESCORE_LIST, "select_rescore_kernel: behind load_list (list and activations in LDS vs the sorts)") \
+  X(RESCORE_SORTED, "select_rescore_kernel: behind the prefix sort, in front of first_round_target's LDS exchange") \
+  X(RESCORE_TARGET, "select_rescore_kernel: behind first_round_target, in front of the round") \
+  X(RESCORE_ROUND, "select_rescore_kernel: behind a round's re-score pass, in front of its result sort") \
+  X(RESCORE_VERIFY, "select_rescore_kernel: behind the result sort, in front of verify") \
+  X(RESCORE_FOLLOWUP, "select_rescore_kernel: in front of a follow-up round's barrier") \
+  X(RESCORE_FM_SCAN, "fm_scan_kernel (feature-major first round): in front of the LDS scan of the waves' partial sums") \
+  X(RESCORE_FM_DOT, "fm_dot_kernel (feature-major first round): workgroup entry (a token's pairs finish in any order)")
+enum MsaePerturbSite {
+#define MSAE_PS_ENUM(name, what) PS_##name,
+  MSAE_PERTURB_SITES(MSAE_PS_ENUM)
+#undef MSAE_PS_ENUM
+  MSAE_PERTURB_NSITES
+};
+#ifdef MSAE_PERTURB
+#ifndef MSAE_PERTURB_MAX       // longest delay in s_sleep units of 64 clocks (32: ~2000 cycles)
+#define MSAE_PERTURB_MAX 32
+#endif
+__device__ unsigned long long g_perturb_hits[MSAE_PERTURB_NSITES];
+__device__ unsigned g_perturb_seed;
+__device__ __forceinline__ unsigned msae_perturb_mix(unsigned h, unsigned v) {
+  h ^= v + 0x9E3779B9u + (h << 6) + (h >> 2);
+  h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
+  return h;
+}
+// `visit` is the wave's visit counter of the site, read off the loop the site stands in (tile id, flat k-tile number, round)
+// instead of being kept in memory: a counter fetched with a returning atomic costs a memory round trip per visit, as long as the
+// delays themselves, on exactly the paths (epilogue exit -> next tile's early park) whose shortness the probes are there to test.
+// The books are one fire-and-forget atomic of the first active lane.
+__device__ __forceinline__ void msae_perturb_at(int site, unsigned visit, unsigned one_in) {
+  const unsigned lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+  if (lane == (unsigned)__builtin_ctzll(__ballot(1))) atomicAdd(&g_perturb_hits[site], 1ull);
+  const unsigned wg = blockIdx.x + gridDim.x * blockIdx.y, wave = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const unsigned seed = g_perturb_seed;   // 0 (the state until a seed is set): count the visit, never sleep
+  unsigned h = msae_perturb_mix(seed, wg);
+  h = msae_perturb_mix(h, wave);
+  h = msae_perturb_mix(h, (unsigned)site);
+  h = msae_perturb_mix(h, (unsigned)__builtin_amdgcn_readfirstlane((int)visit));
+  const unsigned units = seed != 0u && h % one_in == 0u ? (h >> 8) % (unsigned)(MSAE_PERTURB_MAX + 1) : 0u;   // wave-uniform: s_sleep ignores EXEC
+  for (unsigned i = 0; i < units; ++i) __builtin_amdgcn_s_sleep(1);
+}
+#define MSAE_PERTURB_AT(site, visit) msae_perturb_at(PS_##site, (unsigned)(visit), 4u)
+#define MSAE_PERTURB_AT_K(site, visit) msae_perturb_at(PS_##site, (unsigned)(visit), 16u)
+// host side: the last candidate-GEMM launches (gemm_launch), so that a test can ASSERT its tiles per workgroup
+struct MsaePerturbLaunch { int kind, tiles, grid; };   // kind: 0 = sample (DENSE), 1 = main (THRESH)
+constexpr int MSAE_PERTURB_NLAUNCH = 64;
+inline MsaePerturbLaunch g_perturb_launches[MSAE_PERTURB_NLAUNCH];
+inline int g_perturb_n_launches = 0;
+#define MSAE_PERTURB_LAUNCH(kind, tiles, grid) \
+  (g_perturb_launches[g_perturb_n_launches++ % MSAE_PERTURB_NLAUNCH] = MsaePerturbLaunch{(kind), (tiles), (grid)})
+// Exported by the variant only (the one translation unit built with MSAE_PERTURB: encode_fused.hip); the test runner binds them
+// itself.  The seed: MSAE_PERTURB_SEED in the environment, read at the first reset, or msae_perturb_set_seed; seed 0 (the
+// state until one is set) switches the delays off.
+extern "C" __attribute__((visibility("default"))) int msae_perturb_set_seed(unsigned seed) {
+  return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_perturb_seed), &seed, sizeof(seed));
+}
+// zero the site counters and the launch record
+extern "C" __attribute__((visibility("default"))) int msae_perturb_reset() {
+  static const bool seeded = [] {
+    const char *e = getenv("MSAE_PERTURB_SEED");
+    if (e) (void)msae_perturb_set_seed((unsigned)strtoul(e, nullptr, 0));
+    return true;
+  }();
+  (void)seeded;
+  void *hits = nullptr;
+  if (hipDeviceSynchronize() != hipSuccess) return (int)hipGetLastError();
+  if (hipGetSymbolAddress(&hits, HIP_SYMBOL(g_perturb_hits)) != hipSuccess) return (int)hipGetLastError();
+  if (hipMemset(hits, 0, sizeof(g_perturb_hits)) != hipSuccess) return (int)hipGetLastError();
+  g_perturb_n_launches = 0;
+  return (int)hipDeviceSynchronize();
+}
+// out[0, min(n, sites)) = visits per site since the last reset; returns the number of sites (negative: a HIP error)
+extern "C" __attribute__((visibility("default"))) int msae_perturb_hits(unsigned long long *out, int n) {
+  unsigned long long h[MSAE_PERTURB_NSITES];
+  if (hipDeviceSynchronize() != hipSuccess || hipMemcpyFromSymbol(h, HIP_SYMBOL(g_perturb_hits), sizeof(h)) != hipSuccess)
+    return -(int)hipGetLastError() - 1;
+  for (int i = 0; i < n && i < MSAE_PERTURB_NSITES; ++i) out[i] = h[i];
+  return MSAE_PERTURB_NSITES;
+}
+extern "C" __attribute__((visibility("default"))) const char *msae_perturb_site_name(int site) {
+  static const char *const names[] = {
+#define MSAE_PS_NAME(name, what) #name ": " what,
+    MSAE_PERTURB_SITES(MSAE_PS_NAME)
+#undef MSAE_PS_NAME
+  };
+  return site >= 0 && site < MSAE_PERTURB_NSITES ? names[site] : nullptr;
+}
+// out[3 i ..] = (kind, tiles, grid) of the i-th candidate-GEMM launch since the previous call (or reset), oldest first, at most n
+// of the last MSAE_PERTURB_NLAUNCH; returns how many were written and starts the record afresh
+extern "C" __attribute__((visibility("default"))) int msae_perturb_launches(int *out, int n) {
+  const int have = g_perturb_n_launches < MSAE_PERTURB_NLAUNCH ? g_perturb_n_launches : MSAE_PERTURB_NLAUNCH;
+  const int first = g_perturb_n_launches - have, m = have < n ? have : n;
+  for (int i = 0; i < m; ++i) {
+    const MsaePerturbLaunch &l = g_perturb_launches[(first + i) % MSAE_PERTURB_NLAUNCH];
+    out[3 * i] = l.kind; out[3 * i + 1] = l.tiles; out[3 * i + 2] = l.grid;
+  }
+  g_perturb_n_launches = 0;
+  return m;
+}
+#else
+#define MSAE_PERTURB_AT(site, visit) do { } while (0)
+#define MSAE_PERTURB_AT_K(site, visit) do { } while (0)
+#define MSAE_PERTURB_LAUNCH(kind, tiles, grid) do { } while (0)
+#endif
