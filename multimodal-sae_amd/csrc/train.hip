@@ -87,63 +87,6 @@ __device__ __forceinline__ void adam_update(float &w, float g, float &m, float &
   w -= step_size * (m / denom);                      // addcdiv_(m, denom, -step_size)
 }
 
-// One workgroup per row r of W/G/M/V [rows][d]:
-//   c     = min(1, max_norm / (sqrt(*total_sumsq) + 1e-6))        (clip_grad_norm_)
-//   g     = c * G[r][:]
-//   g    -= <g, W[r][:]> * W[r][:]      if project                (sae.py:266-271, after clipping)
-//   Adam(W, g, M, V)
-__global__ __launch_bounds__(256) void adam_rows_kernel(float *__restrict__ W, const float *__restrict__ G,
-                                                        float *__restrict__ M, float *__restrict__ V,
-                                                        int d, const float *__restrict__ total_sumsq,
-                                                        AdamArgs a) {
-  __shared__ float red[4];
-  const size_t base = (size_t)blockIdx.x * d;
-  float clip = 1.f;
-  if (total_sumsq) {
-    const float c = a.max_norm / (sqrtf(*total_sumsq) + 1e-6f);
-    clip = c < 1.f ? c : 1.f;
-  }
-  float along = 0.f;
-  if (a.project) {
-    float dot = 0.f;
-    if ((d & 3) == 0) {
-      for (int c = threadIdx.x * 4; c < d; c += 1024) {
-        const f32x4 g = *reinterpret_cast<const f32x4 *>(G + base + c);
-        const f32x4 w = *reinterpret_cast<const f32x4 *>(W + base + c);
-        dot += (g[0] * clip) * w[0] + (g[1] * clip) * w[1] + (g[2] * clip) * w[2] + (g[3] * clip) * w[3];
-      }
-    } else {
-      for (int c = threadIdx.x; c < d; c += 256) dot += (G[base + c] * clip) * W[base + c];
-    }
-    along = block_sum(dot, red);
-  }
-  if ((d & 3) == 0) {
-    for (int c = threadIdx.x * 4; c < d; c += 1024) {
-      const f32x4 g = *reinterpret_cast<const f32x4 *>(G + base + c);     // L2 hit when projecting
-      f32x4 w = *reinterpret_cast<const f32x4 *>(W + base + c);
-      f32x4 m = *reinterpret_cast<const f32x4 *>(M + base + c);
-      f32x4 v = *reinterpret_cast<const f32x4 *>(V + base + c);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float ge = g[e] * clip, we = w[e], me = m[e], ve = v[e];
-        if (a.project) ge -= along * we;
-        adam_update(we, ge, me, ve, a);
-        w[e] = we; m[e] = me; v[e] = ve;
-      }
-      *reinterpret_cast<f32x4 *>(W + base + c) = w;
-      *reinterpret_cast<f32x4 *>(M + base + c) = m;
-      *reinterpret_cast<f32x4 *>(V + base + c) = v;
-    }
-  } else {
-    for (int c = threadIdx.x; c < d; c += 256) {
-      float ge = G[base + c] * clip, w = W[base + c], m = M[base + c], v = V[base + c];
-      if (a.project) ge -= along * w;
-      adam_update(w, ge, m, v, a);
-      W[base + c] = w; M[base + c] = m; V[base + c] = v;
-    }
-  }
-}
-
 // *accum += sum(v[0 .. n)) in a FIXED order (one workgroup: per-thread strided partial sums, then block_sum): the total of
 // the per-row squared gradient norms the weight-gradient kernel wrote (msae_decode_bwd_wdec_f32: row_sumsq)
 __global__ __launch_bounds__(1024) void sum_fixed_kernel(const float *__restrict__ v, size_t n, float *__restrict__ accum) {
@@ -208,9 +151,15 @@ __global__ __launch_bounds__(256) void weighted_rows_sum_kernel(const float *__r
   out[(size_t)blockIdx.y * d + c] = scale * ((a0 + a1) + (a2 + a3));
 }
 
-// adam_rows_kernel with the NEXT step's passes over the same matrix folded in (d % 4 == 0; the updated row stays in registers
-// for d <= 8192):
-//   renorm_eps >= 0   W[r] /= |W[r]| + eps after the update: the trainer's set_decoder_norm_to_unit_norm at the top of the next
+// ---- the optimiser row passes ------------------------------------------------------------------------------------------------
+// One workgroup per row r of W, G and the moments [rows][d]:
+//   c     = min(1, max_norm / (sqrt(*total_sumsq) + 1e-6))        (clip_grad_norm_)
+//   g     = c * G[r][:]
+//   g    -= <g, W[r][:]> * W[r][:]      if project                (sae.py:266-271, after clipping)
+//   the optimiser's update of W[r] and its moments from g         (the update policies below)
+// opt_rows_kernel is that pass alone, for any d.  opt_rows_fused_kernel (d % 4 == 0; the updated row stays in registers for
+// d <= 8192) folds the NEXT step's passes over the same matrix in:
+//   renorm_eps >= 0  W[r] /= |W[r]| + eps after the update: the trainer's set_decoder_norm_to_unit_norm at the top of the next
 //                     step (sae.py:249-255, trainer.py:352) -- same arithmetic, reduction order and bits as unit_norm_rows_kernel,
 //                     without its read + write of the 2 GiB matrix
 //   REFRESH 1 / 2     the coarse-pass operands of the updated encoder row (int8: row statistics + quantised copies, as
@@ -222,9 +171,7 @@ struct FusedTail {
   unsigned short *wb, *ws;      // REFRESH 2: bf16 copy + bf16 sample rows
 };
 
-// ---- the steps of the fused pass as functions: adam8_rows_kernel (8-bit moments) is built from them.  adam_rows_fused_kernel
-// (float32 moments) uses clip_coef and refresh_row and keeps its projection / KEEP loops written out as they were: it is the
-// benchmarked kernel, and written this way the compiler emits the instructions it emitted before the 8-bit kernel existed.
+// ---- the steps of a row pass, one copy each ---------------------------------------------------------------------------------
 // c = min(1, max_norm / (sqrt(*total_sumsq) + 1e-6)), 1 without a total
 __device__ __forceinline__ float clip_coef(const float *__restrict__ total_sumsq, float max_norm) {
   float clip = 1.f;
@@ -234,14 +181,18 @@ __device__ __forceinline__ float clip_coef(const float *__restrict__ total_sumsq
   }
   return clip;
 }
-// <clip * G[r], W[r]> of the workgroup's row (d % 4 == 0)
+// <clip * G[r], W[r]> of the workgroup's row; vec4: d % 4 == 0, read 16 bytes at a time
 __device__ __forceinline__ float row_along(const float *__restrict__ G, const float *__restrict__ W, size_t base, int d,
-                                           float clip, float *red) {
+                                           float clip, bool vec4, float *red) {
   float dot = 0.f;
-  for (int c = threadIdx.x * 4; c < d; c += 1024) {
-    const f32x4 g = *reinterpret_cast<const f32x4 *>(G + base + c);
-    const f32x4 w = *reinterpret_cast<const f32x4 *>(W + base + c);
-    dot += (g[0] * clip) * w[0] + (g[1] * clip) * w[1] + (g[2] * clip) * w[2] + (g[3] * clip) * w[3];
+  if (vec4) {
+    for (int c = threadIdx.x * 4; c < d; c += 1024) {
+      const f32x4 g = *reinterpret_cast<const f32x4 *>(G + base + c);
+      const f32x4 w = *reinterpret_cast<const f32x4 *>(W + base + c);
+      dot += (g[0] * clip) * w[0] + (g[1] * clip) * w[1] + (g[2] * clip) * w[2] + (g[3] * clip) * w[3];
+    }
+  } else {
+    for (int c = threadIdx.x; c < d; c += 256) dot += (G[base + c] * clip) * W[base + c];
   }
   return block_sum(dot, red);
 }
@@ -283,70 +234,6 @@ __device__ __forceinline__ void refresh_row(float *__restrict__ W, size_t base, 
   }
 }
 
-template <int REFRESH>
-__global__ __launch_bounds__(256) void adam_rows_fused_kernel(float *__restrict__ W, const float *__restrict__ G,
-                                                              float *__restrict__ M, float *__restrict__ V,
-                                                              int d, const float *__restrict__ total_sumsq,
-                                                              AdamArgs a, FusedTail ft) {
-  __shared__ float red[4];
-  __shared__ float red3[3][4];
-  const size_t base = (size_t)blockIdx.x * d;
-  const float clip = clip_coef(total_sumsq, a.max_norm);
-  float along = 0.f;
-  if (a.project) {
-    float dot = 0.f;
-    for (int c = threadIdx.x * 4; c < d; c += 1024) {
-      const f32x4 g = *reinterpret_cast<const f32x4 *>(G + base + c);
-      const f32x4 w = *reinterpret_cast<const f32x4 *>(W + base + c);
-      dot += (g[0] * clip) * w[0] + (g[1] * clip) * w[1] + (g[2] * clip) * w[2] + (g[3] * clip) * w[3];
-    }
-    along = block_sum(dot, red);
-  }
-  const bool renorm = ft.renorm_eps >= 0.f;
-  f32x4 keep[KEEP];
-  float ss = 0.f;
-  {
-    int it = 0;
-    for (int c = threadIdx.x * 4; c < d; c += 1024, ++it) {
-      // the moments are touched exactly once per step (and the gradient, unless the projection has just read it): streaming
-      // accesses, kept out of the caches' way (MSAE_ADAM_PLAIN_LOADS in a tuning build switches the hint off)
-      const f32x4 g = a.project ? *reinterpret_cast<const f32x4 *>(G + base + c)     // L2 hit when projecting
-                                : MSAE_ADAM_LOAD(reinterpret_cast<const f32x4 *>(G + base + c));
-      f32x4 w = *reinterpret_cast<const f32x4 *>(W + base + c);
-      f32x4 m = MSAE_ADAM_LOAD(reinterpret_cast<const f32x4 *>(M + base + c));
-      f32x4 v = MSAE_ADAM_LOAD(reinterpret_cast<const f32x4 *>(V + base + c));
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float ge = g[e] * clip, we = w[e], me = m[e], ve = v[e];
-        if (a.project) ge -= along * we;
-        adam_update(we, ge, me, ve, a);
-        w[e] = we; m[e] = me; v[e] = ve;
-      }
-      MSAE_ADAM_STORE(m, reinterpret_cast<f32x4 *>(M + base + c));
-      MSAE_ADAM_STORE(v, reinterpret_cast<f32x4 *>(V + base + c));
-      if (renorm) {
-#pragma unroll
-        for (int q = 0; q < KEEP; ++q) if (q == it) keep[q] = w;
-        ss += w[0] * w[0] + w[1] * w[1] + w[2] * w[2] + w[3] * w[3];
-      } else {
-        *reinterpret_cast<f32x4 *>(W + base + c) = w;
-      }
-    }
-  }
-  if (renorm) {
-    const float inv = 1.f / (sqrtf(block_sum(ss, red)) + ft.renorm_eps);
-    int it = 0;
-    for (int c = threadIdx.x * 4; c < d; c += 1024, ++it) {
-      f32x4 v = keep[0];
-#pragma unroll
-      for (int q = 1; q < KEEP; ++q) if (q == it) v = keep[q];
-      v[0] *= inv; v[1] *= inv; v[2] *= inv; v[3] *= inv;
-      *reinterpret_cast<f32x4 *>(W + base + c) = v;
-    }
-  }
-  if constexpr (REFRESH != 0) refresh_row<REFRESH>(W, base, d, ft, red3);
-}
-
 // ---- sign momentum ("lion" / "signum", include/msae.h) ----------------------------------------------------------
 struct LionArgs {
   float lr, omb1, omb2, max_norm;      // omb = 1.f - beta, rounded once on the host's float32 values as the device would
@@ -361,83 +248,6 @@ __device__ __forceinline__ void lion_update(float &w, float g, float &m, const L
   const float s = (float)((u > 0.f) - (u < 0.f));          // 0 for u == 0 and for NaN
   w = w - a.lr * s;
   m = __builtin_fmaf(dgm, a.omb2, m);
-}
-
-// adam_rows_kernel's sibling for the shapes lion_rows_fused_kernel does not take (d % 4 != 0: scalar loop; d > 8192)
-__global__ __launch_bounds__(256) void lion_rows_kernel(float *__restrict__ W, const float *__restrict__ G,
-                                                        float *__restrict__ M, int d,
-                                                        const float *__restrict__ total_sumsq, LionArgs a) {
-  __shared__ float red[4];
-  const size_t base = (size_t)blockIdx.x * d;
-  const float clip = clip_coef(total_sumsq, a.max_norm);
-  if ((d & 3) == 0) {
-    const float along = a.project ? row_along(G, W, base, d, clip, red) : 0.f;
-    for (int c = threadIdx.x * 4; c < d; c += 1024) {
-      const f32x4 g = *reinterpret_cast<const f32x4 *>(G + base + c);     // L2 hit when projecting
-      f32x4 w = *reinterpret_cast<const f32x4 *>(W + base + c);
-      f32x4 m = *reinterpret_cast<const f32x4 *>(M + base + c);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float ge = g[e] * clip, we = w[e], me = m[e];
-        if (a.project) ge -= along * we;
-        lion_update(we, ge, me, a);
-        w[e] = we; m[e] = me;
-      }
-      *reinterpret_cast<f32x4 *>(W + base + c) = w;
-      *reinterpret_cast<f32x4 *>(M + base + c) = m;
-    }
-  } else {
-    float along = 0.f;
-    if (a.project) {
-      float dot = 0.f;
-      for (int c = threadIdx.x; c < d; c += 256) dot += (G[base + c] * clip) * W[base + c];
-      along = block_sum(dot, red);
-    }
-    for (int c = threadIdx.x; c < d; c += 256) {
-      float ge = G[base + c] * clip, w = W[base + c], m = M[base + c];
-      if (a.project) ge -= along * w;
-      lion_update(w, ge, m, a);
-      W[base + c] = w; M[base + c] = m;
-    }
-  }
-}
-
-// adam_rows_fused_kernel's sibling: one moment, no second-moment stream (d % 4 == 0, d <= 8192).  20 bytes per element.
-template <int REFRESH>
-__global__ __launch_bounds__(256) void lion_rows_fused_kernel(float *__restrict__ W, const float *__restrict__ G,
-                                                              float *__restrict__ M, int d,
-                                                              const float *__restrict__ total_sumsq, LionArgs a, FusedTail ft) {
-  __shared__ float red[4];
-  __shared__ float red3[3][4];
-  const size_t base = (size_t)blockIdx.x * d;
-  const float clip = clip_coef(total_sumsq, a.max_norm);
-  const float along = a.project ? row_along(G, W, base, d, clip, red) : 0.f;
-  const bool renorm = ft.renorm_eps >= 0.f;
-  f32x4 keep[KEEP];
-  float ss = 0.f;
-  int it = 0;
-  for (int c = threadIdx.x * 4; c < d; c += 1024, ++it) {
-    const f32x4 g = a.project ? *reinterpret_cast<const f32x4 *>(G + base + c)     // L2 hit when projecting
-                              : MSAE_ADAM_LOAD(reinterpret_cast<const f32x4 *>(G + base + c));
-    f32x4 w = *reinterpret_cast<const f32x4 *>(W + base + c);
-    f32x4 m = MSAE_ADAM_LOAD(reinterpret_cast<const f32x4 *>(M + base + c));
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float ge = g[e] * clip, we = w[e], me = m[e];
-      if (a.project) ge -= along * we;
-      lion_update(we, ge, me, a);
-      w[e] = we; m[e] = me;
-    }
-    MSAE_ADAM_STORE(m, reinterpret_cast<f32x4 *>(M + base + c));
-    if (renorm) {
-      keep_put(keep, it, w);
-      ss += w[0] * w[0] + w[1] * w[1] + w[2] * w[2] + w[3] * w[3];
-    } else {
-      *reinterpret_cast<f32x4 *>(W + base + c) = w;
-    }
-  }
-  if (renorm) renorm_store(W, base, d, keep, 1.f / (sqrtf(block_sum(ss, red)) + ft.renorm_eps));
-  if constexpr (REFRESH != 0) refresh_row<REFRESH>(W, base, d, ft, red3);
 }
 
 // ---- 8-bit moments ("adam8", include/msae.h) -------------------------------------------------------------------
@@ -491,42 +301,146 @@ __device__ __forceinline__ void adam8_load(const Adam8Ptrs &st, size_t word, siz
   v = r * r;
 }
 
-// adam_rows_fused_kernel with the moments carried in the adam8 format: decoded on the way in, the update computed from the
-// float32 m', v' of this step, m' and sqrt(v') encoded on the way out.  The trip loop runs a whole wave at a time (the
-// wave_max needs all 64 lanes): a wave whose block lies past d skips the trip, lanes past d inside a block contribute 0.
-template <int REFRESH>
-__global__ __launch_bounds__(256) void adam8_rows_kernel(float *__restrict__ W, const float *__restrict__ G, Adam8Ptrs st,
-                                                         int d, const float *__restrict__ total_sumsq, AdamArgs a,
-                                                         FusedTail ft) {
+// ---- update policies -------------------------------------------------------------------------------------------------------
+// A policy names what differs between the optimisers: State (its moment pointers), Args (max_norm, project and its own
+// constants), NMOM float32 moments per element in registers and update() of one element; for the fused kernel also trip(c, d)
+// (does the thread whose columns start at c run this trip), at() (where that thread's moments lie, worked out once per trip)
+// and load() / store() of one f32x4 of each moment, streaming.
+template <int N>
+struct F32Moments {               // N float32 moments stored as they are
+  static constexpr int NMOM = N;
+  struct State { float *mom[N]; };
+  typedef size_t At;
+  static __device__ __forceinline__ bool trip(int c, int d) { return c < d; }
+  static __device__ __forceinline__ At at(size_t base, int c, int) { return base + c; }
+  static __device__ __forceinline__ void load(const State &st, At p, f32x4 (&mo)[N]) {
+    // the moments are touched exactly once per step: streaming accesses, kept out of the caches' way (MSAE_ADAM_PLAIN_LOADS
+    // in a tuning build switches the hint off)
+#pragma unroll
+    for (int i = 0; i < N; ++i) mo[i] = MSAE_ADAM_LOAD(reinterpret_cast<const f32x4 *>(st.mom[i] + p));
+  }
+  static __device__ __forceinline__ void store(const State &st, At p, bool, const f32x4 (&mo)[N]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) MSAE_ADAM_STORE(mo[i], reinterpret_cast<f32x4 *>(st.mom[i] + p));
+  }
+};
+struct AdamOpt : F32Moments<2> {  // m, v.  28 bytes per element
+  using Args = AdamArgs;
+  static __device__ __forceinline__ void update(float &w, float g, float (&mo)[2], const Args &a) {
+    adam_update(w, g, mo[0], mo[1], a);
+  }
+};
+struct LionOpt : F32Moments<1> {  // one moment, no second-moment stream.  20 bytes per element
+  using Args = LionArgs;
+  static __device__ __forceinline__ void update(float &w, float g, float (&mo)[1], const Args &a) { lion_update(w, g, mo[0], a); }
+};
+// Adam with the moments carried in the adam8 format: decoded on the way in, the update computed from the float32 m', v' of this
+// step, m' and sqrt(v') encoded on the way out.  A trip runs a whole wave at a time (the wave_max needs all 64 lanes): a wave
+// whose block lies past d skips the trip, lanes past d inside a block contribute 0.
+struct Adam8Opt {
+  static constexpr int NMOM = 2;  // m, and v on the way in / sqrt(v') on the way out
+  using State = Adam8Ptrs;
+  using Args = AdamArgs;
+  struct At { size_t word, blk; };  // the lane's word of the code arrays, the wave's block
+  static __device__ __forceinline__ bool trip(int c, int d) { return (c & ~(ADAM8_BLOCK - 1)) < d; }
+  static __device__ __forceinline__ At at(size_t base, int c, int d) {
+    return At{(base + c) >> 2, (size_t)blockIdx.x * ((d + ADAM8_BLOCK - 1) / ADAM8_BLOCK) + (c >> 8)};
+  }
+  static __device__ __forceinline__ void load(const State &st, const At &p, f32x4 (&mo)[2]) {
+    adam8_load(st, p.word, p.blk, mo[0], mo[1]);
+  }
+  static __device__ __forceinline__ void update(float &w, float g, float (&mo)[2], const Args &a) {
+    adam_update(w, g, mo[0], mo[1], a);
+    mo[1] = sqrtf(mo[1]);
+  }
+  static __device__ __forceinline__ void store(const State &st, const At &p, bool live, const f32x4 (&mo)[2]) {
+    adam8_store_block(st, p.word, p.blk, live, mo[0], mo[1]);
+  }
+};
+
+// one element: clip, projection, the policy's update
+template <class Opt>
+__device__ __forceinline__ void update_elem(float &w, float g, float (&mo)[Opt::NMOM], float clip, float along,
+                                            const typename Opt::Args &a) {
+  float ge = g * clip;
+  if (a.project) ge -= along * w;
+  Opt::update(w, ge, mo, a);
+}
+template <class Opt>
+__device__ __forceinline__ void update_vec(f32x4 &w, const f32x4 g, f32x4 (&mo)[Opt::NMOM], float clip, float along,
+                                           const typename Opt::Args &a) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    float we = w[e], me[Opt::NMOM];
+#pragma unroll
+    for (int i = 0; i < Opt::NMOM; ++i) me[i] = mo[i][e];
+    update_elem<Opt>(we, g[e], me, clip, along, a);
+    w[e] = we;
+#pragma unroll
+    for (int i = 0; i < Opt::NMOM; ++i) mo[i][e] = me[i];
+  }
+}
+
+// the pass alone, float32 moments: any d (d % 4 != 0: scalar loop), what the fused kernel does not take included
+template <class Opt>
+__global__ __launch_bounds__(256) void opt_rows_kernel(float *__restrict__ W, const float *__restrict__ G, typename Opt::State st,
+                                                       int d, const float *__restrict__ total_sumsq, typename Opt::Args a) {
+  __shared__ float red[4];
+  const size_t base = (size_t)blockIdx.x * d;
+  const float clip = clip_coef(total_sumsq, a.max_norm);
+  const bool vec4 = (d & 3) == 0;
+  const float along = a.project ? row_along(G, W, base, d, clip, vec4, red) : 0.f;
+  if (vec4) {
+    for (int c = threadIdx.x * 4; c < d; c += 1024) {
+      const f32x4 g = *reinterpret_cast<const f32x4 *>(G + base + c);     // L2 hit when projecting
+      f32x4 w = *reinterpret_cast<const f32x4 *>(W + base + c), mo[Opt::NMOM];
+#pragma unroll
+      for (int i = 0; i < Opt::NMOM; ++i) mo[i] = *reinterpret_cast<const f32x4 *>(st.mom[i] + base + c);
+      update_vec<Opt>(w, g, mo, clip, along, a);
+      *reinterpret_cast<f32x4 *>(W + base + c) = w;
+#pragma unroll
+      for (int i = 0; i < Opt::NMOM; ++i) *reinterpret_cast<f32x4 *>(st.mom[i] + base + c) = mo[i];
+    }
+  } else {
+    for (int c = threadIdx.x; c < d; c += 256) {
+      float w = W[base + c], mo[Opt::NMOM];
+#pragma unroll
+      for (int i = 0; i < Opt::NMOM; ++i) mo[i] = st.mom[i][base + c];
+      update_elem<Opt>(w, G[base + c], mo, clip, along, a);
+      W[base + c] = w;
+#pragma unroll
+      for (int i = 0; i < Opt::NMOM; ++i) st.mom[i][base + c] = mo[i];
+    }
+  }
+}
+
+template <class Opt, int REFRESH>
+__global__ __launch_bounds__(256) void opt_rows_fused_kernel(float *__restrict__ W, const float *__restrict__ G,
+                                                             typename Opt::State st, int d,
+                                                             const float *__restrict__ total_sumsq, typename Opt::Args a,
+                                                             FusedTail ft) {
   __shared__ float red[4];
   __shared__ float red3[3][4];
   const size_t base = (size_t)blockIdx.x * d;
   const float clip = clip_coef(total_sumsq, a.max_norm);
-  const float along = a.project ? row_along(G, W, base, d, clip, red) : 0.f;
+  const float along = a.project ? row_along(G, W, base, d, clip, true, red) : 0.f;
   const bool renorm = ft.renorm_eps >= 0.f;
-  const int bpr = (d + ADAM8_BLOCK - 1) / ADAM8_BLOCK;
   f32x4 keep[KEEP];
   float ss = 0.f;
   int it = 0;
-  for (int c = threadIdx.x * 4; (c & ~(ADAM8_BLOCK - 1)) < d; c += 1024, ++it) {
-    const bool live = c < d;
-    const size_t word = (base + c) >> 2, blk = (size_t)blockIdx.x * bpr + (c >> 8);
-    f32x4 w = {0.f, 0.f, 0.f, 0.f}, m = w, r = w;
+  for (int c = threadIdx.x * 4; Opt::trip(c, d); c += 1024, ++it) {
+    const bool live = c < d;                        // (always, where the trip is c < d)
+    const typename Opt::At at = Opt::at(base, c, d);
+    f32x4 w = {0.f, 0.f, 0.f, 0.f}, mo[Opt::NMOM] = {};
     if (live) {
+      // the gradient is read once too, unless the projection has just read it
       const f32x4 g = a.project ? *reinterpret_cast<const f32x4 *>(G + base + c)     // L2 hit when projecting
                                 : MSAE_ADAM_LOAD(reinterpret_cast<const f32x4 *>(G + base + c));
       w = *reinterpret_cast<const f32x4 *>(W + base + c);
-      f32x4 v;
-      adam8_load(st, word, blk, m, v);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float ge = g[e] * clip, we = w[e], me = m[e], ve = v[e];
-        if (a.project) ge -= along * we;
-        adam_update(we, ge, me, ve, a);
-        w[e] = we; m[e] = me; r[e] = sqrtf(ve);
-      }
+      Opt::load(st, at, mo);
+      update_vec<Opt>(w, g, mo, clip, along, a);
     }
-    adam8_store_block(st, word, blk, live, m, r);
+    Opt::store(st, at, live, mo);
     if (live) {
       if (renorm) {
         keep_put(keep, it, w);
@@ -556,7 +470,7 @@ __global__ __launch_bounds__(256) void adam8_quantize_kernel(const float *__rest
     adam8_store_block(st, (base + c) >> 2, (size_t)blockIdx.x * bpr + (c >> 8), live, m, r);
   }
 }
-// ... and back: the values adam8_rows_kernel computes with
+// ... and back: the values Adam8Opt computes with
 __global__ __launch_bounds__(256) void adam8_dequantize_kernel(Adam8Ptrs st, float *__restrict__ M, float *__restrict__ V, int d) {
   const size_t base = (size_t)blockIdx.x * d;
   const int bpr = (d + ADAM8_BLOCK - 1) / ADAM8_BLOCK;
@@ -617,23 +531,7 @@ extern "C" int msae_grad_sumsq_f32(const float *g, size_t n, float *accum, void 
   return msae_launch_status();
 }
 
-extern "C" int msae_adam_rows_f32(float *W, const float *G, float *M, float *V, int rows, int d,
-                                  const float *total_sumsq, float max_norm, int project, float lr,
-                                  float beta1, float beta2, float eps, int step, void *stream) {
-  if (!W || !G || !M || !V || rows <= 0 || d <= 0 || step < 1) return MSAE_EINVAL;
-  if ((d & 3) == 0 && !(msae_aligned(W, 16) && msae_aligned(G, 16) && msae_aligned(M, 16) && msae_aligned(V, 16)))
-    return MSAE_EALIGN;
-  AdamArgs a{};
-  a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.max_norm = max_norm;
-  a.bc1 = (float)(1.0 - pow((double)beta1, (double)step));
-  a.bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
-  a.project = project ? 1 : 0;
-  hipLaunchKernelGGL(adam_rows_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, W, G, M, V, d,
-                     total_sumsq, a);
-  return msae_launch_status();
-}
-
-// the host half the fused entry points share: Adam's constants ...
+// the host half the optimiser entry points share: Adam's constants ...
 static AdamArgs adam_args(float max_norm, int project, float lr, float beta1, float beta2, float eps, int step) {
   AdamArgs a{};
   a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.max_norm = max_norm;
@@ -675,66 +573,75 @@ static int fused_tail(int rows, int d, float renorm_eps, void *prepared, int T_n
   return 0;
 }
 
+// ... the fused pass: the tail, then the kernel of its REFRESH ...
+template <class Opt>
+static int fused_rows(float *W, const float *G, typename Opt::State st, int rows, int d, const float *total_sumsq,
+                      const typename Opt::Args &a, float renorm_eps, void *prepared, int T_next, const msae_options *opts,
+                      void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  FusedTail ft;
+  int refresh;
+  if (int rc = fused_tail(rows, d, renorm_eps, prepared, T_next, opts, s, &ft, &refresh)) return rc;
+  const auto kernel = refresh == 1 ? opt_rows_fused_kernel<Opt, 1> : refresh == 2 ? opt_rows_fused_kernel<Opt, 2>
+                                                                                    : opt_rows_fused_kernel<Opt, 0>;
+  hipLaunchKernelGGL(kernel, dim3(rows), dim3(256), 0, s, W, G, st, d, total_sumsq, a, ft);
+  return msae_launch_status();
+}
+// ... and the separate passes, for the shapes the fused kernel does not take (d % 4 != 0, d > 8192)
+template <class Opt>
+static int separate_passes(float *W, const float *G, typename Opt::State st, int rows, int d, const float *total_sumsq,
+                           const typename Opt::Args &a, float renorm_eps, void *prepared, int T_next, const msae_options *opts,
+                           void *stream) {
+  hipLaunchKernelGGL(opt_rows_kernel<Opt>, dim3(rows), dim3(256), 0, (hipStream_t)stream, W, G, st, d, total_sumsq, a);
+  if (int rc = msae_launch_status()) return rc;
+  if (renorm_eps >= 0.f) { if (int rc = msae_unit_norm_rows_f32(W, rows, d, renorm_eps, stream)) return rc; }
+  if (prepared) return T_next > 0 ? msae_encoder_refresh_for(W, rows, d, prepared, T_next, opts, stream)
+                                  : msae_encoder_refresh(W, rows, d, prepared, opts, stream);
+  return 0;
+}
+// the choice between the two
+template <class Opt>
+static int opt_rows(float *W, const float *G, typename Opt::State st, int rows, int d, const float *total_sumsq,
+                    const typename Opt::Args &a, float renorm_eps, void *prepared, int T_next, const msae_options *opts,
+                    void *stream) {
+  return ((d & 3) == 0 && d <= 8192 ? fused_rows<Opt> : separate_passes<Opt>)(W, G, st, rows, d, total_sumsq, a, renorm_eps,
+                                                                              prepared, T_next, opts, stream);
+}
+
+// always the plain kernel, whatever the shape
+extern "C" int msae_adam_rows_f32(float *W, const float *G, float *M, float *V, int rows, int d,
+                                  const float *total_sumsq, float max_norm, int project, float lr,
+                                  float beta1, float beta2, float eps, int step, void *stream) {
+  if (!W || !G || !M || !V || rows <= 0 || d <= 0 || step < 1) return MSAE_EINVAL;
+  if ((d & 3) == 0 && !(msae_aligned(W, 16) && msae_aligned(G, 16) && msae_aligned(M, 16) && msae_aligned(V, 16)))
+    return MSAE_EALIGN;
+  return separate_passes<AdamOpt>(W, G, {{M, V}}, rows, d, total_sumsq, adam_args(max_norm, project, lr, beta1, beta2, eps, step),
+                                  -1.f, nullptr, 0, nullptr, stream);
+}
+
 extern "C" int msae_adam_rows_fused_f32(float *W, const float *G, float *M, float *V, int rows, int d,
                                         const float *total_sumsq, float max_norm, int project, float lr,
                                         float beta1, float beta2, float eps, int step, float renorm_eps,
                                         void *prepared, int T_next, const msae_options *opts, void *stream) {
   if (!W || !G || !M || !V || rows <= 0 || d <= 0 || step < 1) return MSAE_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  const bool renorm = renorm_eps >= 0.f;
-  if ((d & 3) != 0 || d > 8192) {                  // shapes the fused kernel does not take: the separate passes
-    int rc = msae_adam_rows_f32(W, G, M, V, rows, d, total_sumsq, max_norm, project, lr, beta1, beta2, eps, step, stream);
-    if (rc) return rc;
-    if (renorm) { rc = msae_unit_norm_rows_f32(W, rows, d, renorm_eps, stream); if (rc) return rc; }
-    if (prepared) return T_next > 0 ? msae_encoder_refresh_for(W, rows, d, prepared, T_next, opts, stream)
-                                    : msae_encoder_refresh(W, rows, d, prepared, opts, stream);
-    return 0;
-  }
-  if (!(msae_aligned(W, 16) && msae_aligned(G, 16) && msae_aligned(M, 16) && msae_aligned(V, 16))) return MSAE_EALIGN;
+  if ((d & 3) == 0 && !(msae_aligned(W, 16) && msae_aligned(G, 16) && msae_aligned(M, 16) && msae_aligned(V, 16)))
+    return MSAE_EALIGN;
   const AdamArgs a = adam_args(max_norm, project, lr, beta1, beta2, eps, step);
-  FusedTail ft;
-  int refresh;
-  if (int rc = fused_tail(rows, d, renorm_eps, prepared, T_next, opts, s, &ft, &refresh)) return rc;
-  if (refresh == 1)
-    hipLaunchKernelGGL(adam_rows_fused_kernel<1>, dim3(rows), dim3(256), 0, s, W, G, M, V, d, total_sumsq, a, ft);
-  else if (refresh == 2)
-    hipLaunchKernelGGL(adam_rows_fused_kernel<2>, dim3(rows), dim3(256), 0, s, W, G, M, V, d, total_sumsq, a, ft);
-  else
-    hipLaunchKernelGGL(adam_rows_fused_kernel<0>, dim3(rows), dim3(256), 0, s, W, G, M, V, d, total_sumsq, a, ft);
-  return msae_launch_status();
+  return opt_rows<AdamOpt>(W, G, {{M, V}}, rows, d, total_sumsq, a, renorm_eps, prepared, T_next, opts, stream);
 }
 
 // ---- sign momentum --------------------------------------------------------------------------------------------------------------
-// d % 4 == 0 and d <= 8192: lion_rows_fused_kernel, with or without tails (ONE kernel: a call without tails and a call with them
-// compute the same W before the renorm and the same M); other shapes: lion_rows_kernel and the separate passes.
+// ONE entry, with or without tails: on a fused shape a call without tails and a call with them run the same kernel and compute
+// the same W before the renorm and the same M.
 extern "C" int msae_lion_rows_f32(float *W, const float *G, float *M, int rows, int d, const float *total_sumsq,
                                   float max_norm, int project, float lr, float beta1, float beta2, float renorm_eps,
                                   void *prepared, int T_next, const msae_options *opts, void *stream) {
   if (!W || !G || !M || rows <= 0 || d <= 0) return MSAE_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
+  if ((d & 3) == 0 && !(msae_aligned(W, 16) && msae_aligned(G, 16) && msae_aligned(M, 16))) return MSAE_EALIGN;
   LionArgs a{};
   a.lr = lr; a.omb1 = 1.f - beta1; a.omb2 = 1.f - beta2; a.max_norm = max_norm;
   a.project = project ? 1 : 0;
-  if ((d & 3) != 0 || d > 8192) {
-    if ((d & 3) == 0 && !(msae_aligned(W, 16) && msae_aligned(G, 16) && msae_aligned(M, 16))) return MSAE_EALIGN;
-    hipLaunchKernelGGL(lion_rows_kernel, dim3(rows), dim3(256), 0, s, W, G, M, d, total_sumsq, a);
-    if (int rc = msae_launch_status()) return rc;
-    if (renorm_eps >= 0.f) { if (int rc = msae_unit_norm_rows_f32(W, rows, d, renorm_eps, stream)) return rc; }
-    if (prepared) return T_next > 0 ? msae_encoder_refresh_for(W, rows, d, prepared, T_next, opts, stream)
-                                    : msae_encoder_refresh(W, rows, d, prepared, opts, stream);
-    return 0;
-  }
-  if (!(msae_aligned(W, 16) && msae_aligned(G, 16) && msae_aligned(M, 16))) return MSAE_EALIGN;
-  FusedTail ft;
-  int refresh;
-  if (int rc = fused_tail(rows, d, renorm_eps, prepared, T_next, opts, s, &ft, &refresh)) return rc;
-  if (refresh == 1)
-    hipLaunchKernelGGL(lion_rows_fused_kernel<1>, dim3(rows), dim3(256), 0, s, W, G, M, d, total_sumsq, a, ft);
-  else if (refresh == 2)
-    hipLaunchKernelGGL(lion_rows_fused_kernel<2>, dim3(rows), dim3(256), 0, s, W, G, M, d, total_sumsq, a, ft);
-  else
-    hipLaunchKernelGGL(lion_rows_fused_kernel<0>, dim3(rows), dim3(256), 0, s, W, G, M, d, total_sumsq, a, ft);
-  return msae_launch_status();
+  return opt_rows<LionOpt>(W, G, {{M}}, rows, d, total_sumsq, a, renorm_eps, prepared, T_next, opts, stream);
 }
 
 // ---- 8-bit moments -------------------------------------------------------------------------------------------------------------
@@ -765,19 +672,9 @@ extern "C" int msae_adam8_rows_f32(float *W, const float *G, uint8_t *M8, uint8_
   if (!W || !G || step < 1) return MSAE_EINVAL;
   if (int rc = adam8_check(M8, R8, SM, SR, rows, d)) return rc;
   if (!(msae_aligned(W, 16) && msae_aligned(G, 16))) return MSAE_EALIGN;
-  hipStream_t s = (hipStream_t)stream;
-  const AdamArgs a = adam_args(max_norm, project, lr, beta1, beta2, eps, step);
   const Adam8Ptrs st{reinterpret_cast<unsigned *>(M8), reinterpret_cast<unsigned *>(R8), SM, SR};
-  FusedTail ft;
-  int refresh;
-  if (int rc = fused_tail(rows, d, renorm_eps, prepared, T_next, opts, s, &ft, &refresh)) return rc;
-  if (refresh == 1)
-    hipLaunchKernelGGL(adam8_rows_kernel<1>, dim3(rows), dim3(256), 0, s, W, G, st, d, total_sumsq, a, ft);
-  else if (refresh == 2)
-    hipLaunchKernelGGL(adam8_rows_kernel<2>, dim3(rows), dim3(256), 0, s, W, G, st, d, total_sumsq, a, ft);
-  else
-    hipLaunchKernelGGL(adam8_rows_kernel<0>, dim3(rows), dim3(256), 0, s, W, G, st, d, total_sumsq, a, ft);
-  return msae_launch_status();
+  return fused_rows<Adam8Opt>(W, G, st, rows, d, total_sumsq, adam_args(max_norm, project, lr, beta1, beta2, eps, step),
+                              renorm_eps, prepared, T_next, opts, stream);
 }
 
 extern "C" int msae_adam8_quantize_f32(const float *M, const float *V, uint8_t *M8, uint8_t *R8, float *SM, float *SR, int rows,

@@ -40,6 +40,11 @@ class MsaeFeatureSample(ctypes.Structure):
 
 c_sample_p = ctypes.POINTER(MsaeFeatureSample)
 
+# the optimiser row passes (W, G, the moments, then ...): rows, d, total_sumsq, max_norm, project
+_OPT_HEAD = [c_int, c_int, c_void_p, c_float, c_int]
+_ADAM_CONSTS = [c_float, c_float, c_float, c_float, c_int]          # lr, beta1, beta2, eps, step
+_OPT_TAIL = [c_float, c_void_p, c_int, c_opts_p, c_void_p]          # renorm_eps, prepared, T_next, opts, stream
+
 # name -> (restype, argtypes); mirrors include/msae.h one to one
 PROTOTYPES = {
     "msae_options_init": (None, [c_opts_p]),
@@ -187,17 +192,11 @@ PROTOTYPES = {
     "msae_sum_f32": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p]),
     "msae_weighted_row_sum_ws_bytes": (c_size_t, [c_int, c_int]),
     "msae_weighted_row_sum_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "msae_adam_rows_fused_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_float,
-                                         c_int, c_float, c_float, c_float, c_float, c_int, c_float, c_void_p, c_int,
-                                         c_opts_p, c_void_p]),
-    "msae_adam_rows_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_float,
-                                   c_int, c_float, c_float, c_float, c_float, c_int, c_void_p]),
-    "msae_lion_rows_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_float, c_int, c_float, c_float,
-                                   c_float, c_float, c_void_p, c_int, c_opts_p, c_void_p]),
+    "msae_adam_rows_fused_f32": (c_int, [c_void_p] * 4 + _OPT_HEAD + _ADAM_CONSTS + _OPT_TAIL),
+    "msae_adam_rows_f32": (c_int, [c_void_p] * 4 + _OPT_HEAD + _ADAM_CONSTS + [c_void_p]),
+    "msae_lion_rows_f32": (c_int, [c_void_p] * 3 + _OPT_HEAD + [c_float] * 3 + _OPT_TAIL),
     "msae_adam8_blocks": (c_size_t, [c_int, c_int]),
-    "msae_adam8_rows_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
-                                    c_float, c_int, c_float, c_float, c_float, c_float, c_int, c_float, c_void_p, c_int,
-                                    c_opts_p, c_void_p]),
+    "msae_adam8_rows_f32": (c_int, [c_void_p] * 6 + _OPT_HEAD + _ADAM_CONSTS + _OPT_TAIL),
     "msae_adam8_quantize_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "msae_adam8_dequantize_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                           c_void_p]),

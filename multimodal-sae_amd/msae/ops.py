@@ -2436,6 +2436,22 @@ def _kernel_rows(p: Tensor) -> Tuple[int, int]:
     return p.numel() // d, d
 
 
+def _opt_rows_args(p: Tensor, g: Tensor, moments: Sequence[Tensor], total_sumsq: Optional[Tensor], max_norm: float,
+                   project: bool, renorm_eps: Optional[float], refresh: Optional[Tensor], tokens_next: int):
+    """What the optimiser row passes share: the checks on p, g and the float32 `moments`, and the two runs of C arguments
+    around an optimiser's own constants -> (device, head, tail).  head = rows, d, total_sumsq, max_norm, project;
+    tail = renorm_eps, prepared, T_next, opts, stream (tail[-1:] is what a call without tails takes)."""
+    dev = _hip.require_device(p, g, *moments, refresh)
+    for t in (p, g, *moments):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == p.shape
+    assert p.dim() == 2 or not project, "the projection is a row operation on a [rows, d] matrix"
+    assert p.dim() == 2 or (renorm_eps is None and refresh is None), "renorm / refresh are row operations on a [rows, d] matrix"
+    head = (*_kernel_rows(p), _hip.ptr(total_sumsq), float(max_norm), int(project))
+    tail = (float(renorm_eps) if renorm_eps is not None else -1.0, _hip.ptr(refresh), int(tokens_next), _opts().ref(),
+            _hip.stream_of(p))
+    return dev, head, tail
+
+
 def adam_rows_(p: Tensor, g: Tensor, m: Tensor, v: Tensor, step: int, lr: float, *,
                total_sumsq: Optional[Tensor] = None, max_norm: float = 1.0, project: bool = False,
                betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, renorm_eps: Optional[float] = None,
@@ -2446,26 +2462,13 @@ def adam_rows_(p: Tensor, g: Tensor, m: Tensor, v: Tensor, step: int, lr: float,
     set_decoder_norm_to_unit_norm (sae.py:249-255), same bits, no extra sweep.  `refresh` (the encoder weight; a
     train_operand_buffer): the coarse-pass operands of the updated rows for the next encode of `tokens_next` tokens,
     as prepare_encoder(..., active_mode_only=True, tokens_next=...) would rebuild them (msae_adam_rows_fused_f32)."""
-    dev = _hip.require_device(p, g, m, v, refresh)
-    for t in (p, g, m, v):
-        assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == p.shape
-    assert p.dim() == 2 or not project
-    rows, d = _kernel_rows(p)
+    dev, head, tail = _opt_rows_args(p, g, (m, v), total_sumsq, max_norm, project, renorm_eps, refresh, tokens_next)
+    fused = renorm_eps is not None or refresh is not None
+    name = "msae_adam_rows_fused_f32" if fused else "msae_adam_rows_f32"
     with torch.cuda.device(dev):
-        if renorm_eps is not None or refresh is not None:
-            assert p.dim() == 2, "renorm / refresh are row operations on a [rows, d] matrix"
-            _hip.check(_hip.load().msae_adam_rows_fused_f32(
-                _hip.ptr(p), _hip.ptr(g), _hip.ptr(m), _hip.ptr(v), rows, d,
-                _hip.ptr(total_sumsq) if total_sumsq is not None else None, float(max_norm), int(project),
-                float(lr), float(betas[0]), float(betas[1]), float(eps), int(step),
-                float(renorm_eps) if renorm_eps is not None else -1.0, _hip.ptr(refresh), int(tokens_next),
-                _opts().ref(), _hip.stream_of(p)), "msae_adam_rows_fused_f32")
-            return
-        _hip.check(_hip.load().msae_adam_rows_f32(
-            _hip.ptr(p), _hip.ptr(g), _hip.ptr(m), _hip.ptr(v), rows, d,
-            _hip.ptr(total_sumsq) if total_sumsq is not None else None, float(max_norm), int(project),
-            float(lr), float(betas[0]), float(betas[1]), float(eps), int(step), _hip.stream_of(p)),
-            "msae_adam_rows_f32")
+        _hip.check(getattr(_hip.load(), name)(
+            _hip.ptr(p), _hip.ptr(g), _hip.ptr(m), _hip.ptr(v), *head, float(lr), float(betas[0]), float(betas[1]), float(eps),
+            int(step), *(tail if fused else tail[-1:])), name)
 
 
 def lion_rows_(p: Tensor, g: Tensor, m: Tensor, lr: float, *,
@@ -2475,20 +2478,10 @@ def lion_rows_(p: Tensor, g: Tensor, m: Tensor, lr: float, *,
     """adam_rows_ with a sign-momentum update (msae_lion_rows_f32): same clip, projection, `renorm_eps` and `refresh` /
     `tokens_next` tails; p -= lr * sign(lerp(m, g, 1 - betas[0])), m = lerp(m, g, 1 - betas[1]) in place.  Lion; with
     betas[0] == betas[1] it is Signum.  One moment, no bias correction, no weight decay."""
-    dev = _hip.require_device(p, g, m, refresh)
-    for t in (p, g, m):
-        assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == p.shape
-    assert p.dim() == 2 or not project
-    if renorm_eps is not None or refresh is not None:
-        assert p.dim() == 2, "renorm / refresh are row operations on a [rows, d] matrix"
-    rows, d = _kernel_rows(p)
+    dev, head, tail = _opt_rows_args(p, g, (m,), total_sumsq, max_norm, project, renorm_eps, refresh, tokens_next)
     with torch.cuda.device(dev):
-        _hip.check(_hip.load().msae_lion_rows_f32(
-            _hip.ptr(p), _hip.ptr(g), _hip.ptr(m), rows, d,
-            _hip.ptr(total_sumsq) if total_sumsq is not None else None, float(max_norm), int(project),
-            float(lr), float(betas[0]), float(betas[1]),
-            float(renorm_eps) if renorm_eps is not None else -1.0, _hip.ptr(refresh), int(tokens_next),
-            _opts().ref(), _hip.stream_of(p)), "msae_lion_rows_f32")
+        _hip.check(_hip.load().msae_lion_rows_f32(_hip.ptr(p), _hip.ptr(g), _hip.ptr(m), *head, float(lr), float(betas[0]),
+                                                  float(betas[1]), *tail), "msae_lion_rows_f32")
 
 
 # ---- blockwise 8-bit Adam moments (the "adam8" format of include/msae.h, DESIGN.md 7e) ---------------------------------
@@ -2539,18 +2532,12 @@ def adam8_rows_(p: Tensor, g: Tensor, state: Adam8State, step: int, lr: float, *
     """adam_rows_ with the moments carried in an Adam8State (msae_adam8_rows_f32): same clip, projection, update, renorm
     and operand refresh; the update uses this step's float32 moments, the state keeps their 8-bit codes.  Raises
     _hip.MsaeNotImplemented for a shape the kernel does not take."""
-    dev = _hip.require_device(p, g, *state.tensors(), refresh)
-    for t in (p, g):
-        assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == p.shape
-    assert p.dim() == 2 or (not project and renorm_eps is None and refresh is None)
-    ptrs, rows, d = _adam8_args(state, p)
+    _hip.require_device(p, *state.tensors())
+    dev, head, tail = _opt_rows_args(p, g, (), total_sumsq, max_norm, project, renorm_eps, refresh, tokens_next)
+    ptrs, _, _ = _adam8_args(state, p)
     with torch.cuda.device(dev):
-        _hip.check(_hip.load().msae_adam8_rows_f32(
-            _hip.ptr(p), _hip.ptr(g), *ptrs, rows, d,
-            _hip.ptr(total_sumsq) if total_sumsq is not None else None, float(max_norm), int(project),
-            float(lr), float(betas[0]), float(betas[1]), float(eps), int(step),
-            float(renorm_eps) if renorm_eps is not None else -1.0, _hip.ptr(refresh), int(tokens_next),
-            _opts().ref(), _hip.stream_of(p)), "msae_adam8_rows_f32")
+        _hip.check(_hip.load().msae_adam8_rows_f32(_hip.ptr(p), _hip.ptr(g), *ptrs, *head, float(lr), float(betas[0]),
+                                                   float(betas[1]), float(eps), int(step), *tail), "msae_adam8_rows_f32")
 
 
 def adam8_quantize(m: Tensor, v: Tensor) -> Adam8State:

@@ -279,6 +279,7 @@ class AdamCase:
 
 ADAM_SHAPES = [(3, 1), (5, 50), (4, 1025),            # scalar path
                (3, 4), (7, 1000), (4, 1028),          # vector path; 1028: the second trip runs with one live thread
+               (3, 252), (3, 256), (3, 260),          # one wave's 256-element trip: one f32x4 short, full, one over
                (3, 8188), (3, 8192),                  # the KEEP = 8 register window, full and one f32x4 short
                (2, 8196), (2, 12288),                 # d > 8192: the fused entry hands back to the separate passes
                (1, 1000), (1, 1024), (1, 4096), (1, 8192), (1, 12288),     # one row

@@ -1,6 +1,6 @@
 #!/bin/sh
 # usage: tools/kernel_regs.sh [pattern] [extra -D flags]  -> register / scratch / static LDS usage of the kernels in encode_fused.hip
-# (SRC=train tools/kernel_regs.sh lion_rows: another file of csrc/)
+# (SRC=train tools/kernel_regs.sh opt_rows: another file of csrc/)
 cd "$(dirname "$0")/.."
 PAT="${1:-gemm_kernel}"; [ $# -gt 0 ] && shift
 SRC="${SRC:-encode_fused}"
