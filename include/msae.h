@@ -51,6 +51,8 @@
  *   msae_recon_curve_f32     reconstruction error at several sparsities in one pass (sae.py:190-202 per checkpoint)
  *   msae_batch_kth_f32, msae_list_filter_f32, msae_decode_prefix_f32   BatchTopK on top-C lists: the batch threshold, the
  *                            threshold filter, the decode with a row length (no reference counterpart)
+ *   msae_jump_filter_f32, msae_jump_bwd_f32   JumpReLU with learned per-feature thresholds on top-C lists: the three-way
+ *                            partition and its straight-through backward (no reference counterpart)
  *   msae_nested_decode_f32, msae_nested_combine_f32, msae_decode_bwd_*_grouped_f32   Matryoshka prefixes: every prefix's
  *                            reconstruction error in one decode pass, and its backward (no reference counterpart)
  *
@@ -917,6 +919,54 @@ int msae_decode_prefix_f32(const int32_t *idx, const float *acts, const int32_t 
                            const float *b_dec, int A, int k, int N, int d, float *out, int32_t *status, void *stream);
 int msae_decode_prefix_i64_f32(const int64_t *idx, const float *acts, const int32_t *len, const float *W_dec,
                                const float *b_dec, int A, int k, int N, int d, float *out, int32_t *status, void *stream);
+
+/* ---- JumpReLU selection: learned per-feature thresholds on top-C lists (ops.jump_select) -----------
+ * z = a * H(a - theta_f) with a threshold theta_f > 0 per feature, trained through straight-through estimators with the
+ * rectangle kernel K(u) = [|u| < 1/2] of bandwidth eps.  Like the batch-level selection it is defined on LISTS.
+ *   Inputs.  vals_in / idx_in [T][ld >= C]: a canonical top-C list; theta f32 [N]; eps > 0; h = 0.5f * eps, rounded once on
+ *     the host and passed as f32.  For an entry with value a and index f every operation is a single f32 operation:
+ *       valid  0 <= f < N && a > 0            (false for NaN, -0.0 and negatives; the table is never read out of bounds)
+ *       kept   valid && a >= theta_f          (msae_list_filter_f32's table rule: inference and training agree)
+ *       near   valid && !kept && theta_f - a < h
+ *       band   valid && fabsf(a - theta_f) < h   (the kept entries within h of theta_f, and every near entry)
+ *   Partition.  Every row is partitioned STABLY into three parts, each in list order: kept, near, rest.  The dropped slots
+ *     (near and rest) come out with activation +0.0 and their own index.  len[t] = the number kept, reach[t] = kept + near,
+ *     src[t][p] = the input slot of output slot p (uint8: C <= 256).
+ *   Counters.  *l0 (int64 device counter) is ADDED to by sum_t len[t]; *n_saturated (int32 device counter) by the number of
+ *     rows with v_last > 0 && v_last >= *floor, v_last the row's last INPUT entry and *floor a device f32 scalar -- the host
+ *     passes min(theta) - h.  With no saturated row every (t, f) outside a list lies below theta_f - h for every f, so the
+ *     kept set and the band equal those of the dense [T, N] latents.
+ *   Pseudo-derivatives.  dz/da = kept; dz/dtheta_f = -(theta_f / eps) * band; dH/dtheta_f = -(1 / eps) * band.
+ *   Backward.  g [T][C] = the gradient of vals_out, *s (device f32 scalar) = the gradient of the float l0.
+ *       g_in[t][src[t][p]] = p < len[t] ? g[t][p] : +0.0                       (a routing copy)
+ *       g_theta[f] = sum over the band entries of feature f of c,  c = -fmaf(theta_f, g[t][p], s) / eps
+ *     c is two f32 operations, one fused multiply-add and one division (the negation is exact): its error is relative to |c|
+ *     even where theta_f g and s cancel, which a separately rounded product would not give.  Every feature is written; one
+ *     without band entries gets +0.0.  Order of the sum, a function of the inputs alone: the feature's band entries e_0, e_1,
+ *     ... in ascending (t, input slot) order; lane l of a wave adds e_l, e_{l + 64}, ... in that order starting from +0.0, and
+ *     the 64 partial sums are joined by the xor butterfly with partner distance 32, 16, ..., 1 (v += shfl_xor(v, off)).  No
+ *     floating-point atomics: two runs give the same bits.
+ * msae_jump_filter_f32 / _i64_f32: one wave per token, the row in registers, three ballot compactions; one integer atomic per
+ *   workgroup and counter.  1 <= C <= 256, ld >= C, N >= 1, h > 0 (else MSAE_EINVAL; a null pointer too -- l0 and n_saturated
+ *   may be null); T == 0 returns 0.  vals_out / idx_out [T][C] are not the inputs.  No workspace.
+ * msae_jump_bwd_f32 / _i64_f32: vals_in / idx_in / theta / h as the filter got them, src / len / reach as it wrote them.
+ *   Two passes of one wave per token (routing and per-feature counts; fill), a one-workgroup scan, one wave per feature that
+ *   sorts its run by (t, slot) and sums it.  ws: msae_jump_bwd_ws_bytes(T, C, N) bytes under the workspace contract above
+ *   (3 (N + 1) ints and T * C 8-byte entries; 0 for a shape the entry refuses).  Envelope: T >= 1, 1 <= C <= 256,
+ *   1 <= N < 2^30, T * C < 2^31, eps > 0, h > 0.  T == 0 writes +0.0 to every g_theta[f] and needs no workspace. */
+int msae_jump_filter_f32(const float *vals_in, const int32_t *idx_in, int T, int C, int ld, const float *theta, int N, float h,
+                         const float *floor, float *vals_out, int32_t *idx_out, int32_t *len, int32_t *reach, uint8_t *src,
+                         int64_t *l0, int32_t *n_saturated, void *stream);
+int msae_jump_filter_i64_f32(const float *vals_in, const int64_t *idx_in, int T, int C, int ld, const float *theta, int N,
+                             float h, const float *floor, float *vals_out, int64_t *idx_out, int32_t *len, int32_t *reach,
+                             uint8_t *src, int64_t *l0, int32_t *n_saturated, void *stream);
+size_t msae_jump_bwd_ws_bytes(int T, int C, int N);
+int msae_jump_bwd_f32(const float *vals_in, const int32_t *idx_in, int T, int C, int ld, const float *theta, int N, float h,
+                      float eps, const uint8_t *src, const int32_t *len, const int32_t *reach, const float *g, const float *s,
+                      float *g_in, float *g_theta, void *ws, size_t ws_bytes, void *stream);
+int msae_jump_bwd_i64_f32(const float *vals_in, const int64_t *idx_in, int T, int C, int ld, const float *theta, int N, float h,
+                          float eps, const uint8_t *src, const int32_t *len, const int32_t *reach, const float *g,
+                          const float *s, float *g_in, float *g_theta, void *ws, size_t ws_bytes, void *stream);
 
 /* ---- nested decode: Matryoshka prefixes of the dictionary (ops.nested_reconstruct) ----------------
  * A Matryoshka SAE asks the first m_0 features to reconstruct x alone, the first m_1 too, ... up to m_{G-1} = N, under ONE

@@ -21,10 +21,14 @@ from .edits import EDIT_MODES, FeatureEdits, RowEdits, as_off_features
 
 
 def _topk_sae_only(sae, what: str) -> None:
-    """The steering and attribution hooks edit per-token top-k lists: not built for a "batchtopk" Sae."""
+    """The steering and attribution hooks edit per-token top-k lists: not built for a "batchtopk" or "jump" Sae (DESIGN.md
+    section 8)."""
     if getattr(getattr(sae, "cfg", None), "activation", "topk") == "batchtopk":
         raise NotImplementedError(f"{what} is not built for an Sae with activation='batchtopk': the hooks edit per-token "
                                   "top-k lists (Sae.encode(threshold=) + Sae.decode(lengths=) are its inference path)")
+    if getattr(getattr(sae, "cfg", None), "activation", "topk") == "jump":
+        raise NotImplementedError(f"{what} is not built for an Sae with activation='jump': the hooks edit per-token "
+                                  "top-k lists (Sae.encode + Sae.decode(lengths=) are its inference path)")
 
 
 def sae_reconstruct(sae, hidden: Tensor, *, set_feature: int = -1, set_value: float = 0.0,

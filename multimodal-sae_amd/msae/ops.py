@@ -1952,11 +1952,11 @@ BATCH_KTH_MAX_VALUES = 1 << 24      # msae_batch_kth_f32's envelope: T * C
 LIST_FILTER_MAX_C = 4096            # the encoder's own limit on a list's width
 
 
-def _list2d(vals: Tensor, idx: Optional[Tensor], what: str) -> Tuple[Tensor, Optional[Tensor], int, int, int]:
+def _list2d(vals: Tensor, idx: Optional[Tensor], what: str, host_f64: bool = False) -> Tuple[Tensor, Optional[Tensor], int, int, int]:
     """A list [..., C] -> ([T, C] views whose rows are read in place where the last dimension is dense, T, C, ld)."""
     if vals.dim() < 1 or vals.shape[-1] < 1:
         raise ValueError(f"{what}: the list must be [..., C] with C >= 1, got {tuple(vals.shape)}")
-    if vals.dtype != torch.float32:
+    if vals.dtype != torch.float32 and not (host_f64 and vals.dtype == torch.float64 and not vals.is_cuda):
         raise ValueError(f"{what}: the list's values must be float32, got {vals.dtype}")
     C = vals.shape[-1]
     T = vals.numel() // C
@@ -2104,6 +2104,171 @@ def batch_select(acts: Tensor, idx: Tensor, k: int) -> Tuple[Tensor, Tensor, Ten
     if int(k) < 1 or int(k) > acts.shape[-1]:
         raise ValueError(f"batch_select: k must be in [1, C = {acts.shape[-1]}], got {k}")
     return _BatchSelect.apply(acts, idx, int(k))
+
+
+# ---- JumpReLU selection: learned per-feature thresholds on top-C lists (csrc/jump_select.hip) -----------------------
+JUMP_MAX_C = 256                    # msae_jump_filter_f32's envelope: one wave per token
+
+
+def jump_half_band(bandwidth: float) -> float:
+    """h = 0.5f * eps as the kernels get it: eps rounded to f32, halved in f32 (exact)."""
+    return 0.5 * ctypes.c_float(bandwidth).value
+
+
+def _jump_classes(v: Tensor, i: Tensor, theta: Tensor, h: float):
+    """(kept, near, band, theta_f) of include/msae.h, "JumpReLU selection", elementwise in f32."""
+    N = theta.numel()
+    ok = (i >= 0) & (i < N) & (v > 0)
+    th = theta[torch.where(ok, i, torch.zeros_like(i)).long()]
+    kept = ok & (v >= th)
+    near = ok & ~kept & ((th - v) < h)
+    band = ok & ((v - th).abs() < h)
+    return kept, near, band, th
+
+
+def _jump_filter_host(v: Tensor, i: Tensor, theta: Tensor, h: float, floor: Tensor):
+    kept, near, _, _ = _jump_classes(v, i, theta, h)
+    part = torch.where(kept, 0, torch.where(near, 1, 2)).to(torch.int8)
+    order = torch.sort(part, dim=1, stable=True).indices                           # kept, near, rest: each in list order
+    lengths = kept.sum(1).to(torch.int32)
+    reach = lengths + near.sum(1).to(torch.int32)
+    live = torch.arange(v.shape[1], device=v.device) < lengths[:, None]
+    vo = torch.where(live, torch.gather(v, 1, order), torch.zeros((), dtype=v.dtype, device=v.device))
+    n_sat = ((v[:, -1] > 0) & (v[:, -1] >= floor)).sum().to(torch.int32)
+    return vo, torch.gather(i, 1, order), lengths, reach, order.to(torch.uint8), lengths.sum(dtype=torch.int64), n_sat
+
+
+def _jump_bwd_host(v: Tensor, i: Tensor, theta: Tensor, h: float, eps: float, src: Tensor, lengths: Tensor, g: Tensor, s: Tensor):
+    C = v.shape[1]
+    order = src.long()
+    live = torch.arange(C, device=v.device) < lengths[:, None]
+    zero = torch.zeros((), dtype=g.dtype, device=g.device)
+    g_in = torch.zeros_like(g).scatter_(1, order, torch.where(live, g, zero))
+    g_at = torch.zeros_like(g).scatter_(1, order, g)                               # the upstream gradient by INPUT slot
+    _, _, band, th = _jump_classes(v, i, theta, h)
+    # (the kernel's c is -fmaf(theta_f, g, s) / eps: here the sum in double, rounded once, so that theta g and s may cancel)
+    c = (-(th.double() * g_at.double() + s.double()) / eps).to(v.dtype)
+    g_theta = torch.zeros(theta.numel(), dtype=v.dtype, device=v.device)
+    g_theta.index_add_(0, i[band].long(), c[band])
+    return g_in, g_theta
+
+
+def jump_filter(vals: Tensor, idx: Tensor, theta: Tensor, bandwidth: float, l0: Optional[Tensor] = None,
+                n_saturated: Optional[Tensor] = None):
+    """The forward of include/msae.h, "JumpReLU selection" -> (vals_out [..., C] f32, idx_out [..., C], lengths int32 [...],
+    reach int32 [...], src uint8 [T, C], l0 int64 scalar, n_saturated int32 scalar).  vals / idx [..., C] with C <= 256 (a
+    [:, :C] view is read in place), theta f32 [N], bandwidth > 0.  l0 / n_saturated: device counters to ADD to (None: fresh
+    zeros).  Not differentiable (ops.jump_select is); nothing is read back."""
+    v, i, T, C, ld = _list2d(vals, idx, "jump_filter", host_f64=True)
+    if C > JUMP_MAX_C:
+        raise ValueError(f"jump_filter: C must be at most {JUMP_MAX_C}, got {C}")
+    if not isinstance(theta, Tensor) or theta.dim() != 1 or theta.numel() < 1:
+        raise ValueError("jump_filter: theta must be a 1-d tensor [N]")
+    h = jump_half_band(bandwidth) if v.dtype == torch.float32 else 0.5 * float(bandwidth)
+    if not (h > 0 and h != float("inf")):
+        raise ValueError(f"jump_filter: the bandwidth must be positive and finite, got {bandwidth}")
+    dev = v.device
+    theta = theta.detach().to(dev, v.dtype).contiguous()
+    N = theta.numel()
+    floor = theta.min() - h
+    lead = tuple(vals.shape[:-1])
+    for name, t, dt in (("l0", l0, torch.int64), ("n_saturated", n_saturated, torch.int32)):
+        if t is not None and (t.dtype != dt or t.numel() != 1 or t.device != dev):
+            raise ValueError(f"jump_filter: {name} must be a {dt} scalar on the list's device")
+    if not v.is_cuda:
+        vo, io, lengths, reach, src, n_kept, n_sat = _jump_filter_host(v, i, theta, h, floor)
+        n_kept = n_kept if l0 is None else l0.add_(n_kept.reshape(l0.shape))
+        n_sat = n_sat if n_saturated is None else n_saturated.add_(n_sat.reshape(n_saturated.shape))
+        return vo.view(*lead, C), io.view(*lead, C), lengths.view(lead), reach.view(lead), src, n_kept, n_sat
+    lib = _hip.load()
+    vo = torch.empty(T, C, dtype=torch.float32, device=dev)
+    io = torch.empty(T, C, dtype=i.dtype, device=dev)
+    lengths = torch.empty(T, dtype=torch.int32, device=dev)
+    reach = torch.empty(T, dtype=torch.int32, device=dev)
+    src = torch.empty(T, C, dtype=torch.uint8, device=dev)
+    n_kept = l0 if l0 is not None else torch.zeros((), dtype=torch.int64, device=dev)
+    n_sat = n_saturated if n_saturated is not None else torch.zeros((), dtype=torch.int32, device=dev)
+    fn, name = (lib.msae_jump_filter_i64_f32, "msae_jump_filter_i64_f32") if i.dtype == torch.int64 else \
+        (lib.msae_jump_filter_f32, "msae_jump_filter_f32")
+    with torch.cuda.device(dev):
+        _hip.check(fn(_hip.ptr(v), _hip.ptr(i), T, C, ld, _hip.ptr(theta), N, h, _hip.ptr(floor), _hip.ptr(vo), _hip.ptr(io),
+                      _hip.ptr(lengths), _hip.ptr(reach), _hip.ptr(src), _hip.ptr(n_kept), _hip.ptr(n_sat),
+                      _hip.stream_of(v)), name)
+    return vo.view(*lead, C), io.view(*lead, C), lengths.view(lead), reach.view(lead), src, n_kept, n_sat
+
+
+def jump_bwd(vals: Tensor, idx: Tensor, theta: Tensor, bandwidth: float, src: Tensor, lengths: Tensor, reach: Tensor,
+             g: Tensor, s: Tensor) -> Tuple[Tensor, Tensor]:
+    """The backward of include/msae.h, "JumpReLU selection" -> (g_in [T, C] f32, g_theta [N] f32): vals / idx / theta /
+    bandwidth as jump_filter got them, src / lengths / reach as it returned them, g [T, C] the gradient of its vals_out and
+    s (a one-element f32 tensor) the gradient of the float l0.  Bit-reproducible; nothing is read back."""
+    v, i, T, C, ld = _list2d(vals, idx, "jump_bwd", host_f64=True)
+    dev = v.device
+    theta = theta.detach().to(dev, v.dtype).contiguous()
+    N = theta.numel()
+    h, eps = jump_half_band(bandwidth), ctypes.c_float(bandwidth).value
+    if v.dtype == torch.float64:           # (host tensors only: the definition itself, in double)
+        h, eps = 0.5 * float(bandwidth), float(bandwidth)
+    g = g.detach().to(v.dtype).reshape(T, C).contiguous()
+    s = s.detach().to(dev, v.dtype).reshape(())
+    ln, rc = lengths.reshape(T), reach.reshape(T)
+    if not v.is_cuda:
+        return _jump_bwd_host(v, i, theta, h, eps, src.reshape(T, C), ln, g, s)
+    lib = _hip.load()
+    g_in = torch.empty(T, C, dtype=torch.float32, device=dev)
+    g_theta = torch.empty(N, dtype=torch.float32, device=dev)
+    ws = _workspace(dev, lib.msae_jump_bwd_ws_bytes(T, C, N)) if T > 0 else None
+    fn, name = (lib.msae_jump_bwd_i64_f32, "msae_jump_bwd_i64_f32") if i.dtype == torch.int64 else \
+        (lib.msae_jump_bwd_f32, "msae_jump_bwd_f32")
+    with torch.cuda.device(dev):
+        _hip.check(fn(_hip.ptr(v), _hip.ptr(i), T, C, ld, _hip.ptr(theta), N, h, eps, _hip.ptr(src.contiguous()),
+                      _hip.ptr(ln.contiguous()), _hip.ptr(rc.contiguous()), _hip.ptr(g), _hip.ptr(s), _hip.ptr(g_in),
+                      _hip.ptr(g_theta), _hip.ptr(ws), 0 if ws is None else ws.numel(), _hip.stream_of(v)), name)
+    return g_in, g_theta
+
+
+class _JumpSelect(torch.autograd.Function):
+    """jump_filter as one autograd node with the straight-through backward jump_bwd."""
+
+    @staticmethod
+    def forward(ctx, acts, idx, theta, bandwidth):
+        kept, idx_out, lengths, reach, src, n_kept, n_sat = jump_filter(acts, idx, theta, bandwidth)
+        v, i, _, _, _ = _list2d(acts, idx, "jump_select", host_f64=True)
+        ctx.save_for_backward(v, i, theta.detach(), src, lengths, reach)
+        ctx.bandwidth, ctx.shape = bandwidth, acts.shape
+        l0 = n_kept.to(v.dtype)
+        ctx.mark_non_differentiable(idx_out, lengths, reach, n_sat)
+        return kept, idx_out, lengths, reach, l0, n_sat
+
+    @staticmethod
+    def backward(ctx, g, _gi, _gl, _gr, g_l0, _gn):
+        v, i, theta, src, lengths, reach = ctx.saved_tensors
+        if g is None:
+            g = torch.zeros(ctx.shape, dtype=v.dtype, device=v.device)
+        if g_l0 is None:
+            g_l0 = torch.zeros((), dtype=v.dtype, device=v.device)
+        g_in, g_theta = jump_bwd(v, i, theta, ctx.bandwidth, src, lengths, reach, g, g_l0)
+        return g_in.view(ctx.shape), None, g_theta, None
+
+
+def jump_select(acts: Tensor, idx: Tensor, theta: Tensor, bandwidth: float):
+    """JumpReLU with per-feature thresholds over canonical top-C lists (include/msae.h, "JumpReLU selection"): an entry of
+    acts / idx [..., C] (C <= 256) is kept iff its index lies in [0, N), a > 0 and a >= theta[idx] -- ops.list_filter's table
+    rule -> (acts_kept [..., C], idx_out [..., C], lengths int32 [...], reach int32 [...], l0 f32 scalar, n_saturated int32
+    scalar), all on the device, no host synchronisation.  Every row is partitioned stably: the kept entries, then the dropped
+    ones inside the straight-through band (theta - a < bandwidth / 2), then the rest, the dropped slots with activation +0.0;
+    reach counts the first two parts, l0 = sum(lengths).  One autograd node: acts_kept and l0 are differentiable, gradients
+    reach acts (the kept entries') and theta (the rectangle-kernel pseudo-derivatives of the band entries, summed per
+    feature in a fixed order: bit-reproducible).  Host tensors take a plain-torch path with the same meaning (float64 lists
+    too: the definition evaluated in double)."""
+    bandwidth = float(bandwidth)
+    if not (bandwidth > 0 and bandwidth != float("inf")):
+        raise ValueError(f"jump_select: the bandwidth must be positive and finite, got {bandwidth}")
+    if not isinstance(theta, Tensor) or theta.dim() != 1 or theta.numel() < 1:
+        raise ValueError("jump_select: theta must be a 1-d tensor [N]")
+    if acts.shape[-1] > JUMP_MAX_C:
+        raise ValueError(f"jump_select: C must be at most {JUMP_MAX_C}, got {acts.shape[-1]}")
+    return _JumpSelect.apply(acts, idx, theta, bandwidth)
 
 
 # ---- cache sparsify ---------------------------------------------------------------------------------

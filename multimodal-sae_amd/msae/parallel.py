@@ -136,6 +136,9 @@ class ShardedSae:
     def from_sae(cls, sae, rank: int = 0, world: int = 1, group=None, mode: str = "topk", **kw) -> "ShardedSae":
         """Rank `rank`'s engine of a G-rank group over a (replicated, loaded) `Sae` module: slices of
         encoder.weight / encoder.bias, the whole W_dec / b_dec."""
+        if sae.cfg.activation == "jump":
+            raise NotImplementedError("ShardedSae is not built for an Sae with activation='jump': the engine merges per-token "
+                                      "top-k lists and holds no threshold table (DESIGN.md section 8)")
         N = sae.num_latents
         assert N % world == 0, "the feature axis must divide over the ranks"
         n_loc = N // world

@@ -40,17 +40,22 @@ class SaeConfig(_Serializable):
     """Kept so older checkpoints' cfg.json load."""
     activation: str = "topk"
     """"topk": k latents per token.  "batchtopk": the T*k largest of the batch in training, a learned threshold in inference
-    (DESIGN.md section 7n)."""
+    (DESIGN.md section 7n).  "jump": JumpReLU, a learned threshold per feature (DESIGN.md section 7s)."""
     batch_cap: int = 0
-    """"batchtopk" only: the most latents one token may keep (the width C of the lists the selection works on).
-    0: min(4k, 256)."""
+    """"batchtopk" and "jump": the most latents one token may keep (the width C of the lists the selection works on).
+    0: min(4k, 256).  "jump": at most 256."""
+    jump_bandwidth: float = 1e-3
+    """"jump" only: the bandwidth eps of the rectangle kernel of the straight-through estimators."""
+    jump_init: float = 1e-3
+    """"jump" only: the threshold every feature starts from."""
     matryoshka: List[int] = field(default_factory=list)
     """Matryoshka prefix sizes m_0 < m_1 < ... < m_{G-1} = num_latents (at most 8): the first m_g latents must reconstruct
     the input on their own, under one selection over all latents (DESIGN.md section 7o).  Empty: a plain SAE."""
     matryoshka_weights: List[float] = field(default_factory=list)
     """One loss weight per prefix (finite, not negative, a positive sum).  Empty: 1 / G each."""
 
-    ACTIVATIONS = ("topk", "batchtopk")
+    ACTIVATIONS = ("topk", "batchtopk", "jump")
+    JUMP_MAX_CAP = 256
     MATRYOSHKA_MAX_GROUPS = 8
 
     def __post_init__(self):
@@ -63,6 +68,18 @@ class SaeConfig(_Serializable):
                 raise ValueError("multi_topk is a per-token TopK loss term: it does not go with activation='batchtopk'")
             if not self.k <= self.cap <= 4096:
                 raise ValueError(f"batch_cap must lie in [k = {self.k}, 4096], got {self.cap}")
+        if self.activation == "jump":
+            if self.multi_topk:
+                raise ValueError("multi_topk is a per-token TopK loss term: it does not go with activation='jump'")
+            if self.matryoshka:
+                raise ValueError("matryoshka with activation='jump' is not built (a follow-up: the nested decode of a "
+                                 "three-way partitioned list)")
+            if not self.k <= self.cap <= self.JUMP_MAX_CAP:
+                raise ValueError(f"batch_cap must lie in [k = {self.k}, {self.JUMP_MAX_CAP}] for activation='jump', got {self.cap}")
+            for name in ("jump_bandwidth", "jump_init"):
+                v = getattr(self, name)
+                if isinstance(v, bool) or not isinstance(v, (int, float)) or not (v > 0 and math.isfinite(v)):
+                    raise ValueError(f"{name} must be a positive finite number, got {v!r}")
         self.matryoshka = list(self.matryoshka or [])
         self.matryoshka_weights = list(self.matryoshka_weights or [])
         if self.matryoshka_weights and not self.matryoshka:
@@ -93,8 +110,8 @@ class SaeConfig(_Serializable):
 
     @property
     def cap(self) -> int:
-        """The list width of the main selection: k for "topk", batch_cap (0: min(4k, 256)) for "batchtopk"."""
-        if self.activation != "batchtopk":
+        """The list width of the main selection: k for "topk", batch_cap (0: min(4k, 256)) for "batchtopk" and "jump"."""
+        if self.activation == "topk":
             return self.k
         return self.batch_cap or min(4 * self.k, 256)
 
@@ -105,9 +122,11 @@ class SaeConfig(_Serializable):
         return list(self.matryoshka_weights) or [1.0 / G] * G
 
     def to_dict(self) -> dict:
-        """The BatchTopK and Matryoshka fields are written only where they differ from the defaults: a TopK cfg.json is the
-        reference's."""
+        """The BatchTopK and Matryoshka fields are written only where they differ from the defaults, the JumpReLU ones only
+        for "jump": a TopK cfg.json is the reference's."""
         d = super().to_dict()
+        if d["activation"] != "jump":
+            del d["jump_bandwidth"], d["jump_init"]
         if d["activation"] == "topk":
             del d["activation"]
         if d["batch_cap"] == 0:

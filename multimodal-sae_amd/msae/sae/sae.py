@@ -19,12 +19,16 @@ unchanged.  What differs is underneath:
 * `SaeConfig(activation="batchtopk")` -> ops.batch_select + ops.decode(lengths=): the T*k largest latents of the batch in
                      `forward`, a learned or given threshold in `encode(threshold=)` (new, opt-in: DESIGN.md section 7n)
 
+* `SaeConfig(activation="jump")` -> ops.jump_select + ops.decode(lengths=reach): JumpReLU with a learned threshold per feature
+                     (`log_threshold`), trained through straight-through estimators (new, opt-in: DESIGN.md section 7s)
+
 SAE math is f32 whatever dtype the LLM hands over, as in the reference (sae.py:140,174).
 There is no CPU implementation: calling a compute method with CPU tensors raises.
 """
 from __future__ import annotations
 
 import json
+import math
 import os
 import re
 from fnmatch import fnmatch
@@ -66,6 +70,20 @@ class BatchForwardOutput(ForwardOutput):
     def __new__(cls, *fields, lengths: Tensor, theta: Tensor, n_saturated: Tensor):
         self = super().__new__(cls, *fields)
         self.lengths, self.theta, self.n_saturated = lengths, theta, n_saturated
+        return self
+
+
+class JumpForwardOutput(ForwardOutput):
+    """The ForwardOutput of a "jump" Sae: the same six fields -- latent_acts / latent_indices are the [T, C] lists in the
+    partitioned order (kept, near, rest), the dropped slots with activation +0.0 -- and four attributes from the JumpReLU
+    selection, all device tensors: `lengths` (int32 [T], the kept entries of every row), `reach`
+    (int32 [T], kept + near: what the decode reads), `l0` (f32 scalar, the mean number kept per token, differentiable
+    with respect to log_threshold) and `n_saturated` (int32 scalar, the rows whose last list entry reaches the band of
+    the lowest threshold)."""
+
+    def __new__(cls, *fields, lengths: Tensor, reach: Tensor, l0: Tensor, n_saturated: Tensor):
+        self = super().__new__(cls, *fields)
+        self.lengths, self.reach, self.l0, self.n_saturated = lengths, reach, l0, n_saturated
         return self
 
 
@@ -185,6 +203,10 @@ class Sae(nn.Module):
             # -1 = not learned yet.  Saved and loaded with the model; a TopK Sae has no such key.
             self.register_buffer("threshold", torch.tensor(-1.0, dtype=torch.float32, device=device))
             self._threshold_checked = None     # the buffer's _version at which a host read last found it learned
+        if cfg.activation == "jump":
+            # theta = exp(log_threshold), a torch op: the kernels get one table of bits and never exponentiate
+            self.log_threshold = nn.Parameter(torch.full((self.num_latents,), math.log(cfg.jump_init), dtype=torch.float32,
+                                                         device=device))
         if cfg.matryoshka:
             # only here is d_in known, and with it the width of the dictionary the prefixes must end at
             if cfg.matryoshka[-1] != self.num_latents:
@@ -348,8 +370,10 @@ class Sae(nn.Module):
         encodes this way: `threshold` defaults to its learned buffer (RuntimeError while that is still -1; checking costs
         one host read per change of the buffer, none with an explicit threshold or after `set_threshold`) and `cap` to
         cfg.cap.  No edits here (ValueError); autograd through a scalar threshold is the mask's, through a table
-        NotImplementedError."""
-        if threshold is not None or self.cfg.activation == "batchtopk":
+        NotImplementedError.  A "jump" Sae ALWAYS encodes this way with its own table
+        exp(log_threshold) and cap = cfg.cap: under no_grad the same filter, with gradients ops.jump_select (the rows then come
+        in its partitioned order and gradients reach log_threshold); a foreign table stays NotImplementedError there."""
+        if threshold is not None or self.cfg.activation in ("batchtopk", "jump"):
             if edits is not None or edit_group is not None or set_feature >= 0 or zero_feature >= 0:
                 raise ValueError("Sae.encode: a threshold encode takes no edits, set_feature or zero_feature (edit a per-token "
                                  "TopK encode instead)")
@@ -409,8 +433,25 @@ class Sae(nn.Module):
 
     # ---- threshold encode ------------------------------------------------------
     @torch.no_grad()
-    def set_threshold(self, value: float) -> None:
-        """Set the inference threshold of a "batchtopk" Sae from a host number (finite, >= 0): no device read."""
+    def set_threshold(self, value) -> None:
+        """Set the inference threshold of a "batchtopk" Sae from a host number (finite, >= 0): no device read.  On a "jump"
+        Sae: a host number or a table [N] (finite, > 0 -- checked on the host for a number, and for a table that lives there;
+        a device table is taken as it is, no read) is written into log_threshold as log(value): a trained BatchTopK scalar or
+        an ActHist.threshold_at_rate table seeds the learned thresholds."""
+        if self.cfg.activation == "jump":
+            if isinstance(value, Tensor):
+                if value.dim() != 1 or value.shape[0] != self.num_latents:
+                    raise ValueError(f"Sae.set_threshold: a table must be [{self.num_latents}], got {tuple(value.shape)}")
+                table = value.detach().to(torch.float32)
+                if not table.is_cuda and not bool((torch.isfinite(table) & (table > 0)).all()):
+                    raise ValueError("Sae.set_threshold: every threshold must be finite and positive")
+                self.log_threshold.copy_(table.to(self.log_threshold.device).log())
+                return
+            value = float(value)
+            if not (value > 0.0 and value != float("inf")):
+                raise ValueError(f"Sae.set_threshold: the threshold must be finite and positive, got {value}")
+            self.log_threshold.fill_(math.log(value))
+            return
         if self.cfg.activation != "batchtopk":
             raise ValueError("Sae.set_threshold: only a 'batchtopk' Sae has a threshold buffer")
         value = float(value)
@@ -438,7 +479,11 @@ class Sae(nn.Module):
             raise ValueError(f"Sae.encode: cap must be in [1, {min(N, ops.LIST_FILTER_MAX_C)}], got {cap}")
         cap = int(cap)
         table = None
-        if threshold is None:
+        own = threshold is None and self.cfg.activation == "jump"      # the Sae's learned table: differentiable
+        if own:
+            table = self.log_threshold.exp()
+            theta = None
+        elif threshold is None:
             theta = self._learned_threshold()
         elif isinstance(threshold, Tensor):
             if threshold.numel() == 1:
@@ -455,14 +500,20 @@ class Sae(nn.Module):
             params = self.encoder.weight.requires_grad or self.encoder.bias.requires_grad or self.b_dec.requires_grad
             differentiable = x.requires_grad or (self.training and params and not (exact or certified or return_status))
         want_grad = torch.is_grad_enabled() and differentiable
-        if want_grad and table is not None:
+        if want_grad and table is not None and not own:
             raise NotImplementedError("Sae.encode: autograd through a per-feature threshold table is not built (the kept "
                                       "entries move inside their row): call it under torch.no_grad(), or use a scalar threshold")
         if want_grad and (exact or certified or return_status):
             raise RuntimeError("Sae.encode(exact / certified / return_status) are inference switches: call them under "
                                "torch.no_grad()")
         status = None
-        if want_grad:
+        if want_grad and own:
+            if cap > ops.JUMP_MAX_C:
+                raise ValueError(f"Sae.encode: a differentiable 'jump' encode takes cap <= {ops.JUMP_MAX_C}, got {cap}")
+            (acts, idx), = ops.sparse_encode(x, self.encoder.weight, self.encoder.bias, self.b_dec, cap,
+                                             prepared=self._prepared_weights())
+            acts, idx, lengths, _, _, _ = ops.jump_select(acts, idx, table, self.cfg.jump_bandwidth)
+        elif want_grad:
             (acts, idx), = ops.sparse_encode(x, self.encoder.weight, self.encoder.bias, self.b_dec, cap,
                                              prepared=self._prepared_weights())
             with torch.no_grad():
@@ -473,6 +524,9 @@ class Sae(nn.Module):
             with torch.no_grad():
                 acts, idx, status = ops.encode_topk(x, self.encoder.weight, self.encoder.bias, self.b_dec,
                                                     self._prepared_weights(), cap, exact=exact, certified=certified)
+                if own:
+                    table = table.detach()
+                    theta = table.min()
                 acts, idx, lengths, _ = ops.list_filter(acts, idx, theta, table)
         out = (EncoderOutput(acts, idx),) + ((status,) if return_status else ()) + ((lengths,) if return_lengths else ())
         return out[0] if len(out) == 1 else out
@@ -628,7 +682,7 @@ class Sae(nn.Module):
             flat = x.reshape(-1, self.d_in)
             T = flat.shape[0]
             if top is None:
-                if self.cfg.activation == "batchtopk":
+                if self.cfg.activation in ("batchtopk", "jump"):
                     enc, lengths = self.encode(flat, exact=exact, return_lengths=True)
                     top = (enc.top_acts, enc.top_indices, lengths)
                 else:
@@ -684,6 +738,8 @@ class Sae(nn.Module):
         new.b_dec = nn.Parameter(b.clone() if copy else b, requires_grad=self.b_dec.requires_grad)
         if cfg.activation == "batchtopk":
             new.threshold = self.threshold.detach().clone()
+        if cfg.activation == "jump":
+            new.log_threshold = nn.Parameter(part(self.log_threshold), requires_grad=self.log_threshold.requires_grad)
         if cfg.matryoshka:
             new._nested_w = torch.tensor(cfg.nested_weights, dtype=torch.float32, device=self.device)
         new.train(self.training)
@@ -694,6 +750,9 @@ class Sae(nn.Module):
         if self.cfg.activation == "batchtopk":
             raise NotImplementedError(f"Sae.{what} is not built for activation='batchtopk': it works on per-token top-k lists "
                                       "(encode with threshold= and decode with lengths= are the BatchTopK inference path)")
+        if self.cfg.activation == "jump":
+            raise NotImplementedError(f"Sae.{what} is not built for activation='jump': it works on per-token top-k lists "
+                                      "(encode and decode with lengths= are the JumpReLU inference path)")
 
     def decode(self, top_acts: Tensor, top_indices: Tensor, lengths: Optional[Tensor] = None) -> Tensor:
         """`lengths` (int32, one per row: what a threshold encode or ops.batch_select returned): only the kept prefix of every
@@ -851,6 +910,7 @@ class Sae(nn.Module):
                 k_aux = min(k_aux, num_dead)
         k_multi = 4 * self.cfg.k if self.cfg.multi_topk else 0
         batch = self.cfg.activation == "batchtopk"
+        jump = self.cfg.activation == "jump"
         k_main = self.cfg.cap                     # cfg.k, or the list width C of the batch-level selection
         if auxk_path == "subset":
             sel = ops.sparse_encode(x, self.encoder.weight, self.encoder.bias, self.b_dec, k_main,
@@ -865,6 +925,11 @@ class Sae(nn.Module):
             # BatchTopK: the T*k largest entries of the batch's top-C lists, and a decode that reads
             # the kept prefix of every row only; theta, the lengths and the saturation count stay on the device
             top_acts, lengths, theta, n_saturated = ops.batch_select(top_acts, top_indices, self.cfg.k)
+        if jump:
+            # JumpReLU: every row partitioned into kept / near / rest; the decode reads kept + near, so
+            # its backward hands the near slots the gradient the straight-through estimator of their threshold needs
+            top_acts, top_indices, lengths, reach, l0_sum, n_saturated = ops.jump_select(
+                top_acts, top_indices, self.log_threshold.exp(), self.cfg.jump_bandwidth)
         if nested:
             # Matryoshka: the full reconstruction and every prefix's squared error from one pass over
             # the decoder rows, one autograd node
@@ -874,6 +939,8 @@ class Sae(nn.Module):
             sae_out = sae_out.view(x.shape)
         elif batch:
             sae_out = self.decode(top_acts, top_indices, lengths)
+        elif jump:
+            sae_out = self.decode(top_acts, top_indices, reach)
         else:
             sae_out = self.decode(top_acts, top_indices)
         # the loss terms in as few T x d sweeps as autograd allows (each elementwise torch op on [T, d] is a 45-us kernel at
@@ -913,6 +980,9 @@ class Sae(nn.Module):
             return NestedForwardOutput(sae_out, top_acts, top_indices, fvu, auxk_loss, multi_topk_fvu, nested_fvu=nested_fvu,
                                        nested_loss=(nested_fvu * self._nested_w).sum(), bounds=bounds, lengths=lengths,
                                        theta=theta, n_saturated=n_saturated)
+        if jump:
+            return JumpForwardOutput(sae_out, top_acts, top_indices, fvu, auxk_loss, multi_topk_fvu, lengths=lengths,
+                                     reach=reach, l0=l0_sum / max(lengths.numel(), 1), n_saturated=n_saturated)
         if batch:
             return BatchForwardOutput(sae_out, top_acts, top_indices, fvu, auxk_loss, multi_topk_fvu, lengths=lengths,
                                       theta=theta, n_saturated=n_saturated)

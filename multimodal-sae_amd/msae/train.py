@@ -82,7 +82,8 @@ class SaeTrainStep:
                  dead_feature_threshold: int = 10_000_000, group=None, grad_acc_steps: int = 1,
                  micro_acc_steps: int = 1, lr_warmup_steps: int = 0, total_steps: Optional[int] = None,
                  init_b_dec: bool = False, fuse_next_step: bool = True, optim_bits: int = 32, auxk_path: str = "dense",
-                 threshold_lr: float = 0.01, optimizer: str = "adam", betas: Optional[Tuple[float, float]] = None):
+                 threshold_lr: float = 0.01, optimizer: str = "adam", betas: Optional[Tuple[float, float]] = None,
+                 l0_alpha: float = 0.0, l0_warmup_steps: int = 0):
         from .parallel import _unpinned
 
         group = _unpinned(group)          # (the default group is addressed as None: nothing here keeps it alive past its destroy)
@@ -122,6 +123,13 @@ class SaeTrainStep:
         # hyper-parameter: the running average inference will encode with), on the device
         self.batch_topk = sae.cfg.activation == "batchtopk"
         self.threshold_lr = threshold_lr
+        # "jump" (DESIGN.md section 7s): the loss adds l0_alpha * warm(t) * out.l0, warm linear from 0 to 1 over l0_warmup_steps
+        # optimiser steps; log_threshold is one more 1-D entry of self.params (clip, row passes and DDP hooks as the biases)
+        self.jump = sae.cfg.activation == "jump"
+        if not (float(l0_alpha) >= 0.0 and float(l0_alpha) != float("inf")) or int(l0_warmup_steps) < 0:
+            raise ValueError(f"l0_alpha must be finite and not negative and l0_warmup_steps not negative, got {l0_alpha}, "
+                             f"{l0_warmup_steps}")
+        self.l0_alpha, self.l0_warmup_steps = float(l0_alpha), int(l0_warmup_steps)
         # per parameter: an ops.Adam8State where the 8-bit format takes the shape, else None and float32 moments
         self.state8 = [ops.adam8_state(p) if optim_bits == 8 else None for p in self.params]
         self.exp_avg = [torch.zeros_like(p) if s8 is None else None for p, s8 in zip(self.params, self.state8)]   # torch.optim.Adam state
@@ -149,6 +157,12 @@ class SaeTrainStep:
     @property
     def current_lr(self) -> float:
         return self.lr * linear_schedule_with_warmup(self.t, self.lr_warmup_steps, self.total_steps)
+
+    @property
+    def current_l0_weight(self) -> float:
+        """l0_alpha * warm(t): the weight of the L0 term in the batches of the optimiser step that comes next."""
+        warm = min(1.0, self.t / self.l0_warmup_steps) if self.l0_warmup_steps > 0 else 1.0
+        return self.l0_alpha * warm
 
     @property
     def optimizer_state_bytes(self) -> int:
@@ -307,7 +321,8 @@ class SaeTrainStep:
         the forward's `nested_loss` in place of its fvu and adds "nested_fvu" ([G], averaged like the others).  A
         "batchtopk" Sae adds "theta" (the mean of
         the micro-chunks' rank-averaged thresholds) and "n_saturated" (this rank's rows that kept all C slots), device tensors
-        as well."""
+        as well.  A "jump" Sae adds "l0" (the mean number of latents kept per token, averaged like the others) and
+        "n_saturated", device tensors too, and descends on fvu + ... + l0_alpha * warm(t) * l0."""
         sae = self.sae
         if self.global_step == 0 and self.init_b_dec:            # trainer.py:325-332
             pts = hiddens.float()
@@ -322,7 +337,8 @@ class SaeTrainStep:
         acc_steps = self.grad_acc_steps * self.micro_acc_steps
         stats = torch.zeros(3, dtype=torch.float32, device=hiddens.device)
         chunks = hiddens.chunk(self.micro_acc_steps)
-        theta_sum = n_saturated = nested_sum = 0
+        theta_sum = n_saturated = nested_sum = l0_sum = 0
+        l0_weight = self.current_l0_weight if self.jump else 0.0
         for ci, chunk in enumerate(chunks):
             self._reduce_now = self.world > 1 and ci == len(chunks) - 1
             self._chunk_tokens = chunk.shape[0]
@@ -331,6 +347,8 @@ class SaeTrainStep:
             nested_loss = getattr(out, "nested_loss", None)
             main = out.fvu if nested_loss is None else nested_loss
             loss = main + self.auxk_alpha * out.auxk_loss + out.multi_topk_fvu / 8
+            if self.jump:
+                loss = loss + l0_weight * out.l0
             if hiddens.is_cuda:
                 with ops.collect_wgrad_sumsq() as self._wgrad_sumsq:
                     loss.div(acc_steps).backward()
@@ -342,6 +360,9 @@ class SaeTrainStep:
             self._note_fired(out)
             if self.batch_topk:
                 theta_sum = theta_sum + self._fold_threshold(out.theta)
+                n_saturated = n_saturated + out.n_saturated
+            if self.jump:
+                l0_sum = l0_sum + out.l0.detach()
                 n_saturated = n_saturated + out.n_saturated
         self._reduce_now = False
         if self.world > 1:
@@ -369,6 +390,11 @@ class SaeTrainStep:
         res = {"fvu": stats[0], "auxk_loss": stats[1], "multi_topk_fvu": stats[2], "stepped": stepped}
         if self.batch_topk:
             res.update(theta=theta_sum / len(chunks), n_saturated=n_saturated)
+        if self.jump:
+            l0_mean = l0_sum / len(chunks)
+            if self.world > 1:
+                self._all_reduce(l0_mean).div_(self.world)
+            res.update(l0=l0_mean, n_saturated=n_saturated)
         if isinstance(nested_sum, Tensor):
             nested_sum = nested_sum / len(chunks)
             if self.world > 1:
