@@ -43,6 +43,7 @@
  *   msae_coact_*             co-activation counters + neighbours (no reference counterpart)
  *   msae_act_hist_*          per-feature activation histograms + quantiles (no reference counterpart)
  *   msae_pos_profile_*       per-feature position profiles + peak bins (no reference counterpart)
+ *   msae_token_profile_*     which tokens a feature fires on: unigram  features/stats.py:50-73
  *   msae_rows_topk_f32       cos + get_neighbors; logits   features/stats.py:76-120; stats.py:12-47
  *   msae_row_inv_norms_f32   F.normalize's norms in cos    features/stats.py:80-81
  *   msae_edit_topk_f32       hook edits with a feature LIST features/steering.py:113-114, patching/utils.py:43-48
@@ -579,6 +580,49 @@ int msae_pos_profile_update(const float *vals, const int32_t *idx, int B, int S,
                             size_t ws_bytes, void *stream);
 int msae_pos_profile_summary(const int32_t *count, const int64_t *bin_positions, int N, int P, int64_t *fired,
                              int32_t *peak, void *stream);
+
+/* ---- token profiles of a query list, and the top tokens read from them (msae.features.TokenProfile) -------------------
+ * ON WHICH TOKENS a feature fires, counted while the cache runs, for F query features (the reference's
+ * features/stats.py::unigram, which joins every record with the token stream on the host).  Input: one batch's top-k
+ * vals/idx[B*S][k], as the feature statistics take it, and the batch's token ids[B*S] (i32 or i64: ids_bits = 32 / 64).
+ * Parameters: slot_of[N] i32, the slot of a query feature and -1 for every other feature (a value outside [0, F) counts as
+ * -1); a vocabulary size V; O offsets o_0 .. o_{O-1} (a HOST array, read during the call: distinct, each in [-64, 64],
+ * 1 <= O <= 4).
+ * An entry (v, f) at position (b, s) is COUNTED iff it is kept (|v| > thresh and 0 <= f < N, no filter bitmap) and v > 0 --
+ * the position profiles' rule: NaN, zero and negative values are counted nowhere; nothing is de-duplicated (a caller's
+ * repeat counts twice).  State, updated in place (initialise to 0), for the query of slot i = slot_of[f]:
+ *   counts[O][F][V]  i32  counts[a][i][t] += 1      for every a with 0 <= s + o_a < S and t = ids[b][s + o_a]
+ *   mass[O][F][V]    u64  mass[a][i][t]   += q(v)   likewise; q is the position profiles' q (above), bit for bit; the sum
+ *                         is mod 2^64.  Optional: NULL keeps no mass.
+ *   tok_count[O][V]  u64  tok_count[a][t] = positions (b, s) with 0 <= s + o_a < S and ids[b][s + o_a] == t, whether or not
+ *                         anything fired there: counts / tok_count is P(the query fires at s | token t at s + o_a).
+ * A token id outside [0, V) is counted nowhere (counts, mass and tok_count alike); offsets never cross a row.  Nothing is
+ * indexed by a list entry's feature, a slot or a token id before its range check: a hostile value costs its own entry's count
+ * at most.
+ * Every update is an integer atomic add: the state is bit-identical however the rows are cut into calls, in whatever order
+ * the calls arrive, and adds over ranks.  A counter wraps at 2^31: the caller keeps the number of positions below.
+ * Envelope: B*S <= 65536, k <= 256, N <= 262144, 1 <= F <= 16384, V >= 1, O * F * V < 2^31 (else MSAE_EINVAL, as are bad
+ * offsets and an ids_bits other than 32 / 64).  Asynchronous on `stream`; no host synchronisation, no allocation, no
+ * workspace.
+ * msae_token_profile_topk: over ONE offset plane (counts[F][V], mass[F][V] or NULL, tok_count[V]), for every row i and
+ * every token t with c = counts[i][t] >= min_count (min_count >= 1):
+ *   MSAE_TOKEN_COUNT      score = (float)c
+ *   MSAE_TOKEN_PRECISION  score = (float)((double)c / (double)tok_count[t])           one f64 quotient, one rounding to f32
+ *   MSAE_TOKEN_MEAN       score = (float)((double)mass[i][t] / (double)c * 2^-20)     mass read as UNSIGNED; one conversion
+ *                         (correctly rounded), one f64 quotient, an exact scaling, one rounding to f32.  MSAE_EINVAL without mass.
+ *   out_val[F][m] f32 / out_tok[F][m] i32: the best m in (score descending, token ascending) order -- the library's rank
+ *   key --, free slots (0.0, -1) at the tail.  The order is that of the f32 SCORE: counts above 2^24 that round to one float
+ *   tie, and the lower token comes first.  out_total[F] i64: the row total of counts (every token, whatever min_count).
+ *   1 <= m <= 64.  A pure function of the state; no scratch, no host synchronisation, no allocation. */
+enum { MSAE_TOKEN_COUNT = 0, MSAE_TOKEN_PRECISION = 1, MSAE_TOKEN_MEAN = 2 };
+int msae_token_profile_update(const float *vals, const int32_t *idx, const void *ids, int ids_bits, int B, int S, int k,
+                              float thresh, int N, const int32_t *slot_of, int F, int V, const int32_t *offsets, int O,
+                              int32_t *counts, uint64_t *mass, uint64_t *tok_count, void *stream);
+int msae_token_profile_update_i64(const float *vals, const int64_t *idx, const void *ids, int ids_bits, int B, int S, int k,
+                                  float thresh, int N, const int32_t *slot_of, int F, int V, const int32_t *offsets, int O,
+                                  int32_t *counts, uint64_t *mass, uint64_t *tok_count, void *stream);
+int msae_token_profile_topk(const int32_t *counts, const uint64_t *mass, const int64_t *tok_count, int F, int V, int m,
+                            int metric, int min_count, float *out_val, int32_t *out_tok, int64_t *out_total, void *stream);
 
 /* ---- probe: segment-pooled feature ranking and activation maps (Sae.probe) ---------------------------------------
  * Replaces the dense probe of tools/probe_activations.py:109-126 (latents = pre_acts(h); latents.mean(0).topk(k);

@@ -16,27 +16,14 @@
 // first one of the highest RATE count[f][b] / bin_positions[b], compared by cross-multiplication in int64 (both factors below
 // 2^31); a wave reduction joins the lanes (equal rates: the lower bin).
 #include "pool_segments.h"
+#include "pos_q.h"
 #include "wave_ops.h"
 
 namespace {
 
 constexpr int PP_MAX_L = 65536, PP_MAX_P = 1024;
 
-// q(v) for v > 0 (not NaN), from the float32 bits: v = m * 2^(e - 150) with the 24-bit significand m, so q = m * 2^(e - 130)
-// rounded half to even; 2^60 from 2^40 on (+inf included).
-__host__ __device__ __forceinline__ unsigned long long pp_q(float v) {
-  unsigned u;
-  __builtin_memcpy(&u, &v, 4);
-  const int eb = (int)((u >> 23) & 0xffu);
-  const unsigned long long m = eb ? ((u & 0x7fffffu) | 0x800000u) : (u & 0x7fffffu);
-  const int sh = (eb ? eb : 1) - 130;
-  if (sh >= 37) return 1ull << 60;                  // v >= 2^40 (eb = 255: +inf)
-  if (sh >= 0) return m << sh;
-  const int r = -sh;
-  if (r > 25) return 0;                             // m < 2^24: below a half
-  const unsigned long long fl = m >> r, rem = m & ((1ull << r) - 1ull), half = 1ull << (r - 1);
-  return fl + ((rem > half || (rem == half && (fl & 1ull))) ? 1ull : 0ull);
-}
+// q(v): pp_q of pos_q.h, shared with the token profiles
 
 struct PpTable {       // where a position falls
   const int32_t *pos_bin;

@@ -5,6 +5,7 @@ from __future__ import annotations
 
 import argparse
 import dataclasses
+import sys
 from dataclasses import dataclass
 from typing import Optional, Sequence, Union
 
@@ -65,6 +66,12 @@ class CacheConfig:
     """Also count where in a row every feature fires (pos_profile.safetensors per module: counts and strength per position bin)"""
     pos_profile_bins: Optional[str] = None
     """Position bins: grid:SIDE:CELL, log2 or linear:P (default: the image grid in cells of 4 on cache_image, log2 on cache)"""
+    token_profile: bool = False
+    """Also count on which tokens the filtered features fire (token_profile.safetensors per module; text cache only)"""
+    token_profile_offsets: Optional[str] = None
+    """Comma-separated token offsets of --token_profile, e.g. -1,0,1: the token at the firing position plus each (default: 0)"""
+    token_profile_mass: bool = False
+    """Also sum the activation strength per (feature, token), for the mean strength on a token"""
 
     def to_dict(self):
         return dataclasses.asdict(self)
@@ -117,6 +124,11 @@ def parse_cache_config(argv: Optional[Sequence[str]] = None) -> CacheConfig:
         else:
             typ = int if f.type in (int, "int") else str
             p.add_argument(f"--{f.name}", type=typ, default=f.default)
+    argv = list(sys.argv[1:] if argv is None else argv)
+    for i in range(len(argv) - 1):       # `--token_profile_offsets -1,0,1`: argparse would read the value as a flag
+        if argv[i] == "--token_profile_offsets" and argv[i + 1][:1] == "-" and argv[i + 1][1:2].isdigit():
+            argv[i:i + 2] = [f"{argv[i]}={argv[i + 1]}"]
+            break
     cfg = CacheConfig(**vars(p.parse_args(argv)))
     if cfg.coact_pool is not None and cfg.coact_pool not in COACT_POOLS:
         p.error(f"--coact_pool must be one of {', '.join(COACT_POOLS)}, got {cfg.coact_pool!r}")
@@ -139,7 +151,40 @@ def parse_cache_config(argv: Optional[Sequence[str]] = None) -> CacheConfig:
             pos_profile_spec(cfg.pos_profile_bins)
         except ValueError as e:
             p.error(str(e))
+    if cfg.token_profile and not cfg.filters_path:
+        p.error("--token_profile needs query features: give --filters_path")
+    if cfg.token_profile_offsets is not None:
+        try:
+            token_profile_offsets(cfg.token_profile_offsets)
+        except ValueError as e:
+            p.error(str(e))
     return cfg
+
+
+def token_profile_offsets(text: str) -> tuple:
+    """'-1,0,1' -> (-1, 0, 1): one to four distinct integers in [-64, 64], within what the token profiles take
+    (include/msae.h)."""
+    try:
+        offs = tuple(int(t) for t in text.split(","))
+    except ValueError:
+        raise ValueError(f"--token_profile_offsets must be comma-separated integers, got {text!r}") from None
+    if not 1 <= len(offs) <= 4 or len(set(offs)) != len(offs) or min(offs) < -64 or max(offs) > 64:
+        raise ValueError(f"--token_profile_offsets must be 1 to 4 distinct integers in [-64, 64], got {text!r}")
+    return offs
+
+
+def token_profile_kwargs(cfg: CacheConfig, vocab_size: int) -> Optional[dict]:
+    """The `tokens=` argument of the text feature cache for a parsed command line (None without --token_profile): the
+    launcher's vocabulary size, the offsets of --token_profile_offsets and --token_profile_mass.  The queries are the
+    filter lists."""
+    if not cfg.token_profile:
+        return None
+    offs = (0,) if cfg.token_profile_offsets is None else token_profile_offsets(cfg.token_profile_offsets)
+    return dict(vocab_size=int(vocab_size), offsets=offs, mass=bool(cfg.token_profile_mass))
+
+
+TOKEN_PROFILE_IMAGE_ERROR = ("--token_profile is for the text cache: image rows carry no token per position (the hidden "
+                             "sequence the SAE sees holds the expanded image features and is not aligned with input_ids)")
 
 
 def recon_ks_list(text: str) -> list:

@@ -36,6 +36,11 @@ and, with `pos=` (opt-in; no reference counterpart), a profile of where in a row
     <save_dir>/<module>/Rank{r}_pos_profile.safetensors        per rank
     <save_dir>/<module>/pos_profile.safetensors                the ranks added in rank order by the concat
 
+and, with `tokens=` (opt-in, text cache only), the tokens a query list of features fires on (msae/features/tokens.py):
+
+    <save_dir>/<module>/Rank{r}_token_profile.safetensors      per rank
+    <save_dir>/<module>/token_profile.safetensors              the ranks added in rank order by the concat
+
 The split files have keys `locations [nnz,3] int64 = (row, pos, feature)` and `activations [nnz] f32`, which is what
 `features/loader.py:143-196` (FeatureDataset) reads.
 
@@ -68,6 +73,7 @@ from .hist import ActHist
 from .pos import PosProfile
 from .recon import ReconStats
 from .stats import FeatureStats
+from .tokens import TokenProfile
 
 
 class _Accumulator(NamedTuple):
@@ -87,7 +93,7 @@ def _new_recon(cache, module_path, c):
                       b_dec=c.sae.b_dec, device=c.device)
 
 
-# add_topk feeds in this order: stats, coact, hist, pos (then sparsify)
+# add_topk feeds in this order: stats, coact, hist, pos, tokens (then sparsify)
 ACCUMULATORS = (
     _Accumulator("stats", "feature_stats", "feature_stats", FeatureStats, "topk",
                  lambda cache, m, c: FeatureStats(c.num_latents, device=c.device, **cache.stats),
@@ -103,6 +109,9 @@ ACCUMULATORS = (
     _Accumulator("pos", "pos_profiles", "pos_profile", PosProfile, "topk",
                  lambda cache, m, c: PosProfile(c.num_latents, device=c.device, **cache.pos),
                  lambda pp, c: pp.update(c.top_acts, c.top_indices)),
+    _Accumulator("tokens", "token_profiles", "token_profile", TokenProfile, "topk",
+                 lambda cache, m, c: cache._new_token_profile(m, c.num_latents, c.device),
+                 lambda tp, c: tp.update(c.top_acts, c.top_indices, c.token_ids)),
 )
 
 
@@ -119,7 +128,7 @@ class Cache:
     def __init__(self, shard_size: int, filters: Optional[Dict[str, Tensor]] = None,
                  batch_size: int = 64, spill_dir: Optional[str] = None, device_budget_bytes: int = 256 << 20,
                  stats: Optional[dict] = None, coact: Optional[dict] = None, recon: Optional[dict] = None,
-                 hist: Optional[dict] = None, pos: Optional[dict] = None):
+                 hist: Optional[dict] = None, pos: Optional[dict] = None, tokens: Optional[dict] = None):
         """`spill_dir`: stream every batch's records to disk instead of holding the whole run in host
         RAM (the reference keeps everything in Python lists until save_splits, cache.py:56-57);
         `save()` reads them back in batch order, so the final tensors are identical.
@@ -140,7 +149,11 @@ class Cache:
         nothing of it is allocated, launched or written.
         `pos`: keyword arguments of `PosProfile` (bins, tail_bin, n_bins, thresh, max_bytes) -- one `PosProfile` per module is
         then updated in `add_topk` from the same top-k pairs, over every feature.  None (default): nothing of it is
-        allocated, launched or written."""
+        allocated, launched or written.
+        `tokens`: keyword arguments of `TokenProfile` (vocab_size, offsets, mass, thresh, max_bytes, queries) -- one
+        `TokenProfile` per module is then updated in `add_topk` from the same top-k pairs and the batch's `token_ids`, which
+        every `add_topk` call must then pass.  `queries` (a list of features, or {module: list}) defaults to the module's
+        filter list; without either it is a ValueError.  None (default): nothing of it is allocated, launched or written."""
         self.feature_locations = defaultdict(list)
         self.feature_activations = defaultdict(list)
         self.spill_dir = spill_dir
@@ -155,15 +168,20 @@ class Cache:
         # groups of batches on their way to the host: (copy-done event, device buffers kept alive, pinned staging, layout)
         self._inflight = []
         self._copy_stream = None
-        # per kind: self.stats / .coact / .recon / .hist / .pos (its keyword arguments, None: off) and the accumulators per module
-        # in self.feature_stats / .coact_stats / .recon_stats / .act_hists / .pos_profiles
-        given = dict(stats=stats, coact=coact, recon=recon, hist=hist, pos=pos)
+        # per kind: self.stats / .coact / .recon / .hist / .pos / .tokens (its keyword arguments, None: off) and the accumulators
+        # per module in self.feature_stats / .coact_stats / .recon_stats / .act_hists / .pos_profiles / .token_profiles
+        given = dict(stats=stats, coact=coact, recon=recon, hist=hist, pos=pos, tokens=tokens)
         for kind in ACCUMULATORS:
             kw = given[kind.keyword]
             setattr(self, kind.keyword, None if kw is None else dict(kw))
             setattr(self, kind.attr, {})
         if self.coact is not None and self.coact.get("queries") is None and filters is None:
             raise ValueError("coact needs query features: pass coact['queries'] or a feature filter")
+        if self.tokens is not None:
+            if self.tokens.get("queries") is None and filters is None:
+                raise ValueError("tokens needs query features: pass tokens['queries'] or a feature filter")
+            if self.tokens.get("vocab_size") is None:
+                raise ValueError("tokens needs the vocabulary size: pass tokens['vocab_size']")
         if self.recon is not None and set(self.recon) - {"ks", "position_edges"}:
             raise ValueError(f"recon takes the keys 'ks' and 'position_edges', got {sorted(self.recon)}")
 
@@ -179,11 +197,14 @@ class Cache:
         return bm
 
     def add_topk(self, top_acts: Tensor, top_indices: Tensor, num_latents: int, batch_number: int,
-                 module_path: str):
-        """Fused equivalent of scatter_ + Cache.add (cache.py:214-217, 42-57) for `[B,S,k]` pairs."""
+                 module_path: str, token_ids: Optional[Tensor] = None):
+        """Fused equivalent of scatter_ + Cache.add (cache.py:214-217, 42-57) for `[B,S,k]` pairs.  `token_ids`: the batch's
+        `[B, S]` input ids, which only the token profiles (`tokens=`) read -- and need."""
+        if self.tokens is not None and token_ids is None:
+            raise ValueError("the cache keeps token profiles (tokens=): add_topk needs the batch's token_ids")
         row_base = batch_number * self.batch_size + self.shard_size  # cache.py:55
         self._feed("topk", module_path, top_acts=top_acts, top_indices=top_indices, num_latents=num_latents,
-                   row_base=row_base, device=top_acts.device)
+                   row_base=row_base, device=top_acts.device, token_ids=token_ids)
         loc, act, nnz = ops.sparsify(top_acts, top_indices, num_latents, row_base=row_base, thresh=1e-5,
                                      filter_bitmap=self._bitmap(module_path, num_latents, top_acts.device), sync=False)
         # stays on the device, stream-ordered (the reference does a nonzero() + two .cpu() per batch inside the
@@ -221,6 +242,17 @@ class Cache:
         if queries is None:
             raise ValueError(f"coact: no query features for module {module_path!r}")
         return CoactStats(num_latents, queries, device=device, **kw)
+
+    def _new_token_profile(self, module_path: str, num_latents: int, device) -> TokenProfile:
+        kw = dict(self.tokens)
+        queries = kw.pop("queries", None)
+        if isinstance(queries, dict):
+            queries = queries.get(module_path)
+        if queries is None and self.filters is not None:
+            queries = self.filters.get(module_path)
+        if queries is None:
+            raise ValueError(f"tokens: no query features for module {module_path!r}")
+        return TokenProfile(num_latents, queries, device=device, **kw)
 
     # free pinned byte buffers, reused from group to group and from Cache to Cache (pinning a few hundred MB takes tens of
     # milliseconds: a pool per instance paid it again for every run)
@@ -324,7 +356,7 @@ class FeatureCache:
     def __init__(self, model, tokenizer, submodule_dict: Dict[str, Sae], batch_size: int,
                  shard_size: int, filters: Optional[Dict[str, Tensor]] = None, stats: Optional[dict] = None,
                  coact: Optional[dict] = None, recon: Optional[dict] = None, hist: Optional[dict] = None,
-                 pos: Optional[dict] = None):
+                 pos: Optional[dict] = None, tokens: Optional[dict] = None):
         # LlavaNextForConditionalGeneration wraps the language model (cache.py:104-109)
         if hasattr(model, "language_model") and hasattr(model, "vision_tower"):
             self.llava_model, self.model = model, model.language_model
@@ -338,7 +370,7 @@ class FeatureCache:
         first = next(iter(submodule_dict.values()))
         self.width = first.cfg.num_latents or first.d_in * first.cfg.expansion_factor
         self.cache = Cache(shard_size, filters, batch_size=batch_size, stats=stats, coact=coact, recon=recon, hist=hist,
-                           pos=pos)
+                           pos=pos, tokens=tokens)
         if filters is not None:
             self.filter_submodules(filters)
 
@@ -367,7 +399,8 @@ class FeatureCache:
                 h.remove()
         return buffer
 
-    def _consume(self, buffer: Dict[str, Tensor], batch_number: int, drop_first_token: bool):
+    def _consume(self, buffer: Dict[str, Tensor], batch_number: int, drop_first_token: bool,
+                 token_ids: Optional[Tensor] = None):
         for module_path, hidden in buffer.items():
             if module_path not in self.submodule_dict:
                 continue
@@ -377,7 +410,8 @@ class FeatureCache:
             with torch.no_grad():
                 top = sae.encode(hidden)  # fused: replaces pre_acts + topk + zeros/scatter_
             self.cache.add_recon(hidden, top.top_acts, top.top_indices, sae, module_path)
-            self.cache.add_topk(top.top_acts, top.top_indices, sae.num_latents, batch_number, module_path)
+            self.cache.add_topk(top.top_acts, top.top_indices, sae.num_latents, batch_number, module_path,
+                                token_ids=token_ids)
 
     def run(self, n_tokens: int, tokens):
         from torch.utils.data import DataLoader
@@ -390,7 +424,7 @@ class FeatureCache:
             ids = batch["input_ids"].to(device)
             target = self.llava_model if self.llava_model is not None else self.model
             buffer = self._capture(lambda: target(ids))
-            self._consume(buffer, batch_number, drop_first_token=False)
+            self._consume(buffer, batch_number, drop_first_token=False, token_ids=ids)
         print(f"Total tokens processed: {total_tokens:,}")
         self.cache.save()
         if dist.is_initialized():
@@ -485,6 +519,12 @@ def merge_rank_pos_profile(module_dir: str, device=None) -> Optional[str]:
     return merge_rank_files(module_dir, "pos_profile", PosProfile, device)
 
 
+def merge_rank_token_profile(module_dir: str, device=None) -> Optional[str]:
+    """Add `Rank{r}_token_profile.safetensors` of `module_dir` in rank order (on `device`; any device, the CPU included) into
+    `token_profile.safetensors` and remove the rank files.  Returns the written path (None: no rank file)."""
+    return merge_rank_files(module_dir, "token_profile", TokenProfile, device)
+
+
 def merge_rank_recon(module_dir: str, device=None) -> Optional[str]:
     """Add `Rank{r}_recon_stats.safetensors` of `module_dir` in rank order (on `device`; any device, the CPU included) into
     `recon_stats.safetensors` and remove the rank files.  Returns the written path (None: no rank file).  Float64 sums: the
@@ -498,7 +538,11 @@ class FeatureImageCache(FeatureCache):
 
     def __init__(self, model, tokenizer, submodule_dict, batch_size: int, shard_size: int,
                  filters=None, processor=None, stats: Optional[dict] = None, coact: Optional[dict] = None,
-                 recon: Optional[dict] = None, hist: Optional[dict] = None, pos: Optional[dict] = None):
+                 recon: Optional[dict] = None, hist: Optional[dict] = None, pos: Optional[dict] = None,
+                 tokens: Optional[dict] = None):
+        if tokens is not None:
+            raise ValueError("tokens= is for the text cache: image rows carry no token per position (the hidden sequence the "
+                             "SAE sees holds the expanded image features and is not aligned with input_ids)")
         super().__init__(model, tokenizer, submodule_dict, batch_size, shard_size, filters, stats=stats, coact=coact,
                          recon=recon, hist=hist, pos=pos)
         if processor is None:  # resolved lazily, not at import time as cache.py:321 does

@@ -11,7 +11,7 @@ import torch
 import torch.distributed as dist
 
 from ...config import (CacheConfig, act_hist_kwargs, cache_config_error, coact_kwargs, parse_cache_config, pos_profile_kwargs,
-                       recon_kwargs)
+                       recon_kwargs, token_profile_kwargs)
 from ...features import FeatureCache
 from ...utils import ddp_setup, load_filter, load_saes, maybe_load_llava_model, shard_offsets
 
@@ -74,6 +74,25 @@ def chunk_and_tokenize(dataset, tokenizer, max_seq_len: int, text_key: str = "te
     return Dataset.from_dict({"input_ids": rows}).with_format("torch", columns=["input_ids"])
 
 
+def token_profiles(cfg: CacheConfig, tokenizer, saes, filters):
+    """The `tokens=` argument of the cache for --token_profile (None without it): V = len(tokenizer), the queries are the
+    filter lists.  Profiles the counters cannot hold end like a bad flag (`cache_config_error`), before the run starts."""
+    kw = token_profile_kwargs(cfg, len(tokenizer)) if cfg.token_profile else None
+    if kw is None:
+        return None
+    from ...features import TokenProfile
+
+    try:
+        if filters is None:
+            raise ValueError("no query features: give --filters_path")
+        for module_path, sae in saes.items():
+            if module_path in filters:       # the sizes and the query list, checked on the host with nothing allocated
+                TokenProfile(sae.num_latents, filters[module_path], device="meta", **kw)
+    except ValueError as e:
+        cache_config_error(f"--token_profile: {e}")
+    return kw
+
+
 def main(cfg: CacheConfig):
     from datasets import load_dataset
     from transformers import AutoTokenizer
@@ -119,7 +138,7 @@ def main(cfg: CacheConfig):
                          filters=filters, stats=stats, coact=coact_kwargs(cfg, COACT_DEFAULT_POOL, device=model.device),
                          recon=recon_kwargs(cfg),      # one position group
                          hist=act_hist_kwargs(cfg, ACT_HIST_DEFAULT_POOL),
-                         pos=pos)
+                         pos=pos, tokens=token_profiles(cfg, tokenizer, saes, filters))
     if ddp:
         dist.barrier()
     cache.run(cfg.ctx_len, dataset)

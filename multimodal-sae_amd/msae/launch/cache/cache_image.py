@@ -5,8 +5,8 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
-from ...config import (CacheConfig, act_hist_kwargs, cache_config_error, coact_kwargs, parse_cache_config,
-                       pos_profile_grid_default, pos_profile_kwargs, recon_kwargs)
+from ...config import (TOKEN_PROFILE_IMAGE_ERROR, CacheConfig, act_hist_kwargs, cache_config_error, coact_kwargs,
+                       parse_cache_config, pos_profile_grid_default, pos_profile_kwargs, recon_kwargs)
 from ...features import FeatureImageCache
 from ...utils import ddp_setup, load_filter, load_saes, maybe_load_llava_model, shard_offsets
 
@@ -15,10 +15,17 @@ COACT_DEFAULT_POOL = "image"
 ACT_HIST_DEFAULT_POOL = "image"
 
 
+def check_config(cfg: CacheConfig) -> None:
+    """What this launcher refuses, before anything is loaded: the token profiles belong to the text cache."""
+    if cfg.token_profile:
+        cache_config_error(TOKEN_PROFILE_IMAGE_ERROR)
+
+
 def main(cfg: CacheConfig):
     from datasets import load_dataset
     from transformers import AutoTokenizer
 
+    check_config(cfg)
     ddp, rank, world = ddp_setup(timeout_s=18000)
     dtype = torch.bfloat16 if torch.cuda.is_bf16_supported() else "auto"
     model, processor = maybe_load_llava_model(cfg.model, rank, dtype, cfg.hf_token)
