@@ -231,6 +231,23 @@ const char *msae_target_arch(void);
 int msae_pre_acts_f32(const void *x, int x_dtype, const float *W_enc, const float *b_enc,
                       const float *b_dec, int T, int d, int N, int relu, float *out, void *stream);
 
+/* The accumulating NT GEMM of a skip transcoder: C[m][p] (+)= sum_j a[m][j] B[p][j].
+ * a is [M][K] row-major with element type a_dtype (MSAE_F32 / MSAE_BF16 / MSAE_F16, up-cast exactly), B is f32 [P][K], C is
+ * f32 with row stride ld_c >= P; columns [P, ld_c) of C are neither read nor written.  C must not overlap a or B.
+ *   1. s[m][p] is the ascending-j f32 fma chain from +0, one accumulator per output: the bits of msae_pre_acts_f32 with no
+ *      biases and relu = 0.
+ *   2. accumulate == 0: C = s.  accumulate != 0: C = C_in + s, ONE rounded f32 add per element, C_in read in the epilogue by
+ *      the thread that writes the element (inf and NaN in C_in propagate as that add propagates them).  No atomics and no
+ *      split-K: the result does not depend on the grid or on timing, and two runs give the same bits.
+ *   3. Any M, K, P >= 1 (M <= 2^31 - 2^23, P <= 2^31 - 129).  K % 4 != 0 or a base that is not aligned to four elements
+ *      takes the tile's generic staging (element loads), with the same bits.  M == 0 returns 0 and touches nothing.  A null
+ *      pointer, a dtype code outside the three, K < 1, P < 1, M < 0 or ld_c < P: MSAE_EINVAL before any launch.
+ *      Asynchronous on `stream`; allocates nothing, never synchronises, needs no workspace.
+ * Uses: the forward skip term accumulated in place into the decode's output (a = x [T][d_in], B = W_skip [d_out][d_in],
+ * C = yhat), and the weight gradient dW_skip (+)= g^T x as a = g^T [d_out][T], B = x^T [d_in][T]. */
+int msae_gemm_nt_acc_f32(const void *a, int a_dtype, const float *B, int M, int K, int P, float *C, int ld_c,
+                         int accumulate, void *stream);
+
 /* Canonical top-k of each row of latents[T][N]: vals[T][k] descending, ties by ascending index.
  * idx is int32 (the host layer widens to int64 where the reference API returns int64). */
 size_t msae_topk_ws_bytes(int T, int N, int k);

@@ -53,6 +53,7 @@ PROTOTYPES = {
     "msae_target_arch": (ctypes.c_char_p, []),
     "msae_pre_acts_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                   c_int, c_void_p, c_void_p]),
+    "msae_gemm_nt_acc_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
     "msae_topk_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "msae_topk_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
                               c_void_p]),

@@ -8,10 +8,10 @@ from .hist import ActHist
 from .pos import PosProfile
 from .tokens import TokenProfile
 from .edits import FeatureEdits, RowEdits
-from .hooks import attribution_sae_hook, clamp_features_max, clamp_features_rows, sae_reconstruct
+from .hooks import attribution_sae_hook, clamp_features_max, clamp_features_rows, sae_reconstruct, transcoder_hook
 from .patching import Attribution
 
 __all__ = ["Cache", "FeatureCache", "FeatureImageCache", "generate_split_indices",
            "clamp_features_max", "attribution_sae_hook", "sae_reconstruct", "grad_times_act", "feature_scores", "FeatureDataset", "FeatureRecords", "split_path", "Attribution",
            "FeatureStats", "FeatureEdits", "RowEdits", "clamp_features_rows", "top_example_records", "sample_example_records", "cos", "get_neighbors", "logits",
-           "CoactStats", "coact_neighbors", "ReconStats", "ActHist", "PosProfile", "TokenProfile"]
+           "CoactStats", "coact_neighbors", "ReconStats", "ActHist", "PosProfile", "TokenProfile", "transcoder_hook"]

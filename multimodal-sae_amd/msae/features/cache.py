@@ -88,6 +88,10 @@ class _Accumulator(NamedTuple):
 
 
 def _new_recon(cache, module_path, c):
+    if getattr(getattr(c.sae, "cfg", None), "transcode", False):
+        raise NotImplementedError("Cache(recon=...) " "is not built for a transcoder (SaeConfig.transcode): the curve compares the reconstruction with the "
+                                      "encoder's own input, and a transcoder predicts another tensor (recon_error(x, y=) is a "
+                                      "follow-up; Sae.transcode and msae.features.hooks.transcoder_hook are its inference paths)")
     ks = cache.recon.get("ks")
     return ReconStats(c.sae.d_in, c.sae.default_recon_ks() if ks is None else ks, cache.recon.get("position_edges") or (0,),
                       b_dec=c.sae.b_dec, device=c.device)

@@ -31,6 +31,14 @@ def _topk_sae_only(sae, what: str) -> None:
                                   "top-k lists (Sae.encode + Sae.decode(lengths=) are its inference path)")
 
 
+def _autoencoder_only(sae, what: str) -> None:
+    """These hooks replace a layer's output by a reconstruction of that SAME output: a transcoder (SaeConfig.transcode)
+    predicts a module's output from its INPUT and is spliced in by `transcoder_hook`."""
+    if getattr(getattr(sae, "cfg", None), "transcode", False):
+        raise ValueError(f"{what} replaces a layer's output by a reconstruction of that same output; this Sae is a transcoder "
+                         "(SaeConfig.transcode): splice it in with msae.features.hooks.transcoder_hook / Sae.transcode")
+
+
 def sae_reconstruct(sae, hidden: Tensor, *, set_feature: int = -1, set_value: float = 0.0,
                     zero_feature: int = -1, out_dtype: Optional[torch.dtype] = None,
                     differentiable: Optional[bool] = None, edits: Optional[FeatureEdits] = None,
@@ -50,6 +58,7 @@ def sae_reconstruct(sae, hidden: Tensor, *, set_feature: int = -1, set_value: fl
     when nothing is edited): the error term is a constant of the forward, so the gradients with respect to the latents and
     the SAE's parameters are exactly the reconstruct path's.  Its values agree with the fused path's within the derived
     bound of tests/intervene_ref.py (the cancelled entries round differently), not bitwise."""
+    _autoencoder_only(sae, "sae_reconstruct")
     _topk_sae_only(sae, "sae_reconstruct")
     if preserve_error:
         return _reconstruct_preserving(sae, hidden, set_feature, set_value, zero_feature, out_dtype, differentiable, edits,
@@ -239,6 +248,7 @@ def clamp_features_max(sae, feature, hooked_module: torch.nn.Module, k: float = 
     "cap" (min(c, k)); it applies to an int, a sequence or a mapping, not to a prebuilt FeatureEdits."""
     import os
 
+    _autoencoder_only(sae, "clamp_features_max")
     _topk_sae_only(sae, "clamp_features_max")
     if preserve_error:
         return _clamp_preserving(sae, hooked_module, _preserving_edits(sae, feature, k, mode))
@@ -320,6 +330,7 @@ def clamp_features_rows(sae, features: Sequence, hooked_module: torch.nn.Module,
     if not isinstance(sae, Sae):
         raise NotImplementedError("clamp_features_rows runs on the single-GPU msae.Sae only: a feature-sharded engine takes "
                                   "one feature (clamp_features_max)")
+    _autoencoder_only(sae, "clamp_features_rows")
     _topk_sae_only(sae, "clamp_features_rows")
     if isinstance(features, (Mapping, Tensor, str)) or not hasattr(features, "__len__"):
         raise ValueError("clamp_features_rows: features must be a sequence with one element per batch row")
@@ -364,6 +375,7 @@ def attribution_sae_hook(sae_dict: Dict[str, Sae], module_to_name: Dict[torch.nn
     runs on reconstructions; sae_reconstruct states the autograd rule."""
     per_module: dict = {}         # a list of features becomes one FeatureEdits per hooked Sae, built at its first call
     for sae in sae_dict.values():
+        _autoencoder_only(sae, "attribution_sae_hook")
         _topk_sae_only(sae, "attribution_sae_hook")
 
     def hook(module, inputs, outputs):
@@ -388,3 +400,31 @@ def attribution_sae_hook(sae_dict: Dict[str, Sae], module_to_name: Dict[torch.nn
         return _replace_first(outputs, out)
 
     return hook
+
+
+def transcoder_hook(sae: Sae, module: torch.nn.Module, edits=None, out_dtype: Optional[torch.dtype] = None):
+    """Splice a transcoder (SaeConfig.transcode) in place of `module`: a forward hook that replaces the
+    module's OUTPUT by `sae.transcode(module input)` -- the first positional input [B, S, d_in] -> [B, S, d_out] in
+    `out_dtype` (None: the replaced output's own dtype).  `edits` (a FeatureEdits, or a RowEdits whose group b is batch row
+    b) apply on prefill only (S != 1), as the clamps' do; every call, the S = 1 steps included, runs eagerly (a captured
+    S = 1 step is a follow-up: DESIGN.md section 8).  Inference only."""
+    if not isinstance(sae, Sae) or not sae.cfg.transcode:
+        raise ValueError("transcoder_hook takes a transcoder (an msae.Sae with SaeConfig.transcode): an auto-encoder is spliced "
+                         "in on a layer's output (clamp_features_max, sae_splice_hook)")
+    if edits is not None:
+        edits.check(sae.num_latents, sae.cfg.k, sae.device)
+
+    def hook(mod, inputs, outputs):
+        if not inputs:
+            raise ValueError("transcoder_hook: the hooked module was called without a positional input")
+        x = inputs[0]
+        old = outputs[0] if isinstance(outputs, tuple) else outputs
+        prefill = x.dim() < 3 or x.shape[1] != 1
+        with torch.no_grad():
+            out = sae.transcode(x.detach(), edits=edits if prefill else None)
+        return _replace_first(outputs, out.to(out_dtype or old.dtype))
+
+    handle = module.register_forward_hook(hook)
+    handle.step_graph = None                    # (eager on every call)
+    handle.edits = edits
+    return [handle]

@@ -45,9 +45,10 @@ def sae_splice_hook(sae_dict: Dict[str, Sae], module_to_name: Dict[torch.nn.Modu
     attribution needs them; `extra_k` asks the encoder for that many latents beyond k (the
     reconstruction still uses the first k).  `preserve_error` (not with `extra_k` / `keep_latents`):
     the layer keeps the SAE's reconstruction error -- msae.features.hooks.attribution_sae_hook(preserve_error=True)."""
-    from ..hooks import _topk_sae_only
+    from ..hooks import _autoencoder_only, _topk_sae_only
 
     for sae in sae_dict.values():
+        _autoencoder_only(sae, "sae_splice_hook")
         _topk_sae_only(sae, "sae_splice_hook")
     if preserve_error:
         if extra_k or keep_latents is not None:

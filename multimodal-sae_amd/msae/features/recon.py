@@ -114,6 +114,10 @@ class ReconStats:
                              f"{tuple(top_indices.shape)}")
         if self.ks[-1] > top_acts.shape[-1]:
             raise ValueError(f"the checkpoints reach {self.ks[-1]}, the lists hold {top_acts.shape[-1]} entries")
+        if getattr(getattr(sae, "cfg", None), "transcode", False):
+            raise NotImplementedError("ReconStats.update " "is not built for a transcoder (SaeConfig.transcode): the curve compares the reconstruction with the "
+                                      "encoder's own input, and a transcoder predicts another tensor (recon_error(x, y=) is a "
+                                      "follow-up; Sae.transcode and msae.features.hooks.transcoder_hook are its inference paths)")
         if getattr(sae, "W_dec", None) is None:
             raise ValueError("ReconStats.update: this Sae has no decoder")
         if hidden.device != self.device:

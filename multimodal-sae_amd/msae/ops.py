@@ -15,6 +15,7 @@ These are the operators the drop-in ``Sae`` module (msae/sae/sae.py) and the fea
     msae::pre_acts_features  pre_acts(x)[..., features]      sae/sae.py:207-225 (AuxK: the dead latents only)
     msae::recon_curve   decode + e.pow(2).sum() per checkpoint  sae/sae.py:190,201 (one pass for several sparsities)
     batch_kth, list_filter, batch_select, decode(lengths=)   BatchTopK on top-C lists (no reference counterpart)
+    gemm_nt_add_, skip_add                                    a transcoder's dense skip term, accumulated in place
 
 All ops run on the tensor's device on the current stream, never synchronise (``sparsify`` reads one
 int64 back, as ``torch.nonzero`` does), and raise on CPU tensors.
@@ -353,6 +354,117 @@ def _pre_acts_backward(ctx, grad_out):
 
 
 pre_acts.register_autograd(_pre_acts_backward, setup_context=_pre_acts_setup)
+
+
+# ---- the skip term of a transcoder (csrc/skip_gemm.hip) ----------------------------------------------
+@torch.library.custom_op("msae::gemm_nt_add_", mutates_args=("C",))
+def _gemm_nt_add(C: Tensor, a: Tensor, B: Tensor, accumulate: bool) -> None:
+    M, K = a.shape
+    P = B.shape[0]
+    if not C.is_cuda:
+        # the host has no exact-chain route (pre_acts has none either): float32 matmul, the meaning and not the bits
+        s = a.detach().to(torch.float32) @ B.detach().to(torch.float32).t()
+        C.copy_(C + s if accumulate else s)
+        return
+    dev = _hip.require_device(C, a, B)
+    aa, Bc = _act(a), _f32c(B)
+    with torch.cuda.device(dev):
+        _hip.check(_hip.load().msae_gemm_nt_acc_f32(_hip.ptr(aa), _hip.DTYPE_CODE[aa.dtype], _hip.ptr(Bc), M, K, P,
+                                                    _hip.ptr(C), C.stride(0), int(accumulate), _hip.stream_of(C)),
+                   "msae_gemm_nt_acc_f32")
+
+
+def gemm_nt_add_(C: Tensor, a: Tensor, B: Tensor, accumulate: bool = True) -> Tensor:
+    """C[m][p] += sum_j a[m][j] B[p][j], in place (accumulate=False: C = the sum): a [M, K] in f32 / bf16 / f16, B [P, K]
+    f32, C f32 [M, P] with unit column stride and a row stride >= P (a row-sliced or column-sliced view works; what lies
+    between the rows is not touched).  The sum is the ascending-j f32 fma chain of the exact encoder GEMM, joined to C by one
+    f32 add: no atomics, the same bits on every run (include/msae.h, msae_gemm_nt_acc_f32).  Host tensors take a float32
+    torch matmul: the same meaning, not the same bits.  No autograd: `skip_add` is the differentiable form."""
+    if C.dim() != 2 or a.dim() != 2 or B.dim() != 2 or C.dtype != torch.float32:
+        raise ValueError(f"gemm_nt_add_: C (f32), a and B must be matrices, got {tuple(C.shape)} {C.dtype}, {tuple(a.shape)}, "
+                         f"{tuple(B.shape)}")
+    if a.shape[1] != B.shape[1] or a.shape[1] < 1 or B.shape[0] < 1 or tuple(C.shape) != (a.shape[0], B.shape[0]):
+        raise ValueError(f"gemm_nt_add_: a [M, K], B [P, K] and C [M, P] do not fit: {tuple(a.shape)}, {tuple(B.shape)}, "
+                         f"{tuple(C.shape)}")
+    if C.shape[0] and (C.stride(1) != 1 or C.stride(0) < C.shape[1]):
+        raise ValueError(f"gemm_nt_add_: C needs unit column stride and a row stride >= {C.shape[1]}, got {C.stride()}")
+    if C.shape[0]:
+        _gemm_nt_add(C, a, B, bool(accumulate))
+    return C
+
+
+_SKIP_GRAD_IN_PLACE = False
+
+
+@contextlib.contextmanager
+def skip_grad_in_place():
+    """Inside the block the backward of `skip_add` ADDS its weight gradient into an existing contiguous float32 W_skip.grad
+    with the kernel's own epilogue (gradient accumulation: no [d_out, d_in] temporary, no separate add; the same bits as
+    autograd's grad + g_W) and hands autograd None for W_skip.  That is a side effect on .grad which autograd does not see: a
+    hook registered on W_skip with register_hook is handed None in place of the gradient for that backward, whether a
+    post-accumulate hook (the data-parallel exchange hangs on those) still fires is the autograd engine's business and is
+    not relied on, and torch.autograd.grad(loss, [W_skip]) would change .grad and report W_skip as unused.  So it is opt-in:
+    SaeTrainStep enters it around `backward()` on a single rank, nothing else does."""
+    global _SKIP_GRAD_IN_PLACE
+    prev, _SKIP_GRAD_IN_PLACE = _SKIP_GRAD_IN_PLACE, True
+    try:
+        yield
+    finally:
+        _SKIP_GRAD_IN_PLACE = prev
+
+
+class _SkipAdd(torch.autograd.Function):
+    """dec_out += x W_skip^T in place.  Backward: g passes through to dec_out; g_W = g^T x as gemm_nt(g^T, x^T), returned to
+    autograd -- or, inside `skip_grad_in_place()` and where W_skip is a leaf that holds a .grad already, accumulated into that
+    .grad by the kernel (see there for what that costs); g_x = g W_skip only where x requires grad.  The GEMM's K is the token
+    count: one that is no multiple of 4 takes the tile's element-load staging (the same bits, not measured)."""
+
+    @staticmethod
+    def forward(ctx, dec_out, x, W_skip):
+        d_out, d_in = W_skip.shape
+        gemm_nt_add_(dec_out.view(-1, d_out), x.detach().reshape(-1, d_in), W_skip.detach())
+        ctx.mark_dirty(dec_out)
+        ctx.save_for_backward(x, W_skip)
+        return dec_out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, W_skip = ctx.saved_tensors
+        d_out, d_in = W_skip.shape
+        _, need_x, need_W = ctx.needs_input_grad
+        g2 = g.reshape(-1, d_out)
+        g_x = g_W = None
+        if need_W:
+            # the two transposes are torch copies (a TN staging path in the tile is a follow-up: DESIGN.md section 8)
+            gt = g2.to(torch.float32).t().contiguous()
+            xt = x.detach().reshape(-1, d_in).t().contiguous()
+            grad = W_skip.grad if _SKIP_GRAD_IN_PLACE and W_skip.is_leaf else None
+            if grad is not None and grad.dtype == torch.float32 and grad.is_contiguous() and grad.device == g.device:
+                gemm_nt_add_(grad, gt, xt)
+            else:
+                g_W = gemm_nt_add_(torch.empty(d_out, d_in, dtype=torch.float32, device=g.device), gt, xt, accumulate=False)
+                g_W = g_W.to(W_skip.dtype)
+        if need_x:
+            Wt = W_skip.detach().to(torch.float32).t()
+            gx = _dense_gemm_nt(g2.to(torch.float32), Wt) if g.is_cuda else g2.to(torch.float32) @ Wt.t()
+            g_x = gx.view(x.shape).to(x.dtype)
+        return g, g_x, g_W
+
+
+def skip_add(dec_out: Tensor, x: Tensor, W_skip: Tensor) -> Tensor:
+    """The dense skip connection of a transcoder: dec_out [..., d_out] (f32, contiguous; the decode's output) += x [..., d_in]
+    W_skip [d_out, d_in]^T, IN PLACE (one T x d_out pass and one allocation less than a GEMM and an add), as one autograd
+    node.  Returns dec_out.  Token counts divisible by 4 keep the weight gradient's GEMM (K = T) on the tile's vector staging;
+    any other count runs its element-load staging (the same bits)."""
+    d_out, d_in = W_skip.shape
+    if dec_out.dtype != torch.float32 or not dec_out.is_contiguous() or dec_out.shape[-1] != d_out or x.shape[-1] != d_in \
+            or dec_out.shape[:-1] != x.shape[:-1]:
+        raise ValueError(f"skip_add: dec_out must be contiguous f32 [..., {d_out}] and x [..., {d_in}] over the same tokens, "
+                         f"got {tuple(dec_out.shape)} {dec_out.dtype}, {tuple(x.shape)}")
+    if torch.is_grad_enabled() and (dec_out.requires_grad or x.requires_grad or W_skip.requires_grad):
+        return _SkipAdd.apply(dec_out, x, W_skip)
+    gemm_nt_add_(dec_out.view(-1, d_out), x.reshape(-1, d_in), W_skip)
+    return dec_out
 
 
 @torch.library.custom_op("msae::topk", mutates_args=())
@@ -2488,8 +2600,9 @@ class _SparseEncode(torch.autograd.Function):
             g_cat = g_cat * ~ctx.row_mask.bool()
         if ctx.gain is not None:                                   # ... or scaled by the edit's own derivative
             g_cat = g_cat * ctx.gain
-        a = x.float() - b_dec
+        a = x.float() if b_dec is None else x.float() - b_dec     # (None: a transcoder's encoder reads x as it is)
         need_x, need_W, need_be, need_bd = ctx.needs_input_grad[:4]
+        need_bd = need_bd and b_dec is not None
         g_x = g_W = g_be = g_bd = None
         rowsum = None
         if need_W:

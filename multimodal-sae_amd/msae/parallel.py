@@ -136,6 +136,10 @@ class ShardedSae:
     def from_sae(cls, sae, rank: int = 0, world: int = 1, group=None, mode: str = "topk", **kw) -> "ShardedSae":
         """Rank `rank`'s engine of a G-rank group over a (replicated, loaded) `Sae` module: slices of
         encoder.weight / encoder.bias, the whole W_dec / b_dec."""
+        if sae.cfg.transcode:
+            raise NotImplementedError("ShardedSae is not built for a transcoder (SaeConfig.transcode): the engine subtracts "
+                                      "b_dec in front of the encoder and decodes into the input space (a follow-up, DESIGN.md "
+                                      "section 8; Sae.transcode and msae.features.hooks.transcoder_hook are the single-GPU paths)")
         if sae.cfg.activation == "jump":
             raise NotImplementedError("ShardedSae is not built for an Sae with activation='jump': the engine merges per-token "
                                       "top-k lists and holds no threshold table (DESIGN.md section 8)")

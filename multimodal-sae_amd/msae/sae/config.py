@@ -53,6 +53,12 @@ class SaeConfig(_Serializable):
     the input on their own, under one selection over all latents (DESIGN.md section 7o).  Empty: a plain SAE."""
     matryoshka_weights: List[float] = field(default_factory=list)
     """One loss weight per prefix (finite, not negative, a positive sum).  Empty: 1 / G each."""
+    transcode: bool = False
+    """A transcoder (DESIGN.md section 7u): the dictionary reads one tensor and predicts ANOTHER (a module's input -> its
+    output).  b_dec lives in the output space and is not subtracted in front of the encoder; W_dec starts at zero and is
+    never normalised."""
+    skip_connection: bool = False
+    """A transcoder only: a dense linear map W_skip [d_out, d_in] (zero-initialised) beside the sparse path."""
 
     ACTIVATIONS = ("topk", "batchtopk", "jump")
     JUMP_MAX_CAP = 256
@@ -63,6 +69,14 @@ class SaeConfig(_Serializable):
             raise ValueError(f"activation must be one of {self.ACTIVATIONS}, got {self.activation!r}")
         if self.batch_cap < 0:
             raise ValueError(f"batch_cap must not be negative, got {self.batch_cap}")
+        for name in ("transcode", "skip_connection"):
+            if not isinstance(getattr(self, name), bool):
+                raise ValueError(f"{name} must be a bool, got {getattr(self, name)!r}")
+        if self.skip_connection and not self.transcode:
+            raise ValueError("skip_connection is the dense path of a transcoder: it needs transcode=True")
+        if self.transcode and self.matryoshka:
+            raise ValueError("matryoshka with transcode is not built (a follow-up: the nested decode node takes ONE tensor as "
+                             "input and as target; a Matryoshka transcoder needs the two apart)")
         if self.activation == "batchtopk":
             if self.multi_topk:
                 raise ValueError("multi_topk is a per-token TopK loss term: it does not go with activation='batchtopk'")
@@ -122,8 +136,8 @@ class SaeConfig(_Serializable):
         return list(self.matryoshka_weights) or [1.0 / G] * G
 
     def to_dict(self) -> dict:
-        """The BatchTopK and Matryoshka fields are written only where they differ from the defaults, the JumpReLU ones only
-        for "jump": a TopK cfg.json is the reference's."""
+        """The BatchTopK, Matryoshka and transcoder fields are written only where they differ from the defaults, the JumpReLU
+        ones only for "jump": a TopK cfg.json is the reference's."""
         d = super().to_dict()
         if d["activation"] != "jump":
             del d["jump_bandwidth"], d["jump_init"]
@@ -131,7 +145,7 @@ class SaeConfig(_Serializable):
             del d["activation"]
         if d["batch_cap"] == 0:
             del d["batch_cap"]
-        for name in ("matryoshka", "matryoshka_weights"):
+        for name in ("matryoshka", "matryoshka_weights", "transcode", "skip_connection"):
             if not d[name]:
                 del d[name]
         return d

@@ -22,6 +22,10 @@ unchanged.  What differs is underneath:
 * `SaeConfig(activation="jump")` -> ops.jump_select + ops.decode(lengths=reach): JumpReLU with a learned threshold per feature
                      (`log_threshold`), trained through straight-through estimators (new, opt-in: DESIGN.md section 7s)
 
+* `SaeConfig(transcode=True[, skip_connection=True])` -> a transcoder: `forward(x, y=)` predicts ANOTHER tensor (a module's output
+                     from its input), W_dec [N, d_out], b_dec [d_out] an output bias the encoder does not subtract, and a dense
+                     skip term x W_skip^T through ops.skip_add (new, opt-in: DESIGN.md section 7u)
+
 SAE math is f32 whatever dtype the LLM hands over, as in the reference (sae.py:140,174).
 There is no CPU implementation: calling a compute method with CPU tensors raises.
 """
@@ -186,18 +190,33 @@ class Sae(nn.Module):
     auxk_path = "dense"          # how `forward` builds the AuxK selection when it is not told: "dense" or "subset"
 
     def __init__(self, d_in: int, cfg: SaeConfig, device: Union[str, torch.device] = "cpu",
-                 dtype: Union[torch.dtype, None] = None, *, decoder: bool = True):
+                 dtype: Union[torch.dtype, None] = None, *, decoder: bool = True, d_out: Optional[int] = None):
         super().__init__()
         self.cfg = cfg
         self.d_in = d_in
         self.num_latents = cfg.num_latents or d_in * cfg.expansion_factor
+        # a transcoder (cfg.transcode) predicts a tensor of its own width: W_dec is [N, d_out] and
+        # b_dec [d_out] lives in the output space
+        self.d_out = d_in if d_out is None else int(d_out)
+        if not cfg.transcode and self.d_out != d_in:
+            raise ValueError(f"d_out = {self.d_out} != d_in = {d_in} needs a transcoder (SaeConfig(transcode=True)): an "
+                             "auto-encoder reconstructs its own input")
+        if self.d_out < 1:
+            raise ValueError(f"d_out must be positive, got {self.d_out}")
 
         self.encoder = nn.Linear(d_in, self.num_latents, device=device, dtype=dtype)
         self.encoder.bias.data.zero_()
-        self.W_dec = nn.Parameter(self.encoder.weight.data.clone()) if decoder else None
-        if decoder and self.cfg.normalize_decoder:
-            self.set_decoder_norm_to_unit_norm()
-        self.b_dec = nn.Parameter(torch.zeros(d_in, dtype=dtype, device=device))
+        if cfg.transcode:
+            # zeros: a clone of the encoder has the wrong width, and zero rows have no direction -- never normalised
+            self.W_dec = nn.Parameter(torch.zeros(self.num_latents, self.d_out, dtype=self.encoder.weight.dtype,
+                                                  device=device)) if decoder else None
+        else:
+            self.W_dec = nn.Parameter(self.encoder.weight.data.clone()) if decoder else None
+            if decoder and self.cfg.normalize_decoder:
+                self.set_decoder_norm_to_unit_norm()
+        self.b_dec = nn.Parameter(torch.zeros(self.d_out, dtype=dtype, device=device))
+        if cfg.skip_connection:
+            self.W_skip = nn.Parameter(torch.zeros(self.d_out, d_in, dtype=torch.float32, device=device))
         if cfg.activation == "batchtopk":
             # the inference threshold BatchTopK learns in training (msae.train.SaeTrainStep folds every batch's theta into it);
             # -1 = not learned yet.  Saved and loaded with the model; a TopK Sae has no such key.
@@ -260,8 +279,9 @@ class Sae(nn.Module):
         with open(path / "cfg.json", "r") as f:
             cfg_dict = json.load(f)
         d_in = cfg_dict.pop("d_in")
+        d_out = cfg_dict.pop("d_out", None)            # written for a transcoder only
         cfg = SaeConfig.from_dict(cfg_dict)
-        sae = Sae(d_in, cfg, device=device, decoder=decoder)
+        sae = Sae(d_in, cfg, device=device, decoder=decoder, d_out=d_out)
         load_model(model=sae, filename=str(path / "sae.safetensors"), device=str(device),
                    strict=decoder)
         sae.invalidate_prepared()
@@ -274,7 +294,19 @@ class Sae(nn.Module):
         path.mkdir(parents=True, exist_ok=True)
         save_model(self, str(path / "sae.safetensors"))
         with open(path / "cfg.json", "w") as f:
-            json.dump({**self.cfg.to_dict(), "d_in": self.d_in}, f)
+            json.dump({**self.cfg.to_dict(), "d_in": self.d_in, **({"d_out": self.d_out} if self.cfg.transcode else {})}, f)
+
+    @property
+    def _b_pre(self) -> Optional[Tensor]:
+        """What the encoder subtracts from its input: b_dec, or nothing for a transcoder (its b_dec is an output bias)."""
+        return None if self.cfg.transcode else self.b_dec
+
+    def _no_transcoder(self, what: str) -> None:
+        """The paths that compare or combine a reconstruction with the encoder's own input are not built for a transcoder."""
+        if self.cfg.transcode:
+            raise NotImplementedError(f"{what} is not built for a transcoder (SaeConfig.transcode): it reconstructs the "
+                                      "encoder's own input, and a transcoder predicts another tensor -- Sae.transcode(x) and "
+                                      "msae.features.hooks.transcoder_hook are the transcoder's inference paths")
 
     @property
     def device(self):
@@ -295,12 +327,12 @@ class Sae(nn.Module):
         [..., N] latents (activation histograms and dashboards of a filter list).  A host list with an index outside
         [0, N) raises ValueError; a tensor's entries are clamped.  Inference only: differentiate the dense `pre_acts`."""
         if features is None:
-            return ops.pre_acts(x, self.encoder.weight, self.encoder.bias, self.b_dec)
+            return ops.pre_acts(x, self.encoder.weight, self.encoder.bias, self._b_pre)
         feats = self._feature_rows(features, "pre_acts")          # validates before any device work
         if torch.is_grad_enabled() and any(t.requires_grad for t in (x, self.encoder.weight, self.encoder.bias, self.b_dec)):
             raise NotImplementedError("Sae.pre_acts(x, features=...) has no autograd: call it under torch.no_grad(), or "
                                       "differentiate the dense pre_acts(x) and index its result")
-        return ops.pre_acts_features(x, self.encoder.weight, self.encoder.bias, self.b_dec, feats)
+        return ops.pre_acts_features(x, self.encoder.weight, self.encoder.bias, self._b_pre, feats)
 
     def select_topk(self, latents: Tensor) -> EncoderOutput:
         """Top-k latents (sae.py:179-181).  Order is canonical (value desc, index asc), a valid
@@ -403,14 +435,14 @@ class Sae(nn.Module):
         if want_grad:
             # autograd must flow (attribution patching: patching/utils.py:33-58, attribution.py:165):
             # same kernel, as one autograd node with the sparse backward
-            (acts, idx), = ops.sparse_encode(x, self.encoder.weight, self.encoder.bias, self.b_dec, self.cfg.k,
+            (acts, idx), = ops.sparse_encode(x, self.encoder.weight, self.encoder.bias, self._b_pre, self.cfg.k,
                                              prepared=self._prepared_weights(), set_feature=set_feature,
                                              set_value=set_value, zero_feature=zero_feature, edits=edits,
                                              edit_group=edit_group)
             return EncoderOutput(acts, idx)
         with torch.no_grad():      # (a custom op without an autograd formula would hang a raising node on the outputs)
             if rows:               # the same two steps with the table of every token's own group
-                acts, idx, status = ops.encode_topk(x, self.encoder.weight, self.encoder.bias, self.b_dec,
+                acts, idx, status = ops.encode_topk(x, self.encoder.weight, self.encoder.bias, self._b_pre,
                                                     self._prepared_weights(), self.cfg.k + edits.E_max, exact=exact,
                                                     certified=certified)
                 if edits.value_dependent:  # scale / add / floor / cap: the edited features' exact latents, one pass
@@ -419,13 +451,13 @@ class Sae(nn.Module):
                 else:
                     acts, idx = ops.edit_topk_rows(acts, idx, edit_group, edits, self.num_latents, self.cfg.k)
             elif edits is not None:  # over-fetch, then edit: `exact` / `certified` only change the first call
-                acts, idx, status = ops.encode_topk(x, self.encoder.weight, self.encoder.bias, self.b_dec,
+                acts, idx, status = ops.encode_topk(x, self.encoder.weight, self.encoder.bias, self._b_pre,
                                                     self._prepared_weights(), self.cfg.k + edits.E, exact=exact,
                                                     certified=certified)
                 acts, idx = ops.edit_topk(acts, idx, edits.feat, edits.val, edits.kind, self.num_latents, self.cfg.k,
                                           cur=self._edit_cur(x, edits.feat) if edits.value_dependent else None)
             else:
-                acts, idx, status = ops.encode_topk(x, self.encoder.weight, self.encoder.bias, self.b_dec,
+                acts, idx, status = ops.encode_topk(x, self.encoder.weight, self.encoder.bias, self._b_pre,
                                                     self._prepared_weights(), self.cfg.k, set_feature,
                                                     float(set_value), zero_feature, exact=exact, certified=certified)
         out = EncoderOutput(acts, idx)
@@ -510,11 +542,11 @@ class Sae(nn.Module):
         if want_grad and own:
             if cap > ops.JUMP_MAX_C:
                 raise ValueError(f"Sae.encode: a differentiable 'jump' encode takes cap <= {ops.JUMP_MAX_C}, got {cap}")
-            (acts, idx), = ops.sparse_encode(x, self.encoder.weight, self.encoder.bias, self.b_dec, cap,
+            (acts, idx), = ops.sparse_encode(x, self.encoder.weight, self.encoder.bias, self._b_pre, cap,
                                              prepared=self._prepared_weights())
             acts, idx, lengths, _, _, _ = ops.jump_select(acts, idx, table, self.cfg.jump_bandwidth)
         elif want_grad:
-            (acts, idx), = ops.sparse_encode(x, self.encoder.weight, self.encoder.bias, self.b_dec, cap,
+            (acts, idx), = ops.sparse_encode(x, self.encoder.weight, self.encoder.bias, self._b_pre, cap,
                                              prepared=self._prepared_weights())
             with torch.no_grad():
                 kept, _, lengths, _ = ops.list_filter(acts, idx, theta)
@@ -522,7 +554,7 @@ class Sae(nn.Module):
             acts = torch.where(kept > 0, acts, torch.zeros((), dtype=acts.dtype, device=acts.device))
         else:
             with torch.no_grad():
-                acts, idx, status = ops.encode_topk(x, self.encoder.weight, self.encoder.bias, self.b_dec,
+                acts, idx, status = ops.encode_topk(x, self.encoder.weight, self.encoder.bias, self._b_pre,
                                                     self._prepared_weights(), cap, exact=exact, certified=certified)
                 if own:
                     table = table.detach()
@@ -534,7 +566,7 @@ class Sae(nn.Module):
     def _edit_cur(self, x: Tensor, feats: Tensor) -> Tensor:
         """The exact latents of the features a value-dependent edit reads: the listed columns of
         `pre_acts`, bit for bit, [..., len(feats)] f32."""
-        return ops.pre_acts_features(x, self.encoder.weight, self.encoder.bias, self.b_dec, feats)
+        return ops.pre_acts_features(x, self.encoder.weight, self.encoder.bias, self._b_pre, feats)
 
     @staticmethod
     def _token_groups(x: Tensor, edits, edit_group: Optional[Tensor]) -> Tensor:
@@ -564,6 +596,7 @@ class Sae(nn.Module):
         include/msae.h, "error-preserving interventions".  Inference only: no host synchronisation, allocations through torch
         alone (capturable in a HIP graph); with gradients enabled on x it raises RuntimeError -- the hooks' autograd path is
         `msae.features.hooks.sae_reconstruct(preserve_error=True)`."""
+        self._no_transcoder("Sae.intervene")
         self._topk_only("intervene")
         if edits is None or not (hasattr(edits, "check") and (hasattr(edits, "offsets") or hasattr(edits, "E"))):
             raise ValueError("Sae.intervene: edits must be a msae.features.FeatureEdits or RowEdits")
@@ -586,7 +619,7 @@ class Sae(nn.Module):
         k = self.cfg.k
         with torch.no_grad():
             flat = x.reshape(-1, self.d_in)
-            acts, idx, _ = ops.encode_topk(flat, self.encoder.weight, self.encoder.bias, self.b_dec, self._prepared_weights(),
+            acts, idx, _ = ops.encode_topk(flat, self.encoder.weight, self.encoder.bias, self._b_pre, self._prepared_weights(),
                                            k + (edits.E_max if rows else edits.E), exact=exact, certified=certified)
             if rows and edits.value_dependent:
                 q_acts, q_idx = ops.edit_topk_rows(acts, idx, edit_group.reshape(-1), edits, self.num_latents, k,
@@ -598,6 +631,35 @@ class Sae(nn.Module):
                                               cur=self._edit_cur(flat, edits.feat) if edits.value_dependent else None)
             out = ops.delta_decode(flat, acts[:, :k], idx[:, :k], q_acts, q_idx, self.W_dec)
         return out.view(x.shape)
+
+    def transcode(self, x: Tensor, *, edits=None, edit_group: Optional[Tensor] = None, exact: bool = False) -> Tensor:
+        """A transcoder's prediction of the module output from the module input: x [..., d_in] in
+        f32 / bf16 / f16 -> f32 [..., d_out] = decode(encode(x)) + b_dec (+ x W_skip^T with cfg.skip_connection, accumulated
+        in place into the decode's output).  `edits` / `edit_group` / `exact` as in `encode`: the edits work on the list as
+        they do there.  A "batchtopk" or "jump" transcoder encodes with its threshold(s) and decodes the kept entries.
+        Inference only: no host synchronisation, allocations through torch alone; with gradients enabled on x it raises
+        RuntimeError (`forward(x, y=)` is the differentiable form)."""
+        if not self.cfg.transcode:
+            raise ValueError("Sae.transcode: this Sae is an auto-encoder (SaeConfig.transcode is off): decode(encode(x)) "
+                             "reconstructs x itself")
+        if self.W_dec is None:
+            raise ValueError("Sae.transcode: this Sae has no decoder")
+        if x.dim() < 1 or x.shape[-1] != self.d_in:
+            raise ValueError(f"Sae.transcode: x must be [..., {self.d_in}], got {tuple(x.shape)}")
+        if x.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+            raise ValueError(f"Sae.transcode: x must be float32, bfloat16 or float16, got {x.dtype}")
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise RuntimeError("Sae.transcode is an inference path: call it under torch.no_grad() or on a detached input "
+                               "(Sae.forward(x, y=) is the differentiable form)")
+        with torch.no_grad():
+            if self.cfg.activation in ("batchtopk", "jump"):
+                top, lengths = self.encode(x, edits=edits, edit_group=edit_group, exact=exact, return_lengths=True)
+            else:
+                top, lengths = self.encode(x, edits=edits, edit_group=edit_group, exact=exact), None
+            out = self.decode(top.top_acts, top.top_indices, lengths)
+            if self.cfg.skip_connection:
+                out = ops.skip_add(out.contiguous(), x, self.W_skip)
+        return out
 
     def default_recon_ks(self) -> tuple:
         """Powers of two up to cfg.k, plus cfg.k itself."""
@@ -612,6 +674,7 @@ class Sae(nn.Module):
         error of `decode` over an Sae with cfg.k = kappa.  `top`: the list of x (an EncoderOutput or (top_acts, top_indices))
         when the caller holds it already; None: `self.encode(x, exact=exact)`.  `chunk`: tokens per kernel call (None: one
         call); the per-token outputs do not depend on it.  Inference only; nothing is read back."""
+        self._no_transcoder("Sae.recon_error")
         self._topk_only("recon_error")
         if self.W_dec is None:
             raise ValueError("Sae.recon_error: this Sae has no decoder")
@@ -663,6 +726,7 @@ class Sae(nn.Module):
         (top_acts, top_indices) or (top_acts, top_indices, lengths); None: `self.encode(x, exact=exact)`.  Available on any
         Sae; inference only, nothing is read back.  Not the same question as `truncate(m)`, which RE-SELECTS the top-k
         among the first m features."""
+        self._no_transcoder("Sae.nested_error")
         if bounds is None:
             bounds = self.cfg.matryoshka
             if not bounds:
@@ -714,6 +778,7 @@ class Sae(nn.Module):
         and restricts it to those below m.  The two agree only where the full selection already lies inside the prefix."""
         import dataclasses
 
+        self._no_transcoder("Sae.truncate")
         m = int(m)
         if not self.cfg.cap <= m <= self.num_latents:
             raise ValueError(f"Sae.truncate: m must lie in [{self.cfg.cap}, {self.num_latents}], got {m}")
@@ -798,7 +863,7 @@ class Sae(nn.Module):
             raise ValueError(f"reduce must be one of {sorted(_probe.REDUCE)}, got {reduce!r}")
         flat, seg, chunks = self._probe_inputs(x, segments, "pooled_acts")
         with torch.no_grad():
-            return ops.pooled_acts(flat, self.encoder.weight, self.encoder.bias, self.b_dec, seg, chunks,
+            return ops.pooled_acts(flat, self.encoder.weight, self.encoder.bias, self._b_pre, seg, chunks,
                                    _probe.REDUCE[reduce])
 
     def probe(self, x: Tensor, k: int, segments=None, reduce: str = "mean", maps: bool = True) -> ProbeOutput:
@@ -815,10 +880,10 @@ class Sae(nn.Module):
             raise ValueError(f"reduce must be one of {sorted(_probe.REDUCE)}, got {reduce!r}")
         flat, seg, chunks = self._probe_inputs(x, segments, "probe")
         with torch.no_grad():
-            pooled = ops.pooled_acts(flat, self.encoder.weight, self.encoder.bias, self.b_dec, seg, chunks,
+            pooled = ops.pooled_acts(flat, self.encoder.weight, self.encoder.bias, self._b_pre, seg, chunks,
                                      _probe.REDUCE[reduce])
             values, indices = ops.topk(pooled, k)
-            m = ops.probe_maps(flat, self.encoder.weight, self.encoder.bias, self.b_dec, seg, indices) if maps else None
+            m = ops.probe_maps(flat, self.encoder.weight, self.encoder.bias, self._b_pre, seg, indices) if maps else None
         return ProbeOutput(values, indices, m)
 
     # ---- neighbours and top logits (features/stats.py:12-47,76-120) -----------------------------------------
@@ -842,7 +907,9 @@ class Sae(nn.Module):
         index.  features: a list or 1-d int tensor of indices, or None for all N; matrix: "decoder" (W_dec) or "encoder"
         (encoder.weight), both [N, d]; exclude_self skips the feature's own index (rank 0 is NOT dropped: with duplicated
         rows the feature itself need not rank first).  One fused GEMM + top-k: the [M, N] cosines are never stored.
-        cos = dot * inv[m] * inv[n] with inv = ops.row_inv_norms (include/msae.h, "neighbours")."""
+        cos = dot * inv[m] * inv[n] with inv = ops.row_inv_norms (include/msae.h, "neighbours").  A transcoder's decoder rows
+        live in the OUTPUT space ([N, d_out]) and its encoder rows in the input space: the two matrices answer different
+        questions there."""
         if matrix not in ("decoder", "encoder"):
             raise ValueError(f"matrix must be 'decoder' or 'encoder', got {matrix!r}")
         W = self.W_dec if matrix == "decoder" else self.encoder.weight
@@ -864,11 +931,11 @@ class Sae(nn.Module):
     def top_logits(self, W_U: Tensor, features=None, k: int = 10):
         """Direct logit attribution (features/stats.py:12-47): the k tokens each selected feature's decoder row pushes
         hardest -> (values f32 [M, k], token ids int64 [M, k]).  W_U: the unembedding [V, d] in f32, bf16 or f16 (up-cast
-        to f32 once); no scales, no exclusion."""
+        to f32 once); no scales, no exclusion.  A transcoder's decoder rows live in the OUTPUT space (d_out wide)."""
         if self.W_dec is None:
             raise ValueError("this Sae has no decoder")
-        if W_U.dim() != 2 or W_U.shape[1] != self.d_in:
-            raise ValueError(f"W_U must be [V, {self.d_in}], got {tuple(W_U.shape)}")
+        if W_U.dim() != 2 or W_U.shape[1] != self.d_out:
+            raise ValueError(f"W_U must be [V, {self.d_out}], got {tuple(W_U.shape)}")
         lim = min(ops.ROWS_TOPK_MAX_K, W_U.shape[0])
         if not 1 <= k <= lim:
             raise ValueError(f"k must be in [1, {lim}], got {k}")
@@ -882,7 +949,8 @@ class Sae(nn.Module):
         sizes its result on the host): it takes the place of `int(dead_mask.sum())`."""
         return torch.nonzero(dead_mask).flatten().to(torch.int32)
 
-    def forward(self, x: Tensor, dead_mask: Union[Tensor, None] = None, *, auxk_path: Optional[str] = None) -> ForwardOutput:
+    def forward(self, x: Tensor, dead_mask: Union[Tensor, None] = None, *, y: Optional[Tensor] = None,
+                auxk_path: Optional[str] = None) -> ForwardOutput:
         """Training forward (sae.py:193-247): reconstruction, FVU, AuxK and Multi-TopK terms, fully
         differentiable.  The encoder is one autograd node with a sparse backward (ops._SparseEncode):
         gradients reach encoder.weight / encoder.bias / b_dec / x only through the selected latents,
@@ -892,7 +960,22 @@ class Sae(nn.Module):
         of a non-empty dead_mask is built.  "dense" materialises the [T, N] latents (pre_acts, where(dead_mask, ., -inf),
         top-k three times).  "subset" (with max(k, 4k) <= 256; otherwise the dense branch runs) keeps the main and
         Multi-TopK selections on the fused encoder and takes the AuxK one from an exact GEMM over the dead features only
-        (ops.topk_within) -- the same selections bit for bit, no [T, N] tensor."""
+        (ops.topk_within) -- the same selections bit for bit, no [T, N] tensor.
+
+        y: the TARGET of a transcoder (cfg.transcode), [..., d_out] over the same tokens as x: required
+        there, a ValueError on a plain Sae.  The encoder reads x without subtracting b_dec, the output is decode + b_dec
+        (+ x W_skip^T with cfg.skip_connection, on the main and the Multi-TopK reconstruction; not on AuxK's e_hat, which
+        models the residual), and every loss term is today's expression with y in the target's place (k_aux = d_out // 2)."""
+        if self.cfg.transcode:
+            if y is None:
+                raise ValueError("Sae.forward: a transcoder (SaeConfig.transcode) needs its target: forward(x, y=...)")
+            if y.shape[:-1] != x.shape[:-1] or y.shape[-1] != self.d_out or x.shape[-1] != self.d_in:
+                raise ValueError(f"Sae.forward: x must be [..., {self.d_in}] and y [..., {self.d_out}] over the same tokens, got "
+                                 f"{tuple(x.shape)} and {tuple(y.shape)}")
+        elif y is not None:
+            raise ValueError("Sae.forward: y= is the target of a transcoder (SaeConfig.transcode); an auto-encoder's target is x")
+        tgt = y if self.cfg.transcode else x
+        skip = self.cfg.skip_connection
         if auxk_path is None:
             auxk_path = self.auxk_path
         if auxk_path not in ops.AUXK_PATHS:
@@ -905,7 +988,7 @@ class Sae(nn.Module):
             else:
                 num_dead = int(dead_mask.sum())
             if num_dead > 0:
-                k_aux = x.shape[-1] // 2                      # heuristic from the paper (sae.py:209)
+                k_aux = tgt.shape[-1] // 2                    # heuristic from the paper (sae.py:209)
                 scale = min(num_dead / k_aux, 1.0)
                 k_aux = min(k_aux, num_dead)
         k_multi = 4 * self.cfg.k if self.cfg.multi_topk else 0
@@ -913,10 +996,10 @@ class Sae(nn.Module):
         jump = self.cfg.activation == "jump"
         k_main = self.cfg.cap                     # cfg.k, or the list width C of the batch-level selection
         if auxk_path == "subset":
-            sel = ops.sparse_encode(x, self.encoder.weight, self.encoder.bias, self.b_dec, k_main,
+            sel = ops.sparse_encode(x, self.encoder.weight, self.encoder.bias, self._b_pre, k_main,
                                     dead_mask, k_aux, k_multi, auxk_path="subset", dead_list=dead_list)
         else:
-            sel = ops.sparse_encode(x, self.encoder.weight, self.encoder.bias, self.b_dec, k_main,
+            sel = ops.sparse_encode(x, self.encoder.weight, self.encoder.bias, self._b_pre, k_main,
                                     dead_mask, k_aux, k_multi)
         top_acts, top_indices = sel[0]
         nested = bool(self.cfg.matryoshka)
@@ -943,27 +1026,30 @@ class Sae(nn.Module):
             sae_out = self.decode(top_acts, top_indices, reach)
         else:
             sae_out = self.decode(top_acts, top_indices)
+        if skip:
+            sae_out = ops.skip_add(sae_out.contiguous(), x, self.W_skip)      # in place, into the decode's output
         # the loss terms in as few T x d sweeps as autograd allows (each elementwise torch op on [T, d] is a 45-us kernel at
         # C2; the reference's expression is ~10 of them forward + backward): squared error and its gradient through _SqErr,
         # the total variance as one column-variance kernel.  An input that itself requires grad keeps the plain expressions.
-        lean = x.is_cuda and x.dim() == 2 and not x.requires_grad and x.dtype == torch.float32
+        # (a transcoder's target is y: tgt below; an auto-encoder's is x itself)
+        lean = tgt.is_cuda and tgt.dim() == 2 and not tgt.requires_grad and tgt.dtype == torch.float32
         if nested:
-            sq_err, e = sq_sum[-1], None if lean else sae_out - x
-            total_variance = _total_variance(x) if lean else (x - x.mean(0)).pow(2).sum()
+            sq_err, e = sq_sum[-1], None if lean else sae_out - tgt
+            total_variance = _total_variance(tgt) if lean else (tgt - tgt.mean(0)).pow(2).sum()
         elif lean:
-            sq_err, e = _SqErr.apply(sae_out, x)
-            total_variance = _total_variance(x)
+            sq_err, e = _SqErr.apply(sae_out, tgt)
+            total_variance = _total_variance(tgt)
         else:
-            e = sae_out - x
+            e = sae_out - tgt
             sq_err = e.pow(2).sum()
-            total_variance = (x - x.mean(0)).pow(2).sum()
+            total_variance = (tgt - tgt.mean(0)).pow(2).sum()
 
         if k_aux > 0:
             auxk_acts, auxk_indices = sel[1]
             e_hat = self.decode(auxk_acts, auxk_indices)
             # (e is the residual the dead latents should explain: a constant target, as in the reference's graph it carries
             # gradient to the main path too -- keep that: use the differentiable residual when it matters)
-            e_t = e if not lean else (sae_out - x)
+            e_t = e if not lean else (sae_out - tgt)
             auxk_loss = scale * (e_hat - e_t).pow(2).sum() / total_variance
         else:
             auxk_loss = sae_out.new_zeros(())           # (built on the device: no host-to-device copy)
@@ -972,7 +1058,9 @@ class Sae(nn.Module):
         if k_multi > 0:
             top_acts, top_indices = sel[-1]
             sae_out = self.decode(top_acts, top_indices)
-            multi_topk_fvu = (_SqErr.apply(sae_out, x)[0] if lean else (sae_out - x).pow(2).sum()) / total_variance
+            if skip:
+                sae_out = ops.skip_add(sae_out.contiguous(), x, self.W_skip)
+            multi_topk_fvu = (_SqErr.apply(sae_out, tgt)[0] if lean else (sae_out - tgt).pow(2).sum()) / total_variance
         else:
             multi_topk_fvu = sae_out.new_zeros(())
         if nested:

@@ -39,6 +39,7 @@ trainer's outer loop and out of scope.
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Optional, Tuple
 
 import torch
@@ -130,6 +131,10 @@ class SaeTrainStep:
             raise ValueError(f"l0_alpha must be finite and not negative and l0_warmup_steps not negative, got {l0_alpha}, "
                              f"{l0_warmup_steps}")
         self.l0_alpha, self.l0_warmup_steps = float(l0_alpha), int(l0_warmup_steps)
+        # a transcoder: step(hiddens, targets); the decoder starts at zero and is never normalised or
+        # projected, whatever cfg.normalize_decoder says; W_skip is one more 2-D entry of self.params
+        self.transcode = sae.cfg.transcode
+        self.normalize_decoder = sae.cfg.normalize_decoder and not self.transcode
         # per parameter: an ops.Adam8State where the 8-bit format takes the shape, else None and float32 moments
         self.state8 = [ops.adam8_state(p) if optim_bits == 8 else None for p in self.params]
         self.exp_avg = [torch.zeros_like(p) if s8 is None else None for p, s8 in zip(self.params, self.state8)]   # torch.optim.Adam state
@@ -258,7 +263,9 @@ class SaeTrainStep:
         self._did_fire |= hits > 0
 
     # ---- compute (overridden with torch-CPU restatements by the gloo tests) ----------------------------------
-    def _forward(self, hiddens: Tensor, dead_mask: Optional[Tensor]):
+    def _forward(self, hiddens: Tensor, dead_mask: Optional[Tensor], targets: Optional[Tensor] = None):
+        if targets is not None:
+            return self.sae(hiddens, dead_mask, y=targets, auxk_path=self.auxk_path)
         return self.sae(hiddens, dead_mask, auxk_path=self.auxk_path)
 
     def _renorm_decoder(self) -> None:
@@ -294,12 +301,12 @@ class SaeTrainStep:
             kw = {}
             is_dec = p is sae.W_dec
             is_enc = p is sae.encoder.weight
-            if fuse and is_dec and sae.cfg.normalize_decoder:
+            if fuse and is_dec and self.normalize_decoder:
                 kw["renorm_eps"] = torch.finfo(p.dtype).eps          # sae.py:252
             if fuse and is_enc and self._chunk_tokens > 0 and ops.coarse_in_force() != "fp8":   # (the fused pass builds int8 / bf16 operands; MSAE_COARSE=fp8 in the environment counts: ADVICE r5)
                 kw["refresh"], kw["tokens_next"] = ops.train_operand_buffer(p), self._chunk_tokens
             kw.update(total_sumsq=self._sumsq, max_norm=self.max_grad_norm, betas=self.betas,
-                      project=sae.cfg.normalize_decoder and is_dec)
+                      project=self.normalize_decoder and is_dec)
             if self.optimizer != "adam":
                 ops.lion_rows_(p.data, p.grad, m, lr, **kw)
             elif s8 is None:
@@ -314,7 +321,7 @@ class SaeTrainStep:
                 ops.mark_train_operands_fresh(p, self._chunk_tokens)
 
     # ---- one batch ---------------------------------------------------------------------------------------------
-    def step(self, hiddens: Tensor) -> dict:
+    def step(self, hiddens: Tensor, targets: Optional[Tensor] = None) -> dict:
         """One global step (one batch of activations of this rank).  Returns device tensors (no host
         synchronisation): {"fvu", "auxk_loss", "multi_topk_fvu"} averaged over micro-batches and ranks,
         "stepped": whether the optimizer moved (every `grad_acc_steps`-th call).  A Matryoshka Sae (cfg.matryoshka) descends on
@@ -322,38 +329,56 @@ class SaeTrainStep:
         "batchtopk" Sae adds "theta" (the mean of
         the micro-chunks' rank-averaged thresholds) and "n_saturated" (this rank's rows that kept all C slots), device tensors
         as well.  A "jump" Sae adds "l0" (the mean number of latents kept per token, averaged like the others) and
-        "n_saturated", device tensors too, and descends on fvu + ... + l0_alpha * warm(t) * l0."""
+        "n_saturated", device tensors too, and descends on fvu + ... + l0_alpha * warm(t) * l0.
+
+        `targets` (a transcoder, SaeConfig.transcode: required; a ValueError otherwise): what the dictionary predicts from
+        `hiddens`, [T, d_out] over the same tokens; cut into micro-chunks with the same cuts.  `init_b_dec` then takes its
+        geometric median from the targets: b_dec is an output bias."""
         sae = self.sae
+        if self.transcode:
+            if targets is None:
+                raise ValueError("SaeTrainStep.step: a transcoder (SaeConfig.transcode) needs its targets: step(hiddens, targets)")
+            if targets.dim() != 2 or targets.shape[0] != hiddens.shape[0] or targets.shape[1] != sae.d_out:
+                raise ValueError(f"SaeTrainStep.step: targets must be [{hiddens.shape[0]}, {sae.d_out}], got "
+                                 f"{tuple(targets.shape)}")
+        elif targets is not None:
+            raise ValueError("SaeTrainStep.step: targets= belongs to a transcoder (SaeConfig.transcode); an auto-encoder's "
+                             "target is its input")
         if self.global_step == 0 and self.init_b_dec:            # trainer.py:325-332
-            pts = hiddens.float()
+            pts = (targets if self.transcode else hiddens).float()
             if self.world > 1:
                 parts = [torch.empty_like(pts) for _ in range(self.world)]
                 dist.all_gather(parts, pts, group=self.group)
                 pts = torch.cat(parts)
             sae.b_dec.data.copy_(geometric_median(pts).to(sae.b_dec.dtype))
-        if sae.cfg.normalize_decoder:
+        if self.normalize_decoder:
             self._renorm_decoder()
         dead_mask = (self.num_tokens_since_fired > self.dead_feature_threshold) if self.auxk_alpha > 0 else None
         acc_steps = self.grad_acc_steps * self.micro_acc_steps
         stats = torch.zeros(3, dtype=torch.float32, device=hiddens.device)
         chunks = hiddens.chunk(self.micro_acc_steps)
+        tchunks = targets.chunk(self.micro_acc_steps) if self.transcode else None
         theta_sum = n_saturated = nested_sum = l0_sum = 0
         l0_weight = self.current_l0_weight if self.jump else 0.0
         for ci, chunk in enumerate(chunks):
             self._reduce_now = self.world > 1 and ci == len(chunks) - 1
             self._chunk_tokens = chunk.shape[0]
-            out = self._forward(chunk, dead_mask)
+            out = self._forward(chunk, dead_mask, tchunks[ci]) if self.transcode else self._forward(chunk, dead_mask)
             # a Matryoshka Sae descends on the weighted sum of its prefixes' FVUs (DESIGN.md section 7o); fvu stays a statistic
             nested_loss = getattr(out, "nested_loss", None)
             main = out.fvu if nested_loss is None else nested_loss
             loss = main + self.auxk_alpha * out.auxk_loss + out.multi_topk_fvu / 8
             if self.jump:
                 loss = loss + l0_weight * out.l0
+            # (a single rank: W_skip's gradient of a later chunk is added into .grad by the GEMM's own epilogue; with more
+            # ranks the post-accumulate hooks must fire, so autograd accumulates)
+            in_place = ops.skip_grad_in_place() if self.world == 1 else contextlib.nullcontext()
             if hiddens.is_cuda:
-                with ops.collect_wgrad_sumsq() as self._wgrad_sumsq:
+                with ops.collect_wgrad_sumsq() as self._wgrad_sumsq, in_place:
                     loss.div(acc_steps).backward()
             else:
-                loss.div(acc_steps).backward()
+                with in_place:
+                    loss.div(acc_steps).backward()
             stats += torch.stack([out.fvu.detach(), out.auxk_loss.detach(), out.multi_topk_fvu.detach()])
             if nested_loss is not None:
                 nested_sum = nested_sum + out.nested_fvu.detach().to(torch.float32)
