@@ -50,6 +50,8 @@
  *   msae_edit_topk_rows_f32  the same with one table per token (a feature per batch row of one generate)
  *   msae_delta_decode_f32    x + decode(edited) - decode(plain): error-preserving hooks (no reference counterpart)
  *   msae_recon_curve_f32     reconstruction error at several sparsities in one pass (sae.py:190-202 per checkpoint)
+ *   msae_support_refit_f32   least-squares refit on the encoder's support: optimal error at every sparsity (no reference
+ *                            counterpart)
  *   msae_batch_kth_f32, msae_list_filter_f32, msae_decode_prefix_f32   BatchTopK on top-C lists: the batch threshold, the
  *                            threshold filter, the decode with a row length (no reference counterpart)
  *   msae_jump_filter_f32, msae_jump_bwd_f32   JumpReLU with learned per-feature thresholds on top-C lists: the three-way
@@ -929,6 +931,60 @@ int msae_recon_curve_f32(const void *x, int x_dtype, const float *vals, const in
 int msae_recon_curve_i64_f32(const void *x, int x_dtype, const float *vals, const int64_t *idx, int ld, const float *W_dec,
                              const float *b_dec, int T, int k, int N, int d, const int32_t *ks, int C, float *mom, float *xx,
                              int32_t *status, void *stream);
+
+/* ---- support refit (Sae.refit, msae.features.ReconStats(refit=True)) -------------------------------
+ * Keep the support the encoder chose -- the first s slots of a token's canonical list -- and refit its coefficients by
+ * least squares against the fixed decoder: min_c |y - D^T c|^2, y = x - b_dec, D = the listed rows of W_dec.  err_enc -
+ * err_fit is what the encoder loses by its magnitudes alone (the amortisation gap); err_fit is what the dictionary cannot
+ * express on that support.  The list is value descending, so the support of the top-kappa list is the first kappa slots;
+ * the Gram matrix of a prefix is a leading block of G, its Cholesky factor a leading block of L, and the forward solve
+ * nests too: yy - sum_{j < kappa} gain[j] is the optimal squared error at EVERY kappa <= s from one factorisation.
+ *   x [T][d]                          the hidden states, x_dtype MSAE_F32 / MSAE_BF16 / MSAE_F16
+ *   vals / idx [T][ld]                the list in the first s columns of each row (ld >= s: a longer list is refit on its
+ *                                     first s slots in place)
+ *   W_dec f32 [N][d], b_dec f32 [d]   both required
+ *   coef f32 [T][s]                   the least-squares coefficients on the full live support, signs as they come
+ *   gain f32 [T][s]                   z_j^2: what slot j takes off the optimal error when it joins the slots before it
+ *   err_fit, err_enc, yy f32 [T]      |y - D^T coef|^2, |y - D^T vals|^2, |y|^2
+ *   n_dependent int32 [T]             live slots dropped as linearly dependent on the slots before them
+ *   status int32 [1] or NULL          bit 0 is ORed in when a slot's feature lies outside [0, N), as msae_recon_curve_f32 does
+ * Asynchronous on `stream`; allocates nothing, needs no workspace, never synchronises.  MSAE_EINVAL: a null pointer
+ * (`status` may be null), s < 1, s > MSAE_REFIT_MAX_S, ld < s, T < 0, N < 1, d < 1, d > 2^22, a bad dtype code.  T == 0
+ * returns 0.
+ * Contract, per token t (nothing depends on T or on the other tokens); u = 2^-24, gamma_n = n u / (1 - n u):
+ *   1. Support.  Slot j is live iff vals[j] != 0 and 0 <= idx[j] < N; an index outside sets `status`.  A dead slot has
+ *      coef = gain = 0 and keeps its place; it is not counted in n_dependent.  Its row of D is zero below.
+ *   2. y[c] = f32(x[t][c]) - b_dec[c], one f32 subtract.
+ *   3. Gram.  G = D D^T (lower triangle), h = D y: each entry is the sum of four f32 fma chains, one per c mod 128 in
+ *      [0, 32), [32, 64), [64, 96), [96, 128), each over its columns in ascending order from +0 (two columns per
+ *      v_mfma_f32_32x32x2_f32, fma(a_c1, b_c1, fma(a_c0, b_c0, acc))), added as ((p0 + p1) + p2) + p3.  yy: a lane owns the
+ *      columns with (c mod 128) / 4 == lane, lane < 32, and chains them in ascending order from +0; the 64 lanes (32 of them
+ *      +0) are added by an xor butterfly, partner distance 32, 16, ..., 1.  Neither order depends on the load path.
+ *   4. Cholesky, G = L L^T in slot order, right-looking: at column j the pivot p is G_jj after the updates of the columns
+ *      before it.  p <= tau G_jj (G_jj as formed in step 3), tau = f32(2 gamma_{d+s}): the slot is dependent -- counted,
+ *      coef = gain = 0, its row and column skipped from then on.  (gamma_{d+s} bounds the relative error of a Gram entry
+ *      plus its at most s pivot updates against sum |terms| <= 2 G_jj: a pivot below tau G_jj is not told from zero.  A
+ *      repeated index leaves |p| <= 3 u G_jj; a row at angle theta to the span before it leaves sin^2 theta G_jj.)
+ *      Otherwise L_jj = sqrt(p), L_ij = G_ij / L_jj, G_im = fma(-L_ij, L_mj, G_im) for j < m <= i: every entry takes its
+ *      updates in ascending j.  sqrt and / are correctly rounded.
+ *   5. Forward solve.  h rides as row s of the same factorisation: z_j = h_j after the same updates, / L_jj.
+ *      gain[j] = z_j * z_j.
+ *   6. Back solve over the slots kept, j descending: coef_j = z_j / L_jj, then z_m = fma(-L_jm, coef_j, z_m) for m < j.
+ *   7. Second walk.  fit[c] and enc[c] are msae_recon_curve_f32's slot-ordered chains over the s slots (from +0, a zero
+ *      coefficient skipped) with coef and with vals (0 for a dead slot; a dependent slot keeps its value);
+ *      err_fit = sum_c (y[c] - fit[c])^2 and err_enc likewise, in the order of msae_recon_curve_f32's moments (step 4 there).
+ *      Neither is taken from yy - sum gain: a wrong solve cannot hide behind its own algebra.
+ * No floating-point atomics: token t's outputs are the same bits alone or in any batch, in any call.
+ * Layout: one workgroup of 256 threads per token; 128-column slabs of the rows through LDS, the matrix (at most 65 x 65)
+ * factored in LDS.  16-byte loads when d % 4 == 0 and W_dec, b_dec, x are aligned to 4 elements, element loads otherwise. */
+#define MSAE_REFIT_MAX_S 64
+int msae_support_refit_f32(const void *x, int x_dtype, const float *vals, const int32_t *idx, int ld, const float *W_dec,
+                           const float *b_dec, int T, int s, int N, int d, float *coef, float *gain, float *err_fit,
+                           float *err_enc, float *yy, int32_t *n_dependent, int32_t *status, void *stream);
+/* the same reading 64-bit indices (msae_encode_topk_i64's output type) */
+int msae_support_refit_i64_f32(const void *x, int x_dtype, const float *vals, const int64_t *idx, int ld, const float *W_dec,
+                               const float *b_dec, int T, int s, int N, int d, float *coef, float *gain, float *err_fit,
+                               float *err_enc, float *yy, int32_t *n_dependent, int32_t *status, void *stream);
 
 /* ---- batch-level selection: capped BatchTopK, threshold filter, length-aware decode -------------
  * BatchTopK keeps the T*k largest pre-activations of a whole batch instead of k per token; inference replaces the batch's

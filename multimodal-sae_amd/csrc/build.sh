@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -munsafe-fp-atomics -Wall -Wno-unused-function -Wno-inline-asm"
 OBJS=""
-for f in capi decode delta_decode recon nested_decode topk sparsify feature_stats coact act_hist pos_profile token_profile encode_f32 skip_gemm probe neighbors edit_topk batch_select jump_select encode_fused train; do
+for f in capi decode delta_decode recon refit nested_decode topk sparsify feature_stats coact act_hist pos_profile token_profile encode_f32 skip_gemm probe neighbors edit_topk batch_select jump_select encode_fused train; do
   "$HIPCC" $FLAGS -c "$HERE/$f.hip" -o "$OUT/$f.o" &
   OBJS="$OBJS $OUT/$f.o"
 done

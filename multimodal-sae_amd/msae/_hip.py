@@ -166,6 +166,11 @@ PROTOTYPES = {
                                      c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "msae_recon_curve_i64_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
                                          c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "msae_support_refit_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                                       c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "msae_support_refit_i64_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
+                                           c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p]),
     "msae_batch_kth_ws_bytes": (c_size_t, [c_int, c_int]),
     "msae_batch_kth_f32": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_size_t,
                                    c_void_p]),

@@ -56,6 +56,8 @@ class CacheConfig:
     """Also measure every SAE's reconstruction error against sparsity and position (recon_stats.safetensors per module)"""
     recon_ks: Optional[str] = None
     """Comma-separated checkpoints of --recon_stats, e.g. 0,1,2,4,8,16,32 (default: powers of two up to k, and k)"""
+    recon_refit: bool = False
+    """With --recon_stats: also refit every token's coefficients on its support by least squares (the amortisation gap)"""
     act_hist: bool = False
     """Also count how strongly every feature fires (act_hist.safetensors per module: a histogram per feature)"""
     act_hist_pool: Optional[str] = None
@@ -139,6 +141,8 @@ def parse_cache_config(argv: Optional[Sequence[str]] = None) -> CacheConfig:
             recon_ks_list(cfg.recon_ks)
         except ValueError as e:
             p.error(str(e))
+    if cfg.recon_refit and not cfg.recon_stats:
+        p.error("--recon_refit adds to --recon_stats: give both")
     if cfg.act_hist_pool is not None and cfg.act_hist_pool not in COACT_POOLS:
         p.error(f"--act_hist_pool must be one of {', '.join(COACT_POOLS)}, got {cfg.act_hist_pool!r}")
     if cfg.act_hist_bins is not None:
@@ -203,7 +207,10 @@ def recon_kwargs(cfg: CacheConfig, position_edges=(0,)) -> Optional[dict]:
     of --recon_ks (None: every SAE's own default) and the launcher's position groups."""
     if not cfg.recon_stats:
         return None
-    return dict(ks=None if cfg.recon_ks is None else recon_ks_list(cfg.recon_ks), position_edges=tuple(position_edges))
+    kw = dict(ks=None if cfg.recon_ks is None else recon_ks_list(cfg.recon_ks), position_edges=tuple(position_edges))
+    if cfg.recon_refit:                                  # (absent without the flag: the off path is what it was)
+        kw["refit"] = True
+    return kw
 
 
 COACT_POOLS = ("token", "window", "image")

@@ -94,7 +94,7 @@ def _new_recon(cache, module_path, c):
                                       "follow-up; Sae.transcode and msae.features.hooks.transcoder_hook are its inference paths)")
     ks = cache.recon.get("ks")
     return ReconStats(c.sae.d_in, c.sae.default_recon_ks() if ks is None else ks, cache.recon.get("position_edges") or (0,),
-                      b_dec=c.sae.b_dec, device=c.device)
+                      b_dec=c.sae.b_dec, device=c.device, refit=bool(cache.recon.get("refit")))
 
 
 # add_topk feeds in this order: stats, coact, hist, pos, tokens (then sparsify)
@@ -145,7 +145,8 @@ class Cache:
         per module is then updated in `add_topk` next to the feature statistics.  `queries` (a list of features, or
         {module: list}) defaults to the module's filter list; without either it is a ValueError.  None (default): nothing
         of it is allocated, launched or written.
-        `recon`: {"ks": checkpoints, "position_edges": first position of every group} (both optional: the SAE's
+        `recon`: {"ks": checkpoints, "position_edges": first position of every group, "refit": also the least-squares
+        optimum on the encoder's support, ReconStats(refit=True)} (all optional: the SAE's
         `default_recon_ks()`, one group) -- one `ReconStats` per module is then updated by `add_recon` with the hidden state
         the loop already holds.  None (default): nothing of it is allocated, launched or written.
         `hist`: keyword arguments of `ActHist` (pool, pool_len, window, thresh, sub_bits, e_lo, octaves, max_bytes) -- one
@@ -186,8 +187,8 @@ class Cache:
                 raise ValueError("tokens needs query features: pass tokens['queries'] or a feature filter")
             if self.tokens.get("vocab_size") is None:
                 raise ValueError("tokens needs the vocabulary size: pass tokens['vocab_size']")
-        if self.recon is not None and set(self.recon) - {"ks", "position_edges"}:
-            raise ValueError(f"recon takes the keys 'ks' and 'position_edges', got {sorted(self.recon)}")
+        if self.recon is not None and set(self.recon) - {"ks", "position_edges", "refit"}:
+            raise ValueError(f"recon takes the keys 'ks', 'position_edges' and 'refit', got {sorted(self.recon)}")
 
     def _bitmap(self, module_path: str, num_latents: int, device) -> Optional[Tensor]:
         if self.filters is None:

@@ -28,6 +28,12 @@ Unlike the integer counters of `FeatureStats` and `CoactStats`, these are FLOAT6
 bit-identical however the rows are cut into calls or ranks; the accumulated sums agree only to float64 rounding (a
 relative 2 n 2^-53 of the sum of the terms' magnitudes), and `merge` is associative to that bound, not bit for bit.
 
+REFIT (`refit=True`).  One `ops.support_refit` call per batch (msae_support_refit_f32) beside the
+curve: the least-squares optimum on the support the encoder chose, at every checkpoint of `ks` up to 64 (`refit_ks`) from
+one factorisation.  Per group `refit_sums [R]` is the float64 sum of that optimal error, next to the encoder's own in
+`sums[..., 0]`: their difference over the total variance is the amortisation gap (`gap`), the optimum over it is what the
+dictionary cannot express on that support (`fvu_fit`).  Without the flag nothing of this exists, in memory or in the file.
+
 The statistics cover exactly the positions handed to `update` -- in the cache loop every position the cache records,
 padding included, as everything else in the loop does."""
 from __future__ import annotations
@@ -65,7 +71,7 @@ class ReconStats:
     `save` and reading a loaded file need no GPU."""
 
     def __init__(self, d: int, ks: Sequence[int], position_edges: Sequence[int] = (0,), b_dec: Optional[Tensor] = None,
-                 device=None):
+                 device=None, refit: bool = False):
         if d < 1:
             raise ValueError(f"d must be positive, got {d}")
         self.d = int(d)
@@ -82,6 +88,10 @@ class ReconStats:
         self.xx_sum = torch.zeros(G, dtype=torch.float64, device=dev)
         self.cos_sum = torch.zeros(G, C1, dtype=torch.float64, device=dev)
         self.x_sum = torch.zeros(G, self.d, dtype=torch.float64, device=dev)
+        self.refit = bool(refit)
+        self.refit_ks = tuple(c for c in self.ks if c <= ops.REFIT_MAX_S) if self.refit else ()
+        self._refit_slot = [self._all_ks.index(c) for c in self.refit_ks]
+        self.refit_sums = torch.zeros(G, len(self.refit_ks), dtype=torch.float64, device=dev) if self.refit else None
         self.b_dec: Optional[Tensor] = None
         if b_dec is not None:
             self._set_centre(b_dec)
@@ -139,9 +149,19 @@ class ReconStats:
                 self.cos_sum[g] += cos[:, a:b].sum((0, 1))
                 self.x_sum[g] += hidden[:, a:b].sum((0, 1), dtype=torch.float64)
                 self.n[g] += B * (b - a)
+            if self.refit_ks:
+                raw = ops.support_refit(hidden.detach(), top_acts.detach(), top_indices, sae.W_dec, sae.b_dec,
+                                        s=max(1, self.refit_ks[-1]))
+                g64 = raw.gain.to(torch.float64)
+                pre = torch.cat([torch.zeros_like(g64[..., :1]), g64.cumsum(-1)], -1)
+                at = torch.stack([pre[..., c] for c in self.refit_ks], -1)                      # (selects: an index list would be copied
+                opt = raw.yy.to(torch.float64)[..., None] - at                                  # to the device) [B, S, R]
+                for g, (a, b) in enumerate(self._ranges(S)):
+                    if b > a:
+                        self.refit_sums[g] += opt[:, a:b].sum((0, 1))
 
     def _kind(self):
-        return (self.d, self.ks, self.position_edges)
+        return (self.d, self.ks, self.position_edges) + ((("refit",) + self.refit_ks,) if self.refit else ())
 
     def merge(self, other: "ReconStats") -> "ReconStats":
         """self += other (another rank's sums over the same checkpoints, groups, width and centre), on self's device."""
@@ -157,6 +177,8 @@ class ReconStats:
         self.xx_sum += other.xx_sum.to(dev)
         self.cos_sum += other.cos_sum.to(dev)
         self.x_sum += other.x_sum.to(dev)
+        if self.refit:
+            self.refit_sums += other.refit_sums.to(dev)
         self.n = [a + b for a, b in zip(self.n, other.n)]
         return self
 
@@ -202,23 +224,60 @@ class ReconStats:
         n, _, _, cos_sum, _ = self._state(group)
         return cos_sum[self._slot] / n if n else torch.full((len(self.ks),), float("nan"), dtype=torch.float64)
 
+    # ---- refit: float64 [R] over `refit_ks` ------------------------------------------------------------------------------
+    def _refit(self, group: Optional[int]):
+        if not self.refit:
+            raise ValueError("these statistics were accumulated without refit=True")
+        if group is not None and not 0 <= group < self.num_groups:
+            raise IndexError(f"group must lie in [0, {self.num_groups}), got {group}")
+        opt = (self.refit_sums.sum(0) if group is None else self.refit_sums[group]).cpu()
+        return opt, self._state(group)[1][self._refit_slot, 0]
+
+    def fvu_fit(self, group: Optional[int] = None) -> Tensor:
+        """Fraction of variance unexplained at the least-squares coefficients on the encoder's support, per refit_ks."""
+        return self._refit(group)[0] / self.total_variance(group)
+
+    def gap(self, group: Optional[int] = None) -> Tensor:
+        """The amortisation gap per refit_ks: (the encoder's error - the optimum on its support) / total variance."""
+        opt, enc = self._refit(group)
+        return (enc - opt) / self.total_variance(group)
+
+    def summary(self, group: Optional[int] = None) -> str:
+        """One line per checkpoint: kappa, fvu, cosine and, with refit, the optimum's fvu and the gap."""
+        fvu, cos = self.fvu(group), self.cosine(group)
+        head = f"{'kappa':>6} {'fvu':>10} {'cosine':>10}" + (f" {'fvu_fit':>10} {'gap':>10}" if self.refit else "")
+        fit, gap = (self.fvu_fit(group), self.gap(group)) if self.refit else (None, None)
+        lines = [head]
+        for c, kappa in enumerate(self.ks):
+            line = f"{kappa:>6} {float(fvu[c]):>10.6f} {float(cos[c]):>10.6f}"
+            if self.refit:
+                r = self.refit_ks.index(kappa) if kappa in self.refit_ks else None
+                line += f" {float(fit[r]):>10.6f} {float(gap[r]):>10.6f}" if r is not None else f" {'-':>10} {'-':>10}"
+            lines.append(line)
+        return "\n".join(lines)
+
     # ---- file --------------------------------------------------------------------------------------------------------
     def metadata(self) -> dict:
-        return {"format": FORMAT, "d": str(self.d), "ks": json.dumps(list(self.ks)),
+        meta = {"format": FORMAT, "d": str(self.d), "ks": json.dumps(list(self.ks)),
                 "position_edges": json.dumps(list(self.position_edges)), "n": json.dumps(self.n)}
+        if self.refit:                                   # (without the flag the file is what it was, byte for byte)
+            meta["refit_ks"] = json.dumps(list(self.refit_ks))
+        return meta
 
     def save(self, path: str) -> None:
         tensors = {"sums": self.sums, "xx_sum": self.xx_sum, "cos_sum": self.cos_sum, "x_sum": self.x_sum}
         if self.b_dec is not None:
             tensors["b_dec"] = self.b_dec
+        if self.refit:
+            tensors["refit_sums"] = self.refit_sums
         save_file({k: v.detach().contiguous().cpu() for k, v in tensors.items()}, path, metadata=self.metadata())
 
     @classmethod
     def load(cls, path: str, device=None) -> "ReconStats":
         meta, tensors = open_stats_file(path, FORMAT, "a reconstruction statistics")
         st = cls(int(meta["d"]), json.loads(meta["ks"]), json.loads(meta["position_edges"]), b_dec=tensors.get("b_dec"),
-                 device=device)
-        for name in ("sums", "xx_sum", "cos_sum", "x_sum"):
+                 device=device, refit="refit_ks" in meta)
+        for name in ("sums", "xx_sum", "cos_sum", "x_sum") + (("refit_sums",) if st.refit else ()):
             getattr(st, name).copy_(tensors[name])
         st.n = [int(v) for v in json.loads(meta["n"])]
         return st

@@ -14,6 +14,7 @@ These are the operators the drop-in ``Sae`` module (msae/sae/sae.py) and the fea
     msae::rows_topk     torch.mm + torch.topk, fused         features/stats.py:35-37,83,107
     msae::pre_acts_features  pre_acts(x)[..., features]      sae/sae.py:207-225 (AuxK: the dead latents only)
     msae::recon_curve   decode + e.pow(2).sum() per checkpoint  sae/sae.py:190,201 (one pass for several sparsities)
+    msae::support_refit least-squares coefficients on the encoder's support (no reference counterpart)
     batch_kth, list_filter, batch_select, decode(lengths=)   BatchTopK on top-C lists (no reference counterpart)
     gemm_nt_add_, skip_add                                    a transcoder's dense skip term, accumulated in place
 
@@ -28,7 +29,7 @@ import ctypes
 import dataclasses
 import os
 import weakref
-from typing import Optional, Sequence, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor
@@ -1549,6 +1550,152 @@ def recon_curve(x: Tensor, top_acts: Tensor, top_indices: Tensor, W_dec: Tensor,
     mom, xx = _recon_curve(x, top_acts, top_indices, W_dec.detach(), b_dec.detach(), ks)      # (weights are constants here)
     lead = tuple(x.shape[:-1])
     return mom.view(*lead, len(ks), 3), xx.view(lead)
+
+
+# ---- least-squares refit on the encoder's support (csrc/refit.hip) ------------------------------------
+REFIT_MAX_S = 64
+
+
+class RefitRaw(NamedTuple):
+    """ops.support_refit's outputs (include/msae.h, "support refit"), all f32 but n_dependent (int32)."""
+    coef: Tensor
+    """The least-squares coefficients on the live support, [..., s]; 0 for a dead or dependent slot."""
+    gain: Tensor
+    """z_j^2, [..., s]: yy - gain[..., :kappa].sum(-1) is the optimal squared error of the top-kappa support."""
+    err_fit: Tensor
+    """|y - D^T coef|^2, [...]."""
+    err_enc: Tensor
+    """|y - D^T vals|^2, [...]: the encoder's own error on the same s slots."""
+    yy: Tensor
+    """|x - b_dec|^2, [...]."""
+    n_dependent: Tensor
+    """Live slots dropped as linearly dependent on the slots before them, [...] int32."""
+
+
+def refit_tau(d: int, s: int) -> float:
+    """The dependence threshold of msae_support_refit_f32, 2 gamma_{d+s} with u = 2^-24, rounded to f32 as the kernel's is."""
+    nu = (d + s) * 2.0 ** -24
+    return float(torch.tensor(2.0 * nu / (1.0 - nu), dtype=torch.float64).to(torch.float32))
+
+
+def _support_refit_host(x: Tensor, vals: Tensor, idx: Tensor, W_dec: Tensor, b_dec: Tensor, s: int):
+    """The meaning of msae_support_refit_f32 in float64 torch (the f32 inputs, the same support and dependence rule, float64
+    arithmetic rounded to f32 at the end): not its bits."""
+    W, b = W_dec.detach().to(torch.float64), b_dec.detach().to(torch.float32)
+    N, d = W.shape
+    k = vals.shape[-1]
+    y = (x.detach().reshape(-1, d).to(torch.float32) - b).to(torch.float64)
+    v, i = vals.detach().reshape(-1, k)[:, :s].to(torch.float64), idx.detach().reshape(-1, k)[:, :s].to(torch.int64)
+    T = y.shape[0]
+    live = (i >= 0) & (i < N) & (v != 0)
+    v = torch.where(live, v, torch.zeros_like(v))
+    D = W[torch.where(live, i, torch.zeros_like(i))] * live[..., None]          # [T, s, d], zero rows for dead slots
+    G, h = D @ D.transpose(1, 2), (D @ y[..., None])[..., 0]
+    tau = refit_tau(d, s)
+    L = torch.zeros(T, s, s, dtype=torch.float64, device=y.device)
+    z = torch.zeros(T, s, dtype=torch.float64, device=y.device)
+    ok = torch.zeros(T, s, dtype=torch.bool, device=y.device)
+    one = torch.ones((), dtype=torch.float64, device=y.device)
+    for j in range(s):
+        p = G[:, j, j] - L[:, j, :j].square().sum(-1)
+        ok[:, j] = live[:, j] & (p > tau * G[:, j, j])
+        r = torch.where(ok[:, j], p, one).sqrt()
+        col = (G[:, j:, j] - (L[:, j:, :j] @ L[:, j, :j, None])[..., 0]) / r[:, None]
+        L[:, j:, j] = torch.where(ok[:, j, None], col, torch.zeros_like(col))
+        L[:, j, j] = r
+        zj = (h[:, j] - (L[:, j, :j] * z[:, :j]).sum(-1)) / r
+        z[:, j] = torch.where(ok[:, j], zj, torch.zeros_like(zj))
+    c = torch.zeros_like(z)
+    for j in range(s - 1, -1, -1):
+        cj = (z[:, j] - (L[:, j + 1:, j] * c[:, j + 1:]).sum(-1)) / L[:, j, j]
+        c[:, j] = torch.where(ok[:, j], cj, torch.zeros_like(cj))
+    e_fit = y - (c[:, None, :] @ D)[:, 0]
+    e_enc = y - (v[:, None, :] @ D)[:, 0]
+    f32 = torch.float32
+    return (c.to(f32), z.square().to(f32), e_fit.square().sum(-1).to(f32), e_enc.square().sum(-1).to(f32),
+            y.square().sum(-1).to(f32), (live & ~ok).sum(-1).to(torch.int32))
+
+
+@torch.library.custom_op("msae::support_refit", mutates_args=())
+def _support_refit(x: Tensor, top_acts: Tensor, top_indices: Tensor, W_dec: Tensor, b_dec: Tensor,
+                   s: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    d = W_dec.shape[1]
+    T = x.numel() // d
+    if not x.is_cuda:
+        return _support_refit_host(x, top_acts, top_indices, W_dec, b_dec, s)
+    dev = _hip.require_device(x, top_acts, top_indices, W_dec, b_dec)
+    lib = _hip.load()
+    xa, W, bd = x.detach().contiguous(), _f32c(W_dec), _f32c(b_dec)
+    N = W.shape[0]
+    coef, gain = (torch.empty(T, s, dtype=torch.float32, device=dev) for _ in range(2))
+    err_fit, err_enc, yy = (torch.empty(T, dtype=torch.float32, device=dev) for _ in range(3))
+    n_dep = torch.empty(T, dtype=torch.int32, device=dev)
+    if T == 0:
+        return coef, gain, err_fit, err_enc, yy, n_dep
+    v, i, ld = _list_rows(top_acts, top_indices, top_acts.shape[-1])
+    wide = i.dtype == torch.int64
+    fn, name = (lib.msae_support_refit_i64_f32, "msae_support_refit_i64_f32") if wide else \
+        (lib.msae_support_refit_f32, "msae_support_refit_f32")
+    flag = _bounds_flag(dev)
+    with torch.cuda.device(dev):
+        _hip.check(fn(_hip.ptr(xa), _hip.DTYPE_CODE[xa.dtype], _hip.ptr(v), _hip.ptr(i), ld, _hip.ptr(W), _hip.ptr(bd), T, s, N,
+                      d, _hip.ptr(coef), _hip.ptr(gain), _hip.ptr(err_fit), _hip.ptr(err_enc), _hip.ptr(yy), _hip.ptr(n_dep),
+                      _hip.ptr(flag), _hip.stream_of(xa)), name)
+    _check_bounds(flag, name)
+    return coef, gain, err_fit, err_enc, yy, n_dep
+
+
+@_support_refit.register_fake
+def _(x, top_acts, top_indices, W_dec, b_dec, s):
+    T = x.numel() // W_dec.shape[1]
+    f = lambda *shape: x.new_empty(shape, dtype=torch.float32)
+    return f(T, s), f(T, s), f(T), f(T), f(T), x.new_empty((T,), dtype=torch.int32)
+
+
+def support_refit(x: Tensor, top_acts: Tensor, top_indices: Tensor, W_dec: Tensor, b_dec: Tensor,
+                  s: Optional[int] = None) -> RefitRaw:
+    """Least-squares refit of each token's coefficients on the support its list chose (include/msae.h, "support refit"):
+    min_c |(x - b_dec) - W_dec[idx[:s]]^T c|^2 per token, the optimal error at every prefix of the support (`gain`), and the
+    refit's and the encoder's own squared errors measured directly.  x [..., d] f32 / bf16 / f16; top_acts / top_indices
+    [..., k] with x's leading shape (or [T, k]), indices int32 or int64; W_dec [N, d], b_dec [d].  `s`: refit the first s
+    slots (None: all k); 1 <= s <= min(k, 64) -- a longer list is refit on its first 64 slots by passing s=64, read in
+    place.  On a HIP device the fused kernel (bit-defined per token); elsewhere a float64 torch composition with the same
+    meaning, not the same bits.  Nothing is read back; bad arguments raise ValueError before any device work."""
+    if x.dim() < 1 or W_dec.dim() != 2 or x.shape[-1] != W_dec.shape[1] or x.shape[-1] < 1:
+        raise ValueError(f"support_refit: x [..., d] and W_dec [N, d] must share d, got {tuple(x.shape)} and {tuple(W_dec.shape)}")
+    if b_dec is None or b_dec.dim() != 1 or b_dec.shape[0] != W_dec.shape[1]:
+        raise ValueError(f"support_refit: b_dec must be [d] = [{W_dec.shape[1]}], got "
+                         f"{None if b_dec is None else tuple(b_dec.shape)}")
+    if x.dtype not in _hip.DTYPE_CODE:
+        raise ValueError(f"support_refit: x must be float32, bfloat16 or float16, got {x.dtype}")
+    if top_acts.shape != top_indices.shape or top_acts.dim() < 1 or top_acts.shape[-1] < 1:
+        raise ValueError(f"support_refit: top_acts and top_indices must share one shape [..., k], got {tuple(top_acts.shape)} "
+                         f"and {tuple(top_indices.shape)}")
+    k = top_acts.shape[-1]
+    if s is None:
+        s = k
+    if isinstance(s, bool) or not isinstance(s, int):
+        raise ValueError(f"support_refit: s must be an integer, got {s!r}")
+    if not 1 <= s <= min(k, REFIT_MAX_S):
+        raise ValueError(f"support_refit: s must be in [1, min(k, {REFIT_MAX_S})] = [1, {min(k, REFIT_MAX_S)}], got {s} "
+                         f"(a longer list is refit on its first {REFIT_MAX_S} slots with s={REFIT_MAX_S})")
+    T = x.numel() // x.shape[-1]
+    if top_acts.numel() != T * k or (top_acts.dim() != 2 and tuple(top_acts.shape[:-1]) != tuple(x.shape[:-1])):
+        raise ValueError(f"support_refit: the list must hold one row per token of x {tuple(x.shape)}, got {tuple(top_acts.shape)}")
+    if top_indices.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"support_refit: top_indices must be int32 or int64, got {top_indices.dtype}")
+    if top_acts.dtype != torch.float32:
+        raise ValueError(f"support_refit: the list's values must be float32, got {top_acts.dtype}")
+    devs = {t.device for t in (x, top_acts, top_indices, W_dec, b_dec)}
+    if len(devs) != 1:
+        raise ValueError(f"support_refit: all tensors must be on one device, got {sorted(str(d) for d in devs)}")
+    if W_dec.shape[1] > 1 << 22:
+        raise ValueError(f"support_refit: d must be at most {1 << 22}, got {W_dec.shape[1]}")
+    _no_grad_inputs("ops.support_refit", x, top_acts)
+    coef, gain, err_fit, err_enc, yy, n_dep = _support_refit(x, top_acts, top_indices, W_dec.detach(), b_dec.detach(), s)
+    lead = tuple(x.shape[:-1])
+    return RefitRaw(coef.view(*lead, s), gain.view(*lead, s), err_fit.view(lead), err_enc.view(lead), yy.view(lead),
+                    n_dep.view(lead))
 
 
 def shard_candidates(x: Tensor, b_enc_shard: Optional[Tensor], b_dec: Optional[Tensor], prepared_shard: Tensor,

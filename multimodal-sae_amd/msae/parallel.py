@@ -465,6 +465,10 @@ class ShardedSae:
         raise NotImplementedError("recon_error (reconstruction error against sparsity) runs on the single-GPU msae.Sae only: a "
                                   "feature-sharded engine holds a slice of W_dec")
 
+    def refit(self, *args, **kwargs):
+        raise NotImplementedError("refit (least-squares refit on the encoder's support) runs on the single-GPU msae.Sae only: a "
+                                  "feature-sharded engine holds a slice of W_dec")
+
     def decode(self, vals: Tensor, idx: Tensor, gather: bool = True, async_gather: bool = False) -> Tensor:
         """Token-sharded decode.  With `async_gather` the all-gather of the reconstruction is issued
         asynchronously (RCCL's own stream) and overlaps whatever the caller enqueues next -- the
@@ -642,6 +646,10 @@ class EmulatedShardGroup:
 
     def recon_error(self, *args, **kwargs):
         raise NotImplementedError("recon_error (reconstruction error against sparsity) runs on the single-GPU msae.Sae only: a "
+                                  "feature-sharded engine holds a slice of W_dec")
+
+    def refit(self, *args, **kwargs):
+        raise NotImplementedError("refit (least-squares refit on the encoder's support) runs on the single-GPU msae.Sae only: a "
                                   "feature-sharded engine holds a slice of W_dec")
 
     def decode(self, vals: Tensor, idx: Tensor, **_):

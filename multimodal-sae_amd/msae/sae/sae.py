@@ -158,6 +158,54 @@ class ReconOutput(NamedTuple):
         return err / self.total_variance
 
 
+class RefitOutput(NamedTuple):
+    """The least-squares refit of a batch on the support its encoder chose (Sae.refit; include/msae.h, "support refit").
+    The tensor fields are the kernel's outputs; the properties are float64."""
+    top_acts: Tensor
+    """The refit coefficients, [..., s] f32: `sae.decode(out.top_acts, out.top_indices)` is the refit reconstruction.  0 for
+    a slot outside the support (a zero activation, a dependent row)."""
+    top_indices: Tensor
+    """The first s columns of the encoder's indices, [..., s]."""
+    gain: Tensor
+    """What slot j takes off the optimal error when it joins the slots before it, [..., s]."""
+    err_fit: Tensor
+    """|x - refit reconstruction|^2, [...]."""
+    err_enc: Tensor
+    """|x - the encoder's reconstruction from the same s slots|^2, [...]."""
+    xx: Tensor
+    """|x - b_dec|^2, [...]: the error at kappa = 0."""
+    n_dependent: Tensor
+    """Live slots dropped as linearly dependent, [...] int32."""
+    total_variance: Tensor
+    """(x - x.mean(0)).pow(2).sum() over this call's tokens, a float64 scalar (as ReconOutput's)."""
+
+    @property
+    def fvu_fit(self) -> Tensor:
+        """Fraction of variance unexplained at the optimal coefficients, a float64 scalar."""
+        return self.err_fit.to(torch.float64).sum() / self.total_variance
+
+    @property
+    def fvu_enc(self) -> Tensor:
+        """Fraction of variance unexplained at the encoder's coefficients, a float64 scalar."""
+        return self.err_enc.to(torch.float64).sum() / self.total_variance
+
+    @property
+    def gap(self) -> Tensor:
+        """The amortisation gap: (err_enc - err_fit) summed over the call / its total variance, a float64 scalar."""
+        return (self.err_enc.to(torch.float64) - self.err_fit.to(torch.float64)).sum() / self.total_variance
+
+    def optimal_curve(self, ks) -> Tensor:
+        """The optimal squared error of the top-kappa support at each kappa in `ks` (integers in [0, s]), [..., len(ks)]
+        float64: xx - gain[..., :kappa].sum(-1).  The lower envelope of `Sae.recon_error(x, ks).err2`."""
+        s = self.gain.shape[-1]
+        ks = [int(c) for c in ks]
+        if not ks or any(c < 0 or c > s for c in ks):
+            raise ValueError(f"RefitOutput.optimal_curve: ks must be one or more integers in [0, {s}], got {ks}")
+        g = self.gain.to(torch.float64)
+        pre = torch.cat([torch.zeros_like(g[..., :1]), g.cumsum(-1)], -1)
+        return self.xx.to(torch.float64)[..., None] - torch.stack([pre[..., c] for c in ks], -1)   # (selects: nothing copied)
+
+
 class _SqErr(torch.autograd.Function):
     """sum((pred - target)^2) -> (scalar, pred - target) with ONE elementwise kernel and one reduction forward and one
     elementwise kernel backward, where the reference's `e = pred - x; e.pow(2).sum()` (sae.py:201,227) costs three
@@ -705,17 +753,75 @@ class Sae(nn.Module):
                 mom, xx = torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
             else:
                 mom, xx = flat.new_empty((0, len(ks), 3), dtype=torch.float32), flat.new_empty((0,), dtype=torch.float32)
-            # this call's own total variance, two passes in float64, a block of rows at a time
-            tv = flat.new_zeros((), dtype=torch.float64)
-            if T:
-                rows = max(1, (32 << 20) // self.d_in)
-                mean = sum(flat[a:a + rows].sum(0, dtype=torch.float64) for a in range(0, T, rows)) / T
-                for a in range(0, T, rows):
-                    tv += (flat[a:a + rows].to(torch.float64) - mean).square().sum()
+            tv = self._total_variance(flat)                # this call's own
         lead = tuple(x.shape[:-1])
         C = len(ks)
         return ReconOutput(tuple(ks), mom[..., 0].reshape(*lead, C), mom[..., 1].reshape(*lead, C),
                            mom[..., 2].reshape(*lead, C), xx.reshape(lead), tv, self.d_in)
+
+    def _total_variance(self, flat: Tensor) -> Tensor:
+        """(flat - flat.mean(0)).pow(2).sum(), two passes in float64, a block of rows at a time."""
+        T = flat.shape[0]
+        tv = flat.new_zeros((), dtype=torch.float64)
+        if T:
+            rows = max(1, (32 << 20) // self.d_in)
+            mean = sum(flat[a:a + rows].sum(0, dtype=torch.float64) for a in range(0, T, rows)) / T
+            for a in range(0, T, rows):
+                tv += (flat[a:a + rows].to(torch.float64) - mean).square().sum()
+        return tv
+
+    def refit(self, x: Tensor, *, s: Optional[int] = None, top=None, exact: bool = False,
+              chunk: Optional[int] = None) -> RefitOutput:
+        """Why the reconstruction of x [..., d_in] (f32 / bf16 / f16) falls short: keep the support the
+        encoder chose and refit its coefficients by least squares against the fixed decoder.  `err_enc - err_fit` is lost
+        to the encoder's magnitudes (the amortisation gap, `gap`); `err_fit` is what the dictionary cannot express on that
+        support.  `s`: refit the first s slots of the list (None: all of them; at most 64 -- a longer list needs an
+        explicit s).  `top`: the list of x (an EncoderOutput or (top_acts, top_indices)) when the caller holds it already;
+        None: `self.encode(x, exact=exact)`.  `chunk`: tokens per kernel call (None: one call); the per-token outputs do
+        not depend on it.  Inference only; nothing is read back."""
+        self._no_transcoder("Sae.refit")
+        self._topk_only("refit")
+        if self.W_dec is None:
+            raise ValueError("Sae.refit: this Sae has no decoder")
+        if x.dim() < 1 or x.shape[-1] != self.d_in:
+            raise ValueError(f"Sae.refit: x must be [..., {self.d_in}], got {tuple(x.shape)}")
+        if x.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+            raise ValueError(f"Sae.refit: x must be float32, bfloat16 or float16, got {x.dtype}")
+        if chunk is not None and chunk < 1:
+            raise ValueError(f"Sae.refit: chunk must be positive, got {chunk}")
+        if top is not None and len(top) != 2:
+            raise ValueError("Sae.refit: top must be an EncoderOutput or a (top_acts, top_indices) pair")
+        k = self.cfg.k if top is None else top[0].shape[-1]
+        if s is None:
+            if k > ops.REFIT_MAX_S:
+                raise ValueError(f"Sae.refit: the list holds {k} slots and at most {ops.REFIT_MAX_S} are refit at once: pass "
+                                 f"s={ops.REFIT_MAX_S} to refit its first {ops.REFIT_MAX_S}")
+            s = k
+        if isinstance(s, bool) or not isinstance(s, int) or not 1 <= s <= min(k, ops.REFIT_MAX_S):
+            raise ValueError(f"Sae.refit: s must be an integer in [1, {min(k, ops.REFIT_MAX_S)}], got {s!r}")
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise RuntimeError("Sae.refit is an inference path: call it under torch.no_grad() or on a detached input")
+        with torch.no_grad():
+            flat = x.reshape(-1, self.d_in)
+            T = flat.shape[0]
+            if top is None:
+                top = self.encode(flat, exact=exact)
+            acts, idx = top[0].reshape(T, k), top[1].reshape(T, k)
+            step = T if chunk is None else chunk
+            parts = [ops.support_refit(flat[a:a + step], acts[a:a + step], idx[a:a + step], self.W_dec, self.b_dec, s)
+                     for a in range(0, T, max(step, 1))]
+            if len(parts) == 1:
+                raw = parts[0]
+            elif parts:
+                raw = ops.RefitRaw(*(torch.cat(f) for f in zip(*parts)))
+            else:
+                e = lambda *shape, dt=torch.float32: flat.new_empty(shape, dtype=dt)
+                raw = ops.RefitRaw(e(0, s), e(0, s), e(0), e(0), e(0), e(0, dt=torch.int32))
+            tv = self._total_variance(flat)
+        lead = tuple(x.shape[:-1])
+        return RefitOutput(raw.coef.reshape(*lead, s), idx[:, :s].reshape(*lead, s), raw.gain.reshape(*lead, s),
+                           raw.err_fit.reshape(lead), raw.err_enc.reshape(lead), raw.yy.reshape(lead),
+                           raw.n_dependent.reshape(lead), tv)
 
     def nested_error(self, x: Tensor, bounds=None, *, top=None, exact: bool = False) -> NestedErrorOutput:
         """How well the first m features alone explain x, GIVEN the selection over all N features: the per-token squared
